@@ -699,7 +699,31 @@ def parse_args(argv=None):
     ap.add_argument("--no-cli-e2e", action="store_true", help="skip the cli_e2e block (the whole CLI with layer 2 on the path, reduced size)")
     ap.add_argument("--calib-stream", action="store_true",
                     help="PMC calibration: every base is 'N' (the kernel only streams the block: known bytes)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last headline step computed to DIR/*.npy (float64): every node's "
+                         "statistics and a fixed, seeded sample of the table's per-row hit counters (summed over the ranks)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_ROW_SAMPLE = 1 << 20      # rows of the hit-counter sample: 2 x 8 MB with its index
+DUMP_SEED = 20231013
+
+
+def dump_outputs(path, st_np, row_counts):
+    """--dump-outputs: the node statistics (NODE_STAT_DTYPE fields but `reserved`) and a seeded sample of the row counters,
+    float64 (exact for every value these hold), about 16 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    for f in ("length", "n_pos", "n_kept", "sum_kept", "median2"):
+        np.save(os.path.join(path, "node_%s.npy" % f), st_np[f].astype(np.float64))
+    n = row_counts.size
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_ROW_SAMPLE, n), replace=False))
+    np.save(os.path.join(path, "row_hits_sample.npy"), row_counts[idx].astype(np.float64))
+    np.save(os.path.join(path, "row_hits_sample_index.npy"), idx.astype(np.float64))
 
 
 def spawn_ranks(args, argv):
@@ -945,9 +969,21 @@ def main(argv=None):
     def drop_sample():
         sample.pop("rs").close()                     # (waits for the step's kernels: ss_reads_destroy's lifetime rule; the slab is kept for the next step)
 
+    def last_step_counts():
+        """--dump-outputs: the table's row counters as the last timed step left them, summed over the ranks"""
+        c = torch.zeros(n_rows, dtype=torch.int32, device=dev)
+        db.counts_rows_dev(c.data_ptr(), stream)
+        if exchange:
+            ssdist.allreduce_counts(c)
+        torch.cuda.synchronize()
+        return c.cpu().numpy()
+
     resident_binned = None
+    dump_counts = None
     if binned:
         dt, (kern_ms, harvest_ms, exch_ms, reduce_ms) = run_timed(scan_sample, stats, bin_sample, drop_sample)
+        if args.dump_outputs:
+            dump_counts = last_step_counts()
         stats_b = torch.zeros_like(stats)
         dt_b, (k_b, h_b, x_b, r_b) = run_timed(scan_binned, stats_b)
         torch.cuda.synchronize()
@@ -959,10 +995,14 @@ def main(argv=None):
                                                       exchange=round(x_b, 3) if exchange else None, node_reduce=round(r_b, 3)))
     else:
         dt, (kern_ms, harvest_ms, exch_ms, reduce_ms) = run_timed(scan_file, stats)
+        if args.dump_outputs:
+            dump_counts = last_step_counts()
     ms_per_step = dt / args.steps * 1e3
     reads_per_s = args.reads * world * args.steps / dt
     tail_ms = exch_ms + reduce_ms
     st_np = stats.cpu().numpy().view(_lib.NODE_STAT_DTYPE)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st_np, dump_counts)
     # the counters of the last step are still in the table (a step resets them at its start): whole-table checksum,
     # and the harvest path against the row-gather path it replaces (ss_counts_rows_dev + ss_nodes_reduce_dev)
     counts_rows = torch.zeros(n_rows, dtype=torch.int32, device=dev)

@@ -511,6 +511,20 @@ def test_revcomp_host_vs_golden(golden_dir):
         assert out.raw[:len(s)] == want.encode()
 
 
+def test_bench_steps_and_dump_arguments():
+    """--steps sets the number of timed steps (at least one: `ms_per_step` divides by it); --dump-outputs names the
+    directory of the last step's outputs and is off by default."""
+    import subprocess
+    import sys
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "out_dir"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out_dir"
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + bad, capture_output=True, timeout=120)
+        assert r.returncode == 2 and b"--" + bad[0][2:].encode() in r.stderr, r.stderr
+
+
 def test_bench_gpus_argument_handling():
     """`python bench.py --gpus 2` without a launcher spawns two fresh rank processes (RANK / WORLD_SIZE /
     MASTER_ADDR=127.0.0.1 set) before anything touches torch, and relays rank 0's line; under a launcher
