@@ -137,7 +137,9 @@ int ss_gz_range_counters(uint64_t *files, uint64_t *pieces);
  * it still serves the chain); 3: this rank leaves range mode WITHOUT serving the chain -- what a crashed peer looks like;
  * 4: which scan kernel of the page index a table goes through -- value 1: tables of k = 31 through the one-lane-per-position
  * kernel, 2: tables of every k through it, 3: tables of every k through the run-queue kernel (k at run time), 0: the product's choice
- * -- so that a test can hold the kernels to each other on one index. */
+ * -- so that a test can hold the kernels to each other on one index; 5: the layout of binned slabs of records of one length --
+ * value 1: they stay ASCII, 0: the product's choice (2-bit codes + invalid flags, 3 bytes per 8 positions, where every record
+ * byte is A C G T or N; see ss_reads_packed_slabs) -- so that a test can hold the two layouts to each other on one read set. */
 int ss_test_hook(int which, long long value);
 
 /* The test sets of ShuffleSplit(n_splits, test_size, random_state=seed).split(range(n)) as scikit-learn 0.23
@@ -272,6 +274,10 @@ int ss_reads_order_timing(double out_ms[3]);
 int ss_reads_order_counters(uint64_t out[2]);
 /* The resident flat blocks copied back to the host, slab after slab (host = NULL: only *len); for tests and debugging. */
 int ss_reads_read_back(const ss_reads *r, char *host, uint64_t cap, uint64_t *len);
+/* How many of the set's slabs are PACKED: binned records of one length whose every byte is A C G T or N, held as 2-bit codes
+ * and invalid flags (57 bytes for a 150-base read instead of 152); the scans read them as they are, ss_reads_read_back
+ * returns the bytes their ASCII form would hold.  Slabs with any other byte (lower case, IUPAC codes, '\r') stay ASCII. */
+int ss_reads_packed_slabs(const ss_reads *r, uint64_t *n_packed);
 /* Lifetime: ss_scan_reads / ss_scan_reads_multi are asynchronous on the caller's stream and read the set's slabs.  Destroying
  * a set WAITS for the device (hipDeviceSynchronize) before its slabs are given up -- the large ones are kept for the next load
  * of this process (ss_dev_big_blocks), the rest go back to the driver -- so a scan still in flight on any stream finishes on

@@ -125,6 +125,7 @@ SIGNATURES = {
     "ss_scan_reads": (i32, [vp, vp, vp]),
     "ss_reads_order_timing": (i32, [vp]),
     "ss_reads_order_counters": (i32, [P(u64)]),
+    "ss_reads_packed_slabs": (i32, [vp, P(u64)]),
     "ss_fastx_to_flat": (i32, [cp, u64, vp, P(u64), P(u64)]),
     "ss_reader_open": (i32, [P(cp), i32, P(vp)]),
     "ss_reader_set_overlap": (i32, [vp, i32]),
@@ -450,6 +451,12 @@ class ReadSet:
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(lib().ss_reads_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "ss_reads_info")
         return dict(n_records=a.value, n_bases=b.value, n_blocks=c.value, device_bytes=d.value)
+
+    def packed_slabs(self):
+        """Slabs of the set held packed (ss_reads_packed_slabs)."""
+        n = C.c_uint64()
+        check(lib().ss_reads_packed_slabs(self._h, C.byref(n)), "ss_reads_packed_slabs")
+        return n.value
 
     def scan_into_many(self, kdbs, stream=None):
         """One pass over the resident reads for several tables (ss_scan_reads_multi); counts as scan_into on each."""

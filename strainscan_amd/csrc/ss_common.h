@@ -123,7 +123,14 @@ struct ss_reads {
     // and padded with '\n' to a multiple of 16 bytes, so a slab is itself one flat base block: one scan
     // launch per slab (one in all for a typical sample) instead of one per 12 MB block, and no device
     // allocation per block while loading.
-    struct Slab { char *d = nullptr; uint64_t cap = 0, used = 0; bool binned = false; };   // binned: ss_reorder.hip has ordered its records
+    // binned: ss_reorder.hip has ordered its records.  packed: ... and holds them as 2-bit codes + invalid flags, 3 bytes per 8
+    // positions (ss_scan_dev.h IN_PACKED): n_pos positions (a multiple of 16) in `used` bytes, every record L bases in a slot of
+    // `slot` positions, the slots back to back from position 0.  Scans take positions(): the length of the block in bases, whichever the layout.
+    struct Slab {
+        char *d = nullptr; uint64_t cap = 0, used = 0; bool binned = false;
+        bool packed = false; uint64_t n_pos = 0; uint32_t L = 0, slot = 0;
+        uint64_t positions() const { return packed ? n_pos : used; }
+    };
     std::vector<Slab> slabs;
     std::mutex mu;
     uint64_t n_records = 0, n_bases = 0, device_bytes = 0, n_blocks = 0;
@@ -172,7 +179,9 @@ struct ss_reads {
 namespace ss {
 // Records of every slab re-ordered by the minimizer of their first k-mer (ss_reorder.hip); `force`: ignore SS_READS_ORDER
 int reads_order_for_locality(ss_reads *R, bool force = false);
-int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used, uint64_t *out_cap);
+// src[0, n) -> *out: a new binned slab (d, cap, used, binned, packed, n_pos, L); packed where its records may be (ss_test_hook 5)
+int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out);
+extern std::atomic<long long> g_hook_ascii_slabs;      // ss_test_hook 5 (ss_reorder.hip): 1 = binned slabs stay ASCII
 void reorder_release();
 void reorder_counters(uint64_t out[2]);      // slabs binned by the one-length passes / by the general ones, in this process
 void reorder_timing(double out[3]);      // the last binning call: count + prefix, slab allocation, place (ms)      // the binning scratch kept between calls goes back to the device (ss_gz_gpu_release)
@@ -228,9 +237,11 @@ int scan_file_parallel(ss_db *db, const char *path, uint64_t *n_records, uint64_
                        int shard_world = 1);
 int scan_text_parallel(ss_db *db, const char *text, uint64_t n, uint64_t *n_records, uint64_t *n_bases, bool *handled,
                        int shard_rank = 0, int shard_world = 1);
+// (packed: the block is a packed binned slab, n counts its positions -- ss_scan_dev.h IN_PACKED)
 int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, unsigned blocks,
-                     uint64_t n_tiles, bool binned = false, uint64_t set_id = 0);
-int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned);
+                     uint64_t n_tiles, bool binned = false, uint64_t set_id = 0, bool packed = false);
+int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned,
+                           bool packed = false);
 // Layer 2 (ss_l2.hip, ss_enet.hip) works on the CALLING THREAD's own stream and takes its temporaries from the stream-ordered
 // pool (round 5): the clusters of a sample are solved on several host threads at once, and on the legacy default stream every
 // synchronous copy of one thread waited for the kernels of all the others, every hipFree for the whole device (four 5 M-row
@@ -254,6 +265,7 @@ inline hipError_t sync() { return hipStreamSynchronize(stream()); }
 // ~25 GB/s and a 50 M-read .gz pair asked for ~47 GB of it, a third of that for blocks that replace each other (ss_host.hip).
 // big_take: a kept block of at least `bytes` (and at most 2.5 x), or nullptr; the caller owns it and gives it back with
 // big_put or hipFree.  big_put keeps blocks of 256 MB and more, at most three and 24 GB, and frees what it does not keep.
+constexpr uint64_t BIG_KEEP_MIN = 256ull << 20;           // blocks big_put keeps (smaller ones go back to the driver)
 void *big_take(uint64_t bytes, uint64_t *cap = nullptr);      // *cap: what the block really holds (the caller keeps that, for the next big_put)
 void big_put(void *p, uint64_t cap);
 void big_release();                                      // everything kept goes back to the driver (ss_gz_gpu_release)
@@ -262,5 +274,6 @@ hipError_t big_malloc(void **p, uint64_t bytes, uint64_t *got);      // big_take
 bool upload_file_to_device(int fd, uint64_t n, uint8_t *d_dst);
 // ss_scan_flat_dev for a block whose records ss_reorder.hip has binned by locus (the scan may add hits up in LDS first)
 // (set_id: ss_reads::serial of the resident set the block belongs to, 0 = none)
-int scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream, bool binned, uint64_t set_id = 0);
+// (packed: a packed binned slab of n positions, ss_scan_dev.h IN_PACKED)
+int scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream, bool binned, uint64_t set_id = 0, bool packed = false);
 }  // namespace ss

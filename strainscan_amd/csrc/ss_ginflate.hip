@@ -2753,7 +2753,8 @@ extern "C" int ss_gz_set_range(int rank, int world, uint64_t slice_bytes, ss_gz_
 // (0 = off), 2 = this process declines .gz inputs on the device (range mode: it still serves the chain), 3 = this rank leaves
 // range mode without serving the chain (what a crashed peer looks like: the others' bounded wait must end it), 4 = which scan
 // kernel of the page index a table goes through (ss_mini.hip launch_scan_mini: 1 = k = 31 through the per-position kernel, 2 = every
-// k through it, 3 = every k through scan_mini_kernel; 0 = the product's choice): the kernels held to each other.
+// k through it, 3 = every k through scan_mini_kernel; 0 = the product's choice): the kernels held to each other, 5 = binned slabs of
+// one length stay ASCII (1) or are packed where they can be (0, the product's choice; ss_reorder.hip order_flat_dev).
 extern "C" int ss_test_hook(int which, long long value)
 {
     switch (which) {
@@ -2761,6 +2762,7 @@ extern "C" int ss_test_hook(int which, long long value)
     case 2: ss::g_hook_decline = value; return SS_OK;
     case 3: ss::g_hook_skip_chain = value; return SS_OK;
     case 4: ss::g_hook_generic_k = value; return SS_OK;
+    case 5: ss::g_hook_ascii_slabs = value; return SS_OK;
     default: return SS_EINVAL;
     }
 }

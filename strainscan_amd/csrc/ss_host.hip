@@ -209,7 +209,7 @@ struct BigBlock { void *p; uint64_t cap; int dev; };      // dev: the device the
 std::mutex g_big_mu;
 std::vector<BigBlock> g_big;
 uint64_t g_big_served = 0;
-constexpr uint64_t BIG_MIN = 256ull << 20, BIG_TOTAL = 24ull << 30;
+constexpr uint64_t BIG_MIN = ss::BIG_KEEP_MIN, BIG_TOTAL = 24ull << 30;
 constexpr size_t BIG_N = 3;
 }
 void *ss::big_take(uint64_t bytes, uint64_t *cap)

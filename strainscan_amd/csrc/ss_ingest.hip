@@ -798,14 +798,11 @@ int ss_reads_from_flat_dev(const void *flat_dev, uint64_t n, int order, ss_reads
     R->n_bases = n;
     if (n && order && n >= 64) {
         // binned straight out of the caller's block (ss_reorder.hip): no intermediate copy
-        char *d = nullptr;
-        uint64_t used = 0, cap = 0;
-        const int rc = ss::order_flat_dev(static_cast<const char *>(flat_dev), n, &d, &used, &cap);
-        if (rc != SS_OK) { ss_reads_destroy(R); return rc; }
         ss_reads::Slab sl;
-        sl.d = d; sl.cap = cap; sl.used = used; sl.binned = true;
+        const int rc = ss::order_flat_dev(static_cast<const char *>(flat_dev), n, &sl);
+        if (rc != SS_OK) { ss_reads_destroy(R); return rc; }
         R->slabs.push_back(sl);
-        R->device_bytes = cap;
+        R->device_bytes = sl.cap;
         R->n_blocks = 1;
     } else if (n) {
         char *dst = R->reserve(n);
@@ -833,19 +830,50 @@ int ss_reads_order_counters(uint64_t out[2])
     return SS_OK;
 }
 
+// a packed slab (ss_scan_dev.h IN_PACKED) as the bytes its ASCII form holds: "ACTG"[code] where valid, 'N' where invalid
+// inside a record, '\n' elsewhere (the slots' padding and the tail)
+static void unpack_slab(const ss_reads::Slab &sl, const uint8_t *pk, char *out)
+{
+    const uint64_t recs_end = sl.n_pos / sl.slot * sl.slot;      // (the tail behind the last slot is shorter than 16 positions)
+    for (uint64_t u = 0; u < sl.n_pos / 8; u++) {
+        const uint32_t code = (uint32_t)pk[3 * u] | ((uint32_t)pk[3 * u + 1] << 8), inv = pk[3 * u + 2];
+        for (uint32_t i = 0; i < 8; i++) {
+            const uint64_t p = 8 * u + i;
+            char c = "ACTG"[(code >> (2 * i)) & 3u];
+            if ((inv >> i) & 1u) c = (p < recs_end && p % sl.slot < sl.L) ? 'N' : '\n';
+            out[p] = c;
+        }
+    }
+}
+
 int ss_reads_read_back(const ss_reads *R, char *host, uint64_t cap, uint64_t *len)
 {
     if (!R || !len) return SS_EINVAL;
     uint64_t total = 0;
-    for (const auto &sl : R->slabs) total += sl.used;
+    for (const auto &sl : R->slabs) total += sl.positions();
     *len = total;
     if (!host) return SS_OK;                       // size query
     if (cap < total) return SS_ERANGE;
     uint64_t o = 0;
     for (const auto &sl : R->slabs) {
-        if (sl.used) SS_HIP(hipMemcpy(host + o, sl.d, sl.used, hipMemcpyDeviceToHost));
-        o += sl.used;
+        if (sl.packed) {
+            std::vector<uint8_t> pk(sl.used);
+            if (sl.used) SS_HIP(hipMemcpy(pk.data(), sl.d, sl.used, hipMemcpyDeviceToHost));
+            unpack_slab(sl, pk.data(), host + o);
+        } else if (sl.used) {
+            SS_HIP(hipMemcpy(host + o, sl.d, sl.used, hipMemcpyDeviceToHost));
+        }
+        o += sl.positions();
     }
+    return SS_OK;
+}
+
+int ss_reads_packed_slabs(const ss_reads *R, uint64_t *n_packed)
+{
+    if (!R || !n_packed) return SS_EINVAL;
+    uint64_t c = 0;
+    for (const auto &sl : R->slabs) c += sl.packed ? 1 : 0;
+    *n_packed = c;
     return SS_OK;
 }
 
@@ -879,7 +907,7 @@ int ss_scan_reads(ss_db *db, const ss_reads *R, void *stream)
     if (R->has_cut_record && k != 31) return SS_ERANGE;   // cut records carry a 30-base overlap
     for (const auto &sl : R->slabs) {
         if (!sl.used) continue;
-        int rc = ss::scan_flat_dev(db, sl.d, sl.used, stream, sl.binned, R->serial);
+        int rc = ss::scan_flat_dev(db, sl.d, sl.positions(), stream, sl.binned, R->serial, sl.packed);
         if (rc) return rc;
     }
     return SS_OK;
@@ -914,8 +942,10 @@ int ss_scan_reads_multi(ss_db *const *dbs, int n_dbs, const ss_reads *R, void *s
         const int ng = (int)std::min<size_t>((size_t)group, mini.size() - g);
         for (const auto &sl : R->slabs) {
             if (!sl.used) continue;
-            int rc = ng == 1 ? ss::scan_flat_dev(mini[g], sl.d, sl.used, stream, sl.binned, R->serial)
-                             : (sl.used < (uint64_t)mini[g]->k ? SS_OK : ss::launch_scan_mini_multi(&mini[g], ng, sl.d, sl.used, ss::as_stream(stream), sl.binned));
+            const uint64_t np = sl.positions();
+            int rc = ng == 1 ? ss::scan_flat_dev(mini[g], sl.d, np, stream, sl.binned, R->serial, sl.packed)
+                             : (np < (uint64_t)mini[g]->k ? SS_OK
+                                                          : ss::launch_scan_mini_multi(&mini[g], ng, sl.d, np, ss::as_stream(stream), sl.binned, sl.packed));
             if (rc) return rc;
         }
     }

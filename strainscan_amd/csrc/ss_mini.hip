@@ -368,7 +368,7 @@ __device__ __forceinline__ void sliding_min(const uint32_t (&x)[32], uint32_t (&
 #define SS_NUM_SGPR 80
 #endif
 // KK: 31 = the k this kernel was tuned for, everything about k a constant; 0 = k is the kernel argument k_rt (17 <= k <= 30, round 6)
-template <bool ALIGNED, bool BLOOM, bool COMB, int WAVES_PER_SIMD, bool MULTI = false, int KK = 31>
+template <int IN, bool BLOOM, bool COMB, int WAVES_PER_SIMD, bool MULTI = false, int KK = 31>
 __global__ __launch_bounds__(MT, WAVES_PER_SIMD) __attribute__((amdgpu_num_sgpr(SS_NUM_SGPR))) void scan_mini_kernel(
     const uint8_t *__restrict__ bases, uint64_t n, uint64_t n_tiles, const uint64_t *__restrict__ mkeys0,
     const uint4 *__restrict__ pages0, uint32_t n_pages0, uint32_t *__restrict__ counts0, uint32_t cbase0,
@@ -470,14 +470,14 @@ __global__ __launch_bounds__(MT, WAVES_PER_SIMD) __attribute__((amdgpu_num_sgpr(
     uint32_t wn[4];
     if (tile < tile_end) {
         const uint64_t b0 = tile * MTILE;
-        load16<ALIGNED>(bases, b0 + (uint64_t)t * 16, n, wn);
+        load_in<IN>(bases, b0 + (uint64_t)t * 16, n, wn);
     }
     for (; tile < tile_end; tile = next_tile(tile)) {
         SS_MARK(20);
         // ---- phase 0: bases -> 2-bit codes in LDS ------------------------------------------------
         {
             uint32_t code, inv;
-            encode16(wn, code, inv);
+            decode_in<IN>(wn, code, inv);
             S.code_[t + 1] = code;
             S.inv[t] = (uint16_t)inv;
             if (t == 1) S.cnt[1] = 0;
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(MT, WAVES_PER_SIMD) __attribute__((amdgpu_num_sgpr(
             const uint64_t nt = next_tile(tile);
             if (nt < tile_end) {
                 const uint64_t nb = nt * (uint64_t)MTILE;
-                load16<ALIGNED>(bases, nb + (uint64_t)t * 16, n, wn);
+                load_in<IN>(bases, nb + (uint64_t)t * 16, n, wn);
             }
         }
         __syncthreads();
@@ -1326,7 +1326,7 @@ struct KShared {
 // times per tile.  Hence: a lane owns FOUR ADJACENT positions and reads their k - 11 keys once, as five 16-byte LDS loads (the
 // four windows share all but three keys on either side); the four page heads are in flight together; positions whose page shows
 // their tag (or is full) are compacted into an LDS queue with ballots and settled ONCE per tile, one candidate per lane.
-template <bool ALIGNED, bool BLOOM>
+template <int IN, bool BLOOM>
 __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restrict__ bases, uint64_t n, uint64_t n_tiles, int k,
                                                         const uint64_t *__restrict__ mkeys, const uint4 *__restrict__ pages, uint32_t n_pages,
                                                         uint32_t *__restrict__ counts, uint32_t cbase, const uint32_t *__restrict__ bloom,
@@ -1385,13 +1385,13 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
         // ---- bases -> codes + invalid flags: 16 bases per lane, the 48 behind the tile by lanes 0..2
         {
             uint32_t w[4], code, inv;
-            load16<ALIGNED>(bases, b0 + (uint64_t)t * 16, n, w);
-            encode16(w, code, inv);
+            load_in<IN>(bases, b0 + (uint64_t)t * 16, n, w);
+            decode_in<IN>(w, code, inv);
             S.code[t] = code;
             S.inv[t] = (uint16_t)inv;
             if (t < 3) {
-                load16<ALIGNED>(bases, b0 + (uint64_t)(KT + t) * 16, n, w);
-                encode16(w, code, inv);
+                load_in<IN>(bases, b0 + (uint64_t)(KT + t) * 16, n, w);
+                decode_in<IN>(w, code, inv);
                 S.code[KT + t] = code;
                 S.inv[KT + t] = (uint16_t)inv;
             } else if (t < 8) {
@@ -1526,26 +1526,29 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
 }
 
 std::atomic<long long> g_hook_generic_k{0};      // ss_test_hook(4, ...)
-static int launch_scan_minik(ss_db *db, const uint8_t *b, uint64_t n, hipStream_t stream)
+static int launch_scan_minik(ss_db *db, const uint8_t *b, uint64_t n, hipStream_t stream, bool packed)
 {
     const uint64_t n_tiles = (n + KPOS - 1) / KPOS;
     // (one-wave workgroups, grid stride; 8 K / 32 K / 131 K / 300 K / 600 K of them: 2.56 / 2.37 / 2.31 / 2.30 / 2.29 ms per 4 M reads at k = 25)
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)256 * 32 * 16);
-    const bool aligned = (((uintptr_t)b) & 15) == 0;
+    const int in = input_layout(b, packed);
     const uint4 *pages = reinterpret_cast<const uint4 *>(db->d_dir);
     const uint32_t cbase = (uint32_t)db->n_mslots, bshift = 30u - db->bloom_bits;
     const bool bl = db->d_bloom && !db->expect_hits;
 #define SS_LAUNCH_K(A, B) hipLaunchKernelGGL((scan_minik_kernel<A, B>), dim3(blocks), dim3(KT), 0, stream, b, n, n_tiles, db->k, db->d_mkeys, pages, db->n_dir, \
                                              db->d_counts, cbase, db->d_bloom, bshift)
-    if (bl) { if (aligned) SS_LAUNCH_K(true, true); else SS_LAUNCH_K(false, true); }
-    else    { if (aligned) SS_LAUNCH_K(true, false); else SS_LAUNCH_K(false, false); }
+#define SS_LAUNCH_KI(B) do { if (in == IN_PACKED) SS_LAUNCH_K(IN_PACKED, B); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH_K(IN_ASCII_ALIGNED, B); \
+                             else SS_LAUNCH_K(IN_ASCII, B); } while (0)
+    if (bl) SS_LAUNCH_KI(true);
+    else    SS_LAUNCH_KI(false);
+#undef SS_LAUNCH_KI
 #undef SS_LAUNCH_K
     SS_HIP(hipGetLastError());
     return SS_OK;
 }
 
 template <int LB>
-static void launch_lb(bool aligned, bool comb, unsigned blocks, hipStream_t stream, const uint8_t *bases, uint64_t n,
+static void launch_lb(int in, bool comb, unsigned blocks, hipStream_t stream, const uint8_t *bases, uint64_t n,
                       uint64_t n_tiles, ss_db *db, bool probe = false)
 {
     const uint4 *pages = reinterpret_cast<const uint4 *>(db->d_dir);
@@ -1562,14 +1565,17 @@ static void launch_lb(bool aligned, bool comb, unsigned blocks, hipStream_t stre
                                 db->d_mkeys, pages, db->n_dir, db->d_counts, cbase, db->d_bloom, bshift, swz, none, db->k);                                 \
     } while (0)
     // a table that expects hits (ss_db_expect_hits) skips its Bloom filter: nearly every minimizer of the reads is in it
-    if (comb)             { if (aligned) SS_LAUNCH(true, false, true); else SS_LAUNCH(false, false, true); }
-    else if (db->d_bloom && !db->expect_hits) { if (aligned) SS_LAUNCH(true, true, false); else SS_LAUNCH(false, true, false); }
-    else                  { if (aligned) SS_LAUNCH(true, false, false); else SS_LAUNCH(false, false, false); }
+#define SS_LAUNCH_I(B, C_) do { if (in == IN_PACKED) SS_LAUNCH(IN_PACKED, B, C_); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH(IN_ASCII_ALIGNED, B, C_); \
+                                else SS_LAUNCH(IN_ASCII, B, C_); } while (0)
+    if (comb)             SS_LAUNCH_I(false, true);
+    else if (db->d_bloom && !db->expect_hits) SS_LAUNCH_I(true, false);
+    else                  SS_LAUNCH_I(false, false);
+#undef SS_LAUNCH_I
 #undef SS_LAUNCH
 }
 
 // one pass of a flat block against up to MULTI_MAX tables of the minimizer layout (all k = 31)
-int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned)
+int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned, bool packed)
 {
     if (n_dbs < 1 || n_dbs > MULTI_MAX) return SS_EINVAL;
     ScanTabs tabs = {};
@@ -1586,7 +1592,7 @@ int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, 
         expect = expect && db->expect_hits;
     }
     tabs.n = n_dbs;
-    const bool aligned = (((uintptr_t)bases_dev) & 15) == 0;
+    const int in = input_layout(bases_dev, packed);
     static const int comb_env = [] { const char *e = getenv("SS_COMBINE"); return e ? atoi(e) : -1; }();
     constexpr uint32_t swz = 1u;
     const bool comb = expect && (comb_env < 0 ? binned : comb_env != 0);
@@ -1602,8 +1608,11 @@ int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, 
                                 tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],                                    \
                                 (const uint32_t *)nullptr, 0u, swz, tabs, k_all);                                                                \
     } while (0)
-    if (comb) { if (aligned) SS_LAUNCH_M(true, true, 6); else SS_LAUNCH_M(false, true, 6); }
-    else      { if (aligned) SS_LAUNCH_M(true, false, 8); else SS_LAUNCH_M(false, false, 8); }
+#define SS_LAUNCH_MI(C_, LB) do { if (in == IN_PACKED) SS_LAUNCH_M(IN_PACKED, C_, LB); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH_M(IN_ASCII_ALIGNED, C_, LB); \
+                                  else SS_LAUNCH_M(IN_ASCII, C_, LB); } while (0)
+    if (comb) SS_LAUNCH_MI(true, 6);
+    else      SS_LAUNCH_MI(false, 8);
+#undef SS_LAUNCH_MI
 #undef SS_LAUNCH_M
     SS_HIP(hipGetLastError());
     for (int i = 0; i < n_dbs; i++) dbs[i]->launches++;
@@ -1653,9 +1662,10 @@ static bool probe_known(ss_db *db, uint64_t set_id, bool *comb)
     return true;
 }
 
-static int launch_plain_or_comb(ss_db *db, bool comb, bool probe, const uint8_t *b, uint64_t n, uint64_t n_tiles, hipStream_t stream)
+static int launch_plain_or_comb(ss_db *db, bool comb, bool probe, const uint8_t *b, uint64_t n, uint64_t n_tiles, hipStream_t stream,
+                                bool packed)
 {
-    const bool aligned = (((uintptr_t)b) & 15) == 0;
+    const int in = input_layout(b, packed);
     // grid-stride over tiles with MANY more blocks than fit the chip: short blocks start at scattered times, so
     // the waves sharing a SIMD stop marching through their ALU and memory phases in step.  Measured with 8 waves
     // per SIMD resident (20 M reads = 3.04 M tiles; blocks = x * 1024): x = 8 (one round of resident blocks)
@@ -1664,14 +1674,14 @@ static int launch_plain_or_comb(ss_db *db, bool comb, bool probe, const uint8_t 
     unsigned blocks = (unsigned)std::min<uint64_t>(units, (uint64_t)2048 * 256 * (256 / MT));
     blocks = (blocks + 7u) & ~7u;                           // a multiple of 8: the same number of workgroups on every XCD
     // (the combining variant needs 71 VGPRs: at 8 waves per SIMD it would spill four of them to scratch)
-    if (comb) launch_lb<6>(aligned, comb, blocks, stream, b, n, n_tiles, db, probe);
-    else launch_lb<8>(aligned, comb, blocks, stream, b, n, n_tiles, db, probe);
+    if (comb) launch_lb<6>(in, comb, blocks, stream, b, n, n_tiles, db, probe);
+    else launch_lb<8>(in, comb, blocks, stream, b, n, n_tiles, db, probe);
     SS_HIP(hipGetLastError());
     return SS_OK;
 }
 
 int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, unsigned /*blocks*/,
-                     uint64_t n_tiles, bool binned, uint64_t set_id)
+                     uint64_t n_tiles, bool binned, uint64_t set_id, bool packed)
 {
     // Which kernel.  k = 31: scan_mini_kernel with k a constant (everything below).  17 <= k <= 30: scan_mini_kernel with k at run time
     // (KK = 0, queues of 256 runs) -- measured against the one-lane-per-position kernel scan_minik_kernel (profiles/r06_k_index.json):
@@ -1685,10 +1695,10 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
     {
         const long long hk = g_hook_generic_k.load();
         if (db->k == 31 ? (hk == 1 || hk == 2) : (hk != 3 && (hk == 2 || (db->k <= 19 && db->expect_hits))))
-            return launch_scan_minik(db, (const uint8_t *)bases_dev, n, stream);
+            return launch_scan_minik(db, (const uint8_t *)bases_dev, n, stream, packed);
         if (db->k != 31) {                                  // (no probe: the flag decides)
             const uint64_t nt = (n + MTILE - 1) / MTILE;
-            return launch_plain_or_comb(db, binned && db->expect_hits, false, (const uint8_t *)bases_dev, n, nt, stream);
+            return launch_plain_or_comb(db, binned && db->expect_hits, false, (const uint8_t *)bases_dev, n, nt, stream, packed);
         }
     }
     n_tiles = (n + MTILE - 1) / MTILE;                      // this kernel's tile is 62 x 16 positions
@@ -1709,7 +1719,7 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
         void *sym = nullptr;
         SS_HIP(hipGetSymbolAddress(&sym, HIP_SYMBOL(ss_probe_runs)));
         SS_HIP(hipMemsetAsync(sym, 0, sizeof(runs), stream));
-        int rc = launch_plain_or_comb(db, false, true, b, n, PROBE_TILES, stream);      // (n: the last tile's k-mers reach beyond it)
+        int rc = launch_plain_or_comb(db, false, true, b, n, PROBE_TILES, stream, packed);      // (n: the last tile's k-mers reach beyond it)
         if (rc) return rc;
         SS_HIP(hipMemcpyAsync(runs, sym, sizeof(runs), hipMemcpyDeviceToHost, stream));
         SS_HIP(hipStreamSynchronize(stream));
@@ -1719,11 +1729,11 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
         comb = db->probe_runs_per_tile >= PROBE_RUNS_PER_TILE;
         db->probe_comb = comb;
         db->probe_set = set_id;
-        b += PROBE_TILES * (uint64_t)MTILE;                 // (a multiple of 16 bytes: the alignment of the block is kept)
+        b += in_bytes(packed, PROBE_TILES * (uint64_t)MTILE);      // (a multiple of 16 bytes / of 8 packed: the alignment of the block is kept)
         n -= PROBE_TILES * (uint64_t)MTILE;
         n_tiles -= PROBE_TILES;
     }
-    return launch_plain_or_comb(db, comb, false, b, n, n_tiles, stream);
+    return launch_plain_or_comb(db, comb, false, b, n, n_tiles, stream, packed);
 }
 
 }  // namespace ss

@@ -31,6 +31,13 @@
 // is every count).  ON by default for resident read sets (SS_READS_ORDER=file keeps the file order): it costs ~2-3 ms per
 // 20 M reads against ~80 ms of parsing and PCIe for the same reads, and every scan of the set is then 0-35 % faster
 // depending on the coverage of the sample (profiles/r03_locality_sweep.json).
+//
+// PACKED slabs.  A slab of one-length records whose every byte is A C G T or N (the count pass checks the alphabet beside the
+// layout) is placed as 2-bit codes + invalid flags, 3 bytes per 8 positions (ss_scan_dev.h IN_PACKED): 57 bytes per 150-base
+// read instead of 152.  Positions, slots, bins and tiles are those of the ASCII slab; packed group g is exactly encode16 of its
+// bytes [16g, 16g + 16), so every scan kernel sees bit-identical codes and flags, without its encode phase.  The placement is
+// meant to gain from the random sectors its scattered writes touch (~3.3 per record ASCII, ~1.9 packed); it gains less: place
+// 2.06 -> 1.93 ms per 20 M reads (profiles/r07_packed_ab.md: it also encodes, at 6 waves per SIMD, with byte stores at the edges).  Any other byte (lower case, IUPAC, '\r'), ragged records, or ss_test_hook 5 = 1: ASCII.
 #include "ss_common.h"
 
 #include <mutex>
@@ -460,9 +467,17 @@ __global__ __launch_bounds__(256) void place_again_kernel(const char *__restrict
 //                 a piece's record comes from the owning lane by a wave shuffle; aligned stores, padded with '\n'
 constexpr uint32_t FIX_MIN_L = 32, FIX_MAX_L = 1023;
 
+// non-zero unless every byte of w is 'A' 'C' 'G' 'T' 'N' or '\n' -- upper case only: a packed slab reads back as exactly these
+__device__ __forceinline__ uint32_t not_packable4(uint32_t w)
+{
+    auto zb = [](uint32_t x) { return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; };      // 0x80 where a byte is zero
+    const uint32_t letter = __builtin_amdgcn_perm(0u, 0x47544341u, (w >> 1) & 0x03030303u);           // code -> 'A' 'C' 'T' 'G'
+    return (zb(w ^ letter) | zb(w ^ 0x4E4E4E4Eu) | zb(w ^ 0x0A0A0A0Au)) ^ 0x80808080u;
+}
+
 __global__ __launch_bounds__(256, 8) void count_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L, uint32_t magic_l1, int bits,
                                                              unsigned long long *__restrict__ hist, uint32_t *__restrict__ bins,
-                                                             unsigned long long *__restrict__ not_fixed)
+                                                             unsigned long long *__restrict__ not_fixed, unsigned long long *__restrict__ not_packable)
 {
     const int lane = threadIdx.x & 63;
     const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u;
@@ -470,19 +485,25 @@ __global__ __launch_bounds__(256, 8) void count_fixed_kernel(const char *__restr
     const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), span = nr * L1;
     const uint64_t base = r0 * L1;
     bool bad = false;
+    uint32_t alpha = 0;
 #ifndef SS_COUNT_NOVERIFY          // (A/B builds only: what the count pass costs when it reads each record's first bytes and nothing else)
     for (uint32_t off = (uint32_t)lane * 16u; off < span; off += 1024u) {
-        const uint32_t m = nl_mask16(load16_nl(b, base + off, n));
+        const uint4 v = load16_nl(b, base + off, n);
+        const uint32_t m = nl_mask16(v);
         const uint32_t pos = off - __umulhi(off, magic_l1) * L1;           // offset of the piece's first byte within its record
         const uint32_t valid = span - off >= 16u ? 0xFFFFu : (1u << (span - off)) - 1u;
         const uint32_t want = L - pos < 16u ? 1u << (L - pos) : 0u;        // (L >= 32: at most one record end in 16 bytes)
         bad |= ((m ^ want) & valid) != 0u;
-    }
+        alpha |= not_packable4(v.x) | not_packable4(v.y) | not_packable4(v.z) | not_packable4(v.w);      // (bytes past the span: the
+    }                                                                      // next wave's records, or padding that must be '\n')
+#else
+    alpha = 1u;
 #endif
     if (r0 + nr == n_rec) {                                                // behind the last record: newlines only (padding)
         for (uint64_t i = base + span + (uint32_t)lane; i < n; i += 64) bad |= b[i] != '\n';
     }
     if (__ballot(bad)) { if (lane == 0) atomicOr(not_fixed, 1ull); return; }
+    if (__ballot(alpha != 0u) && lane == 0) atomicOr(not_packable, 1ull);
     if ((uint32_t)lane < nr) {
         const uint32_t bin = record_bin(b, base + (uint64_t)lane * L1, L, bits);      // (s + 32 <= s + L + 1 <= n)
         bins[r0 + lane] = bin;
@@ -525,6 +546,94 @@ __global__ __launch_bounds__(256, 8) void place_fixed_kernel(const char *__restr
             const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)d0, (int)rec[r], 64), hi = (uint32_t)__shfl((int)(uint32_t)(d0 >> 32), (int)rec[r], 64);
             if (p < total) store_piece(dst, (((uint64_t)hi << 32) | lo) + off[r], v[r], L, slot, off[r]);
         }
+    }
+}
+
+// ---- the same placement into a PACKED slab (ss_scan_dev.h IN_PACKED) ------------------------------------------------------
+// Positions as in the ASCII slab (a record at its bin cursor, slot_of(L) positions), but every 8 positions are one 3-byte unit:
+// a record is one contiguous span of 3 slot / 8 bytes (57 for 150 bases) at byte 3 (cursor / 8), anywhere modulo 4.  The
+// wave's records are encoded first (pieces numbered across the wave as in place_fixed: consecutive lanes, consecutive 16 bytes
+// of the source; encode16, the record's '\n' padding included) into LDS, record r at byte r A + 4 of the wave's area, while the
+// returning atomics are on their way; then every lane stores one destination dword of a record's span, read back from LDS with
+// the span's alignment.  A record's first and last dword may share bytes with its neighbours: those go out as byte stores.
+// Long reads take several rounds of G records (the wave's LDS holds 64 records of up to 151 bases at once).
+constexpr uint32_t PK_LDS = 4352;           // bytes of LDS per wave: 64 records x 68 bytes (L <= 151)
+constexpr int FPK = 4;                      // pieces a lane has in flight (the kernel takes 80 VGPRs: six waves per SIMD, no scratch)
+
+__global__ __launch_bounds__(256, 6) void place_fixed_packed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L,
+                                                                    uint32_t P, uint32_t magic_p, uint32_t A, uint32_t G, uint32_t ND,
+                                                                    uint32_t magic_nd, unsigned long long *__restrict__ cursor,
+                                                                    const uint32_t *__restrict__ bins, uint8_t *__restrict__ dst)
+{
+    __shared__ uint32_t lds[4][PK_LDS / 4 + 1];   // (+1: the second dword of the last record's last read)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave) * 64u;
+    if (r0 >= n_rec) return;
+    const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), slot = slot_of(L), B = slot / 8u * 3u;
+    const uint64_t base = r0 * L1;
+    uint32_t *W = lds[wave];
+    uint8_t *W8 = reinterpret_cast<uint8_t *>(W);
+    unsigned long long d0 = 0;
+    if ((uint32_t)lane < nr) d0 = atomicAdd(&cursor[bins[r0 + lane]], (unsigned long long)slot);      // (answer needed at the stores)
+    for (uint32_t c0 = 0; c0 < nr; c0 += G) {
+        const uint32_t nc = min(G, nr - c0), total = nc * P;
+        for (uint32_t p0 = 0; p0 < total; p0 += 64u * FPK) {
+            uint4 v[FPK];                                                  // (piece, record and offset are worked out twice: registers)
+#pragma unroll
+            for (int r = 0; r < FPK; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
+                v[r] = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
+                if (p < total && L > off) v[r] = load16_nl(b, base + (uint64_t)(c0 + rec) * L1 + off, n);
+            }
+#pragma unroll
+            for (int r = 0; r < FPK; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
+                if (p >= total) continue;
+                uint32_t w[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+                const int keep = (int)min(16u, L > off ? L - off : 0u);      // record bytes in this piece, '\n' behind them
+                if (keep < 16) {
+#pragma unroll
+                    for (int d = 0; d < 4; d++) {
+                        const int k = keep - 4 * d;
+                        if (k <= 0) w[d] = 0x0A0A0A0Au;
+                        else if (k < 4) { const uint32_t m = (1u << (8 * k)) - 1u; w[d] = (w[d] & m) | (0x0A0A0A0Au & ~m); }
+                    }
+                }
+                uint32_t code, inv;
+                ss::dev::encode16(w, code, inv);
+                // the group's 6 bytes: code[0..15] inv[0..7] code[16..31] inv[8..15] (2-byte aligned in LDS)
+                uint16_t *q = reinterpret_cast<uint16_t *>(W8 + rec * A + 4u + (off >> 4) * 6u);
+                q[0] = (uint16_t)code;
+                q[1] = (uint16_t)((inv & 0xFFu) | ((code >> 8) & 0xFF00u));
+                q[2] = (uint16_t)((code >> 24) | (inv & 0xFF00u));
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // the destination dwords of the records' spans: item i = record i / ND, its dword i % ND (counted from the dword of its first byte)
+        const uint32_t items = nc * ND;
+        for (uint32_t i0 = 0; i0 < items; i0 += 64u) {                      // (uniform trip count: every lane takes part in the shuffles)
+            const uint32_t i = i0 + (uint32_t)lane, rec = min(__umulhi(i, magic_nd), nc - 1u), jl = i - rec * ND;
+            const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)d0, (int)(c0 + rec), 64), hi = (uint32_t)__shfl((int)(uint32_t)(d0 >> 32), (int)(c0 + rec), 64);
+            const uint64_t D = ((((uint64_t)hi << 32) | lo) >> 3) * 3u;    // the record's first byte in the packed slab
+            const int o = (int)(4u * jl) - (int)(D & 3u);                   // record byte at the dword's first byte (-3 .. )
+            if (i < items && o < (int)B) {
+                const uint32_t x = rec * A + 4u + (uint32_t)o;              // (>= rec A + 1)
+                const uint32_t val = __builtin_amdgcn_alignbyte(W[(x >> 2) + 1u], W[x >> 2], x & 3u);
+                uint8_t *out = dst + (D & ~3ull) + 4u * jl;
+                if (o >= 0 && o + 4 <= (int)B) {
+                    *reinterpret_cast<uint32_t *>(__builtin_assume_aligned(out, 4)) = val;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (o + k >= 0 && o + k < (int)B) out[k] = (uint8_t)(val >> (8 * k));
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // (the next round's LDS writes come behind these reads)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 }
 
@@ -605,11 +714,14 @@ static double g_order_ms[3] = {0, 0, 0};      // the last order_flat_dev: count 
 static char *g_scr = nullptr;            // the scratch of the last call (bin cursors, per-tile record tables), kept for the next
 static uint64_t g_scr_cap = 0;
 
-// src[0, n) (a flat base block on the device) -> a new buffer with the records
-// binned; *out_d (hipMalloc'ed), *out_used (multiple of 16, '\n' padded), *out_cap.
-int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used, uint64_t *out_cap)
+std::atomic<long long> g_hook_ascii_slabs{0};      // ss_test_hook(5, ...): 1 = binned slabs of one length stay ASCII
+
+// src[0, n) (a flat base block on the device) -> a new slab with the records binned: out->d (hipMalloc'ed or a kept block),
+// out->cap; an ASCII slab of out->used bytes (a multiple of 16, '\n' padded), or -- records of one length, every byte of them
+// A C G T N -- a packed one of out->n_pos positions (the same multiple of 16) in out->used bytes.
+int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
 {
-    *out_d = nullptr; *out_used = 0; *out_cap = 0;
+    *out = ss_reads::Slab();
     const int bits = order_bits(n);
     const uint32_t n_bins = (1u << bits) + 1u;
     static const bool trace = getenv("SS_INGEST_TRACE") != nullptr;
@@ -621,7 +733,7 @@ int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used
     };
     const unsigned nb = (unsigned)((n + RB - 1) / RB), nsb = (n_bins + SCAN_PER - 1) / SCAN_PER;
     // one allocation for the scratch: bin sizes / cursors (+ total), block sums of the prefix, per-tile record counts and table
-    const uint64_t o_sums = ((uint64_t)n_bins + 2) * 8, o_cnt = o_sums + (((uint64_t)nsb + 1) * 8), o_tab = (o_cnt + (uint64_t)nb * 4 + 255) & ~255ull;
+    const uint64_t o_sums = ((uint64_t)n_bins + 3) * 8, o_cnt = o_sums + (((uint64_t)nsb + 1) * 8), o_tab = (o_cnt + (uint64_t)nb * 4 + 255) & ~255ull;
     // records of one length: the first newline says which; the count pass checks every record against it
     uint32_t fix_L = 0;
     uint64_t n_rec = 0;
@@ -651,19 +763,20 @@ int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used
     uint32_t *d_cnt = (uint32_t *)(d_scr + o_cnt);
     unsigned long long *d_tab = (unsigned long long *)(d_scr + o_tab);
     constexpr unsigned pad1 = 0, pad2 = 0;
-    unsigned long long tail[2] = {0, 0};                 // bytes of the new slab; tiles that did not fit the table / "not of one length"
-    bool fixed = false;
+    unsigned long long tail[3] = {0, 0, 0};              // positions of the new slab; tiles that did not fit the table / "not of one
+    bool fixed = false, packed = false;                  // length"; a byte other than A C G T N in the records
     if (fix_L) {
         const uint32_t L1 = fix_L + 1u, P = (::slot_of(fix_L) + 15u) >> 4;
         const unsigned nbf = (unsigned)((n_rec + 255) / 256);
         SS_R(hipMemsetAsync(d_hist, 0, o_sums, 0));
         hipLaunchKernelGGL(count_fixed_kernel, dim3(nbf), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + L1 - 1) / L1), bits, d_hist,
-                           (uint32_t *)d_tab, d_hist + n_bins + 1);
+                           (uint32_t *)d_tab, d_hist + n_bins + 1, d_hist + n_bins + 2);
         hipLaunchKernelGGL(scan_sums_kernel, dim3(nsb), dim3(1024), 0, 0, d_hist, n_bins, d_sums);
         hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, 0, d_sums, nsb, d_hist + n_bins);
         hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(1024), 0, 0, d_hist, n_bins, d_sums);
-        SS_R(hipMemcpy(tail, d_hist + n_bins, 16, hipMemcpyDeviceToHost));
+        SS_R(hipMemcpy(tail, d_hist + n_bins, 24, hipMemcpyDeviceToHost));
         fixed = tail[1] == 0;                            // (else: some record is shorter or longer after all -- the general passes)
+        packed = fixed && tail[2] == 0 && g_hook_ascii_slabs.load() == 0;
         (void)P;
     }
     if (!fixed) {
@@ -677,12 +790,29 @@ int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used
     const unsigned long long total = tail[0];
     lap("count + prefix");
     const auto t_counted = std::chrono::steady_clock::now();
-    const uint64_t cap = std::max<uint64_t>((total + 15) & ~15ull, 16);
-    uint64_t real_cap = cap;                             // (a kept block may be larger)
-    SS_R(ss::big_malloc((void **)&d_new, cap, &real_cap));
+    const uint64_t cap = std::max<uint64_t>((total + 15) & ~15ull, 16);      // positions
+    // packed: 6 bytes per 16 positions, and 8 bytes behind them that the scans' 8-byte loads may touch (IN_PACKED).  A slab whose
+    // ASCII form would be a block the process keeps (ss::big_put) still takes a block of that size: destroyed, it goes back to
+    // the kept blocks and must serve what comes next -- the next sample's file-order slab, or its binning -- which a block of the
+    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones.
+    const uint64_t bytes = packed ? std::max<uint64_t>(ss::dev::in_bytes(true, cap) + 8, cap >= ss::BIG_KEEP_MIN ? cap : 0) : cap;
+    uint64_t real_cap = bytes;                           // (a kept block may be larger)
+    SS_R(ss::big_malloc((void **)&d_new, bytes, &real_cap));
     const auto t_alloc = std::chrono::steady_clock::now();
     lap("new slab");
-    if (fixed) {
+    if (packed) {
+        // a record's LDS area: 4 bytes in front (a span's first dword may begin before it), its groups, 4 behind
+        const uint32_t P = (::slot_of(fix_L) + 15u) >> 4, B = ::slot_of(fix_L) / 8u * 3u, A = (6u * P + 8u + 3u) & ~3u;
+        const uint32_t G = std::min<uint32_t>(64u, PK_LDS / A), ND = ((B + 2u) >> 2) + 1u;      // records per round; dwords a span touches
+        hipLaunchKernelGGL(place_fixed_packed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, P,
+                           (uint32_t)(((1ull << 32) + P - 1) / P), A, G, ND, (uint32_t)(((1ull << 32) + ND - 1) / ND), d_hist,
+                           (const uint32_t *)d_tab, (uint8_t *)d_new);
+        // the tail: '\n' (code 1, invalid) up to the 16-position boundary -- at most one 3-byte unit (slots are multiples of 8) --,
+        // then the slack behind the last group
+        const uint64_t t0 = total / 8u * 3u, t1 = ss::dev::in_bytes(true, cap) + 8;      // (not the rest of a larger block)
+        SS_R(hipMemsetAsync(d_new + t0, 0xFF, t1 - t0, 0));
+        if (cap > total) SS_R(hipMemsetAsync(d_new + t0, 0x55, 2, 0));
+    } else if (fixed) {
         const uint32_t P = (::slot_of(fix_L) + 15u) >> 4;
         hipLaunchKernelGGL(place_fixed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + P - 1) / P),
                            d_hist, (const uint32_t *)d_tab, d_new);
@@ -690,7 +820,7 @@ int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used
         hipLaunchKernelGGL(place_kernel, dim3(nb), dim3(256), pad2, 0, src, n, d_hist, d_cnt, d_tab, d_new);
         if (tail[1]) hipLaunchKernelGGL(place_again_kernel, dim3(nb), dim3(256), 0, 0, src, n, bits, d_hist, d_cnt, d_new);
     }
-    if (cap > total) SS_R(hipMemsetAsync(d_new + total, '\n', cap - total, 0));
+    if (!packed && cap > total) SS_R(hipMemsetAsync(d_new + total, '\n', cap - total, 0));
     SS_R(hipGetLastError());
     SS_R(hipDeviceSynchronize());
     lap("place");
@@ -709,7 +839,9 @@ int order_flat_dev(const char *src, uint64_t n, char **out_d, uint64_t *out_used
         if (!g_scr || g_scr_cap < scr_cap) { std::swap(g_scr, d_scr); std::swap(g_scr_cap, scr_cap); }
     }
     if (d_scr) hipFree(d_scr);
-    *out_d = d_new; *out_used = cap; *out_cap = real_cap;
+    out->d = d_new; out->cap = real_cap; out->binned = true;
+    out->used = packed ? ss::dev::in_bytes(true, cap) : cap;
+    if (packed) { out->packed = true; out->n_pos = cap; out->L = fix_L; out->slot = ::slot_of(fix_L); }
     return SS_OK;
 }
 
@@ -760,12 +892,11 @@ int reads_order_for_locality(ss_reads *R, bool force)
         // (the binned copy lives beside the slab until it replaces it: a slab that leaves no room for that stays in file order)
         const bool room = known && mem_free > sl.used + sl.used / 8 + (1ull << 30);
         if (sl.used >= 64 && (room || force)) {
-            char *d = nullptr;
-            uint64_t used = 0, cap = 0;
-            const int rc = order_flat_dev(sl.d, sl.used, &d, &used, &cap);
+            ss_reads::Slab nsl;
+            const int rc = order_flat_dev(sl.d, sl.used, &nsl);
             if (rc) return rc;
             ss::big_put(sl.d, sl.cap);                    // (kept for the next slab's binned copy)
-            sl.d = d; sl.used = used; sl.cap = cap; sl.binned = true;
+            sl = nsl;
         }
         bytes += sl.cap;
     }

@@ -40,7 +40,7 @@ constexpr uint64_t STAGE_BYTES = 32ull << 20;  // pinned staging chunk for host-
 // mix64 whose next bits address the table, so a lookup costs one more shift.  ~95 % of a sample's k-mers are not in the
 // table and stop at the filter (L2) instead of pulling a random sector of the table (MALL / HBM): 12.5 -> 3.x ms for
 // 4 M reads against a 2 M-row table (scripts/bench_k.py).
-template <bool ALIGNED, bool BLOOM>
+template <int IN, bool BLOOM>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(
     const uint8_t *__restrict__ bases, uint64_t n, uint64_t n_tiles,
     const uint64_t *__restrict__ keys, uint32_t *__restrict__ counts, uint32_t log2cap, int k,
@@ -59,13 +59,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(
         const uint64_t base = tile * (uint64_t)TILE;
         {
             uint32_t w[4], code, inv;
-            load16<ALIGNED>(bases, base + (uint64_t)t * 16, n, w);
-            encode16(w, code, inv);
+            load_in<IN>(bases, base + (uint64_t)t * 16, n, w);
+            decode_in<IN>(w, code, inv);
             s_code[buf][t] = code;
             s_inv[buf][t] = (uint16_t)inv;
             if (t < 2) {  // halo: the last k-mers of the tile reach k-1 bytes past it
-                load16<ALIGNED>(bases, base + TILE + (uint64_t)t * 16, n, w);
-                encode16(w, code, inv);
+                load_in<IN>(bases, base + TILE + (uint64_t)t * 16, n, w);
+                decode_in<IN>(w, code, inv);
                 s_code[buf][SCAN_THREADS + t] = code;
                 s_inv[buf][SCAN_THREADS + t] = (uint16_t)inv;
             }
@@ -405,7 +405,7 @@ int ss_scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream)
 
 }  // extern "C"
 
-int ss::scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream, bool binned, uint64_t set_id)
+int ss::scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream, bool binned, uint64_t set_id, bool packed)
 {
     if (!db || (n && !bases_dev)) return SS_EINVAL;
     if (n < (uint64_t)db->k) return SS_OK;
@@ -413,15 +413,18 @@ int ss::scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream
     const uint64_t max_blocks = (uint64_t)cu_count() * 8;
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, max_blocks);
     if (db->layout == 1) {
-        int rc = ss::launch_scan_mini(db, bases_dev, n, ss::as_stream(stream), blocks, n_tiles, binned, set_id);
+        int rc = ss::launch_scan_mini(db, bases_dev, n, ss::as_stream(stream), blocks, n_tiles, binned, set_id, packed);
         if (rc == SS_OK) db->launches++;
         return rc;
     }
-    const bool aligned = (((uintptr_t)bases_dev) & 15) == 0;
+    const int in = input_layout(bases_dev, packed);
 #define SS_FLAT(A, B) hipLaunchKernelGGL((scan_kernel<A, B>), dim3(blocks), dim3(SCAN_THREADS), 0, ss::as_stream(stream), (const uint8_t *)bases_dev, n, \
                                          n_tiles, db->d_keys, db->d_counts, db->log2cap, db->k, db->d_bloom, db->bloom_bits)
-    if (db->d_bloom) { if (aligned) SS_FLAT(true, true); else SS_FLAT(false, true); }
-    else             { if (aligned) SS_FLAT(true, false); else SS_FLAT(false, false); }
+#define SS_FLAT_I(B) do { if (in == IN_PACKED) SS_FLAT(IN_PACKED, B); else if (in == IN_ASCII_ALIGNED) SS_FLAT(IN_ASCII_ALIGNED, B); \
+                          else SS_FLAT(IN_ASCII, B); } while (0)
+    if (db->d_bloom) SS_FLAT_I(true);
+    else             SS_FLAT_I(false);
+#undef SS_FLAT_I
 #undef SS_FLAT
     SS_HIP(hipGetLastError());
     db->launches++;

@@ -166,5 +166,56 @@ __device__ __forceinline__ void load16(const uint8_t *__restrict__ bases, uint64
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Input layouts of the scan kernels (their IN template parameter):
+//   IN_ASCII          bytes, any alignment (load16<false>)
+//   IN_ASCII_ALIGNED  bytes, 16-byte aligned block (load16<true>)
+//   IN_PACKED         a packed binned slab (ss_reorder.hip): every 8 positions one 3-byte unit -- u16 of 2-bit codes (position
+//                     i at bits 2i, the codes encode16 makes) and a u8 of invalid flags.  Group g of 16 positions is the 6 bytes
+//                     at 6g: code[0..15] inv[0..7] code[16..31] inv[8..15], exactly encode16 of the ASCII binned slab's
+//                     bytes [16g, 16g + 16).  A device allocation: 4-byte aligned, 8 readable bytes behind its last group.
+// `n` counts positions in every layout; positions at or beyond n read as '\n' (code 1, invalid).
+// ---------------------------------------------------------------------------------------------
+enum { IN_ASCII = 0, IN_ASCII_ALIGNED = 1, IN_PACKED = 2 };
+
+// what load_in fetched for 16 positions: ASCII: the 16 bytes; packed: the two dwords around the group's 6 bytes and the
+// byte shift of the group in them (0 or 2, as a byte-selector offset in w[2])
+template <int IN>
+__device__ __forceinline__ void load_in(const uint8_t *__restrict__ bases, uint64_t off, uint64_t n, uint32_t w[4])
+{
+    if (IN != IN_PACKED) {
+        load16<IN == IN_ASCII_ALIGNED>(bases, off, n, w);
+    } else if (off + 16 <= n) {
+        // one 8-byte load at the 4-byte-aligned address below 6g (6g is 0 or 2 modulo 4)
+        const uint64_t g6 = (off >> 4) * 6u;
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        typedef u32x2 u32x2_a4 __attribute__((aligned(4)));
+        const u32x2 q = __builtin_nontemporal_load(reinterpret_cast<const u32x2_a4 *>(bases + (g6 & ~3ull)));
+        w[0] = q.x; w[1] = q.y; w[2] = (uint32_t)(g6 & 2u) * 0x01010101u;
+    } else {                                             // 16 positions of '\n': code 0x5555 / inv 0xFF per 8, at shift 0
+        w[0] = 0x55FF5555u; w[1] = 0x0000FF55u; w[2] = 0u;
+    }
+}
+
+// 16 positions -> 32 bits of 2-bit codes + 16 invalid flags (encode16 for ASCII; two byte permutes for the packed layout)
+template <int IN>
+__device__ __forceinline__ void decode_in(const uint32_t w[4], uint32_t &code, uint32_t &inv)
+{
+    if (IN != IN_PACKED) {
+        encode16(w, code, inv);
+    } else {
+        code = __builtin_amdgcn_perm(w[1], w[0], 0x04030100u + w[2]);                 // bytes s, s+1, s+3, s+4
+        inv = __builtin_amdgcn_perm(w[1], w[0], 0x0C0C0502u + (w[2] & 0xFFFFu));      // bytes s+2, s+5 (0x0C: zero)
+    }
+}
+
+// byte offset of position `pos` (a multiple of 16) in a block of the given layout
+__host__ __device__ __forceinline__ uint64_t in_bytes(bool packed, uint64_t pos) { return packed ? (pos >> 4) * 6u : pos; }
+// the layout a launch instantiates for a block at `p`
+inline int input_layout(const void *p, bool packed)
+{
+    return packed ? IN_PACKED : ((((uintptr_t)p) & 15) == 0 ? IN_ASCII_ALIGNED : IN_ASCII);
+}
+
 
 }}  // namespace ss::dev
