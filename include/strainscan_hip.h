@@ -293,6 +293,9 @@ int ss_scan_reads(ss_db *db, const ss_reads *r, void *stream);
  * Vote_Strain_L2_Lasso_new_sp.py:295-296, re-reads the FASTQ for each, :354-372): equal to ss_scan_reads on each table;
  * k = 31 tables share the encoding and the minimizer runs of every tile, four tables per launch. */
 int ss_scan_reads_multi(ss_db *const *dbs, int n_dbs, const ss_reads *r, void *stream);
+/* Launches of the several-tables kernel so far in this process, per filter kind of the tables it took (diagnostics):
+ * out[0] tables behind their own Bloom filters (tree tables), out[1] tables announced with ss_db_expect_hits, out[2] neither. */
+int ss_scan_multi_launches(uint64_t out[3]);
 
 /* --------------------------------------------------------------------------------------------
  * Host FASTA/FASTQ -> flat base block (what jellyfish's sequence parser feeds its counter).

@@ -78,16 +78,18 @@ def _clock(what):
     cli_clock(what)
 
 
-def main(argv=None):
-    _clock("main() entered")
-    pwd = os.getcwd()
-    ap = argparse.ArgumentParser(prog="StrainScan.py", description=usage)
+def add_arguments(ap, multi=False):
+    """The flags of StrainScan.py:113-148 (multi: -d may be given several times, as `DIR` or `LABEL=DIR`)."""
     ap.add_argument("-i", "--input_fastq", dest="input_fq", type=str, required=True,
                     help="The dir of input fastq data --- Required")
     ap.add_argument("-j", "--input_fastq_2", dest="input_fq2", type=str,
                     help="The dir of input fastq data (for pair-end data).")
-    ap.add_argument("-d", "--database_dir", dest="db_dir", type=str, required=True,
-                    help="The dir of your database --- Required")
+    if multi:
+        ap.add_argument("-d", "--database_dir", dest="db_dir", type=str, action="append", required=True,
+                        help="A database dir, or LABEL=dir; give -d once per database --- Required")
+    else:
+        ap.add_argument("-d", "--database_dir", dest="db_dir", type=str, required=True,
+                        help="The dir of your database --- Required")
     ap.add_argument("-o", "--output_dir", dest="out_dir", type=str,
                     help="Output dir (default: current dir/StrainScan_Result)")
     ap.add_argument("-k", "--kmer_size", dest="ksize", type=str,
@@ -103,34 +105,40 @@ def main(argv=None):
                     help="1: also return strains with extra regions covered (default: -e 0)")
     ap.add_argument("-s", "--minimum_snv_num", dest="msn", type=str,
                     help="The minimum number of SNV at Layer-2 identification. (default: 40)")
-    args = ap.parse_args(argv)
 
-    fq_dir = args.input_fq
-    fq2 = args.input_fq2 or ""
-    db_dir = args.db_dir
-    ksize = args.ksize if args.ksize else 31
-    ldep = int(args.ldep) if args.ldep else 0
-    sprob = int(args.sprob) if args.sprob else 0
-    pmode = int(args.pmode) if args.pmode else 0
-    emode = int(args.emode) if args.emode else 0
-    msn = int(args.msn) if args.msn else 40
+
+def settings(args):
+    """The parsed flags as StrainScan.py:150-160 reads them: dict(ksize, ldep, sprob, pmode, emode, msn)."""
+    return dict(ksize=args.ksize if args.ksize else 31, ldep=int(args.ldep) if args.ldep else 0,
+                sprob=int(args.sprob) if args.sprob else 0, pmode=int(args.pmode) if args.pmode else 0,
+                emode=int(args.emode) if args.emode else 0, msn=int(args.msn) if args.msn else 40)
+
+
+def refuse_plasmid_mode(pmode):
     if pmode in (1, 2):
         print("Warning: plasmid / reference-genome mode (-p) needs the reference's database builder "
               "(StrainScan.py:235) and is not part of this identification path.")
         raise SystemExit(2)
-    out_dir = args.out_dir if args.out_dir else pwd + "/StrainScan_Result"
+
+
+def output_dir(out_dir, pwd):
+    """-o as StrainScan.py:162-165 reads it."""
+    out_dir = out_dir if out_dir else pwd + "/StrainScan_Result"
     if not re.search("/", out_dir):
         out_dir = pwd + "/" + out_dir
-    os.makedirs(out_dir, exist_ok=True)     # (exist_ok: under torchrun every rank arrives here with the same -o at the same moment)
+    return out_dir
 
-    from . import dist
-    rank, world = dist.init_from_env()      # torchrun: one process per GPU, reads shard across ranks
-    if rank != 0:                           # every rank computes; rank 0 owns the output directory
-        import atexit
-        import shutil
-        import tempfile
-        out_dir = tempfile.mkdtemp(prefix="strainscan_rank%d_" % rank)
-        atexit.register(shutil.rmtree, out_dir, True)      # the other ranks' reports are scratch
+
+def identify_database(fq_dir, fq2, db_dir, out_dir, ksize, ldep, sprob, pmode, emode, msn):
+    """One database's work once the flags are read (StrainScan.py:186-271): -b, the cutoff ladder, layer 2.  Ends in
+    SystemExit where the reference exits (no cluster detected; one single-strain cluster)."""
+    cls_dict, l2 = identify_layer1(fq_dir, fq2, db_dir, out_dir, ldep, sprob)
+    Vote_Strain_L2_Lasso_new_sp.vote_strain_L2_batch(fq_dir, fq2, db_dir, out_dir, ksize, dict(cls_dict), l2, msn,
+                                                     pmode, emode)
+
+
+def identify_layer1(fq_dir, fq2, db_dir, out_dir, ldep, sprob):
+    """-b and the cutoff ladder (StrainScan.py:186-227) -> (cls_dict, l2); SystemExit when no cluster is detected."""
     in_fq = (fq_dir, fq2)
     tdb = db_dir + "/Tree_database"
     if sprob == 1:
@@ -144,17 +152,49 @@ def main(argv=None):
     if len(cls_dict) == 0:
         print("Warning: No clusters can be detected!")
         raise SystemExit
-    Vote_Strain_L2_Lasso_new_sp.vote_strain_L2_batch(fq_dir, fq2, db_dir, out_dir, ksize, dict(cls_dict), l2, msn,
-                                                     pmode, emode)
+    return cls_dict, l2
 
 
-def cli():
+def rank_output_dir(out_dir, rank):
+    """Every rank computes; rank 0 owns the output directory, the others write their reports to scratch."""
+    if rank == 0:
+        return out_dir
+    import atexit
+    import shutil
+    import tempfile
+    out_dir = tempfile.mkdtemp(prefix="strainscan_rank%d_" % rank)
+    atexit.register(shutil.rmtree, out_dir, True)      # the other ranks' reports are scratch
+    return out_dir
+
+
+def main(argv=None):
+    _clock("main() entered")
+    pwd = os.getcwd()
+    ap = argparse.ArgumentParser(prog="StrainScan.py", description=usage)
+    add_arguments(ap)
+    args = ap.parse_args(argv)
+
+    fq_dir = args.input_fq
+    fq2 = args.input_fq2 or ""
+    db_dir = args.db_dir
+    opts = settings(args)
+    refuse_plasmid_mode(opts["pmode"])
+    out_dir = output_dir(args.out_dir, pwd)
+    os.makedirs(out_dir, exist_ok=True)     # (exist_ok: under torchrun every rank arrives here with the same -o at the same moment)
+
+    from . import dist
+    rank, world = dist.init_from_env()      # torchrun: one process per GPU, reads shard across ranks
+    out_dir = rank_output_dir(out_dir, rank)
+    identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
+
+
+def cli(main_fn=None):
     """Entry of the `strainscan` command (pyproject.toml, bin/strainscan, python -m): main(), then the process ENDS -- pending
     cache images are written, the streams flushed, and nothing is torn down piece by piece (unpinning the parse buffers,
     freeing GBs of device memory and joining the thread pools cost a fresh process 0.1 s of its 0.65 s; the driver reclaims
-    everything at once)."""
+    everything at once).  (main_fn: another command's main, strainscan-multi's)"""
     try:
-        rc = main()
+        rc = (main_fn or main)()
     except SystemExit as e:
         rc = e.code
     _clock("reports written")

@@ -105,6 +105,7 @@ SIGNATURES = {
     "ss_db_expect_hits": (i32, [vp, i32]),
     "ss_db_probe_info": (i32, [vp, vp]),
     "ss_scan_reads_multi": (i32, [vp, i32, vp, vp]),
+    "ss_scan_multi_launches": (i32, [P(u64)]),
     "ss_scan_reset": (i32, [vp, vp]),
     "ss_scan_flat_dev": (i32, [vp, vp, u64, vp]),
     "ss_scan_flat_host": (i32, [vp, cp, u64]),
@@ -465,6 +466,13 @@ class ReadSet:
 
     def scan_into(self, kdb, stream=None):
         check(lib().ss_scan_reads(kdb.handle, self._h, stream), "ss_scan_reads")
+
+
+def scan_multi_launches():
+    """Launches of the several-tables kernel so far, per filter kind: dict(bloom=, expect_hits=, plain=)."""
+    out = (C.c_uint64 * 3)()
+    check(lib().ss_scan_multi_launches(out), "ss_scan_multi_launches")
+    return dict(bloom=out[0], expect_hits=out[1], plain=out[2])
 
 
 class NodeSet:

@@ -242,6 +242,10 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
                      uint64_t n_tiles, bool binned = false, uint64_t set_id = 0, bool packed = false);
 int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned,
                            bool packed = false);
+// the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster
+// table: the combining variant under binned reads), or none at all.  One launch takes tables of one kind (ss_scan_multi_launches).
+enum { MULTI_BLOOM = 0, MULTI_EXPECT = 1, MULTI_PLAIN = 2 };
+int multi_kind(const ss_db *db);
 // Layer 2 (ss_l2.hip, ss_enet.hip) works on the CALLING THREAD's own stream and takes its temporaries from the stream-ordered
 // pool (round 5): the clusters of a sample are solved on several host threads at once, and on the legacy default stream every
 // synchronous copy of one thread waited for the kernels of all the others, every hipFree for the whole device (four 5 M-row

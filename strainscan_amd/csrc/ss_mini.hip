@@ -330,16 +330,20 @@ __device__ unsigned long long ss_timing[32];
 // Several tables in ONE pass over the reads (layer 2: the reference re-reads the FASTQ once per identified cluster,
 // Vote_Strain_L2_Lasso_new_sp.py:295-296,354-372): bases, codes, minimizers and runs of a tile are made once, the page lookups
 // and candidate checks repeat per table.  Up to four tables per launch (the LDS counters keep the table in the two bits above
-// a bucket start's thirty).
+// a bucket start's thirty).  Tree tables of several databases (strainscan_amd/multi_db.py) go through the BLOOM instantiation:
+// phase 2a probes table tb's own filter and compacts that table's survivors into q1b, phases 2b-3 run on them as for one table.
 constexpr int MULTI_MAX = 4;
 struct ScanTabs {
     const uint64_t *mkeys[MULTI_MAX];
     const uint4 *pages[MULTI_MAX];
     uint32_t *counts[MULTI_MAX];
-    uint32_t n_pages[MULTI_MAX], cbase[MULTI_MAX];
+    const uint32_t *bloom[MULTI_MAX];               // (BLOOM only) table tb's minimizer filter and its 30 - log2(bits)
+    uint32_t n_pages[MULTI_MAX], cbase[MULTI_MAX], bloom_shift[MULTI_MAX];
     int n;
 };
 
+// (the several-tables instantiation behind per-table Bloom filters, <IN, BLOOM, !COMB, 8, MULTI, 31>: 78 SGPRs, 63-64 VGPRs, no
+//  scratch, 528 bytes of kernarg -- the same as its filterless twin; the filter pointers and shifts are read from ScanTabs per table)
 // SGPRs decide the residency of this kernel: a SIMD admits floor(800 / (ceil(sgprs / 16) * 16 + 16)) waves
 // (MI355X_MICROARCH.md, residency), i.e. 8 waves at <= 80, 7 at <= 96, 6 beyond; VGPRs (58) and LDS (4.9 KB per
 // one-wave workgroup = 32 per CU) allow 8.
@@ -374,7 +378,7 @@ __global__ __launch_bounds__(MT, WAVES_PER_SIMD) __attribute__((amdgpu_num_sgpr(
     const uint4 *__restrict__ pages0, uint32_t n_pages0, uint32_t *__restrict__ counts0, uint32_t cbase0,
     const uint32_t *__restrict__ bloom, uint32_t bloom_shift, uint32_t xcd_swizzle, const ScanTabs tabs, int k_rt)
 {
-    static_assert(!(MULTI && BLOOM), "several tables: no minimizer filter (they are tables that expect hits)");
+    static_assert(!(COMB && BLOOM), "a combining scan is for tables that expect hits: they have no use for the minimizer filter");
     static_assert(KK == 31 || KK == 0, "k = 31, or k at run time");
     // the table of this pass over the tile's runs (MULTI: tabs.* in turn)
     const uint64_t *__restrict__ mkeys = mkeys0;
@@ -702,6 +706,7 @@ __global__ __launch_bounds__(MT, WAVES_PER_SIMD) __attribute__((amdgpu_num_sgpr(
         if (MULTI) {
             mkeys = tabs.mkeys[tb]; pages = tabs.pages[tb]; counts = tabs.counts[tb];
             n_pages = tabs.n_pages[tb]; cbase = tabs.cbase[tb]; tab_key = (uint32_t)tb << 30;
+            if (BLOOM) { bloom = tabs.bloom[tb]; bloom_shift = tabs.bloom_shift[tb]; }
             if (tb) {                                   // the found-run queue of the table before has been worked off
                 if (t == 1) S.cnt[1] = 0;
                 __syncthreads();
@@ -1574,48 +1579,67 @@ static void launch_lb(int in, bool comb, unsigned blocks, hipStream_t stream, co
 #undef SS_LAUNCH
 }
 
-// one pass of a flat block against up to MULTI_MAX tables of the minimizer layout (all k = 31)
+// launches of the several-tables kernel per filter kind (MULTI_BLOOM / MULTI_EXPECT / MULTI_PLAIN), ss_scan_multi_launches
+static std::atomic<uint64_t> g_multi_launches[3];
+
+int multi_kind(const ss_db *db)
+{
+    return db->expect_hits ? MULTI_EXPECT : db->d_bloom ? MULTI_BLOOM : MULTI_PLAIN;
+}
+
+// one pass of a flat block against up to MULTI_MAX tables of the minimizer layout, all of one k and one filter kind (multi_kind;
+// the Bloom kind at k = 31 only: ss_scan_reads_multi scans the others table by table)
 int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned, bool packed)
 {
-    if (n_dbs < 1 || n_dbs > MULTI_MAX) return SS_EINVAL;
+    if (n_dbs < 1 || n_dbs > MULTI_MAX || !dbs[0]) return SS_EINVAL;
     ScanTabs tabs = {};
-    bool expect = true;
-    const int k_all = dbs[0] ? dbs[0]->k : 0;              // (one k for the tables of a pass: the tile's minimizers are made once)
+    const int k_all = dbs[0]->k, kind = multi_kind(dbs[0]);    // (one k for the tables of a pass: the tile's minimizers are made once)
+    if (kind == MULTI_BLOOM && k_all != 31) return SS_EINVAL;
     for (int i = 0; i < n_dbs; i++) {
         ss_db *db = dbs[i];
-        if (!db || db->layout != 1 || db->k != k_all) return SS_EINVAL;
+        if (!db || db->layout != 1 || db->k != k_all || multi_kind(db) != kind) return SS_EINVAL;
         tabs.mkeys[i] = db->d_mkeys;
         tabs.pages[i] = reinterpret_cast<const uint4 *>(db->d_dir);
         tabs.counts[i] = db->d_counts;
         tabs.n_pages[i] = db->n_dir;
         tabs.cbase[i] = (uint32_t)db->n_mslots;
-        expect = expect && db->expect_hits;
+        tabs.bloom[i] = db->d_bloom;
+        tabs.bloom_shift[i] = 30u - db->bloom_bits;
     }
     tabs.n = n_dbs;
     const int in = input_layout(bases_dev, packed);
     static const int comb_env = [] { const char *e = getenv("SS_COMBINE"); return e ? atoi(e) : -1; }();
     constexpr uint32_t swz = 1u;
-    const bool comb = expect && (comb_env < 0 ? binned : comb_env != 0);
+    const bool comb = kind == MULTI_EXPECT && (comb_env < 0 ? binned : comb_env != 0);
     const uint64_t n_tiles = (n + MTILE - 1) / MTILE, units = comb ? (n_tiles + COMB_CH - 1) / COMB_CH : n_tiles;
     unsigned blocks = (unsigned)std::min<uint64_t>(units, (uint64_t)2048 * 256 * (256 / MT));
     blocks = (blocks + 7u) & ~7u;
     const uint8_t *b = (const uint8_t *)bases_dev;
-#define SS_LAUNCH_M(A, C_, LB) do {                                                                                                          \
-        if (k_all == 31) hipLaunchKernelGGL((scan_mini_kernel<A, false, C_, LB, true, 31>), dim3(blocks), dim3(MT), 0, stream, b, n, n_tiles,      \
+#define SS_LAUNCH_M(A, B, C_, LB) do {                                                                                                       \
+        if (k_all == 31) hipLaunchKernelGGL((scan_mini_kernel<A, B, C_, LB, true, 31>), dim3(blocks), dim3(MT), 0, stream, b, n, n_tiles,          \
                                             tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],                        \
-                                            (const uint32_t *)nullptr, 0u, swz, tabs, 31);                                                       \
-        else hipLaunchKernelGGL((scan_mini_kernel<A, false, C_, (LB > 5 ? 5 : LB), true, 0>), dim3(blocks), dim3(MT), 0, stream, b, n, n_tiles,      \
-                                tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],                                    \
-                                (const uint32_t *)nullptr, 0u, swz, tabs, k_all);                                                                \
+                                            tabs.bloom[0], tabs.bloom_shift[0], swz, tabs, 31);                                                  \
+        else if (!B) hipLaunchKernelGGL((scan_mini_kernel<A, false, C_, (LB > 5 ? 5 : LB), true, 0>), dim3(blocks), dim3(MT), 0, stream, b, n,   \
+                                        n_tiles, tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],                   \
+                                        (const uint32_t *)nullptr, 0u, swz, tabs, k_all);                                                        \
     } while (0)
-#define SS_LAUNCH_MI(C_, LB) do { if (in == IN_PACKED) SS_LAUNCH_M(IN_PACKED, C_, LB); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH_M(IN_ASCII_ALIGNED, C_, LB); \
-                                  else SS_LAUNCH_M(IN_ASCII, C_, LB); } while (0)
-    if (comb) SS_LAUNCH_MI(true, 6);
-    else      SS_LAUNCH_MI(false, 8);
+#define SS_LAUNCH_MI(B, C_, LB) do { if (in == IN_PACKED) SS_LAUNCH_M(IN_PACKED, B, C_, LB); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH_M(IN_ASCII_ALIGNED, B, C_, LB); \
+                                     else SS_LAUNCH_M(IN_ASCII, B, C_, LB); } while (0)
+    if (comb)                     SS_LAUNCH_MI(false, true, 6);
+    else if (kind == MULTI_BLOOM) SS_LAUNCH_MI(true, false, 8);
+    else                          SS_LAUNCH_MI(false, false, 8);
 #undef SS_LAUNCH_MI
 #undef SS_LAUNCH_M
     SS_HIP(hipGetLastError());
+    g_multi_launches[kind]++;
     for (int i = 0; i < n_dbs; i++) dbs[i]->launches++;
+    return SS_OK;
+}
+
+extern "C" int ss_scan_multi_launches(uint64_t out[3])
+{
+    if (!out) return SS_EINVAL;
+    for (int i = 0; i < 3; i++) out[i] = g_multi_launches[i].load();
     return SS_OK;
 }
 

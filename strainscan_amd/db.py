@@ -578,11 +578,15 @@ class TreeImage:
     def scan(self, paths):
         """Count the table's k-mers in the given FASTA/FASTQ(.gz) files (replaces the
         `jellyfish count` + `dump -c` pair, identify.py:82-87)."""
-        key = tuple((os.path.abspath(p), os.path.getmtime(p), os.path.getsize(p)) for p in paths if p)
+        key = _scan_key(paths)
         if self._scanned == key:
             return
-        from . import dist
         scan_into(self.kdb, paths, allreduce=False)
+        self._mark_scanned(key)
+
+    def _mark_scanned(self, key):
+        """The table holds the counts of the inputs `key` (this rank's share of them under torch.distributed)."""
+        from . import dist
         self._rows_global = not dist.is_distributed()
         self._scanned = key
         self._counts = None
@@ -642,11 +646,90 @@ class TreeImage:
         return _lib.rows_reduce(self.kdb, rows)
 
 
+def _scan_key(paths):
+    return tuple((os.path.abspath(p), os.path.getmtime(p), os.path.getsize(p)) for p in paths if p)
+
+
+def scan_images(images, paths):
+    """Count the sample's reads against the tables of several TreeImages in ONE pass over the resident reads
+    (ReadSet.scan_into_many: a tile's codes and minimizers are made once, every table behind its own Bloom filter), and mark
+    each image as holding this sample's counts, so that its own scan(paths) -- the walk's, -b's -- is a no-op.  Under
+    torch.distributed every rank scans its shard; the walk then exchanges the touched nodes per image (node_stats).
+    Returns False, and scans nothing, when the reads do not fit the resident budget: every image then scans the files
+    itself when it is asked to."""
+    key = _scan_key(paths)
+    todo = [img for img in images if img._scanned != key]
+    if not todo:
+        return True
+    rs = resident_reads(paths)
+    if rs is None:
+        return False
+    for img in todo:
+        img.kdb.reset()
+    rs.scan_into_many([img.kdb for img in todo])
+    for img in todo:
+        img._mark_scanned(key)
+    return True
+
+
 _CACHE = {}
+_PINNED = {}         # key -> TreeImage held resident by pinned_images(), whatever _CACHE does meanwhile
+
+
+def _image_key(db_dir, upper_keys):
+    return (os.path.realpath(db_dir), bool(upper_keys), os.path.getmtime(os.path.join(db_dir, "kmer.fa")))
+
+
+class pinned_images:
+    """`with pinned_images([(tree_db_dir, upper_keys), ...], reads=paths) as imgs:` several database images resident together
+    (one per entry, in order): inside the scope tree_image(dir, upper_keys) returns the pinned image of that key instead of
+    replacing the one cached image, so the walk modules run unchanged against the right table.  Outside the scope
+    tree_image() is what it always was.  With `reads`, the sample is loaded on prefetch_reads' worker thread while this
+    thread loads the images (native parse / index import; under torch.distributed rank0_first orders them, one after the
+    other, the same on every rank).  An image that fails to load is None in the list and is not pinned: tree_image() of
+    that database then raises its error again, in that database's turn."""
+
+    def __init__(self, specs, reads=None):
+        self.specs = [(d, bool(u)) for d, u in specs]
+        self.reads = reads
+        self.images = []
+        self._keys = []
+
+    def __enter__(self):
+        pre = prefetch_reads(self.reads) if self.reads else None
+        try:
+            for d, u in self.specs:
+                try:
+                    img = TreeImage(d, u)
+                except Exception:           # noqa: B902 -- raised again by that database's own tree_image()
+                    img = None
+                self.images.append(img)
+                if img is not None:
+                    key = _image_key(d, u)
+                    _PINNED[key] = img
+                    self._keys.append(key)
+        except BaseException:
+            self.__exit__()
+            raise
+        finally:
+            if pre is not None:
+                pre.join()
+        return self.images
+
+    def __exit__(self, *exc):
+        for key in self._keys:
+            _PINNED.pop(key, None)
+        self._keys = []
+        self.images = []
+        wait_cache_writes()          # (an image that is still being exported must not be dropped)
+        return False
 
 
 def tree_image(db_dir, upper_keys=True):
-    key = (os.path.realpath(db_dir), bool(upper_keys), os.path.getmtime(os.path.join(db_dir, "kmer.fa")))
+    key = _image_key(db_dir, upper_keys)
+    img = _PINNED.get(key)
+    if img is not None:
+        return img
     img = _CACHE.get(key)
     if img is None:
         img = TreeImage(db_dir, upper_keys)
