@@ -20,14 +20,18 @@ ss_reorder.hip; `prepare` reports that once-per-sample cost and the rates includ
 flat block in file order (--no-readset makes that the headline).  Weak scaling: every rank scans its
 own 20 M-read shard (reads shard, the table is replicated).  `python bench.py --gpus N` starts the
 N ranks itself; under torchrun it checks WORLD_SIZE == N; at N > 1 `check.parity_across_ranks`
-compares the exchanged node statistics of a sample of every rank's reads with the oracle.
+compares the exchanged node statistics of a sample of every rank's reads with the oracle (--full).
 
-Extra objects on the JSON line:
-  roofline     -- the scan kernel against the HBM roof: algorithmic bytes per launch
-                  (150 B bases + 120 probes x 8 B per read) / its average duration
-                  from HIP events on the launch stream.
-  cpu_baseline -- the oracle's flat-stream counter (oracle/ss_oracle.c, OpenMP) on a bounded
-                  sample of the same reads against the same table, on this box's host cores.
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line.  Beside the headline fields it carries what the timed steps
+themselves yield: step_breakdown_ms, phases (the same figures at N > 1), check.total_hits and
+roofline -- the scan kernel against the HBM roof: algorithmic bytes per launch (150 B bases +
+120 probes x 8 B per read) / its average duration from HIP events on the launch stream.
+--full adds every other measurement and check after the timed steps (the --no-* options leave
+single ones out): prepare, resident_binned, file_order, check.harvest_equals_gather,
+check.parity_across_ranks, phases with the FASTQ ingest and tree walk, cluster_scan, l2_solve,
+cli_e2e, and cpu_baseline -- the oracle's flat-stream counter (oracle/ss_oracle.c, OpenMP) on a
+bounded sample of the same reads against the same table, on this box's host cores.
 """
 import argparse
 import json
@@ -682,6 +686,10 @@ def parse_args(argv=None):
                     help="node k-mer sets: a random 1-10 %% sample of a longer stretch, rows scattered over kmer.fa "
                          "(what Build_tree.py:590-591 writes for a node above its cap), every k-mer of a stretch, or half "
                          "of the nodes each way (mixed)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (prepare, resident_binned, file_order, the "
+                         "harvest-vs-gather check, parity_across_ranks, cpu_baseline, phases, cluster_scan / l2_solve, cli_e2e); "
+                         "the --no-* options below leave single blocks of a --full run out")
     ap.add_argument("--cpu-sample-reads", type=int, default=0, help="0 = sized for ~15 s of CPU work")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-phases", action="store_true", help="skip the untimed phase breakdown (text -> HBM, walk)")
@@ -863,6 +871,8 @@ def main(argv=None):
 
     rs_loc, prep, prep_parts = None, [], []
     if binned:
+        # (run with --full or without: these loads leave the kept device blocks -- ss_dev_big_blocks -- as every headline step
+        #  finds them, the first one after --warmup 0 included; `prepare` reports their times with --full)
         rs_all = []
         for _ in range(5):                          # first call: first touch of 3 GB of fresh device memory
             # (the five sets stay alive until all are made: freeing a 3 GB slab right before the next one is allocated --
@@ -984,6 +994,11 @@ def main(argv=None):
         dt, (kern_ms, harvest_ms, exch_ms, reduce_ms) = run_timed(scan_sample, stats, bin_sample, drop_sample)
         if args.dump_outputs:
             dump_counts = last_step_counts()
+    else:
+        dt, (kern_ms, harvest_ms, exch_ms, reduce_ms) = run_timed(scan_file, stats)
+        if args.dump_outputs:
+            dump_counts = last_step_counts()
+    if binned and args.full:
         stats_b = torch.zeros_like(stats)
         dt_b, (k_b, h_b, x_b, r_b) = run_timed(scan_binned, stats_b)
         torch.cuda.synchronize()
@@ -993,10 +1008,6 @@ def main(argv=None):
                                unit="M reads/s", node_stats_equal=bool(torch.equal(stats, stats_b)),
                                step_breakdown_ms=dict(scan_kernel=round(k_b, 3), harvest=round(h_b, 3),
                                                       exchange=round(x_b, 3) if exchange else None, node_reduce=round(r_b, 3)))
-    else:
-        dt, (kern_ms, harvest_ms, exch_ms, reduce_ms) = run_timed(scan_file, stats)
-        if args.dump_outputs:
-            dump_counts = last_step_counts()
     ms_per_step = dt / args.steps * 1e3
     reads_per_s = args.reads * world * args.steps / dt
     tail_ms = exch_ms + reduce_ms
@@ -1004,16 +1015,18 @@ def main(argv=None):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, st_np, dump_counts)
     # the counters of the last step are still in the table (a step resets them at its start): whole-table checksum,
-    # and the harvest path against the row-gather path it replaces (ss_counts_rows_dev + ss_nodes_reduce_dev)
+    # and (--full) the harvest path against the row-gather path it replaces (ss_counts_rows_dev + ss_nodes_reduce_dev)
     counts_rows = torch.zeros(n_rows, dtype=torch.int32, device=dev)
     db.counts_rows_dev(counts_rows.data_ptr(), stream)
     hits = int(counts_rows.to(torch.int64).sum().item())
-    stats2 = torch.zeros_like(stats)
-    if exchange:
-        ssdist.allreduce_counts(counts_rows)
-    nodes.reduce_dev(counts_rows.data_ptr(), db.row_valid_dev, stats2.data_ptr(), stream)
-    torch.cuda.synchronize()
-    harvest_equals_gather = bool(torch.equal(stats, stats2))
+    harvest_equals_gather = None
+    if args.full:
+        stats2 = torch.zeros_like(stats)
+        if exchange:
+            ssdist.allreduce_counts(counts_rows)
+        nodes.reduce_dev(counts_rows.data_ptr(), db.row_valid_dev, stats2.data_ptr(), stream)
+        torch.cuda.synchronize()
+        harvest_equals_gather = bool(torch.equal(stats, stats2))
 
     def pmc_entry(key):
         """Counter-derived figures come from separate rocprofv3 --pmc passes of THIS command (scripts/gpu_round.sh writes
@@ -1065,7 +1078,7 @@ def main(argv=None):
         rf["model_saturated"] = bool(frac > 0.9 and (hbm_meas is None or hbm_meas < 0.6 * frac))
         if rf["model_saturated"]:
             rf["model_note"] = ("8(d)'s 1110 B per read is saturated by the minimizer index on this shape: the work is done (counts checked "
-                                "in this run) with far fewer bytes; what bounds the kernel is VALU issue (valu_busy), measured HBM use is "
+                                "by --full runs) with far fewer bytes; what bounds the kernel is VALU issue (valu_busy), measured HBM use is "
                                 "hbm_frac_measured")
         return rf
 
@@ -1075,7 +1088,7 @@ def main(argv=None):
     roofline["read_order"] = "binned (the product's resident read set)" if binned else "file"
 
     prepare, file_order = None, None
-    if binned:
+    if binned and args.full:
         prep_ms = float(np.median(prep))
         parts_med = np.median(np.array(prep_parts), axis=0)
         step_s = dt_b / args.steps                   # a step over the binned resident set; + prepare / n for a sample of n scans
@@ -1106,7 +1119,7 @@ def main(argv=None):
                        policy="always (SS_READS_ORDER=file keeps the file order): binning pays from the SECOND scan of a sample on; a "
                               "sample scanned once loses prepare.ms - (file_order.ms_per_step - ms_per_step), beside a text ingest of "
                               "~80 ms for the same reads")
-    if binned and not args.no_file_order:
+    if binned and args.full and not args.no_file_order:
         stats_f = torch.zeros_like(stats)
         dt_f, (k_f, h_f, x_f, r_f) = run_timed(scan_file, stats_f)
         torch.cuda.synchronize()
@@ -1117,7 +1130,7 @@ def main(argv=None):
                           step_breakdown_ms=dict(scan_kernel=round(k_f, 3), harvest=round(h_f, 3),
                                                  exchange=round(x_f, 3) if exchange else None, node_reduce=round(r_f, 3)))
     parity_ranks = None
-    if world > 1 or self_group:                  # (a one-rank group, SS_BENCH_FORCE_EXCHANGE: the same collectives over RCCL)
+    if args.full and (world > 1 or self_group):  # (a one-rank group, SS_BENCH_FORCE_EXCHANGE: the same collectives over RCCL)
         parity_ranks = parity_across_ranks(torch, dist, dev, args, db, nodes, db_spec, reads, stream, rank, world, ssdist)
     if rs_loc is not None:
         rs_loc.close()
@@ -1135,7 +1148,7 @@ def main(argv=None):
         host["parse_threads_per_rank"] = [int(x) for x in got]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N = 1 only
         from oracle import oracle as orc
         # the CPUs this process may really use (a container's cgroup quota can be far below the hardware threads:
         # 16 CPUs on the 256-thread GPU box; more busy threads than that only get the group throttled)
@@ -1179,7 +1192,7 @@ def main(argv=None):
         cpu["parity_on_sample"] = bool(np.array_equal(chk, got))
 
     phases = None
-    if rank == 0 and world == 1 and not args.no_phases and not args.calib_stream:
+    if args.full and rank == 0 and world == 1 and not args.no_phases and not args.calib_stream:
         phases = measure_phases(torch, dev, args, db, nodes, db_spec, reads, st_np, kern_ms, harvest_ms, reduce_ms, stream)
     elif rank == 0:
         phases = dict(kernel_ms=round(kern_ms, 3), gather_ms=round(harvest_ms, 3), allreduce_ms=round(exch_ms, 3),
@@ -1189,12 +1202,12 @@ def main(argv=None):
                                      "no host synchronisation inside (dist.exchange_touched)",
                       index=index_how)
     config3 = None
-    if rank == 0 and world == 1 and not args.no_config3 and not args.calib_stream:
+    if args.full and rank == 0 and world == 1 and not args.no_config3 and not args.calib_stream:
         del reads
         torch.cuda.empty_cache()
         config3 = measure_config3(torch, dev, args, stream)
     cli_e2e = None
-    if rank == 0 and world == 1 and not args.no_cli_e2e and not args.calib_stream:
+    if args.full and rank == 0 and world == 1 and not args.no_cli_e2e and not args.calib_stream:
         # what a user runs, reduced to a few seconds: fresh `strainscan` processes on a 63-cluster tree with three multi-strain
         # clusters (layer 2 on the path), 2 M reads from text; the full configs[3] shape: scripts/bench_cli_l2.py, profiles/r05_cli_l2_*
         torch.cuda.empty_cache()
@@ -1215,7 +1228,7 @@ def main(argv=None):
         out = dict(metric="M reads/sec vs 1433-strain E. coli DB", value=round(reads_per_s / 1e6, 3),
                    unit="M reads/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
                    ms_per_step=round(ms_per_step, 3), higher_is_better=True, scaling="weak", vs_baseline=None,
-                   dtype="u64", data="synthetic",
+                   dtype="u64", data="synthetic", full=bool(args.full),
                    config=dict(workload=("E. coli 1433-strain/823-cluster DB, 10M synthetic 150 bp PE reads (20M reads), 1xMI355X "
                                          "[BASELINE configs[1]]" if world == 1 and args.reads == 20_000_000 else
                                          "E. coli 1433-strain DB, %dM reads sharded %dxMI355X (%dM per GPU), RCCL all-reduce of per-node "

@@ -3,8 +3,8 @@
 # (20 M reads text, 50 M text, 50 M .gz).  -> gpurun_out/r6_final/
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r6_final; mkdir -p $O; cd $R
-timeout 600 python bench.py > $O/sampled_bench.json 2> $O/sampled_bench.err
-timeout 600 python bench.py --db-shape contiguous > $O/contiguous_bench.json 2> $O/contiguous_bench.err
+timeout 600 python bench.py --full > $O/sampled_bench.json 2> $O/sampled_bench.err
+timeout 600 python bench.py --full --db-shape contiguous > $O/contiguous_bench.json 2> $O/contiguous_bench.err
 timeout 900 python scripts/bench_cli_l2.py 20000000 > $O/cli_l2_text.json 2> $O/cli_l2_text.err
 if [ "${1:-all}" = "all" ]; then
   timeout 1200 python scripts/bench_cli_l2.py 50000000 > $O/cli_l2_text50.json 2> $O/cli_l2_text50.err

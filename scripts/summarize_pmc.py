@@ -29,7 +29,7 @@ for d in sorted(glob.glob(os.path.join(O, "pmc_*"))):
             out.setdefault(tag, {}).setdefault(kn, {})[cn] = v / n
 print("\n".join(lines))
 with open(os.path.join(O, "pmc_summary.txt"), "w") as f:
-    f.write("# rocprofv3 --pmc <counters> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline [--calib-stream]\n")
+    f.write("# rocprofv3 --pmc <counters> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline [--calib-stream]\n")
     f.write("# one pass per counter group; FETCH_SIZE / WRITE_SIZE in KiB\n")
     f.write("\n".join(lines) + "\n")
 with open(os.path.join(O, "pmc_summary.json"), "w") as f:

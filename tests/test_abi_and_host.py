@@ -525,6 +525,16 @@ def test_bench_steps_and_dump_arguments():
         assert r.returncode == 2 and b"--" + bad[0][2:].encode() in r.stderr, r.stderr
 
 
+def test_bench_full_argument():
+    """--full (off by default) adds every measurement and check beside the headline; the --no-* options still parse and
+    select blocks of such a run."""
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.no_cpu_baseline is False
+    a = bench.parse_args(["--full", "--no-config3", "--steps", "3", "--warmup", "2"])
+    assert a.full is True and a.no_config3 is True and a.steps == 3 and a.warmup == 2
+
+
 def test_bench_gpus_argument_handling():
     """`python bench.py --gpus 2` without a launcher spawns two fresh rank processes (RANK / WORLD_SIZE /
     MASTER_ADDR=127.0.0.1 set) before anything touches torch, and relays rank 0's line; under a launcher

@@ -914,14 +914,14 @@ def test_full_size_config1(L, shape):
 
 
 def test_bench_line_contract_and_exchange_path():
-    """bench.py on a small configuration: the JSON line carries the contract's fields (roofline, cpu_baseline with
+    """bench.py --full on a small configuration: the JSON line carries the contract's fields (roofline, cpu_baseline with
     parity_on_sample, phases, e2e_reads_per_s); and the N > 1 code path -- RCCL exchange of the touched nodes between
     harvest and node reductions -- run in a one-rank process group (SS_BENCH_FORCE_EXCHANGE=1), its node statistics
     equal to the row-gather path's."""
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(repo, "bench.py"), "--reads", "300000", "--leaves", "23", "--steps", "2", "--warmup", "1",
+    base = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--reads", "300000", "--leaves", "23", "--steps", "2", "--warmup", "1",
             "--phase-reads", "100000", "--cluster-genome", "200000", "--l2-rows", "300000", "--l2-strains", "40", "--l2-check-rows", "100000"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     for shape in ("sampled", "contiguous"):
@@ -1036,6 +1036,39 @@ def test_bench_dump_outputs_fixed_inputs(tmp_path):
         assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """bench.py without --full sets up, warms up, times the steps, dumps and prints the line: the headline fields and what
+    the timed steps yield (roofline, step breakdown, total hits), every other block null.  The same command with --full
+    adds those blocks after the timed steps and computes the same outputs."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(repo, "bench.py"), "--reads", "300000", "--leaves", "23", "--steps", "2", "--warmup", "1"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for extra in ([], ["--full", "--no-cpu-baseline", "--no-phases", "--no-config3", "--no-cli-e2e"]):
+        out = tmp_path / ("full" if extra else "plain")
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out)], env=env, capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        d = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        assert d["full"] is bool(extra) and d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["metric"] and d["unit"] == "M reads/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+        assert abs(d["value"] - 300000 / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+        assert d["roofline"]["kernel_ms"] > 0 and d["step_breakdown_ms"]["binning"] > 0 and d["check"]["total_hits"] > 0
+        lines.append(d)
+        dumps.append({f: np.load(out / f) for f in sorted(os.listdir(out))})
+    plain, full = lines
+    for key in ("cpu_baseline", "prepare", "resident_binned", "file_order", "cluster_scan", "l2_solve", "cli_e2e", "e2e_reads_per_s"):
+        assert plain[key] is None, key
+    assert plain["check"]["harvest_equals_gather"] is None and plain["check"]["parity_across_ranks"] is None
+    assert full["prepare"]["ms"] > 0 and full["resident_binned"]["node_stats_equal"] is True
+    assert full["file_order"]["node_stats_equal"] is True and full["check"]["harvest_equals_gather"] is True
+    assert plain["check"] == dict(full["check"], harvest_equals_gather=None)
+    assert sorted(dumps[0]) == sorted(dumps[1]) and len(dumps[0]) == 7
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_bench_five_ranks_rehearsal_on_one_gpu():
     """BASELINE.json configs[2]'s launch shape -- `bench.py --gpus N` -- rehearsed on ONE GPU (SS_BENCH_SHARE_GPU=1: the five
     rank processes share device 0 and the group runs over gloo; RCCL refuses two ranks on a device): five per-rank batches,
@@ -1046,7 +1079,7 @@ def test_bench_five_ranks_rehearsal_on_one_gpu():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "5", "--reads", "300000", "--leaves", "23", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "5", "--reads", "300000", "--leaves", "23", "--steps", "2", "--warmup", "1",
            "--phase-reads", "100000", "--no-cli-e2e", "--cluster-genome", "200000", "--l2-rows", "300000", "--l2-strains", "40",
            "--l2-check-rows", "100000"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
