@@ -139,7 +139,10 @@ int ss_gz_range_counters(uint64_t *files, uint64_t *pieces);
  * kernel, 2: tables of every k through it, 3: tables of every k through the run-queue kernel (k at run time), 0: the product's choice
  * -- so that a test can hold the kernels to each other on one index; 5: the layout of binned slabs of records of one length --
  * value 1: they stay ASCII, 0: the product's choice (2-bit codes + invalid flags, 3 bytes per 8 positions, where every record
- * byte is A C G T or N; see ss_reads_packed_slabs) -- so that a test can hold the two layouts to each other on one read set. */
+ * byte is A C G T or N; see ss_reads_packed_slabs) -- so that a test can hold the two layouts to each other on one read set;
+ * 6: how binned slabs of records of one length are made -- value 1: the count pass + atomic placement (records in a bin in
+ * no fixed order), 0: the product's choice (keys, a stable radix sort, a gather: records in a bin in file order) -- so that a
+ * test or an A/B run can hold the two to each other in one process. */
 int ss_test_hook(int which, long long value);
 
 /* The test sets of ShuffleSplit(n_splits, test_size, random_state=seed).split(range(n)) as scikit-learn 0.23
@@ -265,11 +268,13 @@ int ss_ingest_threads(int *n);
 /* A resident read set from a flat base block that is already on the device (copied; order != 0: its records are put
  * in locality order, see below). */
 int ss_reads_from_flat_dev(const void *flat_dev, uint64_t n, int order, ss_reads **out);
-/* Where the last binning of a read set spent its time, in ms: out[0] count pass + prefix over the bins, out[1] the driver's
- * allocation of the new slab (0.3 ms, or 60-90 ms for 3 GB on a box whose driver clears the memory first), out[2] place pass. */
+/* Where the last binning of a read set spent its time, in ms.  Records of one length (the sorted path): out[0] key pass + radix
+ * sort (device time), out[1] the driver's allocation of the new slab (0.3 ms, or 60-90 ms for 3 GB on a box whose driver clears
+ * the memory first), out[2] gather + tail (and the ASCII gather again where a byte is not A C G T N).  The general passes and
+ * ss_test_hook 6: out[0] count pass + prefix over the bins, out[1] the allocation, out[2] place pass. */
 int ss_reads_order_timing(double out_ms[3]);
 /* Slabs this process has binned so far: out[0] through the passes for records of ONE length (every record of the slab as long
- * as its first: a sequencer's 150-base reads; the count pass checks every record and a single exception sends the slab through
+ * as its first: a sequencer's 150-base reads; the key and gather passes check every record and a single exception sends the slab through
  * the general passes), out[1] through the general passes (ragged records).  SS_ORDER_FIXED=0 switches the former off. */
 int ss_reads_order_counters(uint64_t out[2]);
 /* The resident flat blocks copied back to the host, slab after slab (host = NULL: only *len); for tests and debugging. */

@@ -182,9 +182,10 @@ int reads_order_for_locality(ss_reads *R, bool force = false);
 // src[0, n) -> *out: a new binned slab (d, cap, used, binned, packed, n_pos, L); packed where its records may be (ss_test_hook 5)
 int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out);
 extern std::atomic<long long> g_hook_ascii_slabs;      // ss_test_hook 5 (ss_reorder.hip): 1 = binned slabs stay ASCII
+extern std::atomic<long long> g_hook_atomic_binning;   // ss_test_hook 6 (ss_reorder.hip): 1 = one-length slabs take the count + atomic placement
 void reorder_release();
 void reorder_counters(uint64_t out[2]);      // slabs binned by the one-length passes / by the general ones, in this process
-void reorder_timing(double out[3]);      // the last binning call: count + prefix, slab allocation, place (ms)      // the binning scratch kept between calls goes back to the device (ss_gz_gpu_release)
+void reorder_timing(double out[3]);      // the last binning call (ms): key + sort, slab allocation, gather + tail (the sorted one-length path); else count + prefix, slab allocation, place      // the binning scratch kept between calls goes back to the device (ss_gz_gpu_release)
 int build_mini(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64_t n_rows, int upper_keys);
 // the same index built on the device (ss_build_dev.hip); anything but SS_OK / SS_EKEY: nothing was built, use the host build
 int build_mini_dev(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64_t n_rows, int upper_keys);

@@ -2763,6 +2763,7 @@ extern "C" int ss_test_hook(int which, long long value)
     case 3: ss::g_hook_skip_chain = value; return SS_OK;
     case 4: ss::g_hook_generic_k = value; return SS_OK;
     case 5: ss::g_hook_ascii_slabs = value; return SS_OK;
+    case 6: ss::g_hook_atomic_binning = value; return SS_OK;
     default: return SS_EINVAL;
     }
 }

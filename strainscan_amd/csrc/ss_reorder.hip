@@ -12,8 +12,9 @@
 //
 // "About the same time" is all that is needed: the chip has ~8 K scan waves = ~50 K reads in flight, so a total order
 // buys nothing over BINS of a few thousand reads.  Round 2 sorted (hipcub radix sort of 20 M (key, record) pairs, five
-// passes over per-record arrays, a gather copy at 1.3 TB/s: 9.7 ms per 20 M reads); now the records are binned in two
-// streaming passes over the slab, with no per-record array at all:
+// passes over per-record arrays, a gather copy of ragged records at 1.3 TB/s: 9.7 ms per 20 M reads); ragged records are now
+// binned in two streaming passes over the slab, with no per-record array at all (records of one length: sorted again, with a
+// gather that knows where every record is -- "records of ONE length" below):
 //   bin  = top 12 to 22 bits (order_bits) of h = mix30(minimizer of the record's first 31 bases) -- the hash that addresses the
 //          index pages (ss_mini.hip), so a bin's FIRST lookups also walk the page table in ascending order;
 //          records without a first k-mer (shorter, or a non-ACGT base in it) go to one extra bin at the end
@@ -27,21 +28,27 @@
 //           numbered across the wave (prefix sum of the piece counts), every lane finds the record of its piece by
 //           binary search in LDS, loads 16 unaligned bytes, pads behind the record's end with '\n' and stores them
 //           aligned -- ~70 pieces for the ~7 records of a wave's 1 KB, two rounds of full-width loads and stores.
-// Order inside a bin is whatever the atomics decide (not reproducible run to run; the multiset of records is, and so
-// is every count).  ON by default for resident read sets (SS_READS_ORDER=file keeps the file order): it costs ~2-3 ms per
+// Order inside a bin: the general passes leave it to the atomics (not reproducible run to run; the multiset of records is,
+// and so is every count); records of ONE length -- what a sequencer writes, and the usual slab -- are SORTED by their bin
+// instead (key pass, stable radix sort, gather: below), so a bin keeps its records in file order and a slab is the same byte
+// for byte every time.  ON by default for resident read sets (SS_READS_ORDER=file keeps the file order): it costs ~2-3 ms per
 // 20 M reads against ~80 ms of parsing and PCIe for the same reads, and every scan of the set is then 0-35 % faster
 // depending on the coverage of the sample (profiles/r03_locality_sweep.json).
 //
-// PACKED slabs.  A slab of one-length records whose every byte is A C G T or N (the count pass checks the alphabet beside the
+// PACKED slabs.  A slab of one-length records whose every byte is A C G T or N (the gather checks the alphabet beside the
 // layout) is placed as 2-bit codes + invalid flags, 3 bytes per 8 positions (ss_scan_dev.h IN_PACKED): 57 bytes per 150-base
 // read instead of 152.  Positions, slots, bins and tiles are those of the ASCII slab; packed group g is exactly encode16 of its
 // bytes [16g, 16g + 16), so every scan kernel sees bit-identical codes and flags, without its encode phase.  The placement is
 // meant to gain from the random sectors its scattered writes touch (~3.3 per record ASCII, ~1.9 packed); it gains less: place
-// 2.06 -> 1.93 ms per 20 M reads (profiles/r07_packed_ab.md: it also encodes, at 6 waves per SIMD, with byte stores at the edges).  Any other byte (lower case, IUPAC, '\r'), ragged records, or ss_test_hook 5 = 1: ASCII.
+// 2.06 -> 1.93 ms per 20 M reads (profiles/r07_packed_ab.md: it also encodes, at 6 waves per SIMD, with byte stores at the edges);
+// the sorted path writes the packed slab in order instead (profiles/r08_binning_gather_ab.md).  Any other byte (lower case, IUPAC,
+// '\r'): the gather runs again with ASCII output, in the same order; ragged records, or ss_test_hook 5 = 1: ASCII.
 #include "ss_common.h"
 
 #include <mutex>
 #include "ss_scan_dev.h"
+
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -86,6 +93,18 @@ __device__ __forceinline__ uint4 load16_nl(const char *__restrict__ b, uint64_t 
         w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8 * (k & 3)))) | (ch << (8 * (k & 3)));
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// 16 bytes at b + i, i < n, 16 <= n; bytes at or beyond n read as 0 (no per-byte path: a funnel shift of the last 16 bytes)
+__device__ __forceinline__ uint4 load16_clamped(const char *__restrict__ b, uint64_t i, uint64_t n)
+{
+    uint4 v;
+    if (i + 16 <= n) { __builtin_memcpy(&v, b + i, 16); return v; }
+    unsigned __int128 x;
+    __builtin_memcpy(&x, b + n - 16, 16);
+    x >>= 8u * (uint32_t)(i + 16 - n);
+    __builtin_memcpy(&v, &x, 16);
+    return v;
 }
 
 // bin of a record: top `bits` bits of mix30(minimizer of its first 31 bases) (ordering key of the index, leftmost on
@@ -465,6 +484,7 @@ __global__ __launch_bounds__(256) void place_again_kernel(const char *__restrict
 //   place_fixed   the returning atomicAdd on the bin's cursor is issued first; while it is on its way the lanes load the
 //                 span's pieces (numbered across the wave: consecutive lanes, consecutive 16 bytes); the destination of
 //                 a piece's record comes from the owning lane by a wave shuffle; aligned stores, padded with '\n'
+// These two (and place_fixed_packed) are what ss_test_hook 6 = 1 runs; the product sorts instead (key_fixed, gather_fixed below).
 constexpr uint32_t FIX_MIN_L = 32, FIX_MAX_L = 1023;
 
 // non-zero unless every byte of w is 'A' 'C' 'G' 'T' 'N' or '\n' -- upper case only: a packed slab reads back as exactly these
@@ -637,6 +657,132 @@ __global__ __launch_bounds__(256, 6) void place_fixed_packed_kernel(const char *
     }
 }
 
+// ---- records of one length, SORTED: keys, a stable radix sort, a gather in output order -----------------------------------------
+// The two passes above pay for random-address atomics (one per record on the bin counters, one returning one on the cursors) and
+// for scattered partial writes.  With every slot of one size, the output position of a record is its RANK in bin order, times the
+// slot: so the records' keys are sorted instead, and the copy reads at random and writes in order.
+//   key_fixed     one lane per record, no atomics: key[i] = its bin (record_bin, from its first 32 bytes), val[i] = i.  A cheap
+//                 check beside it: the byte in front of every record start, and the last record's newline and the padding behind
+//                 it, must be '\n' (what a shorter, longer or empty record shifts); else not_fixed, and the gather does nothing
+//   (sort)        hipcub::DeviceRadixSort::SortPairs over the key bits [0, bits + 1): stable, so a bin keeps its records in file
+//                 order and a binned slab is the same byte for byte from run to run
+//   gather_fixed  a wave owns 64 consecutive OUTPUT records; output record j is source record perm[j] at byte j R of the new slab
+//                 (R = slot / 8 x 3 packed: 57 bytes for 150 bases; R = slot ASCII).  The pieces of the wave's records (16 bytes of
+//                 a source record each, numbered across the wave) are loaded, CHECKED (a newline at offset L and none before it;
+//                 packed: A C G T N only), padded with '\n', encoded and put into LDS in output layout; then the wave's span goes
+//                 out as aligned 16-byte stores (rounds of G records, G R a multiple of 16: every round's span starts aligned).
+__global__ __launch_bounds__(256) void key_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L, int bits,
+                                                        uint32_t *__restrict__ key, uint32_t *__restrict__ val,
+                                                        unsigned long long *__restrict__ not_fixed)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_rec) return;
+    const uint64_t s = i * (L + 1u);
+    bool bad = i > 0 && b[s - 1] != '\n';
+    if (i + 1 == n_rec)
+        for (uint64_t k = s + L; k < n; k++) bad |= b[k] != '\n';         // (fewer than 64 + 1 bytes: the host chose L so)
+    key[i] = record_bin(b, s, L, bits);                                     // (s + 32 <= s + L + 1 <= n)
+    val[i] = (uint32_t)i;
+    const uint64_t m = __ballot(bad);                                       // (a flag already set is not set again: atomics on ONE
+    if (m && (uint32_t)(threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m) &&       // address from every wave queue up for ms)
+        !*(volatile unsigned long long *)not_fixed) atomicOr(not_fixed, 1ull);
+}
+
+constexpr uint32_t GX_LDS_PK = 6144, GX_LDS_ASCII = 8192;    // LDS a wave may take: 16 records of the longest slot (1024 positions)
+constexpr int GPK = 3;                      // pieces a lane has in flight (70 VGPRs: seven waves per SIMD, no scratch; more pieces spill)
+
+// records per round of the gather: G <= 64, G R a multiple of 16 and within the wave's LDS (the launch takes 4 G R bytes)
+inline uint32_t gather_rows(bool pk, uint32_t L)
+{
+    const uint32_t slot = slot_of(L), R = pk ? slot / 8u * 3u : slot, lim = pk ? GX_LDS_PK : GX_LDS_ASCII;
+    uint32_t G = 64;
+    while (G > 1 && (G * R > lim || (G * R) % 16u)) G--;
+    return G;
+}
+
+template <bool PK>
+__global__ __launch_bounds__(256, 7) void gather_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L,
+                                                              uint32_t P, uint32_t magic_p, uint32_t G, const uint32_t *__restrict__ perm,
+                                                              uint8_t *__restrict__ dst, unsigned long long *__restrict__ not_fixed,
+                                                              unsigned long long *__restrict__ not_packable)
+{
+    extern __shared__ uint4 gx_lds[];       // 4 waves x G R bytes
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave) * 64u;
+    // nothing to do once the slab is known not to be of one length, or (packed) not packable: the general passes, or the ASCII
+    // gather -- which checks the layout again -- come next
+    if (r0 >= n_rec || *(volatile unsigned long long *)not_fixed || (PK && *(volatile unsigned long long *)not_packable)) return;
+    const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), slot = slot_of(L), R = PK ? slot / 8u * 3u : slot;
+    uint4 *W = gx_lds + (size_t)wave * (G * R / 16u);
+    uint8_t *W8 = reinterpret_cast<uint8_t *>(W);
+    const uint32_t mine = (uint32_t)lane < nr ? perm[r0 + lane] : 0u;      // source of the wave's output record `lane`
+    bool bad = false;
+    uint32_t alpha = 0;
+    for (uint32_t c0 = 0; c0 < nr; c0 += G) {
+        const uint32_t nc = min(G, nr - c0), total = nc * P;
+        for (uint32_t p0 = 0; p0 < total; p0 += 64u * GPK) {                // (uniform trip count: every lane takes part in the shuffles)
+            uint4 v[GPK];
+#pragma unroll
+            for (int r = 0; r < GPK; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
+                const uint32_t s = (uint32_t)__shfl((int)mine, (int)(c0 + rec), 64);
+                v[r] = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
+                if (p < total && L >= off) v[r] = load16_clamped(b, (uint64_t)s * L1 + off, n);  // (the piece of byte L is loaded too;
+                                                                    // bytes behind byte L < n are neither checked nor kept)
+            }
+#pragma unroll
+            for (int r = 0; r < GPK; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
+                if (p >= total) continue;
+                uint32_t w[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+                if (L >= off) {                                             // a newline at byte L, none before it
+                    const uint32_t m = nl_mask16(v[r]), e = L - off;
+                    const uint32_t want = e < 16u ? 1u << e : 0u, valid = e < 16u ? (2u << e) - 1u : 0xFFFFu;
+                    bad |= ((m ^ want) & valid) != 0u;
+                }
+                const int keep = (int)min(16u, L > off ? L - off : 0u);      // record bytes in this piece, '\n' behind them
+                if (keep < 16) {
+#pragma unroll
+                    for (int d = 0; d < 4; d++) {
+                        const int k = keep - 4 * d;
+                        if (k <= 0) w[d] = 0x0A0A0A0Au;
+                        else if (k < 4) { const uint32_t mk = (1u << (8 * k)) - 1u; w[d] = (w[d] & mk) | (0x0A0A0A0Au & ~mk); }
+                    }
+                }
+                if (PK) {
+                    alpha |= not_packable4(w[0]) | not_packable4(w[1]) | not_packable4(w[2]) | not_packable4(w[3]);
+                    uint32_t code, inv;
+                    ss::dev::encode16(w, code, inv);
+                    // the group's 6 bytes: code[0..15] inv[0..7] code[16..31] inv[8..15]; the last piece of a slot of 8 x odd
+                    // positions has only its first 3 (the next record's bytes follow)
+                    uint8_t *q = W8 + rec * R + (off >> 4) * 6u;
+                    q[0] = (uint8_t)code; q[1] = (uint8_t)(code >> 8); q[2] = (uint8_t)inv;
+                    if (off + 16u <= slot) { q[3] = (uint8_t)(code >> 16); q[4] = (uint8_t)(code >> 24); q[5] = (uint8_t)(inv >> 8); }
+                } else {
+                    uint64_t *q = reinterpret_cast<uint64_t *>(W8 + rec * R + off);      // (8-byte aligned: slots are multiples of 8)
+                    q[0] = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+                    if (off + 16u <= slot) q[1] = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // the round's span: nc R bytes at (r0 + c0) R -- 16-byte aligned, whole 16-byte stores but at the slab's very end
+        const uint32_t span = nc * R;
+        uint8_t *out = dst + (r0 + c0) * R;
+        for (uint32_t q = (uint32_t)lane * 16u; q < span; q += 1024u) {
+            if (q + 16u <= span) *reinterpret_cast<uint4 *>(__builtin_assume_aligned(out + q, 16)) = W[q >> 4];
+            else for (uint32_t k = q; k < span; k++) out[k] = W8[k];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // (the next round's LDS writes come behind these reads)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (__ballot(bad) && lane == 0 && !*(volatile unsigned long long *)not_fixed) atomicOr(not_fixed, 1ull);
+    if (PK && __ballot(alpha != 0u) && lane == 0 && !*(volatile unsigned long long *)not_packable) atomicOr(not_packable, 1ull);
+}
+
 // ---- exclusive prefix over the bin sizes (up to 4 M of them): block sums, their prefix, local prefixes ----------------------
 constexpr int SCAN_PER = 4096;              // entries per workgroup of 1024 threads
 
@@ -715,6 +861,7 @@ static char *g_scr = nullptr;            // the scratch of the last call (bin cu
 static uint64_t g_scr_cap = 0;
 
 std::atomic<long long> g_hook_ascii_slabs{0};      // ss_test_hook(5, ...): 1 = binned slabs of one length stay ASCII
+std::atomic<long long> g_hook_atomic_binning{0};   // ss_test_hook(6, ...): 1 = slabs of one length go through the count + atomic placement
 
 // src[0, n) (a flat base block on the device) -> a new slab with the records binned: out->d (hipMalloc'ed or a kept block),
 // out->cap; an ASCII slab of out->used bytes (a multiple of 16, '\n' padded), or -- records of one length, every byte of them
@@ -748,11 +895,22 @@ int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
             if (L >= FIX_MIN_L && L <= FIX_MAX_L && n / (L + 1) >= 1 && n - (n / (L + 1)) * (L + 1) < 64) { fix_L = L; n_rec = n / (L + 1); }
         }
     }
-    // (the record table of the general passes and the 4-byte bins of the one-length passes share a region: whichever is larger)
-    const uint64_t scratch = o_tab + std::max<uint64_t>((uint64_t)nb * TCAP * 8, (n_rec * 4 + 255) & ~255ull);
+    // the sorted one-length path (ss_test_hook 6 = 1: the count + atomic placement instead); hipcub counts its items in an int
+    const bool sorted = fix_L && g_hook_atomic_binning.load() == 0 && n_rec < (1ull << 31);
+    const uint64_t a4 = (n_rec * 4 + 255) & ~255ull;    // one per-record array of 4-byte entries
+    size_t sort_tb = 0;
+    if (sorted) {
+        hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
+        if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tb, k, v, (int)n_rec, 0, bits + 1) != hipSuccess) {
+            ss::set_last_error("hipcub::DeviceRadixSort::SortPairs", __FILE__, __LINE__, hipGetLastError()); return SS_EHIP;
+        }
+    }
+    // (the record table of the general passes, the 4-byte bins of the count + atomic placement, and the sort's keys, values (twice)
+    //  and temporary storage share a region: whichever is larger)
+    const uint64_t scratch = o_tab + std::max<uint64_t>((uint64_t)nb * TCAP * 8, sorted ? 4 * a4 + ((sort_tb + 255) & ~255ull) : a4);
     char *d_scr = nullptr, *d_new = nullptr;
 #define SS_R(call) do { if ((call) != hipSuccess) { ss::set_last_error(#call, __FILE__, __LINE__, hipGetLastError()); hipFree(d_scr); hipFree(d_new); return SS_EHIP; } } while (0)
-    // (the scratch of the call before is kept -- 0.19 GB for 20 M reads --: two driver calls fewer per sample)
+    // (the scratch of the call before is kept -- 0.35 GB for 20 M reads --: two driver calls fewer per sample)
     uint64_t scr_cap = 0;
     {
         std::lock_guard<std::mutex> g(g_scr_mu);
@@ -765,8 +923,82 @@ int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
     constexpr unsigned pad1 = 0, pad2 = 0;
     unsigned long long tail[3] = {0, 0, 0};              // positions of the new slab; tiles that did not fit the table / "not of one
     bool fixed = false, packed = false;                  // length"; a byte other than A C G T N in the records
-    if (fix_L) {
-        const uint32_t L1 = fix_L + 1u, P = (::slot_of(fix_L) + 15u) >> 4;
+    uint64_t cap = 0, real_cap = 0;                      // positions of the new slab; bytes of its block (a kept block may be larger)
+    auto t_counted = t_begin, t_alloc = t_begin;
+    float ms_key_sort = -1.f;                            // (the sorted path: key pass + sort, timed on the device)
+    // packed: 6 bytes per 16 positions, and 8 bytes behind them that the scans' 8-byte loads may touch (IN_PACKED).  A slab whose
+    // ASCII form would be a block the process keeps (ss::big_put) still takes a block of that size: destroyed, it goes back to
+    // the kept blocks and must serve what comes next -- the next sample's file-order slab, or its binning -- which a block of the
+    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones.
+    auto block_bytes = [](bool pk, uint64_t c) { return pk ? std::max<uint64_t>(ss::dev::in_bytes(true, c) + 8, c >= ss::BIG_KEEP_MIN ? c : 0) : c; };
+    // behind the records: packed, '\n' (code 1, invalid) up to the 16-position boundary -- at most one 3-byte unit (slots are
+    // multiples of 8) --, then the slack behind the last group (not the rest of a larger block); ASCII, '\n' up to the boundary
+    auto fill_tail = [&](bool pk, uint64_t total) -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (pk) {
+            const uint64_t t0 = total / 8u * 3u, t1 = ss::dev::in_bytes(true, cap) + 8;
+            e = hipMemsetAsync(d_new + t0, 0xFF, t1 - t0, 0);
+            if (e == hipSuccess && cap > total) e = hipMemsetAsync(d_new + t0, 0x55, 2, 0);
+        } else if (cap > total) {
+            e = hipMemsetAsync(d_new + total, '\n', cap - total, 0);
+        }
+        return e;
+    };
+    if (sorted) {
+        // one length: the new slab's size is known before anything runs (n_rec slots), so its block is taken first, and the
+        // flags are read once, after the gather
+        const uint32_t slot = ::slot_of(fix_L), P = (slot + 15u) >> 4;
+        const uint64_t total = n_rec * slot;
+        cap = std::max<uint64_t>((total + 15) & ~15ull, 16);
+        const bool want_packed = g_hook_ascii_slabs.load() == 0;
+        SS_R(ss::big_malloc((void **)&d_new, block_bytes(want_packed, cap), &real_cap));
+        t_alloc = std::chrono::steady_clock::now();
+        lap("new slab");
+        uint32_t *k0 = (uint32_t *)(d_scr + o_tab), *k1 = (uint32_t *)(d_scr + o_tab + a4), *v0 = (uint32_t *)(d_scr + o_tab + 2 * a4),
+                 *v1 = (uint32_t *)(d_scr + o_tab + 3 * a4);
+        void *d_temp = d_scr + o_tab + 4 * a4;
+        unsigned long long *flags = d_hist + n_bins;     // [1] not of one length, [2] not packable
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        SS_R(hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) { hipEventDestroy(ev[0]); SS_R(hipErrorOutOfMemory); }
+        auto gather = [&](bool pk, const uint32_t *perm) {
+            const uint32_t G = gather_rows(pk, fix_L), R = pk ? slot / 8u * 3u : slot;
+            auto kern = pk ? gather_fixed_kernel<true> : gather_fixed_kernel<false>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 4u * G * R, 0, src, n, n_rec, fix_L, P,
+                               (uint32_t)(((1ull << 32) + P - 1) / P), G, perm, (uint8_t *)d_new, flags + 1, flags + 2);
+        };
+        hipError_t e = hipMemsetAsync(flags, 0, 24, 0);
+        if (e == hipSuccess) e = hipEventRecord(ev[0], 0);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(key_fixed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, bits, k0, v0, flags + 1);
+            hipcub::DoubleBuffer<uint32_t> dk(k0, k1), dv(v0, v1);
+            e = hipcub::DeviceRadixSort::SortPairs(d_temp, sort_tb, dk, dv, (int)n_rec, 0, bits + 1, 0);
+            if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
+            const uint32_t *perm = dv.Current();
+            if (e == hipSuccess) { gather(want_packed, perm); e = fill_tail(want_packed, total); }
+            if (e == hipSuccess) e = hipMemcpy(tail + 1, flags + 1, 16, hipMemcpyDeviceToHost);
+            fixed = tail[1] == 0;
+            if (e == hipSuccess && fixed && want_packed && tail[2]) {         // a byte other than A C G T N: the same order, ASCII
+                if (real_cap < cap) {
+                    ss::big_put(d_new, real_cap); d_new = nullptr;
+                    e = ss::big_malloc((void **)&d_new, cap, &real_cap);
+                }
+                if (e == hipSuccess) { gather(false, perm); e = fill_tail(false, total); }
+                // (the packed gather's waves stop once the slab is known not packable: the layout is checked by the ASCII one)
+                if (e == hipSuccess) e = hipMemcpy(tail + 1, flags + 1, 8, hipMemcpyDeviceToHost);
+                fixed = tail[1] == 0;
+            }
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess && fixed) e = hipEventElapsedTime(&ms_key_sort, ev[0], ev[1]);
+        hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
+        SS_R(e);
+        packed = fixed && want_packed && tail[2] == 0;
+        tail[0] = total;
+        if (!fixed) { ss::big_put(d_new, real_cap); d_new = nullptr; }      // (else: some record is shorter or longer after all)
+    } else if (fix_L) {
+        // ss_test_hook 6: the count + atomic placement
+        const uint32_t L1 = fix_L + 1u;
         const unsigned nbf = (unsigned)((n_rec + 255) / 256);
         SS_R(hipMemsetAsync(d_hist, 0, o_sums, 0));
         hipLaunchKernelGGL(count_fixed_kernel, dim3(nbf), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + L1 - 1) / L1), bits, d_hist,
@@ -777,7 +1009,6 @@ int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
         SS_R(hipMemcpy(tail, d_hist + n_bins, 24, hipMemcpyDeviceToHost));
         fixed = tail[1] == 0;                            // (else: some record is shorter or longer after all -- the general passes)
         packed = fixed && tail[2] == 0 && g_hook_ascii_slabs.load() == 0;
-        (void)P;
     }
     if (!fixed) {
         SS_R(hipMemsetAsync(d_hist, 0, o_sums, 0));
@@ -788,39 +1019,30 @@ int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
         SS_R(hipMemcpy(tail, d_hist + n_bins, 16, hipMemcpyDeviceToHost));
     }
     const unsigned long long total = tail[0];
-    lap("count + prefix");
-    const auto t_counted = std::chrono::steady_clock::now();
-    const uint64_t cap = std::max<uint64_t>((total + 15) & ~15ull, 16);      // positions
-    // packed: 6 bytes per 16 positions, and 8 bytes behind them that the scans' 8-byte loads may touch (IN_PACKED).  A slab whose
-    // ASCII form would be a block the process keeps (ss::big_put) still takes a block of that size: destroyed, it goes back to
-    // the kept blocks and must serve what comes next -- the next sample's file-order slab, or its binning -- which a block of the
-    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones.
-    const uint64_t bytes = packed ? std::max<uint64_t>(ss::dev::in_bytes(true, cap) + 8, cap >= ss::BIG_KEEP_MIN ? cap : 0) : cap;
-    uint64_t real_cap = bytes;                           // (a kept block may be larger)
-    SS_R(ss::big_malloc((void **)&d_new, bytes, &real_cap));
-    const auto t_alloc = std::chrono::steady_clock::now();
-    lap("new slab");
-    if (packed) {
-        // a record's LDS area: 4 bytes in front (a span's first dword may begin before it), its groups, 4 behind
-        const uint32_t P = (::slot_of(fix_L) + 15u) >> 4, B = ::slot_of(fix_L) / 8u * 3u, A = (6u * P + 8u + 3u) & ~3u;
-        const uint32_t G = std::min<uint32_t>(64u, PK_LDS / A), ND = ((B + 2u) >> 2) + 1u;      // records per round; dwords a span touches
-        hipLaunchKernelGGL(place_fixed_packed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, P,
-                           (uint32_t)(((1ull << 32) + P - 1) / P), A, G, ND, (uint32_t)(((1ull << 32) + ND - 1) / ND), d_hist,
-                           (const uint32_t *)d_tab, (uint8_t *)d_new);
-        // the tail: '\n' (code 1, invalid) up to the 16-position boundary -- at most one 3-byte unit (slots are multiples of 8) --,
-        // then the slack behind the last group
-        const uint64_t t0 = total / 8u * 3u, t1 = ss::dev::in_bytes(true, cap) + 8;      // (not the rest of a larger block)
-        SS_R(hipMemsetAsync(d_new + t0, 0xFF, t1 - t0, 0));
-        if (cap > total) SS_R(hipMemsetAsync(d_new + t0, 0x55, 2, 0));
-    } else if (fixed) {
-        const uint32_t P = (::slot_of(fix_L) + 15u) >> 4;
-        hipLaunchKernelGGL(place_fixed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + P - 1) / P),
-                           d_hist, (const uint32_t *)d_tab, d_new);
-    } else {
-        hipLaunchKernelGGL(place_kernel, dim3(nb), dim3(256), pad2, 0, src, n, d_hist, d_cnt, d_tab, d_new);
-        if (tail[1]) hipLaunchKernelGGL(place_again_kernel, dim3(nb), dim3(256), 0, 0, src, n, bits, d_hist, d_cnt, d_new);
+    if (!(sorted && fixed)) {
+        lap("count + prefix");
+        t_counted = std::chrono::steady_clock::now();
+        cap = std::max<uint64_t>((total + 15) & ~15ull, 16);      // positions
+        SS_R(ss::big_malloc((void **)&d_new, block_bytes(packed, cap), &real_cap));
+        t_alloc = std::chrono::steady_clock::now();
+        lap("new slab");
+        if (packed) {
+            // a record's LDS area: 4 bytes in front (a span's first dword may begin before it), its groups, 4 behind
+            const uint32_t P = (::slot_of(fix_L) + 15u) >> 4, B = ::slot_of(fix_L) / 8u * 3u, A = (6u * P + 8u + 3u) & ~3u;
+            const uint32_t G = std::min<uint32_t>(64u, PK_LDS / A), ND = ((B + 2u) >> 2) + 1u;      // records per round; dwords a span touches
+            hipLaunchKernelGGL(place_fixed_packed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, P,
+                               (uint32_t)(((1ull << 32) + P - 1) / P), A, G, ND, (uint32_t)(((1ull << 32) + ND - 1) / ND), d_hist,
+                               (const uint32_t *)d_tab, (uint8_t *)d_new);
+        } else if (fixed) {
+            const uint32_t P = (::slot_of(fix_L) + 15u) >> 4;
+            hipLaunchKernelGGL(place_fixed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + P - 1) / P),
+                               d_hist, (const uint32_t *)d_tab, d_new);
+        } else {
+            hipLaunchKernelGGL(place_kernel, dim3(nb), dim3(256), pad2, 0, src, n, d_hist, d_cnt, d_tab, d_new);
+            if (tail[1]) hipLaunchKernelGGL(place_again_kernel, dim3(nb), dim3(256), 0, 0, src, n, bits, d_hist, d_cnt, d_new);
+        }
+        SS_R(fill_tail(packed, total));
     }
-    if (!packed && cap > total) SS_R(hipMemsetAsync(d_new + total, '\n', cap - total, 0));
     SS_R(hipGetLastError());
     SS_R(hipDeviceSynchronize());
     lap("place");
@@ -830,7 +1052,11 @@ int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
         const auto t_end = std::chrono::steady_clock::now();
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::lock_guard<std::mutex> g(g_scr_mu);
-        g_order_ms[0] = ms(t_begin, t_counted); g_order_ms[1] = ms(t_counted, t_alloc); g_order_ms[2] = ms(t_alloc, t_end);
+        if (sorted && fixed) {                           // key + sort, allocation, gather + tail (the first and the last add up to the kernels' wall time)
+            g_order_ms[0] = ms_key_sort; g_order_ms[1] = ms(t_begin, t_alloc); g_order_ms[2] = ms(t_alloc, t_end) - ms_key_sort;
+        } else {                                         // count + prefix, allocation, place
+            g_order_ms[0] = ms(t_begin, t_counted); g_order_ms[1] = ms(t_counted, t_alloc); g_order_ms[2] = ms(t_alloc, t_end);
+        }
         g_order_n[fixed ? 0 : 1]++;
     }
 #undef SS_R
@@ -868,11 +1094,12 @@ void reorder_release()
     if (d) hipFree(d);
 }
 
-// Policy: ALWAYS, unless SS_READS_ORDER=file.  Binning 20 M reads costs ~3.6 ms of kernel time once per sample; a tree scan of
+// Policy: ALWAYS, unless SS_READS_ORDER=file.  Binning 20 M one-length reads costs ~2.5 ms of kernel time once per sample
+// (sorted path; ragged reads ~3.6); a tree scan of
 // the binned set is 1.8 ms faster than in file order on sampled node sets (5.6 -> 3.8 ms), 0.7 ms on contiguous ones, a
 // cluster scan 6 ms (16.8 -> 10.6: the hits of a locus' reads are added up in LDS).  So it pays from the SECOND scan of a sample
 // on -- the tree scan + one cluster's scan, or the two scans of -b -- and a sample that is scanned exactly once (every
-// identified cluster single-strain) loses ~1.5 ms per 20 M reads, beside ~80 ms of text ingest for the same reads.  The
+// identified cluster single-strain) loses ~0.7 ms per 20 M one-length reads, beside ~80 ms of text ingest for the same reads.  The
 // loader cannot know which it will be: the clusters are identified by the first scan.
 bool reads_order_wanted()
 {

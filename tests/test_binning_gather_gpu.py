@@ -1,0 +1,219 @@
+"""Binning of records of one length by sorting (ss_reorder.hip key_fixed_kernel, a stable radix sort, gather_fixed_kernel): the
+binned slab holds the records in bin order and, inside a bin, in FILE order -- so two binnings of one input read back byte for
+byte the same.  ss_test_hook 6 = 1 bins through the count + atomic placement instead: the same records per bin, the same counts.
+Bytes other than A C G T N keep the slab ASCII; a slab that is not of one length after all takes the general passes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def L():
+    from strainscan_amd import _lib
+    _lib.require_gpu()
+    return _lib
+
+
+def _bin(rec, bits, k=31, m=15):
+    """Bin of a record (ss_reorder.hip record_bin): top `bits` bits of mix30 of the minimizer of its first 31 bases."""
+    code = {65: 0, 67: 1, 84: 2, 71: 3}
+    if len(rec) < k:
+        return 1 << bits
+    cs = [code.get(c & 0xDF, -1) for c in rec[:k]]
+    if min(cs) < 0:
+        return 1 << bits
+    km = sum(c << (2 * j) for j, c in enumerate(cs))
+    best, bx = None, 0
+    for i in range(k - m + 1):
+        x = (km >> (2 * i)) & 0x3FFFFFFF
+        h = (((x & 0xFFFFFF) * (0x4F1BB << 5) + 0x7F4A7C00) & 0xFFFFFFFF) & ~31
+        if best is None or h < best:
+            best, bx = h, x
+    M30 = 0x3FFFFFFF
+    h = (bx * 0x9E3779B1) & M30
+    h ^= h >> 15
+    h = (h * 0x2C1B3C6D) & M30
+    h ^= h >> 14
+    return h >> (30 - bits)
+
+
+def _order_bits(n_bytes):
+    bits = 12
+    while bits < 22 and (n_bytes // 152) >> (bits + 2):
+        bits += 1
+    return bits
+
+
+def _order_counters(L):
+    out = (C.c_uint64 * 2)()
+    L.check(L.lib().ss_reads_order_counters(out), "ss_reads_order_counters")
+    return int(out[0]), int(out[1])
+
+
+def _genome(seed, n):
+    rs = np.random.RandomState(seed)
+    return np.frombuffer(b"ACGT", np.uint8)[rs.randint(0, 4, size=n)]
+
+
+def _records(seed, length, n_rec, g, lower_first=False, mid=None):
+    """n_rec reads of `length` bases cut from g (with repeats: several reads per bin); N in the first k-mer of some, N elsewhere
+    in others; lower_first: lower case in the first k-mer of some; mid: a byte put in the middle of some."""
+    rs = np.random.RandomState(seed)
+    starts = rs.randint(0, len(g) - length, size=n_rec)
+    arr = g[starts[:, None] + np.arange(length)[None, :]].copy()
+    arr[7::211, rs.randint(0, min(31, length))] = ord("N")
+    arr[3::97, rs.randint(0, length)] = ord("N")
+    if lower_first:
+        arr[5::503, :31] |= 0x20
+    if mid is not None:
+        arr[11::301, length // 2] = ord(mid)
+    return [a.tobytes() for a in arr]
+
+
+def _kdb(L, g):
+    kfa = b"".join(b">1\n" + g[i:i + 31].tobytes() + b"\n" for i in range(0, len(g) - 31, 7))
+    return L.KmerDB.from_text(kfa, 31, True)
+
+
+def _bin_once(L, block, hook6=0):
+    import torch
+    d = torch.frombuffer(bytearray(block), dtype=torch.uint8).cuda()
+    L.check(L.lib().ss_test_hook(6, hook6), "ss_test_hook")
+    try:
+        f0, g0 = _order_counters(L)
+        rset = L.ReadSet.from_flat_dev(d.data_ptr(), d.numel(), order=True)
+        f1, g1 = _order_counters(L)
+    finally:
+        L.lib().ss_test_hook(6, 0)
+    L.check(L.lib().ss_device_sync(), "sync")
+    return rset, (f1 - f0, g1 - g0)
+
+
+def _counts(L, db, rset):
+    db.reset()
+    rset.scan_into(db)
+    L.check(L.lib().ss_device_sync(), "sync")
+    return db.counts_rows().copy()
+
+
+@pytest.mark.parametrize("length,n_rec,pad,lower", [(150, 20001, 0, False), (150, 20001, 0, True), (151, 4097, 9, False), (32, 70000, 0, False),
+                                                    (33, 64, 0, True), (100, 1, 0, False), (250, 12345, 3, False), (1023, 3000, 0, False),
+                                                    (1023, 700, 5, True), (160, 999, 0, False), (47, 130, 0, False)])
+def test_sorted_binning_keeps_file_order_inside_a_bin(L, length, n_rec, pad, lower):
+    """read_back() equals the records stable-sorted by bin; a second binning reads back the same bytes; the counts equal the
+    flat scan's.  Lengths 32..1023, record counts that are not multiples of 64, one record, newline padding, N / lower case in
+    the first k-mer (lower case: an ASCII slab), slots of 8 x odd and 8 x even positions."""
+    g = _genome(length * 3 + n_rec, 60000 + length)
+    recs = _records(length + n_rec, length, n_rec, g, lower_first=lower)
+    block = b"\n".join(recs) + b"\n" * (1 + pad)
+    assert len(block) >= 64 or n_rec == 1
+    if len(block) < 64:                                         # (one short record: below what the one-length passes take)
+        block += b"\n" * (64 - len(block))
+    db = _kdb(L, g)
+    db.reset()
+    db.scan_flat(block)
+    want = db.counts_rows().copy()
+    bits = _order_bits(len(block))
+    bins = [_bin(r, bits) for r in recs]
+    order = sorted(range(n_rec), key=lambda i: bins[i])         # (stable)
+    first = None
+    for rep in range(2):
+        rset, used = _bin_once(L, block)
+        assert used == (1, 0), (length, n_rec, used)
+        assert rset.packed_slabs() == (0 if lower else 1)
+        assert np.array_equal(_counts(L, db, rset), want)
+        slots = rset.read_back()
+        assert len(slots) % 16 == 0 and slots.endswith(b"\n")
+        back = [r for r in slots.split(b"\n") if r]
+        assert back == [recs[i] for i in order]
+        if first is None:
+            first = slots
+        else:
+            assert slots == first
+        rset.close()
+    timing = np.zeros(3)
+    L.check(L.lib().ss_reads_order_timing(L.ptr(timing)), "ss_reads_order_timing")
+    assert timing[0] > 0 and timing[1] >= 0 and timing[2] > 0
+    db.close()
+
+
+@pytest.mark.parametrize("length,n_rec,lower", [(150, 30000, False), (150, 30000, True), (77, 5001, False)])
+def test_hook6_atomic_placement_agrees_with_the_sort(L, length, n_rec, lower):
+    """ss_test_hook 6 = 1 (count + atomic placement) and 0 (key + sort + gather) on one input: the same records in every bin,
+    the same layout, bit-identical counters after a scan."""
+    g = _genome(91 + length, 40000 + length)
+    recs = _records(17 + n_rec, length, n_rec, g, lower_first=lower)
+    block = b"\n".join(recs) + b"\n"
+    bits = _order_bits(len(block))
+    db = _kdb(L, g)
+    got = {}
+    for hook in (1, 0):
+        rset, used = _bin_once(L, block, hook6=hook)
+        assert used == (1, 0), hook
+        got[hook] = (rset.packed_slabs(), _counts(L, db, rset), [r for r in rset.read_back().split(b"\n") if r])
+        rset.close()
+    assert got[0][0] == got[1][0] == (0 if lower else 1)
+    assert np.array_equal(got[0][1], got[1][1])
+    per_bin = [{}, {}]
+    for h in (0, 1):
+        bins = [_bin(r, bits) for r in got[h][2]]
+        assert bins == sorted(bins)
+        for b_, r in zip(bins, got[h][2]):
+            per_bin[h].setdefault(b_, []).append(r)
+    assert per_bin[0].keys() == per_bin[1].keys()
+    for b_ in per_bin[0]:
+        assert sorted(per_bin[0][b_]) == sorted(per_bin[1][b_]), b_
+    db.close()
+
+
+@pytest.mark.parametrize("letter", ["a", "R", "Y", "\r"])
+def test_bytes_outside_the_alphabet_give_an_ascii_slab(L, letter):
+    """A lower-case or IUPAC letter (or a carriage return) in the middle of some records: the gather's alphabet check sends the
+    slab through the ASCII gather (same order), with correct counts."""
+    g = _genome(5, 50150)
+    recs = _records(23, 150, 9000, g, mid=letter)
+    block = b"\n".join(recs) + b"\n"
+    db = _kdb(L, g)
+    db.reset()
+    db.scan_flat(block)
+    want = db.counts_rows().copy()
+    rset, used = _bin_once(L, block)
+    assert used == (1, 0)
+    assert rset.packed_slabs() == 0
+    assert np.array_equal(_counts(L, db, rset), want)
+    bits = _order_bits(len(block))
+    bins = [_bin(r, bits) for r in recs]
+    back = [r for r in rset.read_back().split(b"\n") if r]
+    assert back == [recs[i] for i in sorted(range(len(recs)), key=lambda i: bins[i])]
+    rset.close()
+    db.close()
+
+
+@pytest.mark.parametrize("variant", ["inner_newline", "one_base_short", "inner_newline_last"])
+def test_not_one_length_takes_the_general_passes(L, variant):
+    """An internal newline (the byte count still divides: only the gather's check sees it) and a record one base short (the
+    records behind it shifted: the key pass sees it) each go through the general passes, with the same counts as the flat scan."""
+    g = _genome(9, 50150)
+    recs = _records(31, 150, 9000, g)
+    if variant == "inner_newline":
+        recs[4000] = recs[4000][:75] + b"\n" + recs[4000][76:]
+    elif variant == "inner_newline_last":
+        recs[-1] = recs[-1][:140] + b"\n" + recs[-1][141:]
+    else:                                                       # (and one a base longer: the byte count still divides)
+        recs[2500] = recs[2500][:-1]
+        recs[6000] = recs[6000] + b"A"
+    block = b"\n".join(recs) + b"\n"
+    db = _kdb(L, g)
+    db.reset()
+    db.scan_flat(block)
+    want = db.counts_rows().copy()
+    rset, used = _bin_once(L, block)
+    assert used == (0, 1), variant
+    assert np.array_equal(_counts(L, db, rset), want)
+    back = [r for r in rset.read_back().split(b"\n") if r]
+    assert sorted(back) == sorted(r for chunk in recs for r in chunk.split(b"\n") if r)
+    rset.close()
+    db.close()
