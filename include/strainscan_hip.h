@@ -308,6 +308,28 @@ int ss_scan_multi_launches(uint64_t out[3]);
  * shard reads themselves (multi-GPU).
  * ------------------------------------------------------------------------------------------ */
 int ss_fastx_to_flat(const char *text, uint64_t len, char *out, uint64_t *out_len, uint64_t *n_records);
+
+/* --------------------------------------------------------------------------------------------
+ * BAM input.  A path is a BAM when its first gzip member inflates to bytes that begin with "BAM\1" (or the file itself
+ * is such an uncompressed stream); ss_reads_load and ss_scan_files(_shard) decode it whole -- inflated and decoded on the
+ * device first (files of 1 MB and more, unless SS_GZ_GPU=0 or policy 2), on the host for what the device declines.  The
+ * reads are those of a default `samtools fastq`: secondary (0x100) and supplementary (0x800) records and records without
+ * bases are skipped, a 0x10 record is reverse-complemented, each 4-bit code becomes its letter of "=ACMGRSVTWYHKDBN"; the
+ * flat block is each kept record's letters and '\n'.  Under sharding a rank keeps the blocks of 4096 KEPT records
+ * b = rank, rank + world, ...  A damaged stream (a member's CRC or length, a record that breaks the layout or runs past the
+ * end, no "BAM\1") makes the call return SS_EIO with nothing loaded; a CRAM file is refused with SS_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+/* What a path holds: *kind = 0 anything else (FASTA/FASTQ, plain or gzip, or unreadable), 1 a gzip'ed (BGZF) BAM, 2 an
+ * uncompressed BAM stream, 3 a CRAM file.  Reads the first 64 KB.  Host only, any thread. */
+int ss_input_kind(const char *path, int *kind);
+/* The host decoder over an inflated BAM stream of n bytes (from "BAM\1"): the flat block of this rank's kept records ->
+ * out (out = NULL: only *out_len), *n_records = this rank's kept records.  SS_ERANGE when cap < *out_len, SS_EIO when the
+ * stream is damaged (nothing written is to be used).  Host only, any thread; the buffers stay the caller's. */
+int ss_bam_decode(const void *stream, uint64_t n, int shard_rank, int shard_world, char *out, uint64_t cap, uint64_t *out_len,
+                  uint64_t *n_records);
+/* BAM inputs so far in this process: out[0] files decoded on the device, out[1] files decoded on the host, out[2] records
+ * kept, out[3] records skipped (over all ranks' shares: every rank walks the whole stream).  Any thread. */
+int ss_bam_counters(uint64_t out[4]);
 typedef struct ss_reader ss_reader;
 int ss_reader_open(const char *const *paths, int n_paths, ss_reader **out);
 /* a record longer than the caller's buffer is cut and its last `overlap` bases are repeated at

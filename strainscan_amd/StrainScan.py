@@ -18,7 +18,7 @@ if __name__ == "__main__" or os.path.basename(sys.argv[0] or "") in ("strainscan
         from . import _lib
         # (plain-text reads in a single process: the parse threads' pinned buffers too; .gz inputs never use them, they have
         #  upload buffers of their own)
-        n_gz = sum(a.endswith(".gz") for a in sys.argv[1:])
+        n_gz = sum(a.endswith(".gz") or _lib.input_kind(a) == "bam" for a in sys.argv[1:])
         _lib.warm_up(ingest=int(os.environ.get("WORLD_SIZE", "1")) <= 1 and not n_gz, gz=min(n_gz, 2))
 
     threading.Thread(target=_early, name="ss-gpu-warm-up", daemon=True).start()
@@ -121,6 +121,16 @@ def refuse_plasmid_mode(pmode):
         raise SystemExit(2)
 
 
+def refuse_cram(*paths):
+    """A CRAM sample is refused (it is not decoded, and never parsed as text): the message, then exit status 2."""
+    from . import _lib
+    try:
+        _lib.refuse_cram(paths)
+    except ValueError as e:
+        print("Error: %s" % e, file=sys.stderr)
+        raise SystemExit(2)
+
+
 def output_dir(out_dir, pwd):
     """-o as StrainScan.py:162-165 reads it."""
     out_dir = out_dir if out_dir else pwd + "/StrainScan_Result"
@@ -179,6 +189,7 @@ def main(argv=None):
     db_dir = args.db_dir
     opts = settings(args)
     refuse_plasmid_mode(opts["pmode"])
+    refuse_cram(fq_dir, fq2)
     out_dir = output_dir(args.out_dir, pwd)
     os.makedirs(out_dir, exist_ok=True)     # (exist_ok: under torchrun every rank arrives here with the same -o at the same moment)
 

@@ -128,6 +128,9 @@ SIGNATURES = {
     "ss_reads_order_counters": (i32, [P(u64)]),
     "ss_reads_packed_slabs": (i32, [vp, P(u64)]),
     "ss_fastx_to_flat": (i32, [cp, u64, vp, P(u64), P(u64)]),
+    "ss_input_kind": (i32, [cp, P(i32)]),
+    "ss_bam_decode": (i32, [vp, u64, i32, i32, vp, u64, P(u64), P(u64)]),
+    "ss_bam_counters": (i32, [P(u64)]),
     "ss_reader_open": (i32, [P(cp), i32, P(vp)]),
     "ss_reader_set_overlap": (i32, [vp, i32]),
     "ss_reader_next": (i32, [vp, vp, u64, P(u64), P(u64)]),
@@ -609,6 +612,48 @@ def fastx_to_flat(text):
     n, nrec = C.c_uint64(), C.c_uint64()
     check(lib().ss_fastx_to_flat(text, len(text), ptr(out), C.byref(n), C.byref(nrec)), "ss_fastx_to_flat")
     return out[:n.value].tobytes(), nrec.value
+
+
+# ss_input_kind: what an input path holds (BAM is told apart by its inflated magic, not by its name)
+INPUT_KINDS = {0: "fastx", 1: "bam", 2: "bam", 3: "cram"}
+
+
+def input_kind(path):
+    """'bam' (gzip'ed or an uncompressed stream), 'cram', or 'fastx' (FASTA/FASTQ, plain or gzip, and unreadable paths)."""
+    k = C.c_int()
+    check(lib().ss_input_kind(os.fsencode(path), C.byref(k)), "ss_input_kind")
+    return INPUT_KINDS[k.value]
+
+
+def refuse_cram(paths):
+    """ValueError naming the format when one of the paths is a CRAM file (not decoded; never parsed as text)."""
+    for p in paths:
+        try:
+            with open(p, "rb") as f:
+                magic = f.read(4)
+        except (OSError, TypeError):
+            continue                         # (no such file: the load reports it)
+        if magic == b"CRAM":
+            raise ValueError("%s is a CRAM file: CRAM input is not supported (BAM, FASTA and FASTQ, plain or gzip, are)" % p)
+
+
+def bam_decode(stream, shard_rank=0, shard_world=1):
+    """The host BAM decoder over an inflated stream (bytes from b'BAM\\1') -> (flat block bytes, this rank's kept records)."""
+    stream = bytes(stream)
+    n, nrec = C.c_uint64(), C.c_uint64()
+    check(lib().ss_bam_decode(stream, len(stream), int(shard_rank), int(shard_world), None, 0, C.byref(n), C.byref(nrec)),
+          "ss_bam_decode")
+    out = np.empty(max(n.value, 1), np.uint8)
+    check(lib().ss_bam_decode(stream, len(stream), int(shard_rank), int(shard_world), ptr(out), n.value, C.byref(n),
+                              C.byref(nrec)), "ss_bam_decode")
+    return out[:n.value].tobytes(), nrec.value
+
+
+def bam_counters():
+    """{'device', 'host', 'kept', 'skipped'}: BAM files decoded on the device / on the host, records kept / skipped."""
+    out = (C.c_uint64 * 4)()
+    check(lib().ss_bam_counters(out), "ss_bam_counters")
+    return dict(zip(("device", "host", "kept", "skipped"), (int(v) for v in out)))
 
 
 def read_flat_blocks(paths, cap=32 << 20, overlap=30):

@@ -234,6 +234,14 @@ int gz_fastq_to_flat_dev(const char *path, int shard_rank, int shard_world, char
 int gz_inputs_on_device(const char *const *paths, int n_paths, int shard_rank, int shard_world,
                         const std::function<int(int, char *, uint64_t, uint64_t, uint64_t)> &flat, std::vector<InflatedText> &texts,
                         std::vector<char> &done);
+// BAM input (ss_bam_dev.hip).  bam_probe: what a path holds, from its first bytes and the start of its first gzip member.
+enum { BAM_NO = 0, BAM_GZ = 1, BAM_RAW = 2, BAM_CRAM = 3 };
+int bam_probe(const char *path);
+// one BAM input (BAM_GZ or BAM_RAW) of a load or a scan: on the device unless SS_GZ_GPU=0 or policy 2, on the host for what the
+// device declines (policy 0 and 2; policy 1: SS_EAGAIN).  on_dev takes over a big_malloc'ed device block (len, cap, n_records),
+// on_host a malloc'ed host block padded like a block of ss_reads (len, n_records; the callee frees it).  SS_EIO: damaged.
+int bam_input(const char *path, int kind, int shard_rank, int shard_world, const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &on_dev,
+              const std::function<int(char *, uint64_t, uint64_t)> &on_host);
 int scan_file_parallel(ss_db *db, const char *path, uint64_t *n_records, uint64_t *n_bases, bool *handled, int shard_rank = 0,
                        int shard_world = 1);
 int scan_text_parallel(ss_db *db, const char *text, uint64_t n, uint64_t *n_records, uint64_t *n_bases, bool *handled,

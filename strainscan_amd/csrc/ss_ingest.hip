@@ -686,6 +686,46 @@ int ss_reads_load(const char *const *paths, int n_paths, int shard_rank, int sha
     std::lock_guard<std::mutex> pool_lock(g_read_workers_mu);
     const auto t_load = std::chrono::steady_clock::now();
     auto load_since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_load).count(); };
+    // BAM inputs (ss_bam_dev.hip), told apart by their inflated magic identically on every rank, are decoded whole here -- on the
+    // device first -- and the paths below never see them (nor do the chain tickets of range mode).  They come first: a set in file
+    // order (SS_READS_ORDER=file) holds a BAM's reads in front of the other inputs' whatever the order of the paths (the order
+    // inside each file is kept; counts do not depend on it).
+    std::vector<const char *> no_bam(paths, paths + n_paths);
+    // strict policy (ss_gz_set_policy(1)) and the device declined a BAM: the call still goes through the other inputs -- in range
+    // mode every rank serves the chain of every .gz file -- and returns SS_EAGAIN at the end
+    bool bam_declined = false;
+    {
+        int rc_bam = SS_OK;
+        for (int i = 0; i < n_paths && rc_bam == SS_OK; i++) {
+            const int kind = paths[i] ? ss::bam_probe(paths[i]) : ss::BAM_NO;
+            if (kind == ss::BAM_NO) continue;
+            no_bam[i] = "";
+            if (kind == ss::BAM_CRAM) { rc_bam = SS_EINVAL; break; }
+            if (bam_declined) continue;                  // (the call ends in SS_EAGAIN: no point in decoding the others)
+            rc_bam = ss::bam_input(paths[i], kind, shard_rank, shard_world,
+                [&](char *d, uint64_t len, uint64_t cap, uint64_t nrec) {
+                    R->adopt(d, cap, len);
+                    recs += nrec;
+                    bases += len;
+                    return (int)SS_OK;
+                },
+                [&](char *h, uint64_t len, uint64_t nrec) {
+                    char *d = nullptr;
+                    uint64_t cap = ss_reads::padded(len);
+                    int r = ss::big_malloc((void **)&d, cap, &cap) == hipSuccess ? SS_OK : SS_ENOMEM;
+                    if (r == SS_OK && hipMemcpy(d, h, ss_reads::padded(len), hipMemcpyHostToDevice) != hipSuccess) { ss::big_put(d, cap); r = SS_EHIP; }
+                    free(h);
+                    if (r != SS_OK) return r;
+                    R->adopt(d, cap, len);
+                    recs += nrec;
+                    bases += len;
+                    return (int)SS_OK;
+                });
+            if (rc_bam == SS_EAGAIN) { bam_declined = true; rc_bam = SS_OK; }
+        }
+        if (rc_bam != SS_OK) { ss_reads_destroy(R); return rc_bam; }
+        paths = no_bam.data();
+    }
     // the parse thread's pinned block goes straight to its place in a slab
     auto keep = [R](const char *h_buf, char *, uint64_t len, hipStream_t stream) -> int {
         char *dst = R->reserve(len);
@@ -717,6 +757,7 @@ int ss_reads_load(const char *const *paths, int n_paths, int shard_rank, int sha
         for (int i = 0; i < n_paths; i++)
             if (on_device[i] || texts[i].p) rest[i] = "";
     }
+    if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;      // (the chain of every .gz file has been served above)
     if (rc == SS_OK) {
         std::vector<ss::InflatedText> more = ss::inflate_gz_inputs(rest.data(), n_paths);     // .gz inputs, inflated concurrently
         if (texts.empty()) texts = more;

@@ -524,6 +524,43 @@ int ss_scan_files_shard(ss_db *db, const char *const *paths, int n_paths, int sh
     const bool allow_parallel = !(seq_env && !strcmp(seq_env, "sequential"));
     for (int i = 0; i < n_paths; i++)
         if (!paths[i]) return SS_EINVAL;
+    // BAM inputs (ss_bam_dev.hip): decoded whole, on the device first, and scanned before the other inputs; the paths below never
+    // see them.  Strict policy and the device declined one: the other inputs still go through (in range mode every rank serves
+    // the chain of every .gz file) and the call returns SS_EAGAIN at the end.
+    std::vector<const char *> no_bam(paths, paths + n_paths);
+    bool bam_declined = false;
+    for (int i = 0; i < n_paths; i++) {
+        const int kind = ss::bam_probe(paths[i]);
+        if (kind == ss::BAM_NO) continue;
+        if (kind == ss::BAM_CRAM) return SS_EINVAL;
+        no_bam[i] = "";
+        if (bam_declined) continue;
+        const int r = ss::bam_input(paths[i], kind, shard_rank, shard_world,
+            [&](char *d, uint64_t len, uint64_t cap, uint64_t nrec) {
+                int e = ss_scan_flat_dev(db, d, ss_reads::padded(len), nullptr);
+                if (e == SS_OK && hipStreamSynchronize(nullptr) != hipSuccess) e = SS_EHIP;
+                ss::big_put(d, cap);
+                recs += nrec;
+                total += len;
+                return e;
+            },
+            [&](char *h, uint64_t len, uint64_t nrec) {
+                char *d = nullptr;
+                const uint64_t plen = ss_reads::padded(len);
+                int e = hipMalloc((void **)&d, plen) == hipSuccess ? SS_OK : SS_ENOMEM;
+                if (e == SS_OK && hipMemcpy(d, h, plen, hipMemcpyHostToDevice) != hipSuccess) e = SS_EHIP;
+                if (e == SS_OK) e = ss_scan_flat_dev(db, d, plen, nullptr);
+                if (e == SS_OK && hipStreamSynchronize(nullptr) != hipSuccess) e = SS_EHIP;
+                if (d) hipFree(d);
+                free(h);
+                recs += nrec;
+                total += len;
+                return e;
+            });
+        if (r == SS_EAGAIN) bam_declined = true;
+        else if (r != SS_OK) return r;
+    }
+    paths = no_bam.data();
     // .gz inputs are inflated whole (libdeflate, all files at once) and parsed like plain text when possible
     std::vector<ss::InflatedText> texts;
     std::vector<char> on_device((size_t)n_paths, 0);
@@ -546,6 +583,7 @@ int ss_scan_files_shard(ss_db *db, const char *const *paths, int n_paths, int sh
             for (int i = 0; i < n_paths; i++)
                 if (on_device[i] || texts[i].p) rest[i] = "";
         }
+        if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;      // (the chain of every .gz file has been served above)
         if (rc == SS_OK) {
             std::vector<ss::InflatedText> more = ss::inflate_gz_inputs(rest.data(), n_paths);
             if (texts.empty()) texts = more;
@@ -563,6 +601,7 @@ int ss_scan_files_shard(ss_db *db, const char *const *paths, int n_paths, int sh
         if (rc == SS_OK && !handled) rc = scan_files_sequential(db, &paths[i], 1, &recs, &total, shard_rank, shard_world);
     }
     for (auto &tx : texts) free(tx.p);
+    if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;          // (SS_INGEST=sequential: nothing was in range mode)
     if (rc) return rc;
     if (n_records) *n_records = recs;
     if (n_bases) *n_bases = total;

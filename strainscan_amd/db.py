@@ -72,7 +72,7 @@ def resident_reads(paths):
     from . import dist
     rank, world = dist.rank_world()
     total = sum(os.path.getsize(p) for p in paths if p)
-    gz = any(str(p).endswith(".gz") for p in paths if p)
+    gz = any(str(p).endswith(".gz") or _lib.input_kind(p) == "bam" for p in paths if p)      # (a BAM: budgeted like a .gz)
     if (total * (4 if gz else 1)) / world > RESIDENT_LIMIT_BYTES or RESIDENT_LIMIT_BYTES <= 0:
         return None
     key = _reads_key(paths, rank, world)

@@ -26,7 +26,7 @@ if __name__ == "__main__" or os.path.basename(sys.argv[0] or "") == "strainscan-
 
     def _early():
         from . import _lib
-        n_gz = sum(a.endswith(".gz") for a in sys.argv[1:])
+        n_gz = sum(a.endswith(".gz") or _lib.input_kind(a) == "bam" for a in sys.argv[1:])
         _lib.warm_up(ingest=int(os.environ.get("WORLD_SIZE", "1")) <= 1 and not n_gz, gz=min(n_gz, 2))
 
     threading.Thread(target=_early, name="ss-gpu-warm-up", daemon=True).start()
@@ -153,6 +153,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
 
 def main(argv=None):
     args, dbs, opts = parse_args(argv)
+    StrainScan.refuse_cram(args.input_fq, args.input_fq2)         # (reads the sample's first bytes: after the checks above)
     out_dir = StrainScan.output_dir(args.out_dir, os.getcwd())
     os.makedirs(out_dir, exist_ok=True)
     from . import dist
