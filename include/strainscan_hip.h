@@ -330,6 +330,21 @@ int ss_bam_decode(const void *stream, uint64_t n, int shard_rank, int shard_worl
 /* BAM inputs so far in this process: out[0] files decoded on the device, out[1] files decoded on the host, out[2] records
  * kept, out[3] records skipped (over all ranks' shares: every rank walks the whole stream).  Any thread. */
 int ss_bam_counters(uint64_t out[4]);
+/* The base-quality mask (jellyfish count -Q; off by default).  With a threshold q in 1..93 every decoder that turns a file or a
+ * text into bases -- ss_reads_load, ss_scan_files, ss_scan_files_shard, ss_reader_open / ss_reader_next (a reader keeps the
+ * threshold it was opened under), ss_fastx_to_flat, ss_bam_decode -- writes 'N' for a base whose quality is below it:
+ *   FASTQ  the i-th sequence character of a record, when the i-th quality character the record grammar consumes for it has a
+ *          byte value < 33 + q (line breaks count on neither side): `jellyfish count -Q chr(33 + q)`;
+ *   FASTA  untouched;
+ *   BAM    base i when qual[i] < q, in the stored order (before a 0x10 record is turned round); a record without qualities
+ *          (qual[0] == 0xFF) is NOT masked and is counted in ss_mask_counters.
+ * Record count, record lengths and order never change.  One process-wide setting: SS_ERANGE outside 0..93, 0 = off.  Set it
+ * before the load it is meant for, not while one runs.  ss_mask_counters: out[0] sequence characters masked (those whose quality
+ * was below the threshold, an 'N' among them counted too), out[1] BAM records that carried no qualities while the mask was on;
+ * cumulative per process, over this process's share of a sharded input.  Host only, any thread. */
+int ss_set_min_base_qual(int q);
+int ss_get_min_base_qual(void);
+int ss_mask_counters(uint64_t out[2]);
 typedef struct ss_reader ss_reader;
 int ss_reader_open(const char *const *paths, int n_paths, ss_reader **out);
 /* a record longer than the caller's buffer is cut and its last `overlap` bases are repeated at

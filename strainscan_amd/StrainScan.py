@@ -1,7 +1,8 @@
 """`strainscan` command line -- drop-in for the identification CLI StrainScan.py:113-271.
 
 Same flags (-i -j -d -o -k -l -b -p -r -e -s), same cutoff ladder, same output files
-(final_report.txt, C<id>/StrainVote.report, strain_prob.txt).  Plasmid mode (-p 1/2) rebuilds a
+(final_report.txt, C<id>/StrainVote.report, strain_prob.txt).  One flag of its own: -q Q masks bases of Phred quality below Q
+(`jellyfish count -Q`; off by default).  Plasmid mode (-p 1/2) rebuilds a
 database with the reference's offline builder (StrainScan.py:235) and is out of scope here.
 """
 import argparse
@@ -105,6 +106,31 @@ def add_arguments(ap, multi=False):
                     help="1: also return strains with extra regions covered (default: -e 0)")
     ap.add_argument("-s", "--minimum_snv_num", dest="msn", type=str,
                     help="The minimum number of SNV at Layer-2 identification. (default: 40)")
+    ap.add_argument("-q", "--min_base_qual", dest="min_base_qual", type=min_base_qual_arg, default=0, metavar="Q",
+                    help="Mask low-quality bases: a base whose Phred quality is below Q (FASTQ: quality character below "
+                         "chr(33+Q), as `jellyfish count -Q`; BAM: qual < Q, records without qualities are left alone) "
+                         "becomes N before k-mers are counted; FASTA input is untouched.  An integer in 0..93 "
+                         "(default: 0, no masking)")
+
+
+def min_base_qual_arg(text):
+    """-q's value: an integer in 0..93, or the parser's error (exit status 2, before any input is opened)."""
+    try:
+        q = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer in 0..93" % text)
+    if not 0 <= q <= 93:
+        raise argparse.ArgumentTypeError("%d is outside 0..93" % q)
+    return q
+
+
+def apply_min_base_qual(q):
+    """-q Q: the process-wide threshold (strainscan_amd.set_min_base_qual); the load of the sample then writes ONE line to stderr
+    (db.resident_reads: the threshold, bases masked / bases read and, if any, the BAM records that carried no qualities).
+    stdout and the report files are untouched."""
+    from . import _lib, db
+    _lib.set_min_base_qual(q)               # (0 as well: the command line states the setting of its run)
+    db.MASK_REPORT.update(on=bool(q), done=False)
 
 
 def settings(args):
@@ -190,6 +216,7 @@ def main(argv=None):
     opts = settings(args)
     refuse_plasmid_mode(opts["pmode"])
     refuse_cram(fq_dir, fq2)
+    apply_min_base_qual(args.min_base_qual)
     out_dir = output_dir(args.out_dir, pwd)
     os.makedirs(out_dir, exist_ok=True)     # (exist_ok: under torchrun every rank arrives here with the same -o at the same moment)
 
@@ -209,6 +236,11 @@ def cli(main_fn=None):
     except SystemExit as e:
         rc = e.code
     _clock("reports written")
+    try:
+        from . import db
+        db.report_mask()                    # (-q and reads that were never resident: the line comes here, over all passes)
+    except Exception:                       # noqa: B902
+        pass
     try:
         from . import db
         db.wait_cache_writes()

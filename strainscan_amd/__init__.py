@@ -12,6 +12,22 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.seqpy.revcomp                              (library/seqpy.c:24)
     strainscan_amd.StrainScan.main                            (StrainScan.py:113, the `strainscan` CLI)
 
+    strainscan_amd.set_min_base_qual / get_min_base_qual      (the base-quality mask of `strainscan -q`; process-wide, off by default)
+
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
 __version__ = "0.1.0"
+
+
+def set_min_base_qual(q):
+    """Every later load of reads in this process turns a base whose Phred quality is below `q` into N before any k-mer is
+    formed (FASTQ: as `jellyfish count -Q chr(33 + q)`; BAM: qual[i] < q, records without qualities untouched; FASTA
+    untouched).  An integer in 0..93; 0 = off, the default.  The reference signatures (identify_cluster(fq_path, db_dir,
+    cutoff), ...) stay as they are: this is the one setting they read."""
+    from . import _lib
+    _lib.set_min_base_qual(q)
+
+
+def get_min_base_qual():
+    from . import _lib
+    return _lib.get_min_base_qual()

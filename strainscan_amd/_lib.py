@@ -131,6 +131,9 @@ SIGNATURES = {
     "ss_input_kind": (i32, [cp, P(i32)]),
     "ss_bam_decode": (i32, [vp, u64, i32, i32, vp, u64, P(u64), P(u64)]),
     "ss_bam_counters": (i32, [P(u64)]),
+    "ss_set_min_base_qual": (i32, [i32]),
+    "ss_get_min_base_qual": (i32, []),
+    "ss_mask_counters": (i32, [P(u64)]),
     "ss_reader_open": (i32, [P(cp), i32, P(vp)]),
     "ss_reader_set_overlap": (i32, [vp, i32]),
     "ss_reader_next": (i32, [vp, vp, u64, P(u64), P(u64)]),
@@ -654,6 +657,27 @@ def bam_counters():
     out = (C.c_uint64 * 4)()
     check(lib().ss_bam_counters(out), "ss_bam_counters")
     return dict(zip(("device", "host", "kept", "skipped"), (int(v) for v in out)))
+
+
+def set_min_base_qual(q):
+    """The base-quality mask of every later load in this process (ss_set_min_base_qual): a base whose Phred quality is below
+    `q` becomes N (FASTQ: quality character < chr(33 + q), as `jellyfish count -Q`; BAM: qual[i] < q; FASTA untouched).
+    0 = off, the default.  ValueError unless q is an integer in 0..93."""
+    if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= int(q) <= 93:
+        raise ValueError("min_base_qual must be an integer in 0..93, not %r" % (q,))
+    check(lib().ss_set_min_base_qual(int(q)), "ss_set_min_base_qual")
+
+
+def get_min_base_qual():
+    return int(lib().ss_get_min_base_qual())
+
+
+def mask_counters():
+    """{'masked', 'bam_no_qual'}: bases the quality mask turned into N so far in this process, BAM records that carried no
+    qualities (left unmasked) while it was on."""
+    out = (C.c_uint64 * 2)()
+    check(lib().ss_mask_counters(out), "ss_mask_counters")
+    return dict(masked=int(out[0]), bam_no_qual=int(out[1]))
 
 
 def read_flat_blocks(paths, cap=32 << 20, overlap=30):

@@ -162,28 +162,58 @@ __device__ __forceinline__ char bam_letter(const uint8_t *seq, uint64_t i, bool 
     return "=ACMGRSVTWYHKDBN"[c];
 }
 
+// ... and under the base-quality mask 'N' where qual[i] < thr -- qual: the l_seq Phred values behind the packed bases, in the
+// same stored order (rec_len has checked that they lie inside the record); *n += 1 then
+template <bool MASK>
+__device__ __forceinline__ char bam_letter_q(const uint8_t *seq, const uint8_t *qual, uint64_t i, bool rev, uint32_t thr, uint32_t *n)
+{
+    if (MASK && qual[i] < thr) { *n += 1; return 'N'; }
+    return bam_letter(seq, i, rev);
+}
+
 // kept record r -> dst + off[r]: its letters (reverse-complemented for 0x10) and '\n'; 16 lanes per record, 16 letters per lane
-// and round
+// and round.  MASK (ss_set_min_base_qual): thr = the lowest quality kept; a record without qualities (qual[0] == 0xFF) is
+// not masked and counted; masked[0] += bases masked, masked[1] += such records
+template <bool MASK>
 __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t *__restrict__ s, const uint64_t *__restrict__ rec,
                                                          const uint64_t *__restrict__ len1, const uint64_t *__restrict__ off,
-                                                         uint64_t n_rec, char *__restrict__ dst)
+                                                         uint64_t n_rec, char *__restrict__ dst, uint32_t thr,
+                                                         unsigned long long *__restrict__ masked)
 {
     const uint64_t r = (uint64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (r >= n_rec || !len1[r]) return;
-    const uint64_t p = rec[r], lseq = len1[r] - 1, o = off[r];
-    const uint8_t *seq = s + p + 36 + s[p + 12] + 4 * (uint64_t)ld16(s, p + 16);
-    const bool rev = (ld16(s, p + 18) & 0x10u) != 0;
-    for (uint64_t c = (uint64_t)(threadIdx.x & 15) * 16; c < lseq; c += 256) {
-        if (c + 16 <= lseq) {
-            char v[16];
+    uint32_t cnt = 0, noq = 0;
+    if (r < n_rec && len1[r]) {
+        const uint64_t p = rec[r], lseq = len1[r] - 1, o = off[r];
+        const uint8_t *seq = s + p + 36 + s[p + 12] + 4 * (uint64_t)ld16(s, p + 16);
+        const uint8_t *qual = seq + (lseq + 1) / 2;
+        const bool rev = (ld16(s, p + 18) & 0x10u) != 0;
+        // (a record without qualities: 0xFF in every place by the format, but only qual[0] is what says so)
+        const uint32_t t = MASK && qual[0] != 0xFF ? thr : 0u;
+        for (uint64_t c = (uint64_t)(threadIdx.x & 15) * 16; c < lseq; c += 256) {
+            if (c + 16 <= lseq) {
+                char v[16];
 #pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = bam_letter(seq, rev ? lseq - 1 - (c + k) : c + k, rev);
-            __builtin_memcpy(dst + o + c, v, 16);
-        } else {
-            for (uint64_t k = c; k < lseq; k++) dst[o + k] = bam_letter(seq, rev ? lseq - 1 - k : k, rev);
+                for (int k = 0; k < 16; k++) v[k] = bam_letter_q<MASK>(seq, qual, rev ? lseq - 1 - (c + k) : c + k, rev, t, &cnt);
+                __builtin_memcpy(dst + o + c, v, 16);
+            } else {
+                for (uint64_t k = c; k < lseq; k++) dst[o + k] = bam_letter_q<MASK>(seq, qual, rev ? lseq - 1 - k : k, rev, t, &cnt);
+            }
+        }
+        if ((threadIdx.x & 15) == 0) {
+            dst[o + lseq] = '\n';
+            if (MASK && qual[0] == 0xFF) noq = 1;
         }
     }
-    if ((threadIdx.x & 15) == 0) dst[o + lseq] = '\n';
+    if (MASK) {
+        for (int d = 32; d; d >>= 1) {
+            cnt += (uint32_t)__shfl_xor((int)cnt, d, 64);
+            noq += (uint32_t)__shfl_xor((int)noq, d, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            if (cnt) atomicAdd(&masked[0], (unsigned long long)cnt);
+            if (noq) atomicAdd(&masked[1], (unsigned long long)noq);
+        }
+    }
 }
 
 __global__ void bam_pad_kernel(char *dst, uint64_t from, uint64_t to)
@@ -232,7 +262,8 @@ int bam_decode(const uint8_t *s, uint64_t n, int shard_rank, int shard_world, ch
     int32_t n_ref = 0;
     if (bam_header(s, n, n, &p, &n_ref) != 1) return SS_EIO;
     static const char letters[] = "=ACMGRSVTWYHKDBN";
-    uint64_t o = 0, kept = 0, skipped = 0, own = 0;
+    uint64_t o = 0, kept = 0, skipped = 0, own = 0, masked = 0, noqual = 0;
+    const uint32_t min_qual = (uint32_t)min_base_qual();
     while (p < n) {
         const uint64_t l = rec_len(s, n, p);
         if (!l) return SS_EIO;
@@ -255,6 +286,13 @@ int bam_decode(const uint8_t *s, uint64_t n, int shard_rank, int shard_world, ch
                         for (uint64_t j = 0; j < lseq; j++) out[o + j] = letters[(j & 1) ? (seq[j >> 1] & 15u) : (seq[j >> 1] >> 4)];
                     }
                     out[o + lseq] = '\n';
+                    // base-quality mask: qual[i] < Q -> 'N', in the stored order; a record without qualities is left as it is
+                    const uint8_t *qual = seq + (lseq + 1) / 2;
+                    if (min_qual && qual[0] == 0xFF) noqual++;
+                    else if (min_qual) {
+                        for (uint64_t j = 0; j < lseq; j++)
+                            if (qual[(flag & 0x10u) ? lseq - 1 - j : j] < min_qual) { out[o + j] = 'N'; masked++; }
+                    }
                 }
                 o += lseq + 1;
                 own++;
@@ -263,6 +301,7 @@ int bam_decode(const uint8_t *s, uint64_t n, int shard_rank, int shard_world, ch
         }
         p += l;
     }
+    if (out) mask_count(masked, noqual);
     *out_len = o;
     if (n_own) *n_own = own;
     if (n_kept) *n_kept = kept;
@@ -342,10 +381,12 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     const uint8_t *s = reinterpret_cast<const uint8_t *>(d_stream);
     uint64_t *d_lo = nullptr, *d_entry = nullptr, *d_exit = nullptr, *d_base = nullptr, *d_rec = nullptr, *d_len1 = nullptr, *d_off = nullptr;
     uint32_t *d_count = nullptr, *d_which = nullptr, *d_keep = nullptr, *d_kidx = nullptr;
+    unsigned long long *d_masked = nullptr;
     void *d_tmp = nullptr;
     char *flat = nullptr;
+    const int min_qual = min_base_qual();
     auto done = [&](int r) {
-        void *scratch[] = {d_lo, d_entry, d_exit, d_base, d_rec, d_len1, d_off, d_count, d_which, d_keep, d_kidx, d_tmp};
+        void *scratch[] = {d_lo, d_entry, d_exit, d_base, d_rec, d_len1, d_off, d_count, d_which, d_keep, d_kidx, d_masked, d_tmp};
         for (void *q : scratch) if (q) hipFreeAsync(q, st);
         hipStreamSynchronize(st);
         call_stream_put(st);
@@ -473,12 +514,21 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     const uint64_t cap = ss_reads::padded(total);
     *flat_cap = cap;
     if (ss::big_malloc((void **)&flat, cap, flat_cap) != hipSuccess) { flat = nullptr; return done(SS_ENOMEM); }
-    if (n_rec)
-        hipLaunchKernelGGL(bam_decode_kernel, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, st, s, (const uint64_t *)d_rec,
-                           (const uint64_t *)d_len1, (const uint64_t *)d_off, n_rec, flat);
+    unsigned long long masked[2] = {0, 0};
+    if (n_rec && min_qual > 0) {
+        BM(hipMallocAsync((void **)&d_masked, 16, st));
+        BM(hipMemsetAsync(d_masked, 0, 16, st));
+        hipLaunchKernelGGL(bam_decode_kernel<true>, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, st, s, (const uint64_t *)d_rec,
+                           (const uint64_t *)d_len1, (const uint64_t *)d_off, n_rec, flat, (uint32_t)min_qual, d_masked);
+        BM(hipMemcpyAsync(masked, d_masked, 16, hipMemcpyDeviceToHost, st));
+    } else if (n_rec) {
+        hipLaunchKernelGGL(bam_decode_kernel<false>, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, st, s, (const uint64_t *)d_rec,
+                           (const uint64_t *)d_len1, (const uint64_t *)d_off, n_rec, flat, 0u, (unsigned long long *)nullptr);
+    }
     hipLaunchKernelGGL(bam_pad_kernel, dim3(1), dim3(64), 0, st, flat, total, cap);
     BM(hipGetLastError());
     BM(hipStreamSynchronize(st));
+    mask_count(masked[0], masked[1]);
 #undef BM
     *d_flat = flat;
     *flat_len = total;

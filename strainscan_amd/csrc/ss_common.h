@@ -65,6 +65,10 @@ inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
 unsigned host_cpus();
 extern std::atomic<long long> g_hook_generic_k;      // ss_test_hook 4 (ss_mini.hip)
 unsigned ingest_threads();      // FASTQ parse threads of this process: its share of host_cpus() (LOCAL_WORLD_SIZE), at most 20 (ss_ingest.hip)
+// The base-quality mask (ss_set_min_base_qual, ss_host.hip): a base whose Phred quality is below the threshold becomes 'N' in
+// whichever decoder turns its file into bases.  0 = off.  mask_count adds to the process-wide counters of ss_mask_counters.
+int min_base_qual();
+void mask_count(uint64_t bases, uint64_t bam_records_without_qual = 0);
 
 }  // namespace ss
 

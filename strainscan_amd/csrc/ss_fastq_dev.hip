@@ -90,22 +90,66 @@ __global__ void fq_records_kernel(const char *__restrict__ t, uint64_t n, const 
     len1[r] = (r >> SHARD_LOG2) % shard_world == shard_rank ? seq + 1 : 0;
 }
 
-// sequence line of record r (with its '\n') -> dst + off[r]; 16 lanes per record, 16 (unaligned) bytes per lane and round
+// four bases and their four quality bytes: a base whose quality is below thr (<= 126) becomes 'N'; *n += how many
+__device__ __forceinline__ uint32_t mask4(uint32_t b, uint32_t q, uint32_t thr4, uint32_t *n)
+{
+    // 0x80 of a byte of `ge` = that quality is >= thr: the low seven bits compared by a subtraction that cannot borrow (every
+    // minuend byte is >= 0x80 > thr), a quality of 0x80 and more by its own top bit
+    const uint32_t ge = (((q & 0x7F7F7F7Fu) | 0x80808080u) - thr4) | q;
+    const uint32_t lt = ~ge & 0x80808080u;
+    *n += (uint32_t)__popc(lt);
+    const uint32_t m = (lt >> 7) * 0xFFu;
+    return (b & ~m) | (0x4E4E4E4Eu & m);
+}
+
+// sequence line of record r (with its '\n') -> dst + off[r]; 16 lanes per record, 16 (unaligned) bytes per lane and round.
+// MASK (ss_set_min_base_qual): the lane that copies 16 bases also loads the 16 quality bytes of the same columns -- line 4r + 3,
+// as long as line 4r + 1 (fq_records_kernel) -- and writes 'N' where the quality is below thr; masked[0] += how many (one
+// atomic per wave that masked any)
+template <bool MASK>
 __global__ __launch_bounds__(256) void fq_copy_kernel(const char *__restrict__ t, const uint64_t *__restrict__ ls,
                                                       const uint64_t *__restrict__ len1, const uint64_t *__restrict__ off,
-                                                      uint64_t n_rec, char *__restrict__ dst)
+                                                      uint64_t n_rec, char *__restrict__ dst, uint32_t thr,
+                                                      unsigned long long *__restrict__ masked)
 {
     const uint64_t r = (uint64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (r >= n_rec) return;
-    const uint64_t s = ls[4 * r + 1], l1 = len1[r], o = off[r];
-    for (uint64_t c = (uint64_t)(threadIdx.x & 15) * 16; c < l1; c += 256) {
-        if (c + 16 <= l1) {
-            uint4 v;
-            __builtin_memcpy(&v, t + s + c, 16);
-            __builtin_memcpy(dst + o + c, &v, 16);
-        } else {
-            for (uint64_t k = c; k < l1; k++) dst[o + k] = t[s + k];
+    uint32_t cnt = 0;
+    if (r < n_rec) {
+        const uint64_t s = ls[4 * r + 1], l1 = len1[r], o = off[r];
+        const uint64_t sq = MASK ? ls[4 * r + 3] : 0, seq = l1 ? l1 - 1 : 0;      // (l1 counts the '\n', which has no quality)
+        const uint32_t thr4 = thr * 0x01010101u;
+        for (uint64_t c = (uint64_t)(threadIdx.x & 15) * 16; c < l1; c += 256) {
+            if (c + 16 <= l1) {
+                uint4 v;
+                __builtin_memcpy(&v, t + s + c, 16);
+                if (MASK) {
+                    uint4 q;
+                    if (c + 16 <= seq) {
+                        __builtin_memcpy(&q, t + sq + c, 16);
+                    } else {                              // the 16th byte is the '\n': the quality line may end the text
+                        unsigned char qb[16];
+#pragma unroll
+                        for (int k = 0; k < 16; k++) qb[k] = c + k < seq ? (unsigned char)t[sq + c + k] : 0xFF;
+                        __builtin_memcpy(&q, qb, 16);
+                    }
+                    v.x = mask4(v.x, q.x, thr4, &cnt);
+                    v.y = mask4(v.y, q.y, thr4, &cnt);
+                    v.z = mask4(v.z, q.z, thr4, &cnt);
+                    v.w = mask4(v.w, q.w, thr4, &cnt);
+                }
+                __builtin_memcpy(dst + o + c, &v, 16);
+            } else {
+                for (uint64_t k = c; k < l1; k++) {
+                    char b = t[s + k];
+                    if (MASK && k < seq && (unsigned char)t[sq + k] < thr) { b = 'N'; cnt++; }
+                    dst[o + k] = b;
+                }
+            }
         }
+    }
+    if (MASK) {
+        for (int d = 32; d; d >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, d, 64);
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(masked, (unsigned long long)cnt);
     }
 }
 
@@ -142,10 +186,12 @@ int fastq_text_to_flat_dev(const char *d_text, uint64_t n, int shard_rank, int s
     const uint64_t n_tiles = (n + TB - 1) / TB;
     uint64_t *d_counts = nullptr, *d_base = nullptr, *d_ls = nullptr, *d_len1 = nullptr, *d_off = nullptr;
     uint32_t *d_bad = nullptr;
+    unsigned long long *d_masked = nullptr;
     void *d_tmp = nullptr;
     char *flat = nullptr;
+    const int min_qual = min_base_qual();
     auto done = [&](int r) {
-        void *scratch[] = {d_counts, d_base, d_ls, d_len1, d_off, d_bad, d_tmp};
+        void *scratch[] = {d_counts, d_base, d_ls, d_len1, d_off, d_bad, d_masked, d_tmp};
         for (void *q : scratch) if (q) hipFreeAsync(q, st);
         hipStreamSynchronize(st);
         call_stream_put(st);
@@ -197,10 +243,21 @@ int fastq_text_to_flat_dev(const char *d_text, uint64_t n, int shard_rank, int s
     const uint64_t cap = ss_reads::padded(total);
     uint64_t real_cap = cap;                             // (a kept block may be larger)
     if (ss::big_malloc((void **)&flat, cap, &real_cap) != hipSuccess) return done(SS_ENOMEM);
-    hipLaunchKernelGGL(fq_copy_kernel, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, st, d_text, d_ls, d_len1, d_off, n_rec, flat);
+    unsigned long long masked = 0;
+    if (min_qual > 0) {
+        FQ(hipMallocAsync((void **)&d_masked, 8, st));
+        FQ(hipMemsetAsync(d_masked, 0, 8, st));
+        hipLaunchKernelGGL(fq_copy_kernel<true>, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, st, d_text, d_ls, d_len1, d_off, n_rec, flat,
+                           33u + (uint32_t)min_qual, d_masked);
+        FQ(hipMemcpyAsync(&masked, d_masked, 8, hipMemcpyDeviceToHost, st));
+    } else {
+        hipLaunchKernelGGL(fq_copy_kernel<false>, dim3((unsigned)((n_rec + 15) / 16)), dim3(256), 0, st, d_text, d_ls, d_len1, d_off, n_rec, flat, 0u,
+                           (unsigned long long *)nullptr);
+    }
     hipLaunchKernelGGL(fq_pad_kernel, dim3(1), dim3(64), 0, st, flat, total, cap);
     FQ(hipGetLastError());
     FQ(hipStreamSynchronize(st));
+    mask_count(masked);
 #undef FQ
     *d_flat = flat;
     *flat_len = total;

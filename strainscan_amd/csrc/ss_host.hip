@@ -134,7 +134,47 @@ struct ss_reader {
     int overlap = 30;
     std::string tail;      // last `overlap` bases of the current record (for cut records)
     bool need_tail = false;
+    // base-quality mask (the threshold as ss_reader_open found it): a FASTQ record's bases are held back in `rec` until
+    // its qualities have been read, masked there, and only then drained into the caller's buffers (cut like any other)
+    int min_qual = 0;
+    std::string rec;
+    size_t rec_pos = 0;
+    bool rec_open = false, draining = false;
+    uint64_t rec_masked = 0;
 };
+
+namespace ss {
+static std::atomic<int> g_min_base_qual{0};
+static std::atomic<uint64_t> g_mask_bases{0}, g_mask_noqual{0};
+int min_base_qual() { return g_min_base_qual.load(); }
+void mask_count(uint64_t bases, uint64_t bam_records_without_qual)
+{
+    if (bases) g_mask_bases += bases;
+    if (bam_records_without_qual) g_mask_noqual += bam_records_without_qual;
+}
+}  // namespace ss
+
+namespace {
+// seq[i] = 'N' where q[i] < thr, i < n; returns how many.  Most 16-byte groups of a read hold no low quality: those are
+// compared and left alone (a byte loop that rewrote every base added 40 % to a 20 M-read text load, profiles/r10_min_qual_ab.md)
+inline uint64_t mask_span(char *seq, const char *q, uint64_t n, unsigned thr)
+{
+    uint64_t c = 0, i = 0;
+#ifdef SS_HOST_X86
+    const __m128i t = _mm_set1_epi8((char)thr), zero = _mm_setzero_si128();
+    for (; i + 16 <= n; i += 16) {
+        const __m128i v = _mm_loadu_si128((const __m128i *)(q + i));
+        // thr -sat- q is zero exactly where q >= thr
+        unsigned low = ~(unsigned)_mm_movemask_epi8(_mm_cmpeq_epi8(_mm_subs_epu8(t, v), zero)) & 0xFFFFu;
+        c += (uint64_t)__builtin_popcount(low);
+        for (; low; low &= low - 1) seq[i + (unsigned)__builtin_ctz(low)] = 'N';
+    }
+#endif
+    for (; i < n; i++)
+        if ((unsigned char)q[i] < thr) { seq[i] = 'N'; c++; }
+    return c;
+}
+}  // namespace
 
 namespace {
 
@@ -158,6 +198,21 @@ bool reader_fill(ss_reader *r)
 extern "C" {
 
 int ss_version(void) { return 100; }
+
+int ss_set_min_base_qual(int q)
+{
+    if (q < 0 || q > 93) return SS_ERANGE;
+    ss::g_min_base_qual.store(q);
+    return SS_OK;
+}
+int ss_get_min_base_qual(void) { return ss::g_min_base_qual.load(); }
+int ss_mask_counters(uint64_t out[2])
+{
+    if (!out) return SS_EINVAL;
+    out[0] = ss::g_mask_bases.load();
+    out[1] = ss::g_mask_noqual.load();
+    return SS_OK;
+}
 
 const char *ss_strerror(int code)
 {
@@ -1256,6 +1311,7 @@ int ss_reader_open(const char *const *paths, int n_paths, ss_reader **out)
         if (paths[i][0]) r->paths.emplace_back(paths[i]);  // '' = no second file (StrainScan.py:182)
     }
     r->in.resize(4 << 20);
+    r->min_qual = ss::min_base_qual();
     for (const auto &p : r->paths) {  // fail early on unreadable inputs
         gzFile f = gzopen(p.c_str(), "rb");
         if (!f) { delete r; return SS_EIO; }
@@ -1285,8 +1341,24 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
     if (!r || !out || !out_len || cap < 4096) return SS_EINVAL;
     uint64_t o = 0, recs = 0;
     const uint64_t ov = (uint64_t)r->overlap;
+    // base-quality mask: the bases of a FASTQ record go to r->rec, not to `out`, until its qualities have been read
+    const bool mq = r->min_qual > 0;
+    const unsigned thr = 33u + (unsigned)r->min_qual;
     auto in_seq = [&] { return r->st == ss_reader::FA_SEQ_BOL || r->st == ss_reader::FA_SEQ ||
-                               r->st == ss_reader::FQ_SEQ_BOL || r->st == ss_reader::FQ_SEQ; };
+                               (!mq && (r->st == ss_reader::FQ_SEQ_BOL || r->st == ss_reader::FQ_SEQ)); };
+    auto cut_here = [&] {  // cut inside a sequence: remember the last `overlap` bases
+        uint64_t s = o;
+        while (s > 0 && out[s - 1] != '\n' && o - s < ov) s--;
+        r->tail.assign(out + s, out + o);
+        r->need_tail = true;
+    };
+    auto release = [&] {   // the held-back record is complete: it goes out next
+        r->rec_open = false;
+        r->draining = true;
+        r->rec_pos = 0;
+        ss::mask_count(r->rec_masked);
+        r->rec_masked = 0;
+    };
     if (r->need_tail) {  // continuation of a record cut at the previous buffer end
         memcpy(out, r->tail.data(), r->tail.size());
         o = r->tail.size();
@@ -1298,12 +1370,28 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
         r->tail.clear();
     };
     for (;;) {
+        if (r->draining) {
+            // exactly what the unmasked states do with the same bases: fill up to cap - 2, cut there, '\n' behind the last base
+            if (o + 2 >= cap) { cut_here(); break; }
+            if (r->rec_pos < r->rec.size()) {
+                const size_t n = (size_t)std::min<uint64_t>(r->rec.size() - r->rec_pos, cap - 2 - o);
+                memcpy(out + o, r->rec.data() + r->rec_pos, n);
+                o += n;
+                r->rec_pos += n;
+            } else {
+                end_record();
+                r->rec.clear();
+                r->draining = false;
+            }
+            continue;
+        }
         if (r->in_pos >= r->in_len) {
             if (!r->f) {
                 // finish a record that the previous file left open, then open the next file
                 if (r->st != ss_reader::START) {
                     if (in_seq()) end_record();
                     r->st = ss_reader::START;
+                    if (r->rec_open) { release(); continue; }      // (its qualities, if any, ended with the file)
                 }
                 if (r->file_idx >= r->paths.size()) break;
                 r->f = gzopen(r->paths[r->file_idx++].c_str(), "rb");
@@ -1314,12 +1402,7 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
         }
         // leave room for the longest thing one step can append: a line chunk is bounded below
         if (o + 2 >= cap) {
-            if (in_seq()) {  // cut inside a sequence: remember the last `overlap` bases
-                uint64_t s = o;
-                while (s > 0 && out[s - 1] != '\n' && o - s < ov) s--;
-                r->tail.assign(out + s, out + o);
-                r->need_tail = true;
-            }
+            if (in_seq()) cut_here();
             break;
         }
         const char *p = r->in.data() + r->in_pos;
@@ -1339,10 +1422,12 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
             const void *nl = memchr(p, '\n', avail);
             if (!nl) { r->in_pos = r->in_len; break; }
             r->in_pos += (size_t)((const char *)nl - p) + 1;
+            if (mq && r->st == ss_reader::FQ_HDR) { r->rec.clear(); r->rec_open = true; }
             r->st = (r->st == ss_reader::FA_HDR)   ? ss_reader::FA_SEQ_BOL
                     : (r->st == ss_reader::FQ_HDR) ? ss_reader::FQ_SEQ_BOL
                     : (r->qlen < r->seqlen)        ? ss_reader::FQ_QUAL
                                                    : ss_reader::START;
+            if (r->rec_open && r->st == ss_reader::START) release();      // (a record without bases)
             break;
         }
         case ss_reader::FA_SEQ_BOL:
@@ -1350,7 +1435,7 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
             else r->st = ss_reader::FA_SEQ;
             break;
         case ss_reader::FQ_SEQ_BOL:
-            if (*p == '+') { end_record(); r->st = ss_reader::FQ_PLUS; }
+            if (*p == '+') { if (!mq) end_record(); r->st = ss_reader::FQ_PLUS; }
             else r->st = ss_reader::FQ_SEQ;
             break;
         case ss_reader::FA_SEQ:
@@ -1359,9 +1444,12 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
             size_t n = nl ? (size_t)((const char *)nl - p) : avail;
             const uint64_t room = cap - 2 - o;
             bool whole = true;
-            if (n > room) { n = (size_t)room; whole = false; }
-            memcpy(out + o, p, n);
-            o += n;
+            if (mq && r->st == ss_reader::FQ_SEQ) r->rec.append(p, n);
+            else {
+                if (n > room) { n = (size_t)room; whole = false; }
+                memcpy(out + o, p, n);
+                o += n;
+            }
             r->seqlen += n;
             r->in_pos += n;
             if (whole && nl) {
@@ -1373,9 +1461,11 @@ int ss_reader_next(ss_reader *r, char *out, uint64_t cap, uint64_t *out_len, uin
         case ss_reader::FQ_QUAL: {
             const void *nl = memchr(p, '\n', avail);
             size_t n = nl ? (size_t)((const char *)nl - p) : avail;
+            if (r->rec_open && r->qlen < r->seqlen)
+                r->rec_masked += mask_span(&r->rec[r->qlen], p, std::min<uint64_t>(n, r->seqlen - r->qlen), thr);
             r->qlen += n;
             r->in_pos += n + (nl ? 1 : 0);
-            if (nl && r->qlen >= r->seqlen) r->st = ss_reader::START;
+            if (nl && r->qlen >= r->seqlen) { r->st = ss_reader::START; if (r->rec_open) release(); }
             break;
         }
         }
@@ -1389,7 +1479,10 @@ int ss_fastx_to_flat(const char *text, uint64_t len, char *out, uint64_t *out_le
 {
     if ((len && !text) || !out || !out_len) return SS_EINVAL;
     // same grammar as ss_reader_next, on an in-memory text (single pass, no cuts)
-    uint64_t i = 0, o = 0, recs = 0;
+    // base-quality mask: a record's bases are in `out` when its qualities come by
+    uint64_t i = 0, o = 0, recs = 0, masked = 0;
+    const int min_qual = ss::min_base_qual();
+    const unsigned thr = min_qual > 0 ? 33u + (unsigned)min_qual : 0u;
     const char *t = text;
     while (i < len) {
         if (t[i] == '\n') { i++; continue; }
@@ -1407,6 +1500,7 @@ int ss_fastx_to_flat(const char *text, uint64_t len, char *out, uint64_t *out_le
             recs++;
         } else if (t[i] == '@') {
             uint64_t seqlen = 0, qlen = 0;
+            const uint64_t o0 = o;
             const void *nl = memchr(t + i, '\n', len - i);
             i = nl ? (uint64_t)((const char *)nl - t) + 1 : len;
             while (i < len && t[i] != '+') {
@@ -1424,6 +1518,7 @@ int ss_fastx_to_flat(const char *text, uint64_t len, char *out, uint64_t *out_le
             while (i < len && qlen < seqlen) {
                 nl = memchr(t + i, '\n', len - i);
                 uint64_t e = nl ? (uint64_t)((const char *)nl - t) : len;
+                if (thr) masked += mask_span(out + o0 + qlen, t + i, std::min<uint64_t>(e - i, seqlen - qlen), thr);
                 qlen += e - i;
                 i = nl ? e + 1 : len;
             }
@@ -1432,6 +1527,7 @@ int ss_fastx_to_flat(const char *text, uint64_t len, char *out, uint64_t *out_le
             i = nl ? (uint64_t)((const char *)nl - t) + 1 : len;
         }
     }
+    ss::mask_count(masked);
     *out_len = o;
     if (n_records) *n_records = recs;
     return SS_OK;

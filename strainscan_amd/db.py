@@ -62,7 +62,37 @@ RESIDENT_LIMIT_BYTES = int(float(os.environ.get("SS_READS_RESIDENT_GB", "160")) 
 
 
 def _reads_key(paths, rank, world):
-    return tuple((os.path.abspath(p), os.path.getmtime(p), os.path.getsize(p)) for p in paths if p) + (rank, world)
+    # (the base-quality mask is part of what a set holds: the same files under another threshold are another set)
+    return tuple((os.path.abspath(p), os.path.getmtime(p), os.path.getsize(p)) for p in paths if p) + (rank, world, _lib.get_min_base_qual())
+
+
+MASK_REPORT = {"on": False, "done": False}      # the commands' -q line (StrainScan.apply_min_base_qual turns it on)
+
+
+def report_mask(masked=None, no_qual=None, bases=None):
+    """-q's one line on stderr: right after the load of the resident reads (its own figures), or -- reads that were streamed
+    for every scan -- at the end of the command, over all passes.  Once per process."""
+    q = _lib.get_min_base_qual()
+    if not MASK_REPORT["on"] or MASK_REPORT["done"] or not q:
+        return
+    MASK_REPORT["done"] = True
+    import sys
+    from . import dist
+    rank, world = dist.rank_world()
+    if masked is None:
+        c = _lib.mask_counters()
+        masked, no_qual = c["masked"], c["bam_no_qual"]
+    line = "min_base_qual %d: %d bases masked" % (q, masked)
+    if bases:
+        line += " of %d read (%.3f %%)" % (bases, 100.0 * masked / bases)
+    else:
+        line += " (over every pass of the streamed input)"
+    if no_qual:
+        line += "; %d BAM records carried no qualities and were not masked" % no_qual
+    if world > 1:
+        line = "rank %d of %d (its share): " % (rank, world) + line
+    print(line, file=sys.stderr)
+    sys.stderr.flush()
 
 
 def resident_reads(paths):
@@ -83,8 +113,13 @@ def resident_reads(paths):
                 old.close()
             _READS.clear()
             # (.gz under torch.distributed: all ranks take the same inflate path for a file, dist.load_agreed)
+            before = _lib.mask_counters() if MASK_REPORT["on"] else None
             rs = dist.load_agreed([p for p in paths if p], lambda use: _lib.ReadSet(use, rank, world), discard=lambda r: r.close())
             _READS[key] = rs
+            if before is not None:
+                after, inf = _lib.mask_counters(), rs.info()
+                report_mask(after["masked"] - before["masked"], after["bam_no_qual"] - before["bam_no_qual"],
+                            inf["n_bases"] - inf["n_records"])
     return rs
 
 
@@ -647,7 +682,7 @@ class TreeImage:
 
 
 def _scan_key(paths):
-    return tuple((os.path.abspath(p), os.path.getmtime(p), os.path.getsize(p)) for p in paths if p)
+    return tuple((os.path.abspath(p), os.path.getmtime(p), os.path.getsize(p)) for p in paths if p) + (("min_base_qual", _lib.get_min_base_qual()),)
 
 
 def scan_images(images, paths):

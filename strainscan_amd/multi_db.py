@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -154,6 +154,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
 def main(argv=None):
     args, dbs, opts = parse_args(argv)
     StrainScan.refuse_cram(args.input_fq, args.input_fq2)         # (reads the sample's first bytes: after the checks above)
+    StrainScan.apply_min_base_qual(args.min_base_qual)
     out_dir = StrainScan.output_dir(args.out_dir, os.getcwd())
     os.makedirs(out_dir, exist_ok=True)
     from . import dist
