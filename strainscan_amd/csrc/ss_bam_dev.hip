@@ -309,37 +309,6 @@ int bam_decode(const uint8_t *s, uint64_t n, int shard_rank, int shard_world, ch
     return SS_OK;
 }
 
-// What a path holds, from its first bytes (and the start of its first gzip member): BAM_NO (anything else: FASTA/FASTQ, plain
-// or gzip), BAM_GZ (a BAM: BGZF or any gzip around "BAM\1"), BAM_RAW (an uncompressed BAM stream), BAM_CRAM.
-int bam_probe(const char *path)
-{
-    if (!path || !path[0]) return BAM_NO;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return BAM_NO;
-    uint8_t head[1 << 16];
-    const ssize_t got = pread(fd, head, sizeof head, 0);
-    close(fd);
-    if (got < 4) return BAM_NO;
-    if (!memcmp(head, "CRAM", 4)) return BAM_CRAM;
-    if (!memcmp(head, "BAM\1", 4)) return BAM_RAW;
-    if (head[0] != 0x1f || head[1] != 0x8b) return BAM_NO;
-    z_stream z;
-    memset(&z, 0, sizeof z);
-    if (inflateInit2(&z, 16 + 15) != Z_OK) return BAM_NO;
-    uint8_t out[4] = {0, 0, 0, 0};
-    z.next_in = head;
-    z.avail_in = (uInt)got;
-    z.next_out = out;
-    z.avail_out = 4;
-    while (z.avail_out > 0) {
-        const int r = inflate(&z, Z_SYNC_FLUSH);
-        if (r != Z_OK) break;                         // (the end of the member, or damage: a BAM needs 4 bytes of it)
-    }
-    const bool bam = z.avail_out == 0 && !memcmp(out, "BAM\1", 4);
-    inflateEnd(&z);
-    return bam ? BAM_GZ : BAM_NO;
-}
-
 // The segments of the inflated stream: the text of every BGZF member (ISIZE of each trailer), cut to 64 KB pieces where a
 // member is larger (a plain gzip BAM is one member).  -> starts, ascending, the first 0
 std::vector<uint64_t> bam_segments(const uint8_t *in, uint64_t in_n, uint64_t n)
@@ -574,7 +543,7 @@ int gz_bam_to_flat_dev(const char *path, int shard_rank, int shard_world, char *
     return rc;
 }
 
-// The host path for one BAM file (BAM_GZ or BAM_RAW): the stream inflated on the host, decoded -> *flat (malloc, padded like a
+// The host path for one BAM file (INPUT_BAM_GZ or INPUT_BAM_RAW): the stream inflated on the host, decoded -> *flat (malloc, padded like a
 // block of ss_reads).  SS_OK, SS_EIO (damaged: a member's CRC or length, a record, the header), SS_ENOMEM.
 int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, char **flat, uint64_t *flat_len, uint64_t *n_records)
 {
@@ -583,7 +552,7 @@ int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, c
     const uint8_t *s = nullptr;
     void *map = nullptr;
     uint64_t map_n = 0;
-    if (kind == BAM_RAW) {
+    if (kind == INPUT_BAM_RAW) {
         const int fd = open(path, O_RDONLY);
         if (fd < 0) return SS_EIO;
         struct stat sb;
@@ -652,7 +621,7 @@ int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, c
 int bam_input(const char *path, int kind, int shard_rank, int shard_world, const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &on_dev,
               const std::function<int(char *, uint64_t, uint64_t)> &on_host)
 {
-    if (kind == BAM_GZ && gz_on_gpu()) {
+    if (kind == INPUT_BAM_GZ && gz_on_gpu()) {
         char *d = nullptr;
         uint64_t len = 0, cap = 0, nrec = 0;
         const int r = gz_bam_to_flat_dev(path, shard_rank, shard_world, &d, &len, &cap, &nrec);
@@ -698,7 +667,8 @@ int ss_bam_counters(uint64_t out[4])
 int ss_input_kind(const char *path, int *kind)
 {
     if (!path || !kind) return SS_EINVAL;
-    *kind = ss::bam_probe(path);
+    const int k = ss::input_kind(path);
+    *kind = k <= ss::INPUT_CRAM ? k : 0;            // (gzip or no file at all: "anything else")
     return SS_OK;
 }
 

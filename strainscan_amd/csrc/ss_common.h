@@ -121,7 +121,7 @@ struct ss_db {
 #include <mutex>
 
 // A sample's reads resident in HBM (ss_ingest.hip loads them, ss_reorder.hip orders them for locality).
-namespace ss { hipError_t big_malloc(void **p, uint64_t bytes, uint64_t *got = nullptr); void big_put(void *p, uint64_t cap); }      // (below)
+namespace ss { hipError_t big_malloc(void **p, uint64_t bytes, uint64_t *got = nullptr); void big_put(void *p, uint64_t cap); bool ingest_trace(); }      // (below)
 struct ss_reads {
     // Blocks live back to back in a few large device slabs; every block is followed by at least one '\n'
     // and padded with '\n' to a multiple of 16 bytes, so a slab is itself one flat base block: one scan
@@ -165,7 +165,7 @@ struct ss_reads {
             sl.cap = std::max<uint64_t>(need, slabs.empty() ? std::max<uint64_t>(first_slab, 64ull << 20) : 512ull << 20);
             const auto t0 = std::chrono::steady_clock::now();
             if (ss::big_malloc((void **)&sl.d, sl.cap, &sl.cap) != hipSuccess) return nullptr;
-            if (getenv("SS_INGEST_TRACE"))
+            if (ss::ingest_trace())
                 fprintf(stderr, "[ingest] slab of %.0f MB: %.4f s\n", sl.cap / 1e6,
                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
             slabs.push_back(sl);
@@ -194,18 +194,14 @@ int build_mini(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64_t n
 // the same index built on the device (ss_build_dev.hip); anything but SS_OK / SS_EKEY: nothing was built, use the host build
 int build_mini_dev(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64_t n_rows, int upper_keys);
 int mark_solid(ss_db *db);      // PG_SOLID flags of the bucket references, after either build (ss_mini.hip)
-using BlockSink = std::function<int(const char *h_buf, char *d_buf, uint64_t len, hipStream_t stream)>;
-int parse_file_parallel(ss_db::Worker *workers, const char *path, int shard_rank, int shard_world,
-                        uint64_t *n_records, uint64_t *n_bases, bool *handled, const BlockSink &sink, bool copy = true);
-int parse_text_parallel(ss_db::Worker *workers, const char *text, uint64_t n, const char *path, int shard_rank,
-                        int shard_world, uint64_t *n_records, uint64_t *n_bases, bool *handled, const BlockSink &sink,
-                        bool copy = true);
 struct InflatedText { char *p = nullptr; uint64_t n = 0; };
 bool inflate_whole(const char *path, uint64_t budget, char **text, uint64_t *len, int mode, unsigned threads);
 uint64_t inflate_budget_bytes();
 hipStream_t ingest_stream(unsigned i);   // a few process-wide non-blocking streams (creating one costs ~13 ms)
 void free_later(char *p);
-std::vector<InflatedText> inflate_gz_inputs(const char *const *paths, int n_paths);
+bool ingest_trace();                     // SS_INGEST_TRACE, read once: the "[ingest]" stage lines of ss_ingest.hip and ss_scan.hip
+// the gzip inputs `gz` (indices into paths) inflated whole on the host, all at once: texts[i] where it worked, left empty where not
+void inflate_gz_inputs(const char *const *paths, const std::vector<int> &gz, std::vector<InflatedText> &texts);
 // unless SS_GZ_GPU=0: .gz inputs are inflated on the device (ss_ginflate.hip) and strict four-line FASTQ is turned into the flat
 // base block there (ss_fastq_dev.hip)
 bool gz_on_gpu();
@@ -232,24 +228,53 @@ bool gpu_gunzip_range(const uint8_t *in, uint64_t in_n, char **text_dev, void **
 int gz_fastq_pieces_dev(const char *path, uint64_t ticket, const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &flat);
 int gz_fastq_to_flat_dev(const char *path, int shard_rank, int shard_world, char **d_flat, uint64_t *flat_len, uint64_t *flat_cap,
                          uint64_t *n_records, char **text, uint64_t *text_len);
-// every gzip input of a call through gz_fastq_to_flat_dev, one host thread per file: `flat(i, d_flat, len, cap, n_records)`
-// takes over the device buffer of input i (called from that file's thread; returns an SS_* code); inputs that were
-// only inflated come back as host texts in `texts`; done[i] = 1 for the inputs that need nothing more
-int gz_inputs_on_device(const char *const *paths, int n_paths, int shard_rank, int shard_world,
-                        const std::function<int(int, char *, uint64_t, uint64_t, uint64_t)> &flat, std::vector<InflatedText> &texts,
+// the gzip inputs `gz` (indices into paths) through gz_fastq_to_flat_dev, one host thread per file (range mode:
+// gz_fastq_pieces_dev): `flat(d_flat, len, cap, n_records)` takes over a device buffer (called from that file's thread; returns
+// an SS_* code); inputs that were only inflated come back as host texts in `texts`; done[i] = 1 for the inputs that need nothing
+// more.  Nothing happens under SS_GZ_GPU=0.  SS_EAGAIN: strict policy and the device declined one (every chain has been served).
+int gz_inputs_on_device(const char *const *paths, const std::vector<int> &gz, int shard_rank, int shard_world,
+                        const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &flat, std::vector<InflatedText> &texts,
                         std::vector<char> &done);
-// BAM input (ss_bam_dev.hip).  bam_probe: what a path holds, from its first bytes and the start of its first gzip member.
-enum { BAM_NO = 0, BAM_GZ = 1, BAM_RAW = 2, BAM_CRAM = 3 };
-int bam_probe(const char *path);
-// one BAM input (BAM_GZ or BAM_RAW) of a load or a scan: on the device unless SS_GZ_GPU=0 or policy 2, on the host for what the
-// device declines (policy 0 and 2; policy 1: SS_EAGAIN).  on_dev takes over a big_malloc'ed device block (len, cap, n_records),
-// on_host a malloc'ed host block padded like a block of ss_reads (len, n_records; the callee frees it).  SS_EIO: damaged.
+// What an input path holds (ss_ingest.hip), from ONE look at its first 64 KB: the magic, and for a gzip file the start of its
+// first member ("BAM\1": BGZF or any gzip around a BAM stream).  "" is the absent second mate; a path that cannot be read counts
+// as text (the reader reports it).  Values up to INPUT_CRAM are those of ss_input_kind.
+enum InputKind { INPUT_TEXT = 0, INPUT_BAM_GZ = 1, INPUT_BAM_RAW = 2, INPUT_CRAM = 3, INPUT_GZ = 4, INPUT_EMPTY = 5 };
+int input_kind(const char *path);
+// one BAM input (INPUT_BAM_GZ or INPUT_BAM_RAW) of a load or a scan (ss_bam_dev.hip): on the device unless SS_GZ_GPU=0 or policy
+// 2, on the host for what the device declines (policy 0 and 2; policy 1: SS_EAGAIN).  on_dev takes over a big_malloc'ed device
+// block (len, cap, n_records), on_host a malloc'ed host block padded like a block of ss_reads (len, n_records; the callee frees
+// it).  SS_EIO: damaged.
 int bam_input(const char *path, int kind, int shard_rank, int shard_world, const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &on_dev,
               const std::function<int(char *, uint64_t, uint64_t)> &on_host);
-int scan_file_parallel(ss_db *db, const char *path, uint64_t *n_records, uint64_t *n_bases, bool *handled, int shard_rank = 0,
-                       int shard_world = 1);
-int scan_text_parallel(ss_db *db, const char *text, uint64_t n, uint64_t *n_records, uint64_t *n_bases, bool *handled,
-                       int shard_rank = 0, int shard_world = 1);
+// What a consumer of input files does with their flat base blocks: ss_scan_files_shard scans them into a table, ss_reads_load
+// keeps them.  ingest_inputs sends every input down the ladder -- BAM, .gz on the device, .gz inflated on the host, the chunked
+// parse, the sequential reader -- and hands each block to the entry of the rung it came from.  `records` / `bases` add up what
+// was handed over (the reader entry counts its own blocks).
+struct InputSink {
+    std::atomic<uint64_t> records{0}, bases{0};
+    // chunked parse (parse_text_parallel): the workers whose pinned buffers it uses; copy: it copies each block to the worker's
+    // device buffer before parsed_block sees it
+    ss_db::Worker *workers = nullptr;
+    bool copy = true;
+    // sequential reader: records longer than a block are cut with this overlap into blocks of reader_cap bytes; block b of file f
+    // is the rank's own when (b + (reader_shard_by_file ? f : 0)) % shard_world == shard_rank; one thread per file, or one file
+    // after the other
+    int reader_overlap = 30;
+    uint64_t reader_cap = 32ull << 20;
+    bool reader_shard_by_file = false, reader_threads = false;
+    // a flat block already on the device, padded like a block of ss_reads (a BAM: big_malloc'ed; a .gz reduced to its sequence
+    // lines: hipMalloc'ed): the sink owns it from here (ss_reads::adopt takes either: big_put, which lets a set's slabs go, frees
+    // what it does not keep with hipFree).  May be called from several threads at once.
+    virtual int device_block(int kind, char *d, uint64_t len, uint64_t cap) = 0;
+    // a parse worker's block: h_buf pinned (64 bytes of slack behind len), d_buf its copy when `copy`, enqueued on `stream`
+    virtual int parsed_block(const char *h_buf, char *d_buf, uint64_t len, hipStream_t stream) = 0;
+    // where the reader of `file` puts its next block (room for reader_cap bytes), then that block: every block of the file is
+    // shown, `mine` says whether it is this rank's
+    virtual int reader_buffer(int file, char **buf) = 0;
+    virtual int reader_block(int file, char *buf, uint64_t len, uint64_t n_records, bool mine) = 0;
+    virtual ~InputSink() = default;
+};
+int ingest_inputs(const char *const *paths, int n_paths, int shard_rank, int shard_world, InputSink &sink);
 // (packed: the block is a packed binned slab, n counts its positions -- ss_scan_dev.h IN_PACKED)
 int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, unsigned blocks,
                      uint64_t n_tiles, bool binned = false, uint64_t set_id = 0, bool packed = false);

@@ -19,6 +19,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
@@ -215,6 +216,41 @@ void free_later(char *p)
     if (p) std::thread([p] { free(p); }).detach();
 }
 
+bool ingest_trace()
+{
+    static const bool on = getenv("SS_INGEST_TRACE") != nullptr;
+    return on;
+}
+
+int input_kind(const char *path)
+{
+    if (!path[0]) return INPUT_EMPTY;
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return INPUT_TEXT;
+    uint8_t head[1 << 16];
+    const ssize_t got = pread(fd, head, sizeof head, 0);
+    close(fd);
+    if (got < 4) return INPUT_TEXT;
+    if (!memcmp(head, "CRAM", 4)) return INPUT_CRAM;
+    if (!memcmp(head, "BAM\1", 4)) return INPUT_BAM_RAW;
+    if (head[0] != 0x1f || head[1] != 0x8b) return INPUT_TEXT;
+    z_stream z;
+    memset(&z, 0, sizeof z);
+    if (inflateInit2(&z, 16 + 15) != Z_OK) return INPUT_GZ;
+    uint8_t out[4] = {0, 0, 0, 0};
+    z.next_in = head;
+    z.avail_in = (uInt)got;
+    z.next_out = out;
+    z.avail_out = 4;
+    while (z.avail_out > 0) {
+        const int r = inflate(&z, Z_SYNC_FLUSH);
+        if (r != Z_OK) break;                         // (the end of the member, or damage: a BAM needs 4 bytes of it)
+    }
+    const bool bam = z.avail_out == 0 && !memcmp(out, "BAM\1", 4);
+    inflateEnd(&z);
+    return bam ? INPUT_BAM_GZ : INPUT_GZ;
+}
+
 uint64_t inflate_budget_bytes()
 {
     if (const char *e = getenv("SS_INFLATE_MAX_GB")) return (uint64_t)(atof(e) * 1e9);
@@ -362,79 +398,51 @@ int ss_gz_inflate_to_file(const char *path, const char *out_path, int threads, u
 
 namespace ss {
 
-// All gzip inputs of a call inflated concurrently (one thread per file); entry i stays empty when path i is not
-// gzip or cannot be inflated here.  The caller frees the texts.
-std::vector<InflatedText> inflate_gz_inputs(const char *const *paths, int n_paths)
+// All gzip inputs of a call inflated concurrently (one thread per file); entry i stays empty when path i cannot be inflated
+// here.  The caller frees the texts.
+void inflate_gz_inputs(const char *const *paths, const std::vector<int> &gz, std::vector<InflatedText> &texts)
 {
-    std::vector<InflatedText> out((size_t)std::max(0, n_paths));
-    const uint64_t budget = inflate_budget_bytes() / (uint64_t)std::max(1, n_paths);
-    std::vector<int> gz;
-    for (int i = 0; i < n_paths; i++) {
-        if (!paths[i] || !paths[i][0]) continue;
-        unsigned char magic[2] = {0, 0};
-        FILE *f = fopen(paths[i], "rb");
-        if (!f) continue;
-        if (fread(magic, 1, 2, f) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) gz.push_back(i);
-        fclose(f);
-    }
-    if (gz.empty()) return out;
+    if (gz.empty()) return;
+    const uint64_t budget = inflate_budget_bytes() / (uint64_t)std::max<size_t>(1, texts.size());
     // the files inflate concurrently and share the CPUs the process may use (not the machine's hardware threads)
     const unsigned per_file = std::max(1u, std::min(32u, host_cpus() / (unsigned)gz.size()));
     std::vector<std::thread> pool;
     for (int i : gz)
-        pool.emplace_back([&out, paths, i, budget, per_file] { if (!inflate_whole(paths[i], budget, &out[i].p, &out[i].n, 0, per_file)) out[i].p = nullptr; });
+        pool.emplace_back([&texts, paths, i, budget, per_file] { if (!inflate_whole(paths[i], budget, &texts[i].p, &texts[i].n, 0, per_file)) texts[i].p = nullptr; });
     for (auto &th : pool) th.join();
-    return out;
 }
 
-int gz_inputs_on_device(const char *const *paths, int n_paths, int shard_rank, int shard_world,
-                        const std::function<int(int, char *, uint64_t, uint64_t, uint64_t)> &flat, std::vector<InflatedText> &texts,
+int gz_inputs_on_device(const char *const *paths, const std::vector<int> &gz, int shard_rank, int shard_world,
+                        const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &flat, std::vector<InflatedText> &texts,
                         std::vector<char> &done)
 {
-    texts.assign((size_t)std::max(0, n_paths), InflatedText());
-    done.assign((size_t)std::max(0, n_paths), 0);
-    if (!gz_on_gpu()) return SS_OK;
-    std::vector<int> gz;
-    for (int i = 0; i < n_paths; i++) {
-        if (!paths[i] || !paths[i][0]) continue;
-        unsigned char magic[2] = {0, 0};
-        FILE *f = fopen(paths[i], "rb");
-        if (!f) continue;
-        if (fread(magic, 1, 2, f) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) gz.push_back(i);
-        fclose(f);
-    }
-    if (gz.empty()) return SS_OK;
+    if (!gz_on_gpu() || gz.empty()) return SS_OK;
+    int device = 0;
+    hipGetDevice(&device);
     if (gz_range_active() && gz_policy() == 1) {
         // the ranks share every file's inflation (ss_gz_set_range); a rank keeps all records that begin in its slices.  The
         // chain of messages between the ranks is per file and the files use it in the order of the paths (gz_range_ticket), but
         // the files are in flight together: while one file's messages travel, the next one's slices are uploaded and inflated
-        int device = 0;
-        hipGetDevice(&device);
         std::mutex mu;
         int rc = SS_OK;
         std::vector<uint64_t> ticket;
         for (size_t q = 0; q < gz.size(); q++) ticket.push_back(gz_range_ticket());
-        constexpr bool serial = false;
         std::vector<std::thread> pool;
         for (size_t q = 0; q < gz.size(); q++) {
-            auto one = [&, q] {
+            pool.emplace_back([&, q] {
                 const int i = gz[q];
                 hipSetDevice(device);
-                const int r = gz_fastq_pieces_dev(paths[i], ticket[q], [&, i](char *d, uint64_t len, uint64_t cap, uint64_t nrec) { return flat(i, d, len, cap, nrec); });
+                const int r = gz_fastq_pieces_dev(paths[i], ticket[q], flat);
                 std::lock_guard<std::mutex> g(mu);
                 if (r == 0) done[i] = 1;
                 else if (r == 1) rc = SS_EAGAIN;      // (the chain of the remaining files is still served: every rank goes through all of them)
                 else if (rc == SS_OK) rc = r;
-            };
-            if (serial) one();
-            else pool.emplace_back(one);
-            if (!serial && pool.size() == 2 && q + 1 < gz.size()) { pool.front().join(); pool.erase(pool.begin()); }      // two files in flight: a pair
+            });
+            if (pool.size() == 2 && q + 1 < gz.size()) { pool.front().join(); pool.erase(pool.begin()); }      // two files in flight: a pair
         }
         for (auto &th : pool) th.join();
         return rc;
     }
-    int device = 0;
-    hipGetDevice(&device);
     std::atomic<int> err(SS_OK);
     std::vector<std::thread> pool;
     for (int i : gz)
@@ -444,7 +452,7 @@ int gz_inputs_on_device(const char *const *paths, int n_paths, int shard_rank, i
             uint64_t len = 0, cap = 0, nrec = 0;
             const int r = gz_fastq_to_flat_dev(paths[i], shard_rank, shard_world, &d, &len, &cap, &nrec, &texts[i].p, &texts[i].n);
             if (r == 0) {
-                const int rc = flat(i, d, len, cap, nrec);
+                const int rc = flat(d, len, cap, nrec);
                 if (rc != SS_OK) err = rc;
                 done[i] = 1;
             } else if (r == 1 && gz_policy() == 1) {
@@ -455,34 +463,12 @@ int gz_inputs_on_device(const char *const *paths, int n_paths, int shard_rank, i
     return err;
 }
 
-// returns SS_OK and *handled = true when the file was scanned here; *handled = false => caller
-// must use the sequential reader for this file
-int scan_file_parallel(ss_db *db, const char *path, uint64_t *n_records, uint64_t *n_bases, bool *handled, int shard_rank,
-                       int shard_world)
-{
-    // SS_INGEST_ZEROCOPY=1: the kernel streams the flat block straight out of the pinned host buffer
-    // (every base is read once, with 16-byte loads) instead of waiting for a DMA copy of it
-    constexpr bool zero_copy = false;
-    return parse_file_parallel(db->workers, path, shard_rank, shard_world, n_records, n_bases, handled,
-                               [db](const char *h_buf, char *d_buf, uint64_t len, hipStream_t stream) {
-                                   return ss_scan_flat_dev(db, zero_copy ? h_buf : d_buf, len, stream);
-                               }, !zero_copy);
-}
+static int parse_text_parallel(InputSink &sink, const char *t, uint64_t n, const char *path, int shard_rank, int shard_world, bool *handled);
 
-int scan_text_parallel(ss_db *db, const char *text, uint64_t n, uint64_t *n_records, uint64_t *n_bases, bool *handled,
-                       int shard_rank, int shard_world)
-{
-    return parse_text_parallel(db->workers, text, n, nullptr, shard_rank, shard_world, n_records, n_bases, handled,
-                               [db](const char *, char *d_buf, uint64_t len, hipStream_t stream) {
-                                   return ss_scan_flat_dev(db, d_buf, len, stream);
-                               }, true);
-}
-
-// Parse `path` with worker threads; each flat block (already copied to the worker's device buffer
-// on `stream`) is handed to `sink`.  Chunks c with c % shard_world != shard_rank are skipped
-// (multi-GPU read sharding without parsing the other ranks' share).
-int parse_file_parallel(ss_db::Worker *workers, const char *path, int shard_rank, int shard_world,
-                        uint64_t *n_records, uint64_t *n_bases, bool *handled, const BlockSink &sink, bool copy)
+// Parse the plain file `path` with worker threads; each flat block (already copied to the worker's device buffer on `stream`
+// when sink.copy) goes to sink.parsed_block.  Chunks c with c % shard_world != shard_rank are skipped (multi-GPU read sharding
+// without parsing the other ranks' share).  SS_OK and *handled = false: the sequential reader must take this file.
+static int parse_file_parallel(InputSink &sink, const char *path, int shard_rank, int shard_world, bool *handled)
 {
     *handled = false;
     const int fd = open(path, O_RDONLY);
@@ -493,19 +479,18 @@ int parse_file_parallel(ss_db::Worker *workers, const char *path, int shard_rank
     const char *t = (const char *)mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
     close(fd);
     if (t == MAP_FAILED) return SS_OK;
-    if ((unsigned char)t[0] == 0x1f) { munmap((void *)t, n); return SS_OK; }
     madvise((void *)t, n, MADV_SEQUENTIAL);
-    const int rc = parse_text_parallel(workers, t, n, path, shard_rank, shard_world, n_records, n_bases, handled, sink, copy);
+    const int rc = parse_text_parallel(sink, t, n, path, shard_rank, shard_world, handled);
     munmap((void *)t, n);
     return rc;
 }
 
 // The chunked parse of a text that is in memory: a mapped file (`path` then names it: chunks are pread() from it)
 // or a buffer (path == nullptr: an inflated .gz, parsed where it lies).
-int parse_text_parallel(ss_db::Worker *workers, const char *t, uint64_t n, const char *path, int shard_rank,
-                        int shard_world, uint64_t *n_records, uint64_t *n_bases, bool *handled, const BlockSink &sink,
-                        bool copy)
+static int parse_text_parallel(InputSink &sink, const char *t, uint64_t n, const char *path, int shard_rank, int shard_world, bool *handled)
 {
+    ss_db::Worker *const workers = sink.workers;
+    const bool copy = sink.copy;
     *handled = false;
     bool fastq = true;
     if (n < (4u << 20) || !head_is_simple(t, n, fastq)) return SS_OK;
@@ -540,7 +525,7 @@ int parse_text_parallel(ss_db::Worker *workers, const char *t, uint64_t n, const
     if (use_pread && fd2 < 0) return SS_EIO;
     int device = 0;
     hipGetDevice(&device);
-    static const bool trace = getenv("SS_INGEST_TRACE") != nullptr;
+    const bool trace = ingest_trace();
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
     auto worker = [&](unsigned wid) {
@@ -588,7 +573,7 @@ int parse_text_parallel(ss_db::Worker *workers, const char *t, uint64_t n, const
             int rc = ss_fastx_to_flat(src, clen, h_buf, &out_len, &nr);
             if (rc != SS_OK) { err = rc; break; }
             if (copy && hipMemcpyAsync(d_buf, h_buf, out_len, hipMemcpyHostToDevice, stream) != hipSuccess) { err = SS_EHIP; break; }
-            rc = sink(h_buf, d_buf, out_len, stream);
+            rc = sink.parsed_block(h_buf, d_buf, out_len, stream);
             if (rc != SS_OK) { err = rc; break; }
             if (hipEventRecord(W.done, stream) != hipSuccess || hipEventSynchronize(W.done) != hipSuccess) { err = SS_EHIP; break; }   // buffers are reused
             recs += nr;
@@ -601,10 +586,116 @@ int parse_text_parallel(ss_db::Worker *workers, const char *t, uint64_t n, const
     if (trace) fprintf(stderr, "[ingest] %s: %zu chunks, %u threads, done %.4f s\n", path ? path : "(inflated text)", n_chunks, nthreads, since());
     if (fd2 >= 0) close(fd2);
     if (err != SS_OK) return err;
-    *n_records += recs;
-    *n_bases += bases;
+    sink.records += recs;
+    sink.bases += bases;
     *handled = true;
     return SS_OK;
+}
+
+// The one ladder every list of input files goes down (ss_scan_files_shard, ss_reads_load); what becomes of a block is the
+// sink's business.  Each path is looked at once (input_kind) before anything is decoded; then, stage by stage:
+//   1. BAM inputs (ss_bam_dev.hip), decoded whole -- on the device first -- so the stages below never see them (nor do the chain
+//      tickets of range mode).  They come first: a set in file order (SS_READS_ORDER=file) holds a BAM's reads in front of the
+//      other inputs' whatever the order of the paths (the order inside each file is kept; counts do not depend on it).
+//   2. (not SS_GZ_GPU=0) .gz inputs inflated AND reduced to their sequence lines on the device.  What that path only inflated
+//      (not strict four-line FASTQ) arrives as text.
+//   3. the remaining .gz inputs inflated whole on the host, all at once.
+//   4. texts and plain files of 4 MB and more: the chunked parse on worker threads.
+//   5. everything else (multi-line records, small files, .gz nobody could inflate whole): the sequential reader.
+// Strict policy (ss_gz_set_policy(1)) and the device declined a BAM: the call still goes through stage 2 -- in range mode every
+// rank serves the chain of every .gz file -- and then returns SS_EAGAIN.  SS_INGEST=sequential (an A/B knob): stages 2 to 4 are
+// left out.
+int ingest_inputs(const char *const *paths, int n_paths, int shard_rank, int shard_world, InputSink &sink)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    const char *mode = getenv("SS_INGEST");
+    const bool parallel = !(mode && !strcmp(mode, "sequential"));
+    std::vector<int> kind((size_t)n_paths), gz;
+    for (int i = 0; i < n_paths; i++) {
+        if (!paths[i]) return SS_EINVAL;
+        kind[i] = input_kind(paths[i]);
+        if (kind[i] == INPUT_GZ) gz.push_back(i);
+    }
+    if (std::count(kind.begin(), kind.end(), (int)INPUT_CRAM)) return SS_EINVAL;
+    auto device_block = [&sink](int k, char *d, uint64_t len, uint64_t cap, uint64_t nrec) {
+        sink.records += nrec;
+        sink.bases += len;
+        return sink.device_block(k, d, len, cap);
+    };
+    bool bam_declined = false;
+    for (int i = 0; i < n_paths && !bam_declined; i++) {
+        if (kind[i] != INPUT_BAM_GZ && kind[i] != INPUT_BAM_RAW) continue;
+        const int k = kind[i];
+        const int r = bam_input(paths[i], k, shard_rank, shard_world,
+            [&](char *d, uint64_t len, uint64_t cap, uint64_t nrec) { return device_block(k, d, len, cap, nrec); },
+            [&](char *h, uint64_t len, uint64_t nrec) {       // what the host decoded: uploaded, then a device block like the other
+                char *d = nullptr;
+                uint64_t cap = ss_reads::padded(len);
+                int e = big_malloc((void **)&d, cap, &cap) == hipSuccess ? SS_OK : SS_ENOMEM;
+                if (e == SS_OK && hipMemcpy(d, h, ss_reads::padded(len), hipMemcpyHostToDevice) != hipSuccess) { big_put(d, cap); e = SS_EHIP; }
+                free(h);
+                return e == SS_OK ? device_block(k, d, len, cap, nrec) : e;
+            });
+        if (r == SS_EAGAIN) bam_declined = true;          // (the call ends in SS_EAGAIN: no point in decoding the others)
+        else if (r != SS_OK) return r;
+    }
+    std::vector<InflatedText> texts((size_t)n_paths);
+    std::vector<char> done((size_t)n_paths, 0);
+    int rc = SS_OK;
+    if (parallel)
+        rc = gz_inputs_on_device(paths, gz, shard_rank, shard_world,
+                                 [&](char *d, uint64_t len, uint64_t cap, uint64_t nrec) { return device_block(INPUT_GZ, d, len, cap, nrec); }, texts, done);
+    if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;      // (the chain of every .gz file has been served above)
+    if (rc == SS_OK && parallel) {
+        std::vector<int> left;
+        for (int i : gz) if (!done[i] && !texts[i].p) left.push_back(i);
+        inflate_gz_inputs(paths, left, texts);
+    }
+    if (ingest_trace()) fprintf(stderr, "[ingest] gz inputs inflated at %.4f s\n", since());
+    std::vector<int> seq_files;
+    for (int i = 0; i < n_paths && rc == SS_OK; i++) {
+        if ((kind[i] != INPUT_TEXT && kind[i] != INPUT_GZ) || done[i]) continue;      // '' = no second file (StrainScan.py:182)
+        bool handled = false;
+        if (texts[i].p) rc = parse_text_parallel(sink, texts[i].p, texts[i].n, nullptr, shard_rank, shard_world, &handled);
+        else if (parallel && kind[i] == INPUT_TEXT) rc = parse_file_parallel(sink, paths[i], shard_rank, shard_world, &handled);
+        free_later(texts[i].p);
+        texts[i].p = nullptr;
+        if (ingest_trace()) fprintf(stderr, "[ingest] file %d parsed at %.4f s\n", i, since());
+        if (rc == SS_OK && !handled) seq_files.push_back(i);
+    }
+    for (auto &tx : texts) free(tx.p);
+    if (rc != SS_OK || seq_files.empty()) return rc;
+    // one thread PER FILE where the sink allows it, so the two mates of a paired .fastq.gz sample inflate concurrently (zlib is
+    // the limiter there).  shard_world > 1: the reader still walks the whole input (a record grammar has no entry points), but
+    // only the rank's own blocks are the sink's to keep
+    std::atomic<int> err(SS_OK);
+    int device = 0;
+    hipGetDevice(&device);
+    auto one_file = [&](int fi) {
+        hipSetDevice(device);
+        ss_reader *rd = nullptr;
+        int r = ss_reader_open(&paths[fi], 1, &rd);
+        if (r) { err = r; return; }
+        ss_reader_set_overlap(rd, sink.reader_overlap);
+        const uint64_t first = sink.reader_shard_by_file ? (uint64_t)fi : 0;
+        for (uint64_t blk = 0; err == SS_OK; blk++) {
+            char *buf = nullptr;
+            uint64_t len = 0, nr = 0;
+            if ((r = sink.reader_buffer(fi, &buf)) != SS_OK || (r = ss_reader_next(rd, buf, sink.reader_cap, &len, &nr)) != SS_OK) { err = r; break; }
+            if (len == 0) break;
+            r = sink.reader_block(fi, buf, len, nr, (int)((blk + first) % (uint64_t)shard_world) == shard_rank);
+            if (r) { err = r; break; }
+        }
+        ss_reader_close(rd);
+    };
+    std::vector<std::thread> pool;
+    for (int fi : seq_files) {
+        if (sink.reader_threads) pool.emplace_back(one_file, fi);
+        else if (err == SS_OK) one_file(fi);
+    }
+    for (auto &th : pool) th.join();
+    return err;
 }
 
 }  // namespace ss
@@ -632,6 +723,54 @@ namespace {
 // 20 x 27 MB costs more than parsing a small sample); one load at a time
 ss_db::Worker g_read_workers[ss_db::MAX_WORKERS];
 std::mutex g_read_workers_mu;
+
+// ss_reads_load's end of the input ladder (ss::ingest_inputs): every block becomes part of the resident set
+struct LoadSink : ss::InputSink {
+    ss_reads *R;
+    std::vector<std::vector<char>> reader_bufs;      // one block per file: the reader files run on a thread each
+    LoadSink(ss_reads *r, int n_paths) : R(r), reader_bufs((size_t)n_paths)
+    {
+        workers = g_read_workers;
+        copy = false;
+        reader_overlap = 30;
+        reader_shard_by_file = true;
+        reader_threads = true;
+    }
+    // a block that is on the device already becomes a slab as it is
+    int device_block(int, char *d, uint64_t len, uint64_t cap) override
+    {
+        R->adopt(d, cap, len);
+        return SS_OK;
+    }
+    // the parse thread's pinned block goes straight to its place in a slab
+    int parsed_block(const char *h_buf, char *, uint64_t len, hipStream_t stream) override
+    {
+        char *dst = R->reserve(len);
+        if (!dst) return SS_ENOMEM;
+        const uint64_t plen = ss_reads::padded(len);
+        memset(const_cast<char *>(h_buf) + len, '\n', plen - len);       // the pinned buffer has 64 bytes of slack
+        return hipMemcpyAsync(dst, h_buf, plen, hipMemcpyHostToDevice, stream) == hipSuccess ? SS_OK : SS_EHIP;
+    }
+    int reader_buffer(int file, char **buf) override
+    {
+        reader_bufs[(size_t)file].resize(reader_cap + 32);
+        *buf = reader_bufs[(size_t)file].data();
+        return SS_OK;
+    }
+    int reader_block(int, char *buf, uint64_t len, uint64_t n_records, bool mine) override
+    {
+        if (buf[len - 1] != '\n') R->has_cut_record = true;
+        if (!mine) return SS_OK;
+        char *dst = R->reserve(len);
+        if (!dst) return SS_ENOMEM;
+        const uint64_t plen = ss_reads::padded(len);
+        memset(buf + len, '\n', plen - len);
+        if (hipMemcpy(dst, buf, plen, hipMemcpyHostToDevice) != hipSuccess) return SS_EHIP;
+        records += n_records;
+        bases += len;
+        return SS_OK;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -674,7 +813,6 @@ int ss_reads_load(const char *const *paths, int n_paths, int shard_rank, int sha
     if (!paths || n_paths < 1 || !out || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) return SS_EINVAL;
     ss_reads *R = new (std::nothrow) ss_reads();
     if (!R) return SS_ENOMEM;
-    uint64_t recs = 0, bases = 0;
     {   // first slab: FASTQ text is a little over 2 bytes per base, this rank's share of it
         uint64_t text = 0;
         for (int i = 0; i < n_paths; i++) {
@@ -686,146 +824,17 @@ int ss_reads_load(const char *const *paths, int n_paths, int shard_rank, int sha
     std::lock_guard<std::mutex> pool_lock(g_read_workers_mu);
     const auto t_load = std::chrono::steady_clock::now();
     auto load_since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_load).count(); };
-    // BAM inputs (ss_bam_dev.hip), told apart by their inflated magic identically on every rank, are decoded whole here -- on the
-    // device first -- and the paths below never see them (nor do the chain tickets of range mode).  They come first: a set in file
-    // order (SS_READS_ORDER=file) holds a BAM's reads in front of the other inputs' whatever the order of the paths (the order
-    // inside each file is kept; counts do not depend on it).
-    std::vector<const char *> no_bam(paths, paths + n_paths);
-    // strict policy (ss_gz_set_policy(1)) and the device declined a BAM: the call still goes through the other inputs -- in range
-    // mode every rank serves the chain of every .gz file -- and returns SS_EAGAIN at the end
-    bool bam_declined = false;
-    {
-        int rc_bam = SS_OK;
-        for (int i = 0; i < n_paths && rc_bam == SS_OK; i++) {
-            const int kind = paths[i] ? ss::bam_probe(paths[i]) : ss::BAM_NO;
-            if (kind == ss::BAM_NO) continue;
-            no_bam[i] = "";
-            if (kind == ss::BAM_CRAM) { rc_bam = SS_EINVAL; break; }
-            if (bam_declined) continue;                  // (the call ends in SS_EAGAIN: no point in decoding the others)
-            rc_bam = ss::bam_input(paths[i], kind, shard_rank, shard_world,
-                [&](char *d, uint64_t len, uint64_t cap, uint64_t nrec) {
-                    R->adopt(d, cap, len);
-                    recs += nrec;
-                    bases += len;
-                    return (int)SS_OK;
-                },
-                [&](char *h, uint64_t len, uint64_t nrec) {
-                    char *d = nullptr;
-                    uint64_t cap = ss_reads::padded(len);
-                    int r = ss::big_malloc((void **)&d, cap, &cap) == hipSuccess ? SS_OK : SS_ENOMEM;
-                    if (r == SS_OK && hipMemcpy(d, h, ss_reads::padded(len), hipMemcpyHostToDevice) != hipSuccess) { ss::big_put(d, cap); r = SS_EHIP; }
-                    free(h);
-                    if (r != SS_OK) return r;
-                    R->adopt(d, cap, len);
-                    recs += nrec;
-                    bases += len;
-                    return (int)SS_OK;
-                });
-            if (rc_bam == SS_EAGAIN) { bam_declined = true; rc_bam = SS_OK; }
-        }
-        if (rc_bam != SS_OK) { ss_reads_destroy(R); return rc_bam; }
-        paths = no_bam.data();
-    }
-    // the parse thread's pinned block goes straight to its place in a slab
-    auto keep = [R](const char *h_buf, char *, uint64_t len, hipStream_t stream) -> int {
-        char *dst = R->reserve(len);
-        if (!dst) return SS_ENOMEM;
-        const uint64_t plen = ss_reads::padded(len);
-        memset(const_cast<char *>(h_buf) + len, '\n', plen - len);       // the pinned buffer has 64 bytes of slack
-        return hipMemcpyAsync(dst, h_buf, plen, hipMemcpyHostToDevice, stream) == hipSuccess ? SS_OK : SS_EHIP;
-    };
-    int rc = SS_OK;
-    // plain files: chunked worker-thread path; everything else (gzip, multi-line records, small files)
-    // goes through the sequential reader -- one thread PER FILE, so the two mates of a paired
-    // .fastq.gz sample inflate concurrently (zlib is the limiter there)
-    std::vector<int> seq_files;
-    // (not SS_GZ_GPU=0) .gz inputs are inflated AND reduced to their sequence lines on the device; the block becomes a
-    // slab as it is.  What that path only inflated (not strict four-line FASTQ) arrives as text, the rest goes on below.
-    std::vector<ss::InflatedText> texts;
-    std::vector<char> on_device;
-    std::vector<const char *> rest(paths, paths + n_paths);
-    {
-        std::atomic<uint64_t> drecs(0), dbases(0);
-        rc = ss::gz_inputs_on_device(paths, n_paths, shard_rank, shard_world, [&](int, char *d, uint64_t len, uint64_t cap, uint64_t nrec) {
-            R->adopt(d, cap, len);
-            drecs += nrec;
-            dbases += len;
-            return (int)SS_OK;
-        }, texts, on_device);
-        recs += drecs;
-        bases += dbases;
-        for (int i = 0; i < n_paths; i++)
-            if (on_device[i] || texts[i].p) rest[i] = "";
-    }
-    if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;      // (the chain of every .gz file has been served above)
-    if (rc == SS_OK) {
-        std::vector<ss::InflatedText> more = ss::inflate_gz_inputs(rest.data(), n_paths);     // .gz inputs, inflated concurrently
-        if (texts.empty()) texts = more;
-        else for (int i = 0; i < n_paths; i++) if (more[i].p) texts[i] = more[i];
-    }
-    if (on_device.empty()) on_device.assign((size_t)n_paths, 0);
-    if (getenv("SS_INGEST_TRACE")) fprintf(stderr, "[ingest] ss_reads_load: gz inputs inflated at %.4f s\n", load_since());
-    for (int i = 0; i < n_paths && rc == SS_OK; i++) {
-        if (!paths[i]) { rc = SS_EINVAL; break; }
-        if (!paths[i][0] || on_device[i]) continue;
-        bool handled = false;
-        if (texts[i].p)
-            rc = ss::parse_text_parallel(g_read_workers, texts[i].p, texts[i].n, nullptr, shard_rank, shard_world, &recs,
-                                         &bases, &handled, keep, false);
-        else
-            rc = ss::parse_file_parallel(g_read_workers, paths[i], shard_rank, shard_world, &recs, &bases, &handled, keep, false);
-        ss::free_later(texts[i].p);
-        texts[i].p = nullptr;
-        if (getenv("SS_INGEST_TRACE")) fprintf(stderr, "[ingest] ss_reads_load: file %d parsed at %.4f s\n", i, load_since());
-        if (rc == SS_OK && !handled) seq_files.push_back(i);
-    }
-    for (auto &tx : texts) free(tx.p);
-    if (rc == SS_OK && !seq_files.empty()) {
-        std::atomic<int> err(SS_OK);
-        std::atomic<uint64_t> srecs(0), sbases(0);
-        int device = 0;
-        hipGetDevice(&device);
-        auto one_file = [&](int fi) {
-            hipSetDevice(device);
-            ss_reader *rd = nullptr;
-            int r = ss_reader_open(&paths[fi], 1, &rd);
-            if (r) { err = r; return; }
-            ss_reader_set_overlap(rd, 30);
-            const uint64_t cap = 32ull << 20;
-            std::vector<char> buf(cap + 32);
-            for (uint64_t blk = 0; err == SS_OK; blk++) {
-                uint64_t len = 0, nr = 0;
-                r = ss_reader_next(rd, buf.data(), cap, &len, &nr);
-                if (r) { err = r; break; }
-                if (len == 0) break;
-                if (buf[len - 1] != '\n') R->has_cut_record = true;
-                if ((int)((blk + (uint64_t)fi) % (uint64_t)shard_world) != shard_rank) continue;
-                char *dst = R->reserve(len);
-                if (!dst) { err = SS_ENOMEM; break; }
-                const uint64_t plen = ss_reads::padded(len);
-                memset(buf.data() + len, '\n', plen - len);
-                if (hipMemcpy(dst, buf.data(), plen, hipMemcpyHostToDevice) != hipSuccess) { err = SS_EHIP; break; }
-                srecs += nr;
-                sbases += len;
-            }
-            ss_reader_close(rd);
-        };
-        std::vector<std::thread> pool;
-        for (int fi : seq_files) pool.emplace_back(one_file, fi);
-        for (auto &th : pool) th.join();
-        rc = err;
-        recs += srecs;
-        bases += sbases;
-    }
+    LoadSink sink(R, n_paths);
+    int rc = ss::ingest_inputs(paths, n_paths, shard_rank, shard_world, sink);
     if (rc != SS_OK) { ss_reads_destroy(R); return rc; }
     const double t_parsed = load_since();
     if (hipDeviceSynchronize() != hipSuccess) { ss_reads_destroy(R); return SS_EHIP; }
-    if (getenv("SS_INGEST_TRACE")) fprintf(stderr, "[ingest] ss_reads_load: files done %.4f s, device idle %.4f s\n", t_parsed, load_since());
-    R->n_records = recs;
-    R->n_bases = bases;
+    if (ss::ingest_trace()) fprintf(stderr, "[ingest] ss_reads_load: files done %.4f s, device idle %.4f s\n", t_parsed, load_since());
+    R->n_records = sink.records;
+    R->n_bases = sink.bases;
     rc = ss::reads_order_for_locality(R);      // unless SS_READS_ORDER=file (ss_reorder.hip)
     if (rc != SS_OK) { ss_reads_destroy(R); return rc; }
-    if (getenv("SS_INGEST_TRACE")) fprintf(stderr, "[ingest] ss_reads_load: ordered for locality at %.4f s\n", load_since());
+    if (ss::ingest_trace()) fprintf(stderr, "[ingest] ss_reads_load: ordered for locality at %.4f s\n", load_since());
     *out = R;
     return SS_OK;
 }

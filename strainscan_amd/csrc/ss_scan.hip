@@ -463,47 +463,57 @@ int ss_scan_flat_host(ss_db *db, const char *bases, uint64_t n)
     return SS_OK;
 }
 
-// shard_world > 1: the reader still walks the whole input (a record grammar has no entry points), but only every
-// shard_world-th block is copied and scanned
-static int scan_files_sequential(ss_db *db, const char *const *paths, int n_paths, uint64_t *n_records,
-                                 uint64_t *n_bases, int shard_rank = 0, int shard_world = 1)
-{
-    int rc = ensure_staging(db);
-    if (rc) return rc;
-    ss_reader *rd = nullptr;
-    rc = ss_reader_open(paths, n_paths, &rd);
-    if (rc) return rc;
-    ss_reader_set_overlap(rd, db->k - 1);
-    uint64_t recs = 0, total = 0, blk = 0;
-    int b = 0;
+}  // extern "C"
+
+namespace {
+// ss_scan_files_shard's end of the input ladder (ss::ingest_inputs): every block is scanned into the table and let go
+struct ScanSink : ss::InputSink {
+    ss_db *db;
+    std::mutex mu;                       // one scan at a time on the default stream
+    int b = 0;                           // the reader's blocks go through the table's two pinned staging buffers in turn
     bool used[2] = {false, false};
-    for (;;) {
-        if (used[b]) {
-            hipError_t e = hipEventSynchronize(db->stage_free[b]);
-            if (e != hipSuccess) { ss_reader_close(rd); ss::set_last_error("hipEventSynchronize", __FILE__, __LINE__, e); return SS_EHIP; }
-        }
-        uint64_t len = 0, nr = 0;
-        rc = ss_reader_next(rd, db->h_stage[b], db->stage_bytes, &len, &nr);
-        if (rc) { ss_reader_close(rd); return rc; }
-        if (len == 0) break;
-        recs += nr;
-        total += len;
-        if ((int)(blk++ % (uint64_t)shard_world) != shard_rank) continue;
-        hipError_t e = hipMemcpyAsync(db->d_stage[b], db->h_stage[b], len, hipMemcpyHostToDevice, db->streams[b]);
-        if (e != hipSuccess) { ss_reader_close(rd); ss::set_last_error("hipMemcpyAsync", __FILE__, __LINE__, e); return SS_EHIP; }
-        rc = ss_scan_flat_dev(db, db->d_stage[b], len, db->streams[b]);
-        if (rc) { ss_reader_close(rd); return rc; }
-        hipEventRecord(db->stage_free[b], db->streams[b]);
+    explicit ScanSink(ss_db *d) : db(d)
+    {
+        workers = d->workers;
+        reader_overlap = d->k - 1;
+        reader_cap = STAGE_BYTES;
+    }
+    // the device path's block of a .gz was hipMalloc'ed, a BAM's comes from (and goes back to) the kept large blocks
+    int device_block(int kind, char *d, uint64_t len, uint64_t cap) override
+    {
+        std::lock_guard<std::mutex> g(mu);
+        int r = ss_scan_flat_dev(db, d, ss_reads::padded(len), nullptr);
+        if (r == SS_OK && hipStreamSynchronize(nullptr) != hipSuccess) r = SS_EHIP;
+        if (kind == ss::INPUT_GZ) hipFree(d);
+        else ss::big_put(d, cap);
+        return r;
+    }
+    int parsed_block(const char *, char *d_buf, uint64_t len, hipStream_t stream) override { return ss_scan_flat_dev(db, d_buf, len, stream); }
+    int reader_buffer(int, char **buf) override
+    {
+        const int rc = ensure_staging(db);
+        if (rc) return rc;
+        if (used[b]) SS_HIP(hipEventSynchronize(db->stage_free[b]));
+        *buf = db->h_stage[b];
+        return SS_OK;
+    }
+    int reader_block(int, char *, uint64_t len, uint64_t n_records, bool mine) override
+    {
+        records += n_records;
+        bases += len;
+        if (!mine) return SS_OK;
+        SS_HIP(hipMemcpyAsync(db->d_stage[b], db->h_stage[b], len, hipMemcpyHostToDevice, db->streams[b]));
+        const int rc = ss_scan_flat_dev(db, db->d_stage[b], len, db->streams[b]);
+        if (rc) return rc;
+        SS_HIP(hipEventRecord(db->stage_free[b], db->streams[b]));
         used[b] = true;
         b ^= 1;
+        return SS_OK;
     }
-    ss_reader_close(rd);
-    for (int i = 0; i < 2; i++)
-        if (used[i]) SS_HIP(hipStreamSynchronize(db->streams[i]));
-    *n_records += recs;
-    *n_bases += total;
-    return SS_OK;
-}
+};
+}  // namespace
+
+extern "C" {
 
 int ss_scan_files(ss_db *db, const char *const *paths, int n_paths, uint64_t *n_records, uint64_t *n_bases)
 {
@@ -519,92 +529,13 @@ int ss_scan_files_shard(ss_db *db, const char *const *paths, int n_paths, int sh
     // it).  On a busy device (three ranks sharing one GPU in the tests) the memset was seen to run AFTER the first chunk's
     // scan, once in ~30 runs: a small file is one chunk, one rank's whole share, and all its counts were gone.
     SS_HIP(hipStreamSynchronize(nullptr));
-    uint64_t recs = 0, total = 0;
-    const char *seq_env = getenv("SS_INGEST");
-    const bool allow_parallel = !(seq_env && !strcmp(seq_env, "sequential"));
-    for (int i = 0; i < n_paths; i++)
-        if (!paths[i]) return SS_EINVAL;
-    // BAM inputs (ss_bam_dev.hip): decoded whole, on the device first, and scanned before the other inputs; the paths below never
-    // see them.  Strict policy and the device declined one: the other inputs still go through (in range mode every rank serves
-    // the chain of every .gz file) and the call returns SS_EAGAIN at the end.
-    std::vector<const char *> no_bam(paths, paths + n_paths);
-    bool bam_declined = false;
-    for (int i = 0; i < n_paths; i++) {
-        const int kind = ss::bam_probe(paths[i]);
-        if (kind == ss::BAM_NO) continue;
-        if (kind == ss::BAM_CRAM) return SS_EINVAL;
-        no_bam[i] = "";
-        if (bam_declined) continue;
-        const int r = ss::bam_input(paths[i], kind, shard_rank, shard_world,
-            [&](char *d, uint64_t len, uint64_t cap, uint64_t nrec) {
-                int e = ss_scan_flat_dev(db, d, ss_reads::padded(len), nullptr);
-                if (e == SS_OK && hipStreamSynchronize(nullptr) != hipSuccess) e = SS_EHIP;
-                ss::big_put(d, cap);
-                recs += nrec;
-                total += len;
-                return e;
-            },
-            [&](char *h, uint64_t len, uint64_t nrec) {
-                char *d = nullptr;
-                const uint64_t plen = ss_reads::padded(len);
-                int e = hipMalloc((void **)&d, plen) == hipSuccess ? SS_OK : SS_ENOMEM;
-                if (e == SS_OK && hipMemcpy(d, h, plen, hipMemcpyHostToDevice) != hipSuccess) e = SS_EHIP;
-                if (e == SS_OK) e = ss_scan_flat_dev(db, d, plen, nullptr);
-                if (e == SS_OK && hipStreamSynchronize(nullptr) != hipSuccess) e = SS_EHIP;
-                if (d) hipFree(d);
-                free(h);
-                recs += nrec;
-                total += len;
-                return e;
-            });
-        if (r == SS_EAGAIN) bam_declined = true;
-        else if (r != SS_OK) return r;
-    }
-    paths = no_bam.data();
-    // .gz inputs are inflated whole (libdeflate, all files at once) and parsed like plain text when possible
-    std::vector<ss::InflatedText> texts;
-    std::vector<char> on_device((size_t)n_paths, 0);
-    int rc = SS_OK;
-    if (allow_parallel) {
-        // (not SS_GZ_GPU=0) inflated and reduced to the sequence lines on the device (ss_ginflate.hip, ss_fastq_dev.hip),
-        // scanned from there
-        std::vector<const char *> rest(paths, paths + n_paths);
-        {
-            std::mutex mu;
-            rc = ss::gz_inputs_on_device(paths, n_paths, shard_rank, shard_world, [&](int, char *d, uint64_t len, uint64_t, uint64_t nrec) {
-                std::lock_guard<std::mutex> g(mu);                    // one scan at a time on the table's stream
-                int r = ss_scan_flat_dev(db, d, ss_reads::padded(len), nullptr);
-                if (r == SS_OK && hipStreamSynchronize(nullptr) != hipSuccess) r = SS_EHIP;
-                hipFree(d);
-                recs += nrec;
-                total += len;
-                return r;
-            }, texts, on_device);
-            for (int i = 0; i < n_paths; i++)
-                if (on_device[i] || texts[i].p) rest[i] = "";
-        }
-        if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;      // (the chain of every .gz file has been served above)
-        if (rc == SS_OK) {
-            std::vector<ss::InflatedText> more = ss::inflate_gz_inputs(rest.data(), n_paths);
-            if (texts.empty()) texts = more;
-            else for (int i = 0; i < n_paths; i++) if (more[i].p) texts[i] = more[i];
-        }
-    }
-    for (int i = 0; i < n_paths && rc == SS_OK; i++) {
-        if (!paths[i][0] || on_device[i]) continue;            // '' = no second file (StrainScan.py:182)
-        bool handled = false;
-        if (allow_parallel) {
-            if (!texts.empty() && texts[i].p) rc = ss::scan_text_parallel(db, texts[i].p, texts[i].n, &recs, &total, &handled, shard_rank, shard_world);
-            else rc = ss::scan_file_parallel(db, paths[i], &recs, &total, &handled, shard_rank, shard_world);
-        }
-        if (!texts.empty()) { ss::free_later(texts[i].p); texts[i].p = nullptr; }
-        if (rc == SS_OK && !handled) rc = scan_files_sequential(db, &paths[i], 1, &recs, &total, shard_rank, shard_world);
-    }
-    for (auto &tx : texts) free(tx.p);
-    if (rc == SS_OK && bam_declined) rc = SS_EAGAIN;          // (SS_INGEST=sequential: nothing was in range mode)
+    ScanSink sink(db);
+    const int rc = ss::ingest_inputs(paths, n_paths, shard_rank, shard_world, sink);
     if (rc) return rc;
-    if (n_records) *n_records = recs;
-    if (n_bases) *n_bases = total;
+    for (int i = 0; i < 2; i++)
+        if (sink.used[i]) SS_HIP(hipStreamSynchronize(db->streams[i]));
+    if (n_records) *n_records = sink.records;
+    if (n_bases) *n_bases = sink.bases;
     return SS_OK;
 }
 
