@@ -96,7 +96,7 @@ struct ss_db {
     uint32_t *d_counts = nullptr;      // [n_slots] occurrences per slot (accumulated by scans)
     int expect_hits = 0;               // ss_db_expect_hits: most read k-mers are in the table (a layer-2 cluster table)
     uint64_t probe_set = 0;            // the resident read set (ss_reads::serial) whose first tiles were last probed against this
-    int probe_comb = 0;                // table, and what they said: add the hits up in LDS (ss_mini.hip choose_comb)
+    int probe_comb = 0;                // table, and what they said: add the hits up in LDS (ss_mini.hip launch_scan_mini)
     double probe_runs_per_tile = 0;    // found runs per tile of that probe (ss_db_info_ex)
     uint32_t *d_slot_of_row = nullptr; // [n_rows]   slot owning row i, SS_NO_SLOT if none
     uint8_t *d_row_valid = nullptr;    // [n_rows]   1 iff row i is a key of match_results
@@ -276,14 +276,15 @@ struct InputSink {
 };
 int ingest_inputs(const char *const *paths, int n_paths, int shard_rank, int shard_world, InputSink &sink);
 // (packed: the block is a packed binned slab, n counts its positions -- ss_scan_dev.h IN_PACKED)
-int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, unsigned blocks,
-                     uint64_t n_tiles, bool binned = false, uint64_t set_id = 0, bool packed = false);
+int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned = false, uint64_t set_id = 0,
+                     bool packed = false);
 int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned,
                            bool packed = false);
 // the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster
 // table: the combining variant under binned reads), or none at all.  One launch takes tables of one kind (ss_scan_multi_launches).
 enum { MULTI_BLOOM = 0, MULTI_EXPECT = 1, MULTI_PLAIN = 2 };
 int multi_kind(const ss_db *db);
+bool may_share_pass(const ss_db *db);      // may go through launch_scan_mini_multi, with tables of its k and kind (ss_mini.hip)
 // Layer 2 (ss_l2.hip, ss_enet.hip) works on the CALLING THREAD's own stream and takes its temporaries from the stream-ordered
 // pool (round 5): the clusters of a sample are solved on several host threads at once, and on the legacy default stream every
 // synchronous copy of one thread waited for the kernels of all the others, every hipFree for the whole device (four 5 M-row

@@ -949,64 +949,4 @@ int ss_reads_info(const ss_reads *R, uint64_t *n_records, uint64_t *n_bases, uin
     return SS_OK;
 }
 
-int ss_scan_reads(ss_db *db, const ss_reads *R, void *stream)
-{
-    if (!db || !R) return SS_EINVAL;
-    int k = 0;
-    ss_db_info(db, nullptr, nullptr, nullptr, &k);
-    if (R->has_cut_record && k != 31) return SS_ERANGE;   // cut records carry a 30-base overlap
-    for (const auto &sl : R->slabs) {
-        if (!sl.used) continue;
-        int rc = ss::scan_flat_dev(db, sl.d, sl.positions(), stream, sl.binned, R->serial, sl.packed);
-        if (rc) return rc;
-    }
-    return SS_OK;
-}
-
-// The resident reads against SEVERAL tables in one pass (Vote_Strain_L2_Lasso_new_sp.py:295-296 loops over the identified
-// clusters, :354-372 re-reads the FASTQ for each; strainscan_amd/multi_db.py counts one sample against the tree tables of several
-// databases): tables of the minimizer layout go four at a time through one kernel that makes a tile's codes, minimizers and runs
-// once; anything else is scanned on its own.  A launch takes tables of one k and one filter kind (ss::multi_kind): tree tables
-// behind their own Bloom filters, tables that expect hits (the combining variant under binned reads), tables with neither.
-int ss_scan_reads_multi(ss_db *const *dbs, int n_dbs, const ss_reads *R, void *stream)
-{
-    if (!dbs || n_dbs < 1 || !R) return SS_EINVAL;
-    std::vector<ss_db *> mini_all;
-    for (int i = 0; i < n_dbs; i++) {
-        if (!dbs[i]) return SS_EINVAL;
-        for (int j = 0; j < i; j++) if (dbs[j] == dbs[i]) return SS_EINVAL;           // a table twice would count twice
-        int k = 0;
-        ss_db_info(dbs[i], nullptr, nullptr, nullptr, &k);
-        if (R->has_cut_record && k != 31) return SS_ERANGE;
-        // (several tables per pass: k = 31, and k >= 20 where scan_mini_kernel with k at run time serves every table -- ss_mini.hip
-        //  launch_scan_mini; the Bloom kind has a several-tables instantiation at k = 31 only)
-        const bool multi = dbs[i]->layout == 1 && k >= 20 && (k == 31 || ss::multi_kind(dbs[i]) != ss::MULTI_BLOOM);
-        if (multi) mini_all.push_back(dbs[i]);
-        else { int rc = ss_scan_reads(dbs[i], R, stream); if (rc) return rc; }
-    }
-    // the tables of ONE k and one filter kind go through the several-tables kernel together (a tile's minimizers are made once per k)
-    std::stable_sort(mini_all.begin(), mini_all.end(), [](const ss_db *a, const ss_db *b) {
-        return a->k != b->k ? a->k < b->k : ss::multi_kind(a) < ss::multi_kind(b);
-    });
-    constexpr int group = 4;
-    for (size_t k0 = 0; k0 < mini_all.size();) {
-    size_t k1 = k0;
-    while (k1 < mini_all.size() && mini_all[k1]->k == mini_all[k0]->k && ss::multi_kind(mini_all[k1]) == ss::multi_kind(mini_all[k0])) k1++;
-    std::vector<ss_db *> mini(mini_all.begin() + (long)k0, mini_all.begin() + (long)k1);
-    k0 = k1;
-    for (size_t g = 0; g < mini.size(); g += (size_t)group) {
-        const int ng = (int)std::min<size_t>((size_t)group, mini.size() - g);
-        for (const auto &sl : R->slabs) {
-            if (!sl.used) continue;
-            const uint64_t np = sl.positions();
-            int rc = ng == 1 ? ss::scan_flat_dev(mini[g], sl.d, np, stream, sl.binned, R->serial, sl.packed)
-                             : (np < (uint64_t)mini[g]->k ? SS_OK
-                                                          : ss::launch_scan_mini_multi(&mini[g], ng, sl.d, np, ss::as_stream(stream), sl.binned, sl.packed));
-            if (rc) return rc;
-        }
-    }
-    }
-    return SS_OK;
-}
-
 }  // extern "C"

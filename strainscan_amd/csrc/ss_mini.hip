@@ -1536,68 +1536,71 @@ static int launch_scan_minik(ss_db *db, const uint8_t *b, uint64_t n, hipStream_
     const uint64_t n_tiles = (n + KPOS - 1) / KPOS;
     // (one-wave workgroups, grid stride; 8 K / 32 K / 131 K / 300 K / 600 K of them: 2.56 / 2.37 / 2.31 / 2.30 / 2.29 ms per 4 M reads at k = 25)
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)256 * 32 * 16);
-    const int in = input_layout(b, packed);
-    const uint4 *pages = reinterpret_cast<const uint4 *>(db->d_dir);
-    const uint32_t cbase = (uint32_t)db->n_mslots, bshift = 30u - db->bloom_bits;
-    const bool bl = db->d_bloom && !db->expect_hits;
-#define SS_LAUNCH_K(A, B) hipLaunchKernelGGL((scan_minik_kernel<A, B>), dim3(blocks), dim3(KT), 0, stream, b, n, n_tiles, db->k, db->d_mkeys, pages, db->n_dir, \
-                                             db->d_counts, cbase, db->d_bloom, bshift)
-#define SS_LAUNCH_KI(B) do { if (in == IN_PACKED) SS_LAUNCH_K(IN_PACKED, B); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH_K(IN_ASCII_ALIGNED, B); \
-                             else SS_LAUNCH_K(IN_ASCII, B); } while (0)
-    if (bl) SS_LAUNCH_KI(true);
-    else    SS_LAUNCH_KI(false);
-#undef SS_LAUNCH_KI
-#undef SS_LAUNCH_K
+    with_input_layout(b, packed, [&](auto in) {
+        with_bool(multi_kind(db) == MULTI_BLOOM, [&](auto bloom) {
+            hipLaunchKernelGGL((scan_minik_kernel<decltype(in)::value, decltype(bloom)::value>), dim3(blocks), dim3(KT), 0, stream, b, n, n_tiles, db->k, db->d_mkeys,
+                               reinterpret_cast<const uint4 *>(db->d_dir), db->n_dir, db->d_counts, (uint32_t)db->n_mslots, db->d_bloom,
+                               30u - db->bloom_bits);
+        });
+    });
     SS_HIP(hipGetLastError());
     return SS_OK;
 }
 
-template <int LB>
-static void launch_lb(int in, bool comb, unsigned blocks, hipStream_t stream, const uint8_t *bases, uint64_t n,
-                      uint64_t n_tiles, ss_db *db, bool probe = false)
+// Which kernel scans a BINNED block (ss_reorder.hip: the reads of a locus lie together) against this table: the plain one,
+// whose every hit is a global atomic, or the combining one (COMB: the hits of four consecutive tiles are added up in LDS
+// first).  With few hits the plain kernel is the faster (tree tables at their usual 5 % of the read k-mers: 3.8 vs 4.5 ms
+// per 20 M reads on sampled node sets, 2.7 vs 3.2 on contiguous ones); with many, the same-address atomics of a locus'
+// reads queue up and the combining one wins by up to 3x (half of the read k-mers in the table: 17.1 -> 10.6 ms sampled,
+// 14.8 -> 4.9 contiguous; file order 14.1 / 10.2; profiles/r05_ab_log.md 1).  The caller's flag (ss_db_expect_hits: the table of
+// an identified cluster) is a hint that saves the probe; every other table is asked: its first PROBE_TILES tiles run
+// through the plain kernel with the probe bit set -- they count for real, the main launch starts behind them -- and
+// report their found runs (minimizers of the reads that have a bucket in the table); at PROBE_RUNS_PER_TILE and above
+// the rest of the block, and every later block of the same read set, goes through the combining kernel.  One probe per
+// (read set, table): ~40 us and one stream synchronisation on the first scan of a sample against a table.
+constexpr uint64_t PROBE_TILES = 8192;          // one wave per tile: one round of the chip's 8192 wave slots
+constexpr double PROBE_RUNS_PER_TILE = 8.0;     // measured crossover: 4 (plain wins by 15 %) ... 8-10 (even) ... 16 (COMB by 30 %)
+static std::mutex probe_mu;                     // the probe's device words are one set per process
+
+// (the probe's verdict is read and written under probe_mu: two threads may scan the same table)
+static bool probe_known(ss_db *db, uint64_t set_id, bool *comb)
 {
-    const uint4 *pages = reinterpret_cast<const uint4 *>(db->d_dir);
-    const uint32_t cbase = (uint32_t)db->n_mslots, bshift = 30u - db->bloom_bits;
-    constexpr uint32_t swz0 = 1u;
-    const uint32_t swz = swz0 | (probe ? 2u : 0u);
-    const ScanTabs none = {};
-    // (the combining variant needs 79 VGPRs: there is no 8-waves-per-SIMD build of it -- it carried 32 bytes of scratch)
-    // k = 31: the instantiation with k a constant; any other k (17..30): k at run time (its queues of 256 runs: five waves per SIMD)
-#define SS_LAUNCH(A, B, C_) do {                                                                                                                         \
-        if (db->k == 31) hipLaunchKernelGGL((scan_mini_kernel<A, B, C_, (C_ && LB > 6) ? 6 : LB, false, 31>), dim3(blocks), dim3(MT), 0, stream, bases, n,    \
-                                            n_tiles, db->d_mkeys, pages, db->n_dir, db->d_counts, cbase, db->d_bloom, bshift, swz, none, 31);               \
-        else hipLaunchKernelGGL((scan_mini_kernel<A, B, C_, (LB > 5 ? 5 : LB), false, 0>), dim3(blocks), dim3(MT), 0, stream, bases, n, n_tiles,               \
-                                db->d_mkeys, pages, db->n_dir, db->d_counts, cbase, db->d_bloom, bshift, swz, none, db->k);                                 \
-    } while (0)
-    // a table that expects hits (ss_db_expect_hits) skips its Bloom filter: nearly every minimizer of the reads is in it
-#define SS_LAUNCH_I(B, C_) do { if (in == IN_PACKED) SS_LAUNCH(IN_PACKED, B, C_); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH(IN_ASCII_ALIGNED, B, C_); \
-                                else SS_LAUNCH(IN_ASCII, B, C_); } while (0)
-    if (comb)             SS_LAUNCH_I(false, true);
-    else if (db->d_bloom && !db->expect_hits) SS_LAUNCH_I(true, false);
-    else                  SS_LAUNCH_I(false, false);
-#undef SS_LAUNCH_I
-#undef SS_LAUNCH
+    std::lock_guard<std::mutex> g(probe_mu);
+    if (db->probe_set != set_id) return false;
+    *comb = db->probe_comb != 0;
+    return true;
 }
 
-// launches of the several-tables kernel per filter kind (MULTI_BLOOM / MULTI_EXPECT / MULTI_PLAIN), ss_scan_multi_launches
-static std::atomic<uint64_t> g_multi_launches[3];
-
-int multi_kind(const ss_db *db)
+// The combining kernel or not, for a pass over a block that is `binned` or not, against a table that is flagged (ss_db_expect_hits)
+// or not.  SS_COMBINE (A/B runs and tests) is read here and nowhere else; each kind of pass keeps the meaning it has given it:
+//   one table, k = 31        unset: binned blocks only -- flagged tables always, the others as the probe says (`verdict`);
+//                            0: never; 1: every scan of a flagged table, binned or not; 2: every binned scan, flagged or not
+//   several tables, any k    flagged tables only -- unset: binned blocks; 0: never; 1 and above: every pass, binned or not
+//   one table, 17 <= k <= 30 flagged tables under binned blocks, whatever the variable says (no probe either)
+static bool choose_comb(bool flagged, bool binned, bool several, int k, bool verdict)
 {
-    return db->expect_hits ? MULTI_EXPECT : db->d_bloom ? MULTI_BLOOM : MULTI_PLAIN;
+    static const int env = [] { const char *e = getenv("SS_COMBINE"); return e ? atoi(e) : -1; }();
+    if (several) return flagged && (env < 0 ? binned : env != 0);
+    if (k != 31 || env < 0) return binned && (flagged || (k == 31 && verdict));
+    return env == 2 ? binned : (flagged && env != 0);
 }
 
-// one pass of a flat block against up to MULTI_MAX tables of the minimizer layout, all of one k and one filter kind (multi_kind;
-// the Bloom kind at k = 31 only: ss_scan_reads_multi scans the others table by table)
-int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned, bool packed)
+// The waves-per-SIMD bound of an instantiation.  k at run time: five (its queues of 256 runs); the combining variant six (it needs
+// 71-79 VGPRs: at eight it carried scratch); everything else eight.
+constexpr int scan_mini_waves(bool comb, int kk) { return kk == 0 ? 5 : (comb ? 6 : 8); }
+
+// ONE launch of scan_mini_kernel: a pass of the block over one table (several = false: the single-table instantiations) or over up
+// to MULTI_MAX tables of one k and one filter kind (several = true).  bloom: behind the tables' minimizer filters; comb: the
+// combining variant; probe: the first PROBE_TILES tiles only, which report their found runs (launch_scan_mini).  Exactly the
+// instantiations a caller can reach exist: no filter in front of a combining scan, none in a several-tables pass with k at run time.
+static int launch_scan_mini_pass(ss_db *const *dbs, int n_dbs, bool several, bool bloom, bool comb, bool probe, const uint8_t *b,
+                                 uint64_t n, bool packed, hipStream_t stream)
 {
-    if (n_dbs < 1 || n_dbs > MULTI_MAX || !dbs[0]) return SS_EINVAL;
+    const int k = dbs[0]->k;
+    if ((bloom && comb) || (bloom && several && k != 31)) return SS_EINVAL;
     ScanTabs tabs = {};
-    const int k_all = dbs[0]->k, kind = multi_kind(dbs[0]);    // (one k for the tables of a pass: the tile's minimizers are made once)
-    if (kind == MULTI_BLOOM && k_all != 31) return SS_EINVAL;
     for (int i = 0; i < n_dbs; i++) {
-        ss_db *db = dbs[i];
-        if (!db || db->layout != 1 || db->k != k_all || multi_kind(db) != kind) return SS_EINVAL;
+        const ss_db *db = dbs[i];
         tabs.mkeys[i] = db->d_mkeys;
         tabs.pages[i] = reinterpret_cast<const uint4 *>(db->d_dir);
         tabs.counts[i] = db->d_counts;
@@ -1607,30 +1610,58 @@ int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, 
         tabs.bloom_shift[i] = 30u - db->bloom_bits;
     }
     tabs.n = n_dbs;
-    const int in = input_layout(bases_dev, packed);
-    static const int comb_env = [] { const char *e = getenv("SS_COMBINE"); return e ? atoi(e) : -1; }();
-    constexpr uint32_t swz = 1u;
-    const bool comb = kind == MULTI_EXPECT && (comb_env < 0 ? binned : comb_env != 0);
-    const uint64_t n_tiles = (n + MTILE - 1) / MTILE, units = comb ? (n_tiles + COMB_CH - 1) / COMB_CH : n_tiles;
+    const uint64_t n_tiles = probe ? PROBE_TILES : (n + MTILE - 1) / MTILE;      // (this kernel's tile is 62 x 16 positions)
+    // grid-stride over tiles with MANY more blocks than fit the chip: short blocks start at scattered times, so
+    // the waves sharing a SIMD stop marching through their ALU and memory phases in step.  Measured with 8 waves
+    // per SIMD resident (20 M reads = 3.04 M tiles; blocks = x * 1024): x = 8 (one round of resident blocks)
+    // 4.03 ms, 32: 3.76, 128: 3.59, 512: 3.55, 2048 (1.5 tiles per block): 3.50, 4096 (one tile each): 3.51
+    const uint64_t units = comb ? (n_tiles + COMB_CH - 1) / COMB_CH : n_tiles;
     unsigned blocks = (unsigned)std::min<uint64_t>(units, (uint64_t)2048 * 256 * (256 / MT));
-    blocks = (blocks + 7u) & ~7u;
-    const uint8_t *b = (const uint8_t *)bases_dev;
-#define SS_LAUNCH_M(A, B, C_, LB) do {                                                                                                       \
-        if (k_all == 31) hipLaunchKernelGGL((scan_mini_kernel<A, B, C_, LB, true, 31>), dim3(blocks), dim3(MT), 0, stream, b, n, n_tiles,          \
-                                            tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],                        \
-                                            tabs.bloom[0], tabs.bloom_shift[0], swz, tabs, 31);                                                  \
-        else if (!B) hipLaunchKernelGGL((scan_mini_kernel<A, false, C_, (LB > 5 ? 5 : LB), true, 0>), dim3(blocks), dim3(MT), 0, stream, b, n,   \
-                                        n_tiles, tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],                   \
-                                        (const uint32_t *)nullptr, 0u, swz, tabs, k_all);                                                        \
-    } while (0)
-#define SS_LAUNCH_MI(B, C_, LB) do { if (in == IN_PACKED) SS_LAUNCH_M(IN_PACKED, B, C_, LB); else if (in == IN_ASCII_ALIGNED) SS_LAUNCH_M(IN_ASCII_ALIGNED, B, C_, LB); \
-                                     else SS_LAUNCH_M(IN_ASCII, B, C_, LB); } while (0)
-    if (comb)                     SS_LAUNCH_MI(false, true, 6);
-    else if (kind == MULTI_BLOOM) SS_LAUNCH_MI(true, false, 8);
-    else                          SS_LAUNCH_MI(false, false, 8);
-#undef SS_LAUNCH_MI
-#undef SS_LAUNCH_M
+    blocks = (blocks + 7u) & ~7u;                           // a multiple of 8: the same number of workgroups on every XCD
+    const uint32_t swz = 1u | (probe ? 2u : 0u);            // the XCD swizzle, always; bit 1: a probe launch
+    with_input_layout(b, packed, [&](auto in) { with_bool(several, [&](auto multi) { with_bool(k == 31, [&](auto k31) {
+        with_bool(bloom, [&](auto bl) { with_bool(comb, [&](auto cb) {
+            // k = 31: the instantiation with k a constant; any other k (17..30): k at run time
+            constexpr int IN = decltype(in)::value, KK = decltype(k31)::value ? 31 : 0;
+            constexpr bool MULTI = decltype(multi)::value, BLOOM = decltype(bl)::value, COMB = decltype(cb)::value;
+            if constexpr (!(BLOOM && COMB) && !(BLOOM && MULTI && KK == 0))
+                hipLaunchKernelGGL((scan_mini_kernel<IN, BLOOM, COMB, scan_mini_waves(COMB, KK), MULTI, KK>), dim3(blocks), dim3(MT), 0,
+                                   stream, b, n, n_tiles, tabs.mkeys[0], tabs.pages[0], tabs.n_pages[0], tabs.counts[0], tabs.cbase[0],
+                                   tabs.bloom[0], tabs.bloom_shift[0], swz, tabs, k);
+        }); });
+    }); }); });
     SS_HIP(hipGetLastError());
+    return SS_OK;
+}
+
+// launches of the several-tables kernel per filter kind (MULTI_BLOOM / MULTI_EXPECT / MULTI_PLAIN), ss_scan_multi_launches
+static std::atomic<uint64_t> g_multi_launches[3];
+
+// a table that expects hits (ss_db_expect_hits) skips its Bloom filter: nearly every minimizer of the reads is in it
+int multi_kind(const ss_db *db)
+{
+    return db->expect_hits ? MULTI_EXPECT : db->d_bloom ? MULTI_BLOOM : MULTI_PLAIN;
+}
+
+// May this table share a several-tables pass?  Tables of the page index at k = 31, and at k >= SHARE_K_MIN where scan_mini_kernel
+// with k at run time serves every table (below it launch_scan_mini sends the flagged ones to the per-position kernel); the Bloom
+// kind has a several-tables instantiation at k = 31 only.  ss_scan_reads_multi scans the others table by table.
+constexpr int SHARE_K_MIN = 20;
+bool may_share_pass(const ss_db *db)
+{
+    return db->layout == 1 && db->k >= SHARE_K_MIN && (db->k == 31 || multi_kind(db) != MULTI_BLOOM);
+}
+
+// one pass of a flat block against up to MULTI_MAX tables that may share it, all of one k and one filter kind (multi_kind)
+int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned, bool packed)
+{
+    if (n_dbs < 1 || n_dbs > MULTI_MAX || !dbs[0]) return SS_EINVAL;
+    const int kind = multi_kind(dbs[0]);      // (one k for the tables of a pass: the tile's minimizers are made once)
+    for (int i = 0; i < n_dbs; i++)
+        if (!dbs[i] || !may_share_pass(dbs[i]) || dbs[i]->k != dbs[0]->k || multi_kind(dbs[i]) != kind) return SS_EINVAL;
+    const bool comb = choose_comb(kind == MULTI_EXPECT, binned, true, dbs[0]->k, false);
+    int rc = launch_scan_mini_pass(dbs, n_dbs, true, kind == MULTI_BLOOM, comb, false, (const uint8_t *)bases_dev, n, packed, stream);
+    if (rc) return rc;
     g_multi_launches[kind]++;
     for (int i = 0; i < n_dbs; i++) dbs[i]->launches++;
     return SS_OK;
@@ -1662,79 +1693,29 @@ extern "C" int ss_debug_timing(unsigned long long *out32, int reset)
 }
 #endif
 
-// Which kernel scans a BINNED block (ss_reorder.hip: the reads of a locus lie together) against this table: the plain one,
-// whose every hit is a global atomic, or the combining one (COMB: the hits of four consecutive tiles are added up in LDS
-// first).  With few hits the plain kernel is the faster (tree tables at their usual 5 % of the read k-mers: 3.8 vs 4.5 ms
-// per 20 M reads on sampled node sets, 2.7 vs 3.2 on contiguous ones); with many, the same-address atomics of a locus'
-// reads queue up and the combining one wins by up to 3x (half of the read k-mers in the table: 17.1 -> 10.6 ms sampled,
-// 14.8 -> 4.9 contiguous; file order 14.1 / 10.2; profiles/r05_ab_log.md 1).  The caller's flag (ss_db_expect_hits: the table of
-// an identified cluster) is a hint that saves the probe; every other table is asked: its first PROBE_TILES tiles run
-// through the plain kernel with the probe bit set -- they count for real, the main launch starts behind them -- and
-// report their found runs (minimizers of the reads that have a bucket in the table); at PROBE_RUNS_PER_TILE and above
-// the rest of the block, and every later block of the same read set, goes through the combining kernel.  One probe per
-// (read set, table): ~40 us and one stream synchronisation on the first scan of a sample against a table.
-constexpr uint64_t PROBE_TILES = 8192;          // one wave per tile: one round of the chip's 8192 wave slots
-constexpr double PROBE_RUNS_PER_TILE = 8.0;     // measured crossover: 4 (plain wins by 15 %) ... 8-10 (even) ... 16 (COMB by 30 %)
-static std::mutex probe_mu;                     // the probe's device words are one set per process
-
-// (the probe's verdict is read and written under probe_mu: two threads may scan the same table)
-static bool probe_known(ss_db *db, uint64_t set_id, bool *comb)
+int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned, uint64_t set_id, bool packed)
 {
-    std::lock_guard<std::mutex> g(probe_mu);
-    if (db->probe_set != set_id) return false;
-    *comb = db->probe_comb != 0;
-    return true;
-}
-
-static int launch_plain_or_comb(ss_db *db, bool comb, bool probe, const uint8_t *b, uint64_t n, uint64_t n_tiles, hipStream_t stream,
-                                bool packed)
-{
-    const int in = input_layout(b, packed);
-    // grid-stride over tiles with MANY more blocks than fit the chip: short blocks start at scattered times, so
-    // the waves sharing a SIMD stop marching through their ALU and memory phases in step.  Measured with 8 waves
-    // per SIMD resident (20 M reads = 3.04 M tiles; blocks = x * 1024): x = 8 (one round of resident blocks)
-    // 4.03 ms, 32: 3.76, 128: 3.59, 512: 3.55, 2048 (1.5 tiles per block): 3.50, 4096 (one tile each): 3.51
-    const uint64_t units = comb ? (n_tiles + COMB_CH - 1) / COMB_CH : n_tiles;
-    unsigned blocks = (unsigned)std::min<uint64_t>(units, (uint64_t)2048 * 256 * (256 / MT));
-    blocks = (blocks + 7u) & ~7u;                           // a multiple of 8: the same number of workgroups on every XCD
-    // (the combining variant needs 71 VGPRs: at 8 waves per SIMD it would spill four of them to scratch)
-    if (comb) launch_lb<6>(in, comb, blocks, stream, b, n, n_tiles, db, probe);
-    else launch_lb<8>(in, comb, blocks, stream, b, n, n_tiles, db, probe);
-    SS_HIP(hipGetLastError());
-    return SS_OK;
-}
-
-int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t stream, unsigned /*blocks*/,
-                     uint64_t n_tiles, bool binned, uint64_t set_id, bool packed)
-{
-    // Which kernel.  k = 31: scan_mini_kernel with k a constant (everything below).  17 <= k <= 30: scan_mini_kernel with k at run time
+    // Which kernel.  k = 31: scan_mini_kernel with k a constant.  17 <= k <= 30: scan_mini_kernel with k at run time
     // (KK = 0, queues of 256 runs) -- measured against the one-lane-per-position kernel scan_minik_kernel (profiles/r06_k_index.json):
     // a table with few hits, 4 M reads, k = 29 / 25 / 21 / 20 / 19 / 17: 1.38 / 1.51 / 1.73 / 1.82 / 2.63 / 3.46 ms against 2.24 / 2.31 /
     // 2.75 / 2.95 / 3.18 / 3.64 (k = 31: 1.34); a cluster table under binned reads (the combining variant), 8 M reads, k = 29 / 25 / 21 /
-    // 20: 3.3 / 4.1 / 7.3 / 9.1 against 8.9 / 9.9 / 15.3 / 16.6.  The exception: tables that expect hits at k <= 19, where a tile's
-    // ~330+ runs overflow the queues and the per-position kernel is as fast or faster (k = 19: 18.5 binned / 18.9 in file order
-    // against 17.5 / 22.2).
+    // 20: 3.3 / 4.1 / 7.3 / 9.1 against 8.9 / 9.9 / 15.3 / 16.6.  The exception: tables that expect hits below SHARE_K_MIN (k <= 19),
+    // where a tile's ~330+ runs overflow the queues and the per-position kernel is as fast or faster (k = 19: 18.5 binned / 18.9 in
+    // file order against 17.5 / 22.2) -- which is why may_share_pass stops there: a several-tables pass is always scan_mini_kernel.
     // ss_test_hook 4 (tests: the kernels held to each other on one index): 1 = tables of k = 31 through the per-position kernel,
     // 2 = tables of every k through it, 3 = tables of every k through scan_mini_kernel.
-    {
-        const long long hk = g_hook_generic_k.load();
-        if (db->k == 31 ? (hk == 1 || hk == 2) : (hk != 3 && (hk == 2 || (db->k <= 19 && db->expect_hits))))
-            return launch_scan_minik(db, (const uint8_t *)bases_dev, n, stream, packed);
-        if (db->k != 31) {                                  // (no probe: the flag decides)
-            const uint64_t nt = (n + MTILE - 1) / MTILE;
-            return launch_plain_or_comb(db, binned && db->expect_hits, false, (const uint8_t *)bases_dev, n, nt, stream, packed);
-        }
-    }
-    n_tiles = (n + MTILE - 1) / MTILE;                      // this kernel's tile is 62 x 16 positions
     const uint8_t *b = (const uint8_t *)bases_dev;
-    // SS_COMBINE (A/B runs and tests): 0 never, 1 every scan of a table that expects hits -- binned or not --, 2 every binned scan
-    static const int comb_env = [] { const char *e = getenv("SS_COMBINE"); return e ? atoi(e) : -1; }();
-    bool comb = false;
-    if (comb_env >= 0) comb = comb_env == 2 ? binned : (db->expect_hits && comb_env != 0);
-    else if (!binned) comb = false;
-    else if (db->expect_hits) comb = true;
-    else if (set_id && probe_known(db, set_id, &comb)) {}
-    else if (n_tiles >= 4 * PROBE_TILES) {
+    const long long hk = g_hook_generic_k.load();
+    if (db->k == 31 ? (hk == 1 || hk == 2) : (hk != 3 && (hk == 2 || (db->k < SHARE_K_MIN && db->expect_hits))))
+        return launch_scan_minik(db, b, n, stream, packed);
+    auto comb_if = [&](bool verdict) { return choose_comb(db->expect_hits != 0, binned, false, db->k, verdict); };
+    auto pass = [&](bool comb, bool probe) {
+        return launch_scan_mini_pass(&db, 1, false, !comb && multi_kind(db) == MULTI_BLOOM, comb, probe, b, n, packed, stream);
+    };
+    bool verdict = false;
+    if (comb_if(false) == comb_if(true)) {}                 // the probe has no say
+    else if (set_id && probe_known(db, set_id, &verdict)) {}
+    else if ((n + MTILE - 1) / MTILE >= 4 * PROBE_TILES) {
         // The first scan of a (read set, table) pair makes ONE stream synchronisation here (~40 us of probe tiles, a memset and a
         // 256-byte copy back): ss_scan_reads is asynchronous from the second scan of the pair on, and this first launch cannot
         // be captured into a hipGraph (include/strainscan_hip.h says so at ss_scan_reads).
@@ -1743,21 +1724,20 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
         void *sym = nullptr;
         SS_HIP(hipGetSymbolAddress(&sym, HIP_SYMBOL(ss_probe_runs)));
         SS_HIP(hipMemsetAsync(sym, 0, sizeof(runs), stream));
-        int rc = launch_plain_or_comb(db, false, true, b, n, PROBE_TILES, stream, packed);      // (n: the last tile's k-mers reach beyond it)
+        int rc = pass(false, true);                         // (the whole n: the last probe tile's k-mers reach beyond it)
         if (rc) return rc;
         SS_HIP(hipMemcpyAsync(runs, sym, sizeof(runs), hipMemcpyDeviceToHost, stream));
         SS_HIP(hipStreamSynchronize(stream));
         uint64_t total = 0;
         for (uint32_t r : runs) total += r;
         db->probe_runs_per_tile = (double)total / (double)PROBE_TILES;
-        comb = db->probe_runs_per_tile >= PROBE_RUNS_PER_TILE;
-        db->probe_comb = comb;
+        verdict = db->probe_runs_per_tile >= PROBE_RUNS_PER_TILE;
+        db->probe_comb = verdict;
         db->probe_set = set_id;
         b += in_bytes(packed, PROBE_TILES * (uint64_t)MTILE);      // (a multiple of 16 bytes / of 8 packed: the alignment of the block is kept)
         n -= PROBE_TILES * (uint64_t)MTILE;
-        n_tiles -= PROBE_TILES;
     }
-    return launch_plain_or_comb(db, comb, false, b, n, n_tiles, stream, packed);
+    return pass(comb_if(verdict), false);
 }
 
 }  // namespace ss

@@ -409,29 +409,73 @@ int ss::scan_flat_dev(ss_db *db, const void *bases_dev, uint64_t n, void *stream
 {
     if (!db || (n && !bases_dev)) return SS_EINVAL;
     if (n < (uint64_t)db->k) return SS_OK;
-    const uint64_t n_tiles = (n + TILE - 1) / TILE;
-    const uint64_t max_blocks = (uint64_t)cu_count() * 8;
-    const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, max_blocks);
     if (db->layout == 1) {
-        int rc = ss::launch_scan_mini(db, bases_dev, n, ss::as_stream(stream), blocks, n_tiles, binned, set_id, packed);
+        int rc = ss::launch_scan_mini(db, bases_dev, n, ss::as_stream(stream), binned, set_id, packed);
         if (rc == SS_OK) db->launches++;
         return rc;
     }
-    const int in = input_layout(bases_dev, packed);
-#define SS_FLAT(A, B) hipLaunchKernelGGL((scan_kernel<A, B>), dim3(blocks), dim3(SCAN_THREADS), 0, ss::as_stream(stream), (const uint8_t *)bases_dev, n, \
-                                         n_tiles, db->d_keys, db->d_counts, db->log2cap, db->k, db->d_bloom, db->bloom_bits)
-#define SS_FLAT_I(B) do { if (in == IN_PACKED) SS_FLAT(IN_PACKED, B); else if (in == IN_ASCII_ALIGNED) SS_FLAT(IN_ASCII_ALIGNED, B); \
-                          else SS_FLAT(IN_ASCII, B); } while (0)
-    if (db->d_bloom) SS_FLAT_I(true);
-    else             SS_FLAT_I(false);
-#undef SS_FLAT_I
-#undef SS_FLAT
+    const uint64_t n_tiles = (n + TILE - 1) / TILE;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)cu_count() * 8);
+    with_input_layout(bases_dev, packed, [&](auto in) {
+        with_bool(db->d_bloom != nullptr, [&](auto bloom) {
+            hipLaunchKernelGGL((scan_kernel<decltype(in)::value, decltype(bloom)::value>), dim3(blocks), dim3(SCAN_THREADS), 0, ss::as_stream(stream),
+                               (const uint8_t *)bases_dev, n, n_tiles, db->d_keys, db->d_counts, db->log2cap, db->k, db->d_bloom, db->bloom_bits);
+        });
+    });
     SS_HIP(hipGetLastError());
     db->launches++;
     return SS_OK;
 }
 
 extern "C" {
+
+int ss_scan_reads(ss_db *db, const ss_reads *R, void *stream)
+{
+    if (!db || !R) return SS_EINVAL;
+    if (R->has_cut_record && db->k != 31) return SS_ERANGE;   // cut records carry a 30-base overlap
+    for (const auto &sl : R->slabs) {
+        if (!sl.used) continue;
+        int rc = ss::scan_flat_dev(db, sl.d, sl.positions(), stream, sl.binned, R->serial, sl.packed);
+        if (rc) return rc;
+    }
+    return SS_OK;
+}
+
+// The resident reads against SEVERAL tables in one pass (Vote_Strain_L2_Lasso_new_sp.py:295-296 loops over the identified
+// clusters, :354-372 re-reads the FASTQ for each; strainscan_amd/multi_db.py counts one sample against the tree tables of several
+// databases): tables of the minimizer layout go four at a time through one kernel that makes a tile's codes, minimizers and runs
+// once; anything else is scanned on its own.  A launch takes tables of one k and one filter kind (ss::multi_kind): tree tables
+// behind their own Bloom filters, tables that expect hits (the combining variant under binned reads), tables with neither.
+int ss_scan_reads_multi(ss_db *const *dbs, int n_dbs, const ss_reads *R, void *stream)
+{
+    if (!dbs || n_dbs < 1 || !R) return SS_EINVAL;
+    std::vector<ss_db *> mini;
+    for (int i = 0; i < n_dbs; i++) {
+        if (!dbs[i]) return SS_EINVAL;
+        for (int j = 0; j < i; j++) if (dbs[j] == dbs[i]) return SS_EINVAL;           // a table twice would count twice
+        if (R->has_cut_record && dbs[i]->k != 31) return SS_ERANGE;
+        if (ss::may_share_pass(dbs[i])) mini.push_back(dbs[i]);
+        else { int rc = ss_scan_reads(dbs[i], R, stream); if (rc) return rc; }
+    }
+    // the tables of ONE k and one filter kind go through the several-tables kernel together (a tile's minimizers are made once per
+    // k): sorted once, then every run of equal (k, kind) four at a time; a table left alone takes the single-table scan
+    std::stable_sort(mini.begin(), mini.end(), [](const ss_db *a, const ss_db *b) {
+        return a->k != b->k ? a->k < b->k : ss::multi_kind(a) < ss::multi_kind(b);
+    });
+    for (size_t g = 0, end; g < mini.size(); g = end) {
+        for (end = g + 1; end < mini.size() && end - g < 4 && mini[end]->k == mini[g]->k && ss::multi_kind(mini[end]) == ss::multi_kind(mini[g]);) end++;
+        const int ng = (int)(end - g);
+        for (const auto &sl : R->slabs) {
+            if (!sl.used) continue;
+            const uint64_t np = sl.positions();
+            int rc = ng == 1 ? ss::scan_flat_dev(mini[g], sl.d, np, stream, sl.binned, R->serial, sl.packed)
+                   : np < (uint64_t)mini[g]->k ? SS_OK
+                   : ss::launch_scan_mini_multi(&mini[g], ng, sl.d, np, ss::as_stream(stream), sl.binned, sl.packed);
+            if (rc) return rc;
+        }
+    }
+    return SS_OK;
+}
 
 int ss_scan_flat_host(ss_db *db, const char *bases, uint64_t n)
 {

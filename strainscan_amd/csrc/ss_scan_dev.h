@@ -2,6 +2,7 @@
 #pragma once
 #include "ss_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace ss {
 
@@ -216,6 +217,21 @@ inline int input_layout(const void *p, bool packed)
 {
     return packed ? IN_PACKED : ((((uintptr_t)p) & 15) == 0 ? IN_ASCII_ALIGNED : IN_ASCII);
 }
-
+// ... handed to the launch as a compile-time value: f(std::integral_constant<int, IN_...>()), so that a launch names its kernel
+// once -- scan_kernel<decltype(in)::value, ...> -- whatever the layout; with_bool does the same for a template flag
+template <class F>
+inline void with_input_layout(const void *p, bool packed, F &&f)
+{
+    switch (input_layout(p, packed)) {
+    case IN_PACKED: f(std::integral_constant<int, IN_PACKED>()); break;
+    case IN_ASCII_ALIGNED: f(std::integral_constant<int, IN_ASCII_ALIGNED>()); break;
+    default: f(std::integral_constant<int, IN_ASCII>()); break;
+    }
+}
+template <class F>
+inline void with_bool(bool v, F &&f)
+{
+    if (v) f(std::true_type()); else f(std::false_type());
+}
 
 }}  // namespace ss::dev
