@@ -1151,35 +1151,11 @@ __global__ __launch_bounds__(256) void lastwin_kernel(const uint8_t *text, uint6
     if (i < WSIZE) prev[i] = total >= WSIZE - i ? text[total - (WSIZE - i)] : (uint8_t)0;
 }
 
-// CRC-32 (zlib's polynomial) of the text's segments [seg_at[s], seg_at[s] + seg_len[s]), one lane per segment, byte-wise
-// table in LDS (the segments of a member start at its first byte: any alignment)
-__global__ __launch_bounds__(64) void crc_kernel(const uint8_t *text, const uint64_t *seg_at, const uint32_t *seg_len, uint64_t n_seg,
-                                                 const uint32_t *table, uint32_t *crc)
-{
-    __shared__ uint32_t tab[256];
-    for (int i = threadIdx.x; i < 256; i += 64) tab[i] = table[i];
-    __syncthreads();
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n_seg) return;
-    uint64_t i = seg_at[s];
-    const uint64_t e = i + seg_len[s];
-    uint32_t k = 0xFFFFFFFFu;
-    for (; i < e && (i & 3); i++) k = tab[(k ^ text[i]) & 0xFFu] ^ (k >> 8);
-    for (; i + 4 <= e; i += 4) {
-        const uint32_t w = *reinterpret_cast<const uint32_t *>(text + i);
-        k = tab[(k ^ w) & 0xFFu] ^ (k >> 8);
-        k = tab[(k ^ (w >> 8)) & 0xFFu] ^ (k >> 8);
-        k = tab[(k ^ (w >> 16)) & 0xFFu] ^ (k >> 8);
-        k = tab[(k ^ (w >> 24)) & 0xFFu] ^ (k >> 8);
-    }
-    for (; i < e; i++) k = tab[(k ^ text[i]) & 0xFFu] ^ (k >> 8);
-    crc[s] = k ^ 0xFFFFFFFFu;
-}
-
-// The same for the members of a file, segments of 2^lg bytes from every member's first byte: segment s belongs to the member
+// CRC-32 (zlib's polynomial) of the members of a file, one lane per segment of 2^lg bytes from every member's first byte (any
+// alignment), byte-wise table in LDS: segment s belongs to the member
 // m with first[m] <= s < first[m + 1] (binary search: a bgzip file has thousands) and begins (s - first[m]) << lg bytes into it.
-// Nothing but the member table travels to the device (the list of segments was 12 bytes per 4 KB of text, and three
-// pageable copies in front of the kernel); the byte table is made here.
+// Nothing but the member table travels to the device (a list of the segments would be 12 bytes per 4 KB of text); the byte
+// table is made here.
 struct CrcMember { uint64_t at, len, first; };
 __global__ __launch_bounds__(64) void crc_members_kernel(const uint8_t *text, const CrcMember *mem, uint32_t n_mem, uint64_t n_seg, int lg, uint32_t *crc)
 {
@@ -1444,9 +1420,7 @@ bool upload_file(int fd, uint64_t n, uint8_t *d_in, const std::function<void(uin
     // one file at a time on the link: the files of a call would otherwise arrive together, late, and their searches start together;
     // in turn the first one is searched while the second one travels
     static std::mutex link;
-    constexpr bool turns = true;
-    std::unique_lock<std::mutex> my_turn(link, std::defer_lock);
-    if (turns) my_turn.lock();
+    std::lock_guard<std::mutex> my_turn(link);
     PinSet *pins = pin_get();
     if (!pins) return false;
     const double t_pins = since();
@@ -1459,8 +1433,7 @@ bool upload_file(int fd, uint64_t n, uint8_t *d_in, const std::function<void(uin
     // every thread's pinned buffer is used in two halves: the copy of one block travels while the next is read.  Blocks
     // of 1/16 of the file (2 MB .. half a buffer), handed out in order, so that the prefix grows steadily
     const uint64_t half = PIN_BYTES / 2;
-    constexpr uint64_t div = 16;
-    const uint64_t blk = std::min<uint64_t>(half, std::max<uint64_t>(2ull << 20, ((n / div) + (1ull << 20) - 1) & ~((1ull << 20) - 1)));
+    const uint64_t blk = std::min<uint64_t>(half, std::max<uint64_t>(2ull << 20, ((n / 16) + (1ull << 20) - 1) & ~((1ull << 20) - 1)));
     const uint64_t n_blocks = (n + blk - 1) / blk;
     std::vector<uint8_t> done((size_t)n_blocks, 0);
     std::mutex mu;
@@ -1619,6 +1592,7 @@ void gz_range_pass(uint64_t ticket)
 
 struct RangeRun {
     uint32_t rank = 0, world = 1, slice_chunks = 0, n_slices = 0;
+    uint64_t slice_bytes = 0;             // ss_gz_set_range's (0: by the file's size)
     ss_gz_chain_fn fn = nullptr;
     void *user = nullptr;
     std::vector<uint32_t> mine;           // my slices, ascending
@@ -1687,6 +1661,7 @@ bool gpu_gunzip_range(const uint8_t *in, uint64_t in_n, char **text_dev, void **
         std::lock_guard<std::mutex> one(g_range_mu);
         if (!gz_range_active()) return false;
         rr.rank = (uint32_t)g_range.rank; rr.world = (uint32_t)g_range.world; rr.fn = g_range.fn; rr.user = g_range.user;
+        rr.slice_bytes = g_range.slice_bytes;
     }
     if (g_hook_skip_chain.load()) return false;               // test hook: a rank that leaves WITHOUT serving the chain (the peers' bounded wait)
     rr.ticket = ticket;
@@ -1698,258 +1673,364 @@ bool gpu_gunzip_range(const uint8_t *in, uint64_t in_n, char **text_dev, void **
     return ok;
 }
 
-static bool gpu_gunzip_impl(const uint8_t *in, uint64_t in_n, char **text_dev, uint64_t *len, void **lease, int fd, RangeRun *rr)
+namespace {
+
+// ---- one call of the device gunzip: its state, and its stages as member functions ------------------------------------------------
+// The file's chunks: one per entry (a chunk of the search without one belongs to its predecessor).  `fresh`: the first
+// chunk of a gzip member (nothing in front of it); `last`: it ends with the member's final block, the trailer follows
+// at `trailer`.
+// `hdr`: ~0, or -- an entry INSIDE a block (subsync_kernel) -- where that block's header is.
+struct Chunk { uint64_t start; bool fresh, last; uint64_t trailer; uint64_t hdr = ~0ull; };
+// range mode: one segment per slice of this rank, its look-ahead entries [gj, gj + n_ph) behind it
+struct Seg { size_t gi, gj, n_ph; uint32_t slice; uint64_t hdr_bit; };
+struct Member { uint64_t at, len; uint32_t crc, isize; bool open; uint32_t crc0; uint64_t len0; };      // crc0, len0: range mode -- the member's part in the slices before
+// A chunk while its segment is inflated: its symbol region [off, off + cap) and what inflate_kernel reported for it
+struct Rec : Chunk { uint64_t off = 0, cap = 0, len = 0, end = 0; int status = 0; };
+// One segment on its way from chunks to text.  `ph`: up to two look-ahead entries behind the chunks (what a chunk may run over)
+struct Segment {
+    size_t gi = 0, gj = 0;                // G[gi, gj)
+    std::vector<Rec> ch;
+    std::vector<Chunk> ph;
+    uint32_t consumed_ph = 0;             // look-ahead entries that turned out to lie inside a block of this segment
+    std::vector<uint64_t> text_off;       // where every chunk's text begins
+    size_t m_first = 0;                   // members[m_first, ...) have text in this segment
+};
+// the host's side of the per-chunk device arrays (lives until the stream has been synchronised)
+struct Staging { std::vector<uint64_t> start, stop, off, cap, hdr, len, end; std::vector<int> status; };
+// range mode: what came down the chain in front of a slice
+struct ChainIn { uint64_t nl = 0, len = 0; uint32_t crc = (uint32_t)crc32(0L, Z_NULL, 0); std::vector<uint8_t> carry; };
+
+constexpr size_t SEG_CHUNKS = 16384;      // chunks of a segment at most
+constexpr uint32_t LOOK = 64;             // search chunks behind a slice in which its last chunk's stop is looked for
+constexpr uint64_t SYM_RATIO = 12;        // symbols reserved per byte of deflate data
+
+// What the environment sets, read on EVERY call (the tests change it between the calls of one process)
+struct Tunables {
+    // SS_GZ_SPLIT_KB: blocks are entered every so many KB of deflate data (subsync_kernel; 0 = at their starts only)
+    uint64_t split_bytes = 12 << 10, chunk_bytes = 0, seg_bytes = 128ull << 20, slice_bytes = 0;      // (slice_bytes 0: not set here)
+    const bool run_over = getenv("SS_GZ_NO_RUNOVER") == nullptr;      // (test hook: wrong entries are then handled by the host only)
+    Tunables()
+    {
+        if (const char *e = getenv("SS_GZ_SPLIT_KB")) split_bytes = (uint64_t)std::max<long long>(0, atoll(e)) << 10;
+        chunk_bytes = split_bytes ? 16 << 10 : 32 << 10;      // (split: every block's start should be found)
+        if (const char *e = getenv("SS_GZ_CHUNK")) chunk_bytes = std::max<uint64_t>(4096, (uint64_t)atoll(e));
+        if (const char *e = getenv("SS_GZ_SEG_KB")) seg_bytes = std::max<uint64_t>(64, (uint64_t)atoll(e)) << 10;      // (tests: many segments)
+        seg_bytes = std::max(seg_bytes, 8 * chunk_bytes);
+        if (const char *e = getenv("SS_GZ_SLICE_KB")) slice_bytes = std::max<uint64_t>(64, (uint64_t)atoll(e)) << 10;      // (tests: many slices)
+    }
+};
+
+// symbols of a segment whose chunks need `need`: + what run-over and further members add
+static uint64_t sym_room(uint64_t need) { return need + need / 4 + 64 * (4096 + 64 * SYM_RATIO); }
+
+// The scratch of a call: an arena of at least cap_chunks chunks and sym_elems symbols whose text buffer holds text_cap bytes.
+// `a`: one the call holds already, or null -- then a waiting one that needs no allocation, or, if the device has the memory
+// (`beside`: what the call allocates apart from it), a new one.  null: *why says what was missing.
+struct Why { const char *what = nullptr; long long arg = 0; };
+static Arena *acquire_scratch(Arena *a, uint64_t cap_chunks, uint64_t sym_elems, uint64_t text_cap, uint64_t beside, Why *why)
 {
-    static const bool trace = getenv("SS_INGEST_TRACE") != nullptr;
+    if (!a) a = arena_take_if_fits(cap_chunks, sym_elems, text_cap);
+    if (!a) {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { *why = Why{"hipMemGetInfo"}; return nullptr; }
+        const uint64_t need = 2 * text_cap + sym_elems * 2 + cap_chunks * WSIZE * 5 + (256ull << 20);
+        if (need + beside > mem_free / 2) { *why = Why{"device memory", (long long)(need >> 20)}; return nullptr; }
+        a = arena_get(cap_chunks, sym_elems);
+        if (!a) { *why = Why{"scratch"}; return nullptr; }
+    }
+    if (a->text_cap < text_cap) {
+        if (a->text) hipFree(a->text);
+        a->text = nullptr;
+        a->text_cap = 0;
+        uint64_t got = text_cap;
+        if (ss::big_malloc((void **)&a->text, text_cap, &got) != hipSuccess) { arena_put(a); *why = Why{"text buffer", (long long)(text_cap >> 20)}; return nullptr; }
+        a->text_cap = got;
+    }
+    return a;
+}
+
+#define GI(call) do { if ((call) != hipSuccess) return no(#call); } while (0)
+#define GB(call) do { if (!(call)) return no(#call); } while (0)
+
+struct Gunzip {
+    const uint8_t *const in;
+    const uint64_t in_n;
+    const int fd;
+    RangeRun *const rr;
+    const bool trace;
+    const Tunables tn;
     // own stream: the two mates of a paired sample are inflated by two host threads, and the legacy default stream would
     // serialise them
-    hipStream_t st = call_stream_get();
-    const bool have_stream = st != nullptr;                  // (checked once the slices are known: a rank that fails here still serves the chain)
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace) return;
-        hipStreamSynchronize(st);
-        fprintf(stderr, "[ginflate] %-18s at %.4f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
-    };
+    hipStream_t st = call_stream_get();                       // (null: checked once the slices are known -- a rank that fails here still serves the chain)
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    Why why;                                                  // why the call declines
+
+    uint64_t data_off = 0, data_n = 0;                        // the first member's deflate data
+    uint32_t n_chunks0 = 0;                                   // chunks of the search
     uint8_t *d_in = nullptr, *d_text = nullptr;
     uint64_t *d_entry = nullptr;
-    uint32_t *d_crc = nullptr, *d_tab = nullptr;
+    uint32_t *d_crc = nullptr;
+    CrcMember *d_tab = nullptr;
+    uint32_t c_searched = 0;                                  // search chunks [0, c_searched) have been launched
+    std::vector<Bgzf> bgzf;                                   // a bgzip file: its members ARE the chunks, no search
+
+    std::vector<Chunk> G;
+    std::vector<Seg> segs;
+    uint32_t n_sub = 0;                                       // entries inside blocks
+
     Arena *A = nullptr;
     std::future<Arena *> ahead;                               // (a large file: the arena allocated while the image travels)
-    auto cleanup = [&](bool keep_text) {
+    uint64_t cap_chunks = 0, text_cap = 0;
+    uint64_t *d_start = nullptr, *d_stop = nullptr, *d_off = nullptr, *d_cap = nullptr, *d_len = nullptr, *d_end = nullptr, *d_toff = nullptr, *d_hdr = nullptr;
+
+    std::vector<Member> members;
+    uint64_t total = 0, last_end_bit = 0;                     // the text so far
+    bool have_prev = false, ended = false;
+    uint32_t n_segments = 0;
+
+    Gunzip(const uint8_t *in_, uint64_t in_n_, int fd_, RangeRun *rr_) : in(in_), in_n(in_n_), fd(fd_), rr(rr_), trace(tracing()) {}
+    static bool tracing() { static const bool t = getenv("SS_INGEST_TRACE") != nullptr; return t; }
+
+    double since() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); }
+    void lap(const char *what)
+    {
+        if (!trace) return;
+        hipStreamSynchronize(st);
+        fprintf(stderr, "[ginflate] %-18s at %.4f s\n", what, since());
+    }
+    bool h2d(void *dst, const void *src, uint64_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess; }
+    bool d2h(void *dst, const void *src, uint64_t bytes)
+    {
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+
+    // ---- the two ways out ------------------------------------------------------------------------------------------------------
+    // A stage that cannot go on says why and returns false; nothing else happens there.
+    bool no(const char *what, long long arg = 0) { why = Why{what, arg}; return false; }
+    void cleanup(bool keep_text)
+    {
         if (ahead.valid()) arena_put(ahead.get());            // (a call that leaves before it took the arena over)
-        auto now = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
-        const double c0 = now();
+        const double c0 = since();
         void *scratch[] = {d_in, d_entry, d_crc, d_tab};
         for (int q = 0; q < 4; q++) {
             if (!scratch[q]) continue;
             if (keep_text && A) A->late_free[q] = scratch[q];      // (freed by gpu_gunzip_done)
             else hipFreeAsync(scratch[q], st);
         }
-        const double c1 = now();
+        const double c1 = since();
         hipStreamSynchronize(st);
-        const double c2 = now();
+        const double c2 = since();
         call_stream_put(st);
-        if (trace) fprintf(stderr, "[ginflate] cleanup: free %.4f, sync %.4f, stream back %.4f s\n", c1 - c0, c2 - c1, now() - c2);
+        if (trace) fprintf(stderr, "[ginflate] cleanup: free %.4f, sync %.4f, stream back %.4f s\n", c1 - c0, c2 - c1, since() - c2);
         if (!keep_text) { arena_put(A); A = nullptr; }            // (else the caller holds it, with the text, until gpu_gunzip_done)
-    };
-    auto no = [&](const char *why, long long a = 0) {
-        if (trace) fprintf(stderr, "[ginflate] not handled: %s (%lld)\n", why, a);
+    }
+    // EVERY call that declines leaves through here: a rank that leaves must still serve the chain
+    bool declined()
+    {
+        if (trace) fprintf(stderr, "[ginflate] not handled: %s (%lld)\n", why.what ? why.what : "?", why.arg);
         if (rr) rr->abort_chain();                            // (the other ranks' chain goes on through this one)
         g_declined++;
         cleanup(false);
         return false;
-    };
-    auto h2d = [&](void *dst, const void *src, uint64_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
-    auto d2h = [&](void *dst, const void *src, uint64_t bytes) {
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-    };
-#define GI(call) do { if ((call) != hipSuccess) return no(#call); } while (0)
-#define GB(call) do { if (!(call)) return no(#call); } while (0)
-    // (a rank that only serves the chain may hold no more than the first 70 KB of the file: ss_fastq_dev.hip)
-    const uint64_t data_off = gzip_header_len(in, rr && rr->inject_decline ? std::min<uint64_t>(in_n, 70u << 10) : in_n);
-    if (!data_off) return no("header");
-    // SS_GZ_SPLIT_KB: blocks are entered every so many KB of deflate data (subsync_kernel; 0 = at their starts only)
-    uint64_t split_bytes = 12 << 10;
-    if (const char *e = getenv("SS_GZ_SPLIT_KB")) split_bytes = (uint64_t)std::max<long long>(0, atoll(e)) << 10;
-    uint64_t chunk_bytes = split_bytes ? 16 << 10 : 32 << 10, ratio = 12, seg_bytes = 128ull << 20;      // (split: every block's start should be found)
-    if (const char *e = getenv("SS_GZ_CHUNK")) chunk_bytes = std::max<uint64_t>(4096, (uint64_t)atoll(e));
-    if (const char *e = getenv("SS_GZ_SEG_KB")) seg_bytes = std::max<uint64_t>(64, (uint64_t)atoll(e)) << 10;      // (tests: many segments)
-    const uint64_t data_n = in_n - 8 - data_off;
-    seg_bytes = std::max(seg_bytes, 8 * chunk_bytes);
-    constexpr size_t SEG_CHUNKS = 16384;                      // chunks of a segment at most
-    const uint64_t n_chunks0_ = std::max<uint64_t>(1, (data_n + chunk_bytes - 1) / chunk_bytes);
-    if (n_chunks0_ > 0x7FFFFFF0ull) return no("size");
-    const uint32_t n_chunks0 = (uint32_t)n_chunks0_;
-    constexpr uint32_t LOOK = 64;                             // search chunks behind a slice in which its last chunk's stop is looked for
-    if (rr) {
-        // the slices, before anything can fail: every rank derives the same ones from the file's size
-        uint64_t slice_bytes = g_range.slice_bytes ? g_range.slice_bytes : std::min<uint64_t>(128ull << 20, std::max<uint64_t>(4ull << 20, data_n / (2ull * rr->world)));
-        if (const char *e = getenv("SS_GZ_SLICE_KB")) slice_bytes = std::max<uint64_t>(64, (uint64_t)atoll(e)) << 10;      // (tests: many slices)
-        rr->slice_chunks = (uint32_t)std::max<uint64_t>(2 * LOOK, slice_bytes / chunk_bytes);
-        rr->n_slices = (n_chunks0 + rr->slice_chunks - 1) / rr->slice_chunks;
-        rr->slice_chunks = (n_chunks0 + rr->n_slices - 1) / rr->n_slices;      // equal slices (no sliver at the end)
-        rr->n_slices = (n_chunks0 + rr->slice_chunks - 1) / rr->slice_chunks;
-        for (uint32_t sl = rr->rank; sl < rr->n_slices; sl += rr->world) rr->mine.push_back(sl);
-        if (rr->n_slices < 2) return no("one slice");         // nothing to share out: the whole-file path
-        if (rr->inject_decline) return no("declined on request (test hook, or the file could not be mapped)");
-        if (trace) fprintf(stderr, "[ginflate] range mode: rank %u of %u, %u slices of %u chunks, %zu mine\n", rr->rank, rr->world, rr->n_slices,
-                           rr->slice_chunks, rr->mine.size());
+    }
+    void hand_out(char **text_dev, uint64_t *len, void **lease)
+    {
+        cleanup(true);
+        g_handled++;
+        if (rr) { g_range_files++; g_range_pieces += rr->pieces->size(); }
+        *text_dev = (char *)d_text;
+        *len = total;
+        *lease = A;
     }
 
-    if (!have_stream) return no("hipStreamCreateWithFlags");
-    auto text_guess = [&] {
+    // ---- the header, the search chunks and -- range mode -- the slices -----------------------------------------------------------
+    bool plan()
+    {
+        // (a rank that only serves the chain may hold no more than the first 70 KB of the file: ss_fastq_dev.hip)
+        data_off = gzip_header_len(in, rr && rr->inject_decline ? std::min<uint64_t>(in_n, 70u << 10) : in_n);
+        if (!data_off) return no("header");
+        data_n = in_n - 8 - data_off;
+        const uint64_t n_chunks0_ = std::max<uint64_t>(1, (data_n + tn.chunk_bytes - 1) / tn.chunk_bytes);
+        if (n_chunks0_ > 0x7FFFFFF0ull) return no("size");
+        n_chunks0 = (uint32_t)n_chunks0_;
+        if (rr) {
+            // the slices, before anything can fail: every rank derives the same ones from the file's size
+            const uint64_t slice_bytes = tn.slice_bytes ? tn.slice_bytes : rr->slice_bytes ? rr->slice_bytes
+                                         : std::min<uint64_t>(128ull << 20, std::max<uint64_t>(4ull << 20, data_n / (2ull * rr->world)));
+            rr->slice_chunks = (uint32_t)std::max<uint64_t>(2 * LOOK, slice_bytes / tn.chunk_bytes);
+            rr->n_slices = (n_chunks0 + rr->slice_chunks - 1) / rr->slice_chunks;
+            rr->slice_chunks = (n_chunks0 + rr->n_slices - 1) / rr->n_slices;      // equal slices (no sliver at the end)
+            rr->n_slices = (n_chunks0 + rr->slice_chunks - 1) / rr->slice_chunks;
+            for (uint32_t sl = rr->rank; sl < rr->n_slices; sl += rr->world) rr->mine.push_back(sl);
+            if (rr->n_slices < 2) return no("one slice");         // nothing to share out: the whole-file path
+            if (rr->inject_decline) return no("declined on request (test hook, or the file could not be mapped)");
+            if (trace) fprintf(stderr, "[ginflate] range mode: rank %u of %u, %u slices of %u chunks, %zu mine\n", rr->rank, rr->world, rr->n_slices,
+                               rr->slice_chunks, rr->mine.size());
+        }
+        return st ? true : no("hipStreamCreateWithFlags");
+    }
+    uint64_t text_guess() const
+    {
         const uint8_t *t8 = in + in_n - 8;
         uint64_t guess = (uint64_t)t8[4] | (uint64_t)t8[5] << 8 | (uint64_t)t8[6] << 16 | (uint64_t)t8[7] << 24;      // ISIZE of the last member
         while (guess < in_n) guess += 1ull << 32;
         return (guess <= 16 * in_n ? guess : 3 * in_n) + 64;
-    };
-    // A LARGE file (round 5): its scratch arena and text buffer are allocated on a thread of their own WHILE the image travels --
+    }
+
+    // ---- a LARGE file: its scratch arena and text buffer are allocated on a thread of their own WHILE the image travels --
     // sized by what a segment can need at most (SEG_CHUNKS chunks, seg_bytes of data) instead of what this file's largest one
     // does, which is known only after the search.  A fresh process is handed new device memory at ~25 GB/s: for a 3.4 GB file
     // (4 GB of symbols + 7.7 GB of text) that was 0.14-0.38 s of waiting between the search and the first segment.
-    const bool big = fd >= 0 && !rr && in_n >= (256ull << 20);
-    if (big) {
+    void scratch_ahead()
+    {
+        if (fd < 0 || rr || in_n < (256ull << 20)) return;
         int device = 0;
         hipGetDevice(&device);
-        const uint64_t ub_chunks = SEG_CHUNKS + 80;
-        const uint64_t ub_need = (seg_bytes + chunk_bytes + SEG_CHUNKS) * ratio + SEG_CHUNKS * 4096;
-        const uint64_t ub_sym = ub_need + ub_need / 4 + 64 * (4096 + 64 * ratio), ub_text = text_guess();
+        const uint64_t ub_chunks = SEG_CHUNKS + 80, stage = in_n;
+        const uint64_t ub_sym = sym_room((tn.seg_bytes + tn.chunk_bytes + SEG_CHUNKS) * SYM_RATIO + SEG_CHUNKS * 4096), ub_text = text_guess();
         ahead = std::async(std::launch::async, [=]() -> Arena * {
-            if (hipSetDevice(device) != hipSuccess) return nullptr;
-            Arena *a = arena_take_if_fits(ub_chunks, ub_sym, ub_text);
-            if (!a) {
-                size_t mem_free = 0, mem_total = 0;
-                if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) return nullptr;
-                if (2 * ub_text + ub_sym * 2 + ub_chunks * WSIZE * 5 + (256ull << 20) + in_n > mem_free / 2) return nullptr;      // (decided below, with the real sizes)
-                a = arena_get(ub_chunks, ub_sym);
-            }
-            if (a && a->text_cap < ub_text) {
-                if (a->text) hipFree(a->text);
-                a->text = nullptr;
-                a->text_cap = 0;
-                uint64_t got = ub_text;
-                if (ss::big_malloc((void **)&a->text, ub_text, &got) == hipSuccess) a->text_cap = got;
-            }
-            return a;
+            Why w;                                            // (null: decided in take_scratch, with the real sizes)
+            return hipSetDevice(device) == hipSuccess ? acquire_scratch(nullptr, ub_chunks, ub_sym, ub_text, stage, &w) : nullptr;
         });
     }
-    GI(hipMallocAsync((void **)&d_in, in_n + 8192, st));                 // the stage is filled 1 KB at a time, up to 2 KB ahead
-    constexpr bool no_pread = false;
-    bool uploaded = false;
-    // (pinned buffers cost ~40 ms to make: a file of less than 256 MB takes that way only when a set is there already --
-    //  ss_gz_warm_up, or an earlier call -- and then arrives in 8 ms instead of 12-30)
-    const uint64_t pread_from = pin_waiting() ? 32ull << 20 : 256ull << 20;
-    const std::vector<Bgzf> bgzf = bgzf_members(in, in_n);            // a bgzip file: its members ARE the chunks, no search
-    uint64_t probe = 512;
-    uint32_t c_searched = 0;                                   // search chunks [0, c_searched) have been launched
-    auto search_to = [&](uint32_t c_hi) {
+
+    // ---- the image on the device, and the search for block starts in it -------------------------------------------------------------
+    void search_to(uint32_t c_hi)
+    {
+        // (the search in pieces, each started on the prefix of the image that had arrived.  Measured (26 loads of each setting
+        // interleaved in one process, a pair of 66 MB files): 1 piece -- upload, then search -- 26.0 ms, 2 pieces 26.3, 4 pieces
+        // 27.0, 8 pieces 28.4: the search is bound by the chip's throughput (4.5 ms for the pair), a piece takes as long as its
+        // slowest chunk, and the pieces of a stream run one after another.  So: one piece, when all of it is there.)
         if (c_hi > c_searched)
-            hipLaunchKernelGGL(sync_kernel, dim3(c_hi - c_searched), dim3(64), 0, st, d_in, in_n - 8, data_off, chunk_bytes, n_chunks0, d_entry, probe,
+            hipLaunchKernelGGL(sync_kernel, dim3(c_hi - c_searched), dim3(64), 0, st, d_in, in_n - 8, data_off, tn.chunk_bytes, n_chunks0, d_entry, (uint64_t)512,
                                trace ? 1 : 0, rr ? rr->slice_chunks : 0u, rr ? rr->rank : 0u, rr ? rr->world : 1u, LOOK, c_searched);
         c_searched = std::max(c_searched, c_hi);
-    };
-    if (fd >= 0 && in_n >= pread_from && !no_pread && !rr) {    // (`fd`: the same file; smaller ones are there before the buffers are)
+    }
+    bool stage_image()
+    {
+        GI(hipMallocAsync((void **)&d_in, in_n + 8192, st));                 // the stage is filled 1 KB at a time, up to 2 KB ahead
+        bool uploaded = false;
+        // (pinned buffers cost ~40 ms to make: a file of less than 256 MB takes that way only when a set is there already --
+        //  ss_gz_warm_up, or an earlier call -- and then arrives in 8 ms instead of 12-30)
+        const uint64_t pread_from = pin_waiting() ? 32ull << 20 : 256ull << 20;
+        const uint64_t margin = 64 << 10;
+        if (fd >= 0 && in_n >= pread_from && !rr) {               // (`fd`: the same file; smaller ones are there before the buffers are)
+            GI(hipMemsetAsync(d_in + in_n, 0, 8192, st));
+            GI(hipMallocAsync((void **)&d_entry, (uint64_t)n_chunks0 * 8, st));
+            GI(hipStreamSynchronize(st));                         // the allocations are stream-ordered
+            lap("stage allocated");
+            // the sync search runs on the prefix of the image that has arrived (a candidate's probe reads a few KB beyond its chunk)
+            uploaded = upload_file(fd, in_n, d_in, [&](uint64_t ready) {
+                // (runs on an upload thread, which has set the device; calls are serialised by upload_file)
+                if (!bgzf.empty()) return;
+                const uint64_t usable = ready >= in_n ? in_n : (ready > margin + data_off ? ready - margin - data_off : 0);
+                const uint32_t c_hi = ready >= in_n ? n_chunks0 : (uint32_t)std::min<uint64_t>(n_chunks0, usable / tn.chunk_bytes);
+                if (c_hi == n_chunks0 || c_hi >= c_searched + n_chunks0) {
+                    if (trace) fprintf(stderr, "[ginflate] search to chunk %u of %u at %.4f s\n", c_hi, n_chunks0, since());
+                    search_to(c_hi);
+                }
+            });
+            if (!uploaded) c_searched = 0;                         // (the image is copied again below: search everything)
+        }
+        if (!uploaded && rr) {
+            // range mode: only this rank's slices travel (+ the search chunks behind each in which its last chunk stops, + the
+            // header and the trailer); the rest of the image is never read
+            auto part = [&](uint64_t lo, uint64_t hi) { hi = std::min(hi, in_n); return lo >= hi || h2d(d_in + lo, in + lo, hi - lo); };
+            GB(part(0, data_off + margin));
+            GB(part(in_n > margin ? in_n - margin : 0, in_n));
+            for (uint32_t sl : rr->mine) {
+                const uint64_t lo = data_off + (uint64_t)sl * rr->slice_chunks * tn.chunk_bytes, hi = lo + ((uint64_t)rr->slice_chunks + LOOK + 8) * tn.chunk_bytes;
+                GB(part(lo > margin ? lo - margin : 0, hi + margin));
+            }
+            uploaded = true;
+        }
+        if (!uploaded) GB(h2d(d_in, in, in_n));
         GI(hipMemsetAsync(d_in + in_n, 0, 8192, st));
-        GI(hipMallocAsync((void **)&d_entry, (uint64_t)n_chunks0 * 8, st));
-        GI(hipStreamSynchronize(st));                         // the allocations are stream-ordered
-        lap("stage allocated");
-        // the sync search runs on the prefix of the image that has arrived (a candidate's probe reads a few KB beyond its chunk)
-        constexpr bool pipelined = true;
-        const uint64_t margin = 64 << 10;
-        uploaded = upload_file(fd, in_n, d_in, [&](uint64_t ready) {
-            if (!pipelined || !bgzf.empty()) return;
-            // (runs on an upload thread, which has set the device; calls are serialised by upload_file)
-            const uint64_t usable = ready >= in_n ? in_n : (ready > margin + data_off ? ready - margin - data_off : 0);
-            // (round 4, pieces > 1: the search starts on the prefix that has arrived, in that many pieces.  Measured (26 loads of each
-            // setting interleaved in one process, a pair of 66 MB files): 1 piece -- upload, then search -- 26.0 ms, 2 pieces 26.3,
-            // 4 pieces 27.0, 8 pieces 28.4: the search is bound by the chip's throughput (4.5 ms for the pair), a piece takes as
-            // long as its slowest chunk, and the pieces of a stream run one after another.  So: off.
-            constexpr uint32_t pieces = 1;
-            const uint32_t c_hi = ready >= in_n ? n_chunks0 : (uint32_t)std::min<uint64_t>(n_chunks0, usable / chunk_bytes);
-            if (c_hi == n_chunks0 || c_hi >= c_searched + (n_chunks0 + pieces - 1) / pieces) {
-                if (trace) fprintf(stderr, "[ginflate] search to chunk %u of %u at %.4f s\n", c_hi, n_chunks0, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
-                search_to(c_hi);
+        if (!d_entry) GI(hipMallocAsync((void **)&d_entry, (uint64_t)n_chunks0 * 8, st));
+        lap("input on device");
+        return true;
+    }
+    // entry[c]: the bit of the first block start in search chunk c, or ~0
+    bool search(std::vector<uint64_t> &entry)
+    {
+        entry.assign(n_chunks0, 0);
+        if (bgzf.empty()) {
+            search_to(n_chunks0);
+            GB(d2h(entry.data(), d_entry, (uint64_t)n_chunks0 * 8));
+        }
+        if (trace && bgzf.empty()) {
+            unsigned tries = 0;
+            hipMemcpyFromSymbol(&tries, HIP_SYMBOL(g_sync_tries), 4);
+            fprintf(stderr, "[ginflate] %u chunks, %u candidate blocks decoded\n", n_chunks0, tries);
+            tries = 0;
+            hipMemcpyToSymbol(HIP_SYMBOL(g_sync_tries), &tries, 4);
+        }
+        lap("sync");
+        if (g_hook_entry.load() > 0) {                           // test hook (ss_test_hook): a wrong entry (a position inside a block) in chunk <n>
+            const uint64_t c = (uint64_t)g_hook_entry.load();
+            if (c > 0 && c < n_chunks0) entry[c] = (data_off + c * tn.chunk_bytes) * 8 + 12345 % (tn.chunk_bytes * 8);
+        }
+        return true;
+    }
+
+    // ---- the chunk list G (range mode: and this rank's segments), from the search's entries or the members of a bgzip file: host only
+    bool chunk_list(const std::vector<uint64_t> &entry)
+    {
+        if (rr && !bgzf.empty()) {
+            // bgzip in range mode: a slice's chunks are the members whose deflate data begins in its byte range -- complete in
+            // themselves (no search, no look-ahead, nothing unknown in front of any); the chain still carries the newline count,
+            // the record that straddles the cut and the position the slice must begin at (hdr_bit: where its first member's header starts)
+            size_t mi = 0;
+            for (uint32_t sl : rr->mine) {
+                const uint64_t lo = sl == 0 ? 0 : data_off + (uint64_t)sl * rr->slice_chunks * tn.chunk_bytes;
+                const uint64_t hi = sl + 1 == rr->n_slices ? ~0ull : data_off + (uint64_t)(sl + 1) * rr->slice_chunks * tn.chunk_bytes;
+                while (mi < bgzf.size() && bgzf[mi].data < lo) mi++;
+                Seg sg{G.size(), 0, 0, sl, mi ? (bgzf[mi - 1].trailer + 8) * 8 : 0};
+                for (; mi < bgzf.size() && bgzf[mi].data < hi; mi++) G.push_back(Chunk{bgzf[mi].data * 8, true, true, bgzf[mi].trailer});
+                sg.gj = G.size();
+                if (sg.gj == sg.gi) return no("slice without a member", sl);
+                segs.push_back(sg);
             }
-        });
-        if (!uploaded) c_searched = 0;                         // (the image is copied again below: search everything)
-    }
-    if (!uploaded && rr) {
-        // range mode: only this rank's slices travel (+ the search chunks behind each in which its last chunk stops, + the
-        // header and the trailer); the rest of the image is never read
-        const uint64_t margin = 64 << 10;
-        auto part = [&](uint64_t lo, uint64_t hi) { hi = std::min(hi, in_n); return lo >= hi || h2d(d_in + lo, in + lo, hi - lo); };
-        GB(part(0, data_off + margin));
-        GB(part(in_n > margin ? in_n - margin : 0, in_n));
-        for (uint32_t sl : rr->mine) {
-            const uint64_t lo = data_off + (uint64_t)sl * rr->slice_chunks * chunk_bytes, hi = lo + ((uint64_t)rr->slice_chunks + LOOK + 8) * chunk_bytes;
-            GB(part(lo > margin ? lo - margin : 0, hi + margin));
-        }
-        uploaded = true;
-    }
-    if (!uploaded) GB(h2d(d_in, in, in_n));
-    GI(hipMemsetAsync(d_in + in_n, 0, 8192, st));
-    if (!d_entry) GI(hipMallocAsync((void **)&d_entry, (uint64_t)n_chunks0 * 8, st));
-    lap("input on device");
-    std::vector<uint64_t> entry(n_chunks0);
-    if (bgzf.empty()) {
-        search_to(n_chunks0);
-        GB(d2h(entry.data(), d_entry, (uint64_t)n_chunks0 * 8));
-    }
-    if (trace && bgzf.empty()) {
-        unsigned tries = 0;
-        hipMemcpyFromSymbol(&tries, HIP_SYMBOL(g_sync_tries), 4);
-        fprintf(stderr, "[ginflate] %u chunks, %u candidate blocks decoded\n", n_chunks0, tries);
-        tries = 0;
-        hipMemcpyToSymbol(HIP_SYMBOL(g_sync_tries), &tries, 4);
-    }
-    lap("sync");
-    if (g_hook_entry.load() > 0) {                           // test hook (ss_test_hook): a wrong entry (a position inside a block) in chunk <n>
-        const uint64_t c = (uint64_t)g_hook_entry.load();
-        if (c > 0 && c < n_chunks0) entry[c] = (data_off + c * chunk_bytes) * 8 + 12345 % (chunk_bytes * 8);
-    }
-    // The file's chunks: one per entry (a chunk of the search without one belongs to its predecessor).  `fresh`: the first
-    // chunk of a gzip member (nothing in front of it); `last`: it ends with the member's final block, the trailer follows
-    // at `trailer`.
-    // `hdr`: ~0, or -- an entry INSIDE a block (subsync_kernel) -- where that block's header is.
-    struct Chunk { uint64_t start; bool fresh, last; uint64_t trailer; uint64_t hdr = ~0ull; };
-    std::vector<Chunk> G;
-    struct Seg { size_t gi, gj, n_ph; uint32_t slice; uint64_t hdr_bit; };
-    std::vector<Seg> segs;                                   // range mode: one segment per slice of this rank, its look-ahead entries behind it
-    const bool is_bgzf = !bgzf.empty();
-    if (rr && is_bgzf) {
-        // bgzip in range mode: a slice's chunks are the members whose deflate data begins in its byte range -- complete in
-        // themselves (no search, no look-ahead, nothing unknown in front of any); the chain still carries the newline count,
-        // the record that straddles the cut and the position the slice must begin at (hdr_bit: where its first member's header starts)
-        size_t mi = 0;
-        for (uint32_t sl : rr->mine) {
-            const uint64_t lo = sl == 0 ? 0 : data_off + (uint64_t)sl * rr->slice_chunks * chunk_bytes;
-            const uint64_t hi = sl + 1 == rr->n_slices ? ~0ull : data_off + (uint64_t)(sl + 1) * rr->slice_chunks * chunk_bytes;
-            while (mi < bgzf.size() && bgzf[mi].data < lo) mi++;
-            Seg sg{G.size(), 0, 0, sl, mi ? (bgzf[mi - 1].trailer + 8) * 8 : 0};
-            for (; mi < bgzf.size() && bgzf[mi].data < hi; mi++) G.push_back(Chunk{bgzf[mi].data * 8, true, true, bgzf[mi].trailer});
-            sg.gj = G.size();
-            if (sg.gj == sg.gi) return no("slice without a member", sl);
-            segs.push_back(sg);
-        }
-        if (trace) fprintf(stderr, "[ginflate] bgzip: %zu members, %zu in this rank's slices\n", bgzf.size(), G.size());
-    } else if (rr) {
-        for (uint32_t sl : rr->mine) {
-            const uint32_t c_lo = sl * rr->slice_chunks, c_hi = std::min<uint32_t>(n_chunks0, c_lo + rr->slice_chunks);
-            Seg sg{G.size(), 0, 0, sl, 0};
-            for (uint32_t c = c_lo; c < c_hi; c++)
+            if (trace) fprintf(stderr, "[ginflate] bgzip: %zu members, %zu in this rank's slices\n", bgzf.size(), G.size());
+        } else if (rr) {
+            for (uint32_t sl : rr->mine) {
+                const uint32_t c_lo = sl * rr->slice_chunks, c_hi = std::min<uint32_t>(n_chunks0, c_lo + rr->slice_chunks);
+                Seg sg{G.size(), 0, 0, sl, 0};
+                for (uint32_t c = c_lo; c < c_hi; c++)
+                    if (entry[c] != ~0ull) G.push_back(Chunk{entry[c], c == 0, false, 0});
+                sg.gj = G.size();
+                if (sg.gj == sg.gi) return no("slice without a block start", sl);
+                if (sl + 1 < rr->n_slices) {
+                    for (uint32_t c = c_hi; c < std::min<uint32_t>(n_chunks0, c_hi + LOOK) && sg.n_ph < 2; c++)
+                        if (entry[c] != ~0ull) { G.push_back(Chunk{entry[c], false, false, 0}); sg.n_ph++; }
+                    if (!sg.n_ph) return no("no block start behind the slice", sl);
+                } else {
+                    G[sg.gj - 1].last = true;
+                    G[sg.gj - 1].trailer = in_n - 8;
+                }
+                segs.push_back(sg);
+            }
+        } else if (bgzf.empty()) {
+            for (uint32_t c = 0; c < n_chunks0; c++)
                 if (entry[c] != ~0ull) G.push_back(Chunk{entry[c], c == 0, false, 0});
-            sg.gj = G.size();
-            if (sg.gj == sg.gi) return no("slice without a block start", sl);
-            if (sl + 1 < rr->n_slices) {
-                for (uint32_t c = c_hi; c < std::min<uint32_t>(n_chunks0, c_hi + LOOK) && sg.n_ph < 2; c++)
-                    if (entry[c] != ~0ull) { G.push_back(Chunk{entry[c], false, false, 0}); sg.n_ph++; }
-                if (!sg.n_ph) return no("no block start behind the slice", sl);
-            } else {
-                G[sg.gj - 1].last = true;
-                G[sg.gj - 1].trailer = in_n - 8;
-            }
-            segs.push_back(sg);
+            G.back().last = true;
+            G.back().trailer = in_n - 8;
+        } else {
+            for (const Bgzf &m : bgzf) G.push_back(Chunk{m.data * 8, true, true, m.trailer});
+            if (trace) fprintf(stderr, "[ginflate] bgzip: %zu members\n", bgzf.size());
         }
-    } else if (bgzf.empty()) {
-        for (uint32_t c = 0; c < n_chunks0; c++)
-            if (entry[c] != ~0ull) G.push_back(Chunk{entry[c], c == 0, false, 0});
-        G.back().last = true;
-        G.back().trailer = in_n - 8;
-    } else {
-        for (const Bgzf &m : bgzf) G.push_back(Chunk{m.data * 8, true, true, m.trailer});
-        if (trace) fprintf(stderr, "[ginflate] bgzip: %zu members\n", bgzf.size());
+        return true;
     }
-    entry.clear();
-    entry.shrink_to_fit();
-    uint32_t n_sub = 0;
-    if (split_bytes && !is_bgzf && !G.empty()) {
-        // ---- entries inside the blocks: a block [its start, the next entry) of more than 2 x split_bytes is entered at
-        //      equidistant places as well (at most eight pieces; range mode: the look-ahead entries stay whole)
+
+    // ---- entries inside the blocks: a block [its start, the next entry) of more than 2 x split_bytes is entered at
+    //      equidistant places as well (at most eight pieces; range mode: the look-ahead entries stay whole)
+    bool enter_blocks()
+    {
+        if (!tn.split_bytes || !bgzf.empty() || G.empty()) return true;
         std::vector<uint64_t> b_hdr, s_from, s_lim;
         std::vector<uint32_t> b_first, s_of;                   // positions of a block: [b_first[b], b_first[b + 1]); s_of: which chunk of G
         auto want = [&](size_t i, uint64_t endb) {
-            const uint64_t len = endb - G[i].start, pieces = std::min<uint64_t>(8, len / (split_bytes * 8));
+            const uint64_t len = endb - G[i].start, pieces = std::min<uint64_t>(8, len / (tn.split_bytes * 8));
             if (pieces < 2) return;
             b_hdr.push_back(G[i].start);
             b_first.push_back((uint32_t)s_of.size());
@@ -1996,193 +2077,251 @@ static bool gpu_gunzip_impl(const uint8_t *in, uint64_t in_n, char **text_dev, u
                 }
             }
             at[G.size()] = G2.size();
-            for (Seg &sg : segs) { const size_t ph = sg.n_ph; sg.gi = at[sg.gi]; sg.gj = at[sg.gj]; sg.n_ph = ph; }
+            for (Seg &sg : segs) { sg.gi = at[sg.gi]; sg.gj = at[sg.gj]; }
             G.swap(G2);
         }
         if (trace) fprintf(stderr, "[ginflate] %zu entries inside blocks wanted, %u found: %zu chunks\n", ns, n_sub, G.size());
         lap("sub-entries");
+        return true;
     }
-
     // What a wave decodes alone is the stretch from its entry to the next.  Entries are dynamic blocks' starts (and places inside
     // them): zlib, pigz and libdeflate begin one every 16-300 KB, but a stream of stored or fixed-Huffman blocks only (level 0,
     // Z_FIXED, some hardware compressors) has none, and ONE wave would then decode the whole file -- minutes of a kernel that looks
     // like a hang.  Such a file goes to the host inflaters, which read it at memory speed.
-    if (!rr && !is_bgzf) {
+    bool no_lonely_stretch()
+    {
+        if (rr || !bgzf.empty()) return true;
         constexpr uint64_t LONELY_BYTES = 8ull << 20;
         uint64_t longest = 0;
         for (size_t i = 0; i < G.size(); i++)
             longest = std::max(longest, ((i + 1 < G.size() ? G[i + 1].start : (in_n - 8) * 8) - G[i].start) / 8);
-        if (longest > LONELY_BYTES) return no("a stretch of deflate data without a dynamic block's start (MB)", (long long)(longest >> 20));
+        return longest <= LONELY_BYTES ? true : no("a stretch of deflate data without a dynamic block's start (MB)", (long long)(longest >> 20));
     }
-    // The chunks are inflated SEGMENT by segment (seg_bytes of deflate data, 128 MB): the scratch stays a few GB whatever
-    // the file's size, and the text of one segment is complete -- bytes -- before the next one starts, so the 32 KB in
+
+    // ---- scratch.  The chunks are inflated SEGMENT by segment (seg_bytes of deflate data, 128 MB): the scratch stays a few GB
+    // whatever the file's size, and the text of one segment is complete -- bytes -- before the next one starts, so the 32 KB in
     // front of a segment's first chunk are simply the end of the text so far.
-    auto segment_end = [&](size_t gi) {
-        size_t gj = gi + 1;
-        while (gj < G.size() && (G[gj].start - G[gi].start) / 8 < seg_bytes && gj - gi < SEG_CHUNKS) gj++;
-        return gj;
-    };
-    uint64_t need_sym = 0, need_chunks = 0;                   // the largest segment decides the scratch
-    for (size_t gi = 0, si = 0; gi < G.size(); si++) {
-        const size_t gj = rr ? segs[si].gj : segment_end(gi);
-        const bool more = rr ? segs[si].n_ph > 0 : gj < G.size();
-        const uint64_t bytes = ((more ? G[gj].start : G[gj - 1].last ? G[gj - 1].trailer * 8 : (in_n - 8) * 8) - G[gi].start) / 8;
-        need_sym = std::max<uint64_t>(need_sym, (bytes + (gj - gi)) * ratio + (gj - gi) * 4096);
-        need_chunks = std::max<uint64_t>(need_chunks, gj - gi);
-        gi = rr ? (si + 1 < segs.size() ? segs[si + 1].gi : G.size()) : gj;
-    }
-    const uint64_t cap_chunks = need_chunks + 80;
-    const uint64_t sym_elems = need_sym + need_sym / 4 + 64 * (4096 + 64 * ratio);      // (+ what run-over and further members add)
-    if (sym_elems * 2 > (24ull << 30)) return no("segment", (long long)(sym_elems >> 20));      // (GBs without a single block start)
-    uint64_t text_cap;
-    if (ahead.valid()) {
-        A = ahead.get();
-        if (A && (A->cap_chunks < cap_chunks || A->sym_elems < sym_elems)) { arena_put(A); A = nullptr; }      // (cannot happen: the bounds are bounds)
-    }
+    size_t segment_end(size_t gi) const
     {
+        size_t gj = gi + 1;
+        while (gj < G.size() && (G[gj].start - G[gi].start) / 8 < tn.seg_bytes && gj - gi < SEG_CHUNKS) gj++;
+        return gj;
+    }
+    bool take_scratch()
+    {
+        uint64_t need_sym = 0, need_chunks = 0;                   // the largest segment decides the scratch
+        for (size_t gi = 0, si = 0; gi < G.size(); si++) {
+            const size_t gj = rr ? segs[si].gj : segment_end(gi);
+            const bool more = rr ? segs[si].n_ph > 0 : gj < G.size();
+            const uint64_t bytes = ((more ? G[gj].start : G[gj - 1].last ? G[gj - 1].trailer * 8 : (in_n - 8) * 8) - G[gi].start) / 8;
+            need_sym = std::max<uint64_t>(need_sym, (bytes + (gj - gi)) * SYM_RATIO + (gj - gi) * 4096);
+            need_chunks = std::max<uint64_t>(need_chunks, gj - gi);
+            gi = rr ? (si + 1 < segs.size() ? segs[si + 1].gi : G.size()) : gj;
+        }
+        cap_chunks = need_chunks + 80;
+        const uint64_t sym_elems = sym_room(need_sym);
+        if (sym_elems * 2 > (24ull << 30)) return no("segment", (long long)(sym_elems >> 20));      // (GBs without a single block start)
+        if (ahead.valid()) {
+            A = ahead.get();
+            if (A && (A->cap_chunks < cap_chunks || A->sym_elems < sym_elems)) { arena_put(A); A = nullptr; }      // (cannot happen: the bounds are bounds)
+        }
         text_cap = text_guess();
         if (rr) text_cap = text_cap / rr->n_slices * rr->mine.size() * 13 / 10 + (1ull << 20);      // this rank's share (it grows when short)
-        if (!A) A = arena_take_if_fits(cap_chunks, sym_elems, text_cap);
-        if (!A) {
-            size_t mem_free = 0, mem_total = 0;
-            GI(hipMemGetInfo(&mem_free, &mem_total));
-            const uint64_t need = 2 * text_cap + sym_elems * 2 + cap_chunks * WSIZE * 5 + (256ull << 20);
-            if (need > mem_free / 2) return no("device memory", (long long)(need >> 20));
-        }
-    }
-    if (!A) A = arena_get(cap_chunks, sym_elems);
-    if (!A) return no("scratch");
-    if (A->text_cap < text_cap) {
-        if (A->text) hipFree(A->text);
-        A->text = nullptr;
-        A->text_cap = 0;
-        GI(ss::big_malloc((void **)&A->text, text_cap, &text_cap));
-        A->text_cap = text_cap;
-    } else {
+        Why w;
+        A = acquire_scratch(A, cap_chunks, sym_elems, text_cap, 0, &w);
+        if (!A) return no(w.what, w.arg);
         text_cap = A->text_cap;
+        d_text = A->text;
+        lap("buffers");
+        d_start = A->meta; d_stop = A->meta + cap_chunks; d_off = A->meta + 2ull * cap_chunks; d_cap = A->meta + 3ull * cap_chunks;
+        d_len = A->meta + 4ull * cap_chunks; d_end = A->meta + 5ull * cap_chunks; d_toff = A->meta + 6ull * cap_chunks; d_hdr = A->meta + 7ull * cap_chunks;
+        return true;
     }
-    d_text = A->text;
-    lap("buffers");
-    uint64_t *d_start = A->meta, *d_stop = A->meta + cap_chunks, *d_off = A->meta + 2ull * cap_chunks, *d_cap = A->meta + 3ull * cap_chunks,
-             *d_len = A->meta + 4ull * cap_chunks, *d_end = A->meta + 5ull * cap_chunks, *d_toff = A->meta + 6ull * cap_chunks, *d_hdr = A->meta + 7ull * cap_chunks;
-    const uint32_t max_over = getenv("SS_GZ_NO_RUNOVER") ? 0u : n_sub ? 4u : 2u;      // (test hook: wrong entries are then handled by the host only)
-    struct Member { uint64_t at, len; uint32_t crc, isize; bool open; uint32_t crc0; uint64_t len0; };      // crc0, len0: range mode -- the member's part in the slices before
-    std::vector<Member> members;
-    uint64_t total = 0, last_end_bit = 0;
-    bool have_prev = false, ended = false;
-    uint32_t n_segments = 0;
 
-    // CRC-32 of text[at, at + n) for a list of (at, n) (range mode: every member's part in one slice, ONE launch for all of them --
-    // a bgzip slice holds thousands of members; the members of the whole-file path are done together below)
-    auto pieces_crc = [&](const std::vector<std::pair<uint64_t, uint64_t>> &items, std::vector<uint32_t> &out) -> bool {
-        constexpr int LG = 12;
-        const uint64_t sg = 1ull << LG;
-        std::vector<uint64_t> at_v;
-        std::vector<uint32_t> ln_v, tabv(256);
-        for (const auto &it : items)
-            for (uint64_t a0 = 0; a0 < it.second; a0 += sg) { at_v.push_back(it.first + a0); ln_v.push_back((uint32_t)std::min<uint64_t>(sg, it.second - a0)); }
-        const uint64_t ns = at_v.size();
-        out.assign(items.size(), (uint32_t)crc32(0L, Z_NULL, 0));
-        if (!ns) return true;
-        std::vector<uint32_t> got(ns);
-        for (uint32_t i = 0; i < 256; i++) { uint32_t kx = i; for (int j = 0; j < 8; j++) kx = (kx & 1u) ? 0xEDB88320u ^ (kx >> 1) : kx >> 1; tabv[i] = kx; }
-        uint32_t *pt = nullptr, *pc = nullptr;
-        if (hipMallocAsync((void **)&pt, 1024 + ns * 12, st) != hipSuccess) return false;
-        if (hipMallocAsync((void **)&pc, ns * 4, st) != hipSuccess) { hipFreeAsync(pt, st); return false; }
-        uint64_t *p_at = reinterpret_cast<uint64_t *>(pt + 256);
-        uint32_t *p_ln = reinterpret_cast<uint32_t *>(p_at + ns);
-        bool ok = h2d(pt, tabv.data(), 1024) && h2d(p_at, at_v.data(), ns * 8) && h2d(p_ln, ln_v.data(), ns * 4);
-        if (ok) {
-            hipLaunchKernelGGL(crc_kernel, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st, d_text, p_at, p_ln, ns, pt, pc);
-            ok = d2h(got.data(), pc, ns * 4);
+    // ---- one segment: lay out, inflate, repair ------------------------------------------------------------------------------------------
+    uint64_t bit_behind(const Segment &s, uint32_t c) const      // where chunk c's input ends at the latest
+    {
+        if (s.ch[c].last) return s.ch[c].trailer * 8;
+        if (c + 1 < s.ch.size()) return s.ch[c + 1].start;
+        if (!s.ph.empty()) return s.ph[0].start;
+        return (in_n - 8) * 8;
+    }
+    // every chunk a symbol region of its own, by the length of its input, and nothing in it yet.  false: more than the arena has
+    bool lay_out(Segment &s) const
+    {
+        uint64_t sym_total = 0;
+        for (uint32_t c = 0; c < s.ch.size(); c++) {
+            Rec &r = s.ch[c];
+            r.off = sym_total;
+            r.cap = ((bit_behind(s, c) - r.start) / 8 + 1) * SYM_RATIO + 4096;
+            r.len = r.end = 0;
+            r.status = 0;
+            sym_total += r.cap;
         }
-        hipFreeAsync(pt, st);
-        hipFreeAsync(pc, st);
-        if (!ok) return false;
-        uint32_t op[32];
-        crc_zero_operator(op, LG);
-        uint64_t si = 0;
-        for (size_t k = 0; k < items.size(); k++) {
-            uint32_t crc = out[k];
-            for (uint64_t a0 = 0; a0 < items[k].second; a0 += sg, si++)
-                crc = ln_v[si] == sg ? gf2_times(op, crc) ^ got[si] : (uint32_t)crc32_combine(crc, got[si], (z_off_t)ln_v[si]);
-            out[k] = crc;
+        return sym_total <= A->sym_elems;
+    }
+    // the device arrays of the segment's chunks and look-ahead entries, from the records (`todo` not empty: only those are
+    // inflated, what the other chunks produced stays as it is)
+    bool chunks_to_device(const Segment &s, const std::vector<uint32_t> &todo, Staging &h)
+    {
+        const uint32_t nc = (uint32_t)s.ch.size();
+        for (uint32_t c = 0; c < nc; c++) {
+            const Rec &r = s.ch[c];
+            h.start.push_back(r.start | (r.fresh ? 1ull << 63 : 0ull));
+            h.stop.push_back(r.last ? ~0ull : bit_behind(s, c));
+            h.off.push_back(r.off); h.cap.push_back(r.cap); h.hdr.push_back(r.hdr);
+            h.len.push_back(r.len); h.end.push_back(r.end); h.status.push_back(r.status);
+        }
+        for (size_t k = 0; k < s.ph.size(); k++) {              // look-ahead: only their stops are read
+            h.start.push_back(s.ph[k].start);
+            h.hdr.push_back(s.ph[k].hdr);
+            // (range mode: what follows the look-ahead entries in G is another slice: a chunk that runs over both of them is
+            //  stopped a few search chunks further on and declined)
+            h.stop.push_back(s.ph[k].last ? ~0ull : (k + 1 < s.ph.size() ? s.ph[k + 1].start
+                                                      : rr ? s.ph[k].start + 4 * tn.chunk_bytes * 8 : (s.gj + k + 1 < G.size() ? G[s.gj + k + 1].start : ~0ull)));
+            h.off.push_back(0);
+            h.cap.push_back(0);
+        }
+        const uint64_t n_all = nc + s.ph.size();
+        GB(h2d(d_start, h.start.data(), n_all * 8));
+        GB(h2d(d_stop, h.stop.data(), n_all * 8));
+        GB(h2d(d_off, h.off.data(), n_all * 8));
+        GB(h2d(d_cap, h.cap.data(), n_all * 8));
+        GB(h2d(d_hdr, h.hdr.data(), n_all * 8));
+        if (!todo.empty()) {
+            GB(h2d(A->status, h.status.data(), (uint64_t)nc * 4));
+            GB(h2d(d_len, h.len.data(), (uint64_t)nc * 8));
+            GB(h2d(d_end, h.end.data(), (uint64_t)nc * 8));
+            GB(h2d(A->todo, todo.data(), todo.size() * 4));
         }
         return true;
-    };
-    size_t seg_i = 0;
-    for (size_t gi = 0; gi < G.size();) {
-        // ---- the segment's chunks [gi, gj) and up to two look-ahead entries behind them (what a chunk may run over)
-        const size_t gj = rr ? segs[seg_i].gj : segment_end(gi);
-        const size_t ph_end = rr ? gj + segs[seg_i].n_ph : std::min(G.size(), gj + 2);
-        std::vector<Chunk> ch(G.begin() + (long)gi, G.begin() + (long)gj), ph(G.begin() + (long)gj, G.begin() + (long)ph_end);
-        uint32_t nc = (uint32_t)ch.size();
-        std::vector<uint64_t> start, stop, off, cap, hdrs;
-        uint64_t sym_total = 0;
-        auto bit_behind = [&](uint32_t c) -> uint64_t {      // where chunk c's input ends at the latest
-            if (ch[c].last) return ch[c].trailer * 8;
-            if (c + 1 < nc) return ch[c + 1].start;
-            if (!ph.empty()) return ph[0].start;
-            return (in_n - 8) * 8;
+    }
+    // Two things show only when the chunks have been inflated:
+    //  * An entry is a position where a valid dynamic header parses and 512 symbols decode -- a position INSIDE a
+    //    block passes that about once in a million candidates (every bit string decodes under a complete code).  The
+    //    chunk in front of it ends a block BEHIND it and goes on to the entry after it (inflate_kernel); the wrong
+    //    entry's chunk is dropped.  (No room left in its symbol region, or more than two in a row: -21, the two
+    //    chunks are merged here and inflated again.)
+    //  * A file of several members (lanes joined with `cat a.gz b.gz`): the chunk that meets a final block before its
+    //    stop (-20) ends a member if a trailer and a gzip header follow; the next member's first block becomes a chunk
+    //    and the segment is inflated again.
+    // -> s.ch: the new list of records, with what the unchanged chunks produced; `again`: positions in it that must be inflated
+    // (again; none, and nothing else new: *settled); `relayout`: new chunks need room of their own, lay everything out anew
+    bool repair(Segment &s, std::vector<uint32_t> &again, bool &relayout, bool *settled)
+    {
+        std::vector<Rec> &ch = s.ch;
+        const uint32_t nc = (uint32_t)ch.size(), n_all = nc + (uint32_t)s.ph.size();
+        std::vector<Rec> nxt;
+        std::vector<char> drop(nc, 0);
+        uint32_t n_drop = 0, n_members = 0, n_over = 0, over_ph = 0;
+        auto keep = [&](const Rec &r, bool last, uint64_t trailer) { nxt.push_back(r); nxt.back().last = last; nxt.back().trailer = trailer; };
+        // an entry inside a block whose chunk means nothing is no entry: the chunk in front (the last of nxt) takes its bytes
+        // and is inflated again
+        auto give_to_the_one_in_front = [&](const Rec &r) {
+            Rec &pv = nxt.back();
+            pv.last = r.last;
+            pv.trailer = r.trailer;
+            if (r.off == pv.off + pv.cap) pv.cap += r.cap;      // their symbol regions are neighbours
+            else relayout = true;
+            if (again.empty() || again.back() != (uint32_t)nxt.size() - 1) again.push_back((uint32_t)nxt.size() - 1);
+            n_drop++;
         };
-        auto lay_out = [&] {
-            start.clear(); stop.clear(); off.clear(); cap.clear(); hdrs.clear();
-            sym_total = 0;
-            for (uint32_t c = 0; c < nc; c++) {
-                hdrs.push_back(ch[c].hdr);
-                start.push_back(ch[c].start | (ch[c].fresh ? 1ull << 63 : 0ull));
-                stop.push_back(ch[c].last ? ~0ull : bit_behind(c));
-                const uint64_t cbits = bit_behind(c) - ch[c].start;
-                const uint64_t cp = (cbits / 8 + 1) * ratio + 4096;
-                off.push_back(sym_total);
-                cap.push_back(cp);
-                sym_total += cp;
+        for (uint32_t c = 0; c < nc; c++) {
+            if (drop[c]) continue;                                     // its own outcome means nothing
+            const uint64_t e = (ch[c].end + 7) / 8;
+            if (ch[c].status >= 0) {
+                // done; `over` entries behind it were positions inside its blocks: their chunks go, nothing is inflated again
+                const uint32_t over = (uint32_t)ch[c].status >> 4;
+                const int stc = ch[c].status & 15;
+                if (c + over < n_all) {
+                    const Chunk &eff = c + over < nc ? ch[c + over] : s.ph[c + over - nc];
+                    if (stc == (eff.last ? 1 : 0) && (!eff.last || e == eff.trailer)) {
+                        keep(ch[c], eff.last, eff.trailer);
+                        nxt.back().status = stc;
+                        for (uint32_t k = 1; k <= over; k++) {
+                            if (c + k < nc) drop[c + k] = 1;
+                            else over_ph = std::max(over_ph, c + k - nc + 1);
+                        }
+                        n_over += over;
+                        continue;
+                    }
+                }
+                ch[c].status = stc == 1 ? 1 : -21;                     // (falls through: a member's end, or not explainable)
             }
-            for (size_t k = 0; k < ph.size(); k++) {              // look-ahead: only their stops are read
-                start.push_back(ph[k].start);
-                hdrs.push_back(ph[k].hdr);
-                // (range mode: what follows the look-ahead entries in G is another slice: a chunk that runs over both of them is
-                //  stopped a few search chunks further on and declined)
-                stop.push_back(ph[k].last ? ~0ull : (k + 1 < ph.size() ? ph[k + 1].start
-                                                     : rr ? ph[k].start + 4 * chunk_bytes * 8 : (gj + k + 1 < G.size() ? G[gj + k + 1].start : ~0ull)));
-                off.push_back(0);
-                cap.push_back(0);
+            if (ch[c].status == -21 && c + 1 < nc) {                   // ran past the next entry: the two chunks become one
+                // (... and with them the entries inside blocks that follow: found with the tables of a block they are not in --
+                //  a chunk of the search that held two block starts --, what they decoded means nothing)
+                uint32_t k = c + 1;
+                while (k + 1 < nc && ch[k + 1].hdr != ~0ull) k++;
+                keep(ch[c], ch[k].last, ch[k].trailer);
+                for (uint32_t d = c + 1; d <= k; d++) {
+                    drop[d] = 1;
+                    n_drop++;
+                    if (ch[d].off == ch[c].off + nxt.back().cap) nxt.back().cap += ch[d].cap;      // their symbol regions are neighbours
+                    else relayout = true;
+                }
+                again.push_back((uint32_t)nxt.size() - 1);
+                continue;
             }
-        };
-        lay_out();
-        if (sym_total > A->sym_elems) return no("segment", (long long)gi);
-        std::vector<int> status(nc, 0);
-        std::vector<uint64_t> out_len(nc, 0), end_bit(nc, 0);
+            if (ch[c].status == -20 || ch[c].status == 1) {      // a final block before the next entry / before the file's end (its own, or run over to it)
+                const uint64_t hdr = e + 8 + 18 <= in_n ? gzip_header_len(in + e + 8, in_n - (e + 8)) : 0;
+                if (!hdr && ch[c].hdr != ~0ull && !nxt.empty()) { give_to_the_one_in_front(ch[c]); continue; }      // (an entry inside a block that decoded garbage)
+                if (!hdr) return no("chunk status", ch[c].status * 1000000ll + c);
+                keep(ch[c], true, e);
+                const uint64_t d = (e + 8 + hdr) * 8;                  // the next member's first block
+                bool was_last = ch[c].last;                            // (the new chunk ends the file if what it replaces did)
+                uint64_t was_trailer = ch[c].trailer;
+                // "entries" within the block, trailer and header -- and entries that claim to lie inside a block of the member that ends here
+                for (uint32_t k = c + 1; k < nc && (ch[k].start < d || (ch[k].hdr != ~0ull && ch[k].hdr < d)); k++) {
+                    drop[k] = 1;
+                    n_drop++;
+                    if (ch[k].last) { was_last = true; was_trailer = ch[k].trailer; }
+                }
+                if (c + 1 >= nc || drop[nc - 1])                       // (the look-ahead entries too)
+                    for (size_t k = 0; k < s.ph.size() && s.ph[k].start < d; k++) over_ph = std::max<uint32_t>(over_ph, (uint32_t)k + 1);
+                nxt.push_back(Rec{Chunk{d, true, was_last, was_trailer}});
+                n_members++;
+                relayout = true;
+                continue;
+            }
+            // (the chunk in front did not arrive at this entry: what it decoded means nothing)
+            if (ch[c].hdr != ~0ull && !nxt.empty()) { give_to_the_one_in_front(ch[c]); continue; }
+            return no("chunk status", ch[c].status * 1000000ll + c);
+        }
+        if (over_ph) {                                             // look-ahead entries that were run over are no chunks any more
+            over_ph = (uint32_t)std::min<size_t>(over_ph, s.ph.size());
+            s.consumed_ph += over_ph;
+            s.ph.erase(s.ph.begin(), s.ph.begin() + over_ph);
+        }
+        if (trace && n_over) fprintf(stderr, "[ginflate] %u entries were inside a block: run over\n", n_over);
+        ch.swap(nxt);                                              // (nothing dropped or run over: the same list)
+        *settled = !n_drop && !n_members;
+        if (trace && !*settled)
+            fprintf(stderr, "[ginflate] %u entries were inside a block, %u further members found: %s inflated again\n", n_drop, n_members,
+                    relayout ? "the segment" : "their chunks");
+        return true;
+    }
+    // the chunks G[s.gi, s.gj) to symbols, s.gj chosen here
+    bool inflate_segment(Segment &s, size_t seg_i)
+    {
+        s.gj = rr ? segs[seg_i].gj : segment_end(s.gi);
+        const size_t ph_end = rr ? s.gj + segs[seg_i].n_ph : std::min(G.size(), s.gj + 2);
+        for (size_t i = s.gi; i < s.gj; i++) s.ch.push_back(Rec{G[i]});
+        s.ph.assign(G.begin() + (long)s.gj, G.begin() + (long)ph_end);
+        if (!lay_out(s)) return no("segment", (long long)s.gi);
+        const uint32_t max_over = !tn.run_over ? 0u : n_sub ? 4u : 2u;
         std::vector<uint32_t> todo;                                // empty = all chunks
-        uint32_t consumed_ph = 0;
-        // Two things show only when the chunks have been inflated:
-        //  * An entry is a position where a valid dynamic header parses and 512 symbols decode -- a position INSIDE a
-        //    block passes that about once in a million candidates (every bit string decodes under a complete code).  The
-        //    chunk in front of it ends a block BEHIND it and goes on to the entry after it (inflate_kernel); the wrong
-        //    entry's chunk is dropped.  (No room left in its symbol region, or more than two in a row: -21, the two
-        //    chunks are merged here and inflated again.)
-        //  * A file of several members (lanes joined with `cat a.gz b.gz`): the chunk that meets a final block before its
-        //    stop (-20) ends a member if a trailer and a gzip header follow; the next member's first block becomes a chunk
-        //    and the segment is inflated again.
         for (int attempt = 0;; attempt++) {
-            const uint32_t n_all = nc + (uint32_t)ph.size();
-            GB(h2d(d_start, start.data(), (uint64_t)n_all * 8));
-            GB(h2d(d_stop, stop.data(), (uint64_t)n_all * 8));
-            GB(h2d(d_off, off.data(), (uint64_t)n_all * 8));
-            GB(h2d(d_cap, cap.data(), (uint64_t)n_all * 8));
-            GB(h2d(d_hdr, hdrs.data(), (uint64_t)n_all * 8));
-            if (!todo.empty()) {                                   // what the other chunks produced stays as it is
-                GB(h2d(A->status, status.data(), (uint64_t)nc * 4));
-                GB(h2d(d_len, out_len.data(), (uint64_t)nc * 8));
-                GB(h2d(d_end, end_bit.data(), (uint64_t)nc * 8));
-                GB(h2d(A->todo, todo.data(), todo.size() * 4));
-            }
+            const uint32_t nc = (uint32_t)s.ch.size(), n_all = nc + (uint32_t)s.ph.size();
+            Staging h;
+            if (!chunks_to_device(s, todo, h)) return false;
             const uint32_t n_run = todo.empty() ? nc : (uint32_t)todo.size();
             hipLaunchKernelGGL(inflate_kernel, dim3(n_run), dim3(64), 0, st, d_in, in_n - 8, d_start, d_stop, d_hdr, n_all, A->sym, d_off, d_cap, d_len, d_end, A->status,
                                todo.empty() ? (const uint32_t *)nullptr : A->todo, max_over);
-            GB(d2h(status.data(), A->status, (uint64_t)nc * 4));
-            GB(d2h(out_len.data(), d_len, (uint64_t)nc * 8));
-            GB(d2h(end_bit.data(), d_end, (uint64_t)nc * 8));
+            GB(d2h(h.status.data(), A->status, (uint64_t)nc * 4));
+            GB(d2h(h.len.data(), d_len, (uint64_t)nc * 8));
+            GB(d2h(h.end.data(), d_end, (uint64_t)nc * 8));
+            for (uint32_t c = 0; c < nc; c++) { s.ch[c].status = h.status[c]; s.ch[c].len = h.len[c]; s.ch[c].end = h.end[c]; }
 #ifdef SS_GZ_TIMING
             {
                 unsigned long long t[12], z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -2193,194 +2332,52 @@ static bool gpu_gunzip_impl(const uint8_t *in, uint64_t in_n, char **text_dev, u
                 fprintf(stderr, "[ginflate] matches %llu (symbols %llu), beyond the ring %llu, into the unknown window %llu; windows %llu\n", t[6], t[7], t[8], t[9], t[5]);
             }
 #endif
-            // the new chunk list, with what the unchanged chunks produced; `again`: positions in it that must be inflated (again)
-            std::vector<Chunk> nxt;
-            std::vector<uint64_t> n_off, n_cap, n_len, n_end;
-            std::vector<int> n_status;
             std::vector<uint32_t> again;
-            std::vector<char> drop(nc, 0);
-            uint32_t n_drop = 0, n_members = 0, n_over = 0, over_ph = 0;
-            bool relayout = false;                                 // new chunks need room of their own: lay everything out anew
-            auto keep = [&](uint32_t c, const Chunk &a) {
-                nxt.push_back(a); n_off.push_back(off[c]); n_cap.push_back(cap[c]); n_len.push_back(out_len[c]); n_end.push_back(end_bit[c]);
-                n_status.push_back(status[c]);
-            };
-            for (uint32_t c = 0; c < nc; c++) {
-                if (drop[c]) continue;                                     // its own outcome means nothing
-                const uint64_t e = (end_bit[c] + 7) / 8;
-                if (status[c] >= 0) {
-                    // done; `over` entries behind it were positions inside its blocks: their chunks go, nothing is inflated again
-                    const uint32_t over = (uint32_t)status[c] >> 4;
-                    const int stc = status[c] & 15;
-                    if (c + over < n_all) {
-                        const Chunk &eff = c + over < nc ? ch[c + over] : ph[c + over - nc];
-                        if (stc == (eff.last ? 1 : 0) && (!eff.last || e == eff.trailer)) {
-                            Chunk a = ch[c];
-                            a.last = eff.last;
-                            a.trailer = eff.trailer;
-                            keep(c, a);
-                            n_status.back() = stc;
-                            for (uint32_t k = 1; k <= over; k++) {
-                                if (c + k < nc) drop[c + k] = 1;
-                                else over_ph = std::max(over_ph, c + k - nc + 1);
-                            }
-                            n_over += over;
-                            continue;
-                        }
-                    }
-                    status[c] = stc == 1 ? 1 : -21;                        // (falls through: a member's end, or not explainable)
-                }
-                if (status[c] == -21 && c + 1 < nc) {                      // ran past the next entry: the two chunks become one
-                    // (... and with them the entries inside blocks that follow: found with the tables of a block they are not in --
-                    //  a chunk of the search that held two block starts --, what they decoded means nothing)
-                    uint32_t k = c + 1;
-                    while (k + 1 < nc && ch[k + 1].hdr != ~0ull) k++;
-                    Chunk a = ch[c];
-                    a.last = ch[k].last;
-                    a.trailer = ch[k].trailer;
-                    keep(c, a);
-                    for (uint32_t d = c + 1; d <= k; d++) {
-                        drop[d] = 1;
-                        n_drop++;
-                        if (off[d] == off[c] + n_cap.back()) n_cap.back() += cap[d];      // their symbol regions are neighbours
-                        else relayout = true;
-                    }
-                    again.push_back((uint32_t)nxt.size() - 1);
-                    continue;
-                }
-                if (status[c] == -20 || status[c] == 1) {      // a final block before the next entry / before the file's end (its own, or run over to it)
-                    const uint64_t hdr = e + 8 + 18 <= in_n ? gzip_header_len(in + e + 8, in_n - (e + 8)) : 0;
-                    if (!hdr && ch[c].hdr != ~0ull && !nxt.empty()) {         // (an entry inside a block that decoded garbage: see below)
-                        Chunk &pv = nxt.back();
-                        pv.last = ch[c].last;
-                        pv.trailer = ch[c].trailer;
-                        if (n_off.size() == nxt.size() && off[c] == n_off.back() + n_cap.back()) n_cap.back() += cap[c];
-                        else relayout = true;
-                        if (again.empty() || again.back() != (uint32_t)nxt.size() - 1) again.push_back((uint32_t)nxt.size() - 1);
-                        n_drop++;
-                        continue;
-                    }
-                    if (!hdr) return no("chunk status", status[c] * 1000000ll + c);
-                    Chunk a = ch[c];
-                    a.last = true;
-                    a.trailer = e;
-                    keep(c, a);
-                    const uint64_t d = (e + 8 + hdr) * 8;                  // the next member's first block
-                    bool was_last = ch[c].last;                            // (the new chunk ends the file if what it replaces did)
-                    uint64_t was_trailer = ch[c].trailer;
-                    // "entries" within the block, trailer and header -- and entries that claim to lie inside a block of the member that ends here
-                    for (uint32_t k = c + 1; k < nc && (ch[k].start < d || (ch[k].hdr != ~0ull && ch[k].hdr < d)); k++) {
-                        drop[k] = 1;
-                        n_drop++;
-                        if (ch[k].last) { was_last = true; was_trailer = ch[k].trailer; }
-                    }
-                    if (c + 1 >= nc || drop[nc - 1])                       // (the look-ahead entries too)
-                        for (size_t k = 0; k < ph.size() && ph[k].start < d; k++) over_ph = std::max<uint32_t>(over_ph, (uint32_t)k + 1);
-                    nxt.push_back(Chunk{d, true, was_last, was_trailer});
-                    n_members++;
-                    relayout = true;
-                    continue;
-                }
-                if (ch[c].hdr != ~0ull && !nxt.empty()) {
-                    // an entry inside a block whose chunk cannot be explained (the chunk in front did not arrive there: what it decoded
-                    // means nothing): no entry -- the chunk in front takes its bytes and is inflated again
-                    Chunk &pv = nxt.back();
-                    pv.last = ch[c].last;
-                    pv.trailer = ch[c].trailer;
-                    if (n_off.size() == nxt.size() && off[c] == n_off.back() + n_cap.back()) n_cap.back() += cap[c];
-                    else relayout = true;
-                    if (again.empty() || again.back() != (uint32_t)nxt.size() - 1) again.push_back((uint32_t)nxt.size() - 1);
-                    n_drop++;
-                    continue;
-                }
-                return no("chunk status", status[c] * 1000000ll + c);
-            }
-            if (over_ph) {                                             // look-ahead entries that were run over are no chunks any more
-                over_ph = (uint32_t)std::min<size_t>(over_ph, ph.size());
-                consumed_ph += over_ph;
-                ph.erase(ph.begin(), ph.begin() + over_ph);
-                // (the arrays' look-ahead part is only read by chunks that run over again: rebuilt below when something is inflated again)
-            }
-            if (trace && n_over) fprintf(stderr, "[ginflate] %u entries were inside a block: run over\n", n_over);
-            if (!n_drop && !n_members) {
-                if (n_over) {                                          // the shorter chunk list, everything else as it is
-                    ch.swap(nxt);
-                    nc = (uint32_t)ch.size();
-                    off.swap(n_off); cap.swap(n_cap); out_len.swap(n_len); end_bit.swap(n_end); status.swap(n_status);
-                }
-                break;
-            }
-            if (trace) fprintf(stderr, "[ginflate] %u entries were inside a block, %u further members found: %s inflated again\n", n_drop, n_members,
-                               relayout ? "the segment" : "their chunks");
-            if (attempt >= 6 || nxt.size() + ph.size() > cap_chunks - 4) return no("chunk list", (long long)nxt.size());
-            ch.swap(nxt);
-            nc = (uint32_t)ch.size();
+            bool relayout = false, settled = false;
+            if (!repair(s, again, relayout, &settled)) return false;
+            if (settled) return true;
+            if (attempt >= 6 || s.ch.size() + s.ph.size() > cap_chunks - 4) return no("chunk list", (long long)s.ch.size());
             if (relayout) {
-                lay_out();
-                if (sym_total > A->sym_elems) return no("symbol budget");
+                if (!lay_out(s)) return no("symbol budget");
                 todo.clear();
-                status.assign(nc, 0);
-                out_len.assign(nc, 0); end_bit.assign(nc, 0);
             } else {
-                off.swap(n_off); cap.swap(n_cap); out_len.swap(n_len); end_bit.swap(n_end); status.swap(n_status);
-                const std::vector<uint64_t> o2 = off, c2 = cap;
-                lay_out();                                             // (starts, stops, look-ahead) ...
-                off = o2; cap = c2;                                    // ... the symbol regions stay where they are
-                off.resize(nc + ph.size(), 0); cap.resize(nc + ph.size(), 0);
-                todo.swap(again);
+                todo.swap(again);                                  // (the symbol regions stay where they are)
             }
         }
-        // ---- range mode: what lies in front of this slice comes down the chain now (the symbols are ready: the ranks did that
-        //      part at the same time); the slice must begin exactly where the one before ended
-        const uint32_t my_slice = rr ? segs[seg_i].slice : 0;
-        uint64_t nl_before = 0, len_before = 0;
-        uint32_t crc_before = (uint32_t)crc32(0L, Z_NULL, 0);
-        std::vector<uint8_t> carry_in;
-        if (rr) {
-            if (consumed_ph || ch.size() == 0) return no("range: entries dropped at the slice edge", my_slice);
-            if (my_slice > 0) {
-                if (!rr->recv_for(my_slice)) return no("chain receive", my_slice);
-                if (rr->msg.status < 0) return no("chain: a rank before this one declined", my_slice);
-                if (rr->msg.end_bit != (is_bgzf ? segs[seg_i].hdr_bit : ch[0].start) || rr->msg.carry_len > CARRY_MAX)
-                    return no("range: the slice before ends elsewhere", my_slice);
-                GB(h2d(A->prev, rr->msg.window, WSIZE));
-                have_prev = true;
-                nl_before = rr->msg.nl; len_before = rr->msg.len; crc_before = rr->msg.crc;
-                carry_in.assign(rr->msg.carry, rr->msg.carry + rr->msg.carry_len);
-            } else {
-                have_prev = false;
-            }
-            // the member that is open at the cut goes on in this slice (several members -- lanes joined with cat -- are followed
-            // as in the whole-file path: a member that ends inside the slice is checked against its trailer here, the next one
-            // starts with nothing in front of it; CRC-32 and length of the open member travel down the chain)
-            if (!ch[0].fresh) members.push_back(Member{total, 0, 0, 0, true, crc_before, len_before});
-        }
-        const size_t m_first = members.empty() ? 0 : members.size() - ((rr && !ch[0].fresh) ? 1 : 0);      // members of this segment: [m_first, ...)
-        // ---- the segment's text
-        std::vector<uint64_t> text_off(nc, 0);
+    }
+
+    // ---- symbols to text -------------------------------------------------------------------------------------------------------------
+    bool segment_text(Segment &s)
+    {
+        const uint32_t nc = (uint32_t)s.ch.size();
+        s.m_first = members.empty() ? 0 : members.size() - ((rr && !s.ch[0].fresh) ? 1 : 0);
+        s.text_off.assign(nc, 0);
+        std::vector<uint64_t> off(nc), len(nc);
         for (uint32_t c = 0; c < nc; c++) {
-            if (ch[c].fresh) members.push_back(Member{total, 0, 0, 0, true, (uint32_t)crc32(0L, Z_NULL, 0), 0});
+            const Rec &r = s.ch[c];
+            if (r.fresh) members.push_back(Member{total, 0, 0, 0, true, (uint32_t)crc32(0L, Z_NULL, 0), 0});
             if (members.empty() || !members.back().open) return no("member start");
-            text_off[c] = total;
-            total += out_len[c];
-            members.back().len += out_len[c];
-            if (ch[c].last) {
-                const uint8_t *t8 = in + ch[c].trailer;
+            s.text_off[c] = total;
+            off[c] = r.off;
+            len[c] = r.len;
+            total += r.len;
+            members.back().len += r.len;
+            if (r.last) {
+                const uint8_t *t8 = in + r.trailer;
                 Member &m = members.back();
                 m.crc = (uint32_t)t8[0] | (uint32_t)t8[1] << 8 | (uint32_t)t8[2] << 16 | (uint32_t)t8[3] << 24;
                 m.isize = (uint32_t)t8[4] | (uint32_t)t8[5] << 8 | (uint32_t)t8[6] << 16 | (uint32_t)t8[7] << 24;
                 m.open = false;
                 if ((uint32_t)(m.len + m.len0) != m.isize) return no("isize", (long long)members.size());      // (range mode: + its part in the slices before)
-                ended = ch[c].trailer == in_n - 8;
+                ended = r.trailer == in_n - 8;
             }
         }
-        last_end_bit = end_bit[nc - 1];
+        last_end_bit = s.ch[nc - 1].end;
         if (total + 64 > text_cap) {                                   // (several members: the last ISIZE said little)
             const uint64_t ncap = std::max(total + 64, text_cap + text_cap / 2);
             uint8_t *nt = nullptr;
             GI(hipMalloc((void **)&nt, ncap));
-            const uint64_t have = total - (total - text_off[0]);
-            const bool ok = hipMemcpyAsync(nt, d_text, have, hipMemcpyDeviceToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+            const bool ok = hipMemcpyAsync(nt, d_text, s.text_off[0], hipMemcpyDeviceToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
             hipFree(d_text);
             d_text = nt;
             text_cap = ncap;
@@ -2389,154 +2386,218 @@ static bool gpu_gunzip_impl(const uint8_t *in, uint64_t in_n, char **text_dev, u
             if (!ok) return no("text copy");
         }
         GB(h2d(d_off, off.data(), (uint64_t)nc * 8));
-        GB(h2d(d_len, out_len.data(), (uint64_t)nc * 8));
-        GB(h2d(d_toff, text_off.data(), (uint64_t)nc * 8));
-        {
-            uint32_t group = 1;
-            while ((uint64_t)group * group < nc) group++;               // ~sqrt: as many groups as chunks in a group
-            group = std::max<uint32_t>(group, 8);
-            const uint32_t n_groups = (nc + group - 1) / group;
-            hipLaunchKernelGGL(tails_kernel, dim3(16, nc), dim3(256), 0, st, A->sym, d_off, d_len, nc, A->map[0]);
-            hipLaunchKernelGGL(group_maps_kernel, dim3(n_groups), dim3(1024), 0, st, A->map[0], nc, group, A->map[1]);
-            hipLaunchKernelGGL(group_windows_kernel, dim3(1), dim3(1024), 0, st, A->map[1], nc, group, n_groups,
-                               have_prev ? (const uint8_t *)A->prev : (const uint8_t *)nullptr, A->gwin);
-            hipLaunchKernelGGL(windows_kernel, dim3(16, nc), dim3(256), 0, st, A->map[1], nc, group, (const uint8_t *)A->gwin, A->win);
-            hipLaunchKernelGGL(bytes_kernel, dim3(64, nc), dim3(256), 0, st, A->sym, d_off, d_len, d_toff, A->win, d_text);
-            hipLaunchKernelGGL(lastwin_kernel, dim3(WSIZE / 256), dim3(256), 0, st, d_text, total, A->prev);
-            GI(hipGetLastError());
-            GI(hipStreamSynchronize(st));                          // (the host arrays of this segment go out of scope)
-        }
+        GB(h2d(d_len, len.data(), (uint64_t)nc * 8));
+        GB(h2d(d_toff, s.text_off.data(), (uint64_t)nc * 8));
+        uint32_t group = 1;
+        while ((uint64_t)group * group < nc) group++;               // ~sqrt: as many groups as chunks in a group
+        group = std::max<uint32_t>(group, 8);
+        const uint32_t n_groups = (nc + group - 1) / group;
+        hipLaunchKernelGGL(tails_kernel, dim3(16, nc), dim3(256), 0, st, A->sym, d_off, d_len, nc, A->map[0]);
+        hipLaunchKernelGGL(group_maps_kernel, dim3(n_groups), dim3(1024), 0, st, A->map[0], nc, group, A->map[1]);
+        hipLaunchKernelGGL(group_windows_kernel, dim3(1), dim3(1024), 0, st, A->map[1], nc, group, n_groups,
+                           have_prev ? (const uint8_t *)A->prev : (const uint8_t *)nullptr, A->gwin);
+        hipLaunchKernelGGL(windows_kernel, dim3(16, nc), dim3(256), 0, st, A->map[1], nc, group, (const uint8_t *)A->gwin, A->win);
+        hipLaunchKernelGGL(bytes_kernel, dim3(64, nc), dim3(256), 0, st, A->sym, d_off, d_len, d_toff, A->win, d_text);
+        hipLaunchKernelGGL(lastwin_kernel, dim3(WSIZE / 256), dim3(256), 0, st, d_text, total, A->prev);
+        GI(hipGetLastError());
+        GI(hipStreamSynchronize(st));                          // (the host arrays of this segment go out of scope)
         have_prev = true;
         n_segments++;
-        if (rr) {
-            // ---- this slice's piece: CRC, newlines, the bytes behind its last complete record; then the chain goes on
-            const uint64_t p_at = text_off[0], p_len = total - text_off[0];
-            if (p_len < WSIZE && my_slice + 1 < rr->n_slices) return no("range: a slice with less text than a window", my_slice);      // (the window it hands on would reach into another piece)
-            // CRC-32 of every member's part in this slice: a member that ended here against its trailer, the open one goes on
-            uint32_t crc_now = (uint32_t)crc32(0L, Z_NULL, 0);
-            uint64_t len_now = 0;
-            std::vector<std::pair<uint64_t, uint64_t>> m_items;
-            for (size_t mi = m_first; mi < members.size(); mi++) m_items.emplace_back(members[mi].at, members[mi].len);
-            std::vector<uint32_t> m_crc;
-            if (!pieces_crc(m_items, m_crc)) return no("piece crc", my_slice);
-            for (size_t mi = m_first; mi < members.size(); mi++) {
-                const Member &m = members[mi];
-                const uint32_t c = m.len ? (uint32_t)crc32_combine(m.crc0, m_crc[mi - m_first], (z_off_t)m.len) : m.crc0;
-                if (!m.open) { if (c != m.crc) return no("crc (range mode)", (long long)mi); }
-                else if (mi + 1 == members.size()) { crc_now = c; len_now = m.len0 + m.len; }
-                else return no("member left open", (long long)mi);
-            }
-            unsigned long long p_nl = 0;
-            GI(hipMemsetAsync(d_entry, 0, 8, st));                   // (the entries are on the host by now: a free device word)
-            hipLaunchKernelGGL(count_nl_kernel, dim3(1024), dim3(256), 0, st, d_text + p_at, p_len, reinterpret_cast<unsigned long long *>(d_entry));
-            GB(d2h(&p_nl, d_entry, 8));
-            const bool final_slice = my_slice + 1 == rr->n_slices;
-            uint64_t keep = p_len;                                   // bytes of the piece up to the end of its last complete record
-            if (!final_slice) {
-                // records end at newlines whose number in the file is a multiple of four: the last such newline of this piece is
-                // among its last four; the tail of the piece is looked at on the host
-                const uint64_t drop = (nl_before + p_nl) % 4;        // newlines behind the last complete record
-                if (p_nl < drop + 1) return no("range: a slice without a complete record", my_slice);
-                const uint64_t tail = std::min<uint64_t>(p_len, (uint64_t)CARRY_MAX + 1);
-                std::vector<uint8_t> tb(tail);
-                GB(d2h(tb.data(), d_text + p_at + (p_len - tail), tail));
-                uint64_t seen = 0, q = tail;
-                while (q > 0) {                                      // q - 1: the newline that ends the last complete record
-                    if (tb[q - 1] == '\n') { if (seen == drop) break; seen++; }
-                    q--;
-                }
-                if (q == 0) return no("range: a record longer than the chain carries", my_slice);
-                keep = p_len - tail + q;
-                rr->msg.status = 0;
-                rr->msg.crc = crc_now;
-                rr->msg.len = len_now;
-                rr->msg.nl = nl_before + p_nl;
-                rr->msg.end_bit = is_bgzf ? (ch[nc - 1].trailer + 8) * 8 : end_bit[nc - 1];      // (bgzip: the next member's header)
-                rr->msg.carry_len = (uint32_t)(p_len - keep);
-                memcpy(rr->msg.carry, tb.data() + q, p_len - keep);
-                GB(d2h(rr->msg.window, A->prev, WSIZE));
-                if (!rr->send_from(my_slice)) return no("chain send", my_slice);
-            } else if (members.empty() || members.back().open) {
-                return no("the last member is not closed (range mode)");     // (every closed member was checked against its trailer above)
-            }
-            rr->pieces->push_back(GzPiece{p_at, p_len, keep, carry_in});
-            rr->duty++;
-            rr->received = false;
-            seg_i++;
-            gi = seg_i < segs.size() ? segs[seg_i].gi : G.size();
-        } else {
-            gi = gj + consumed_ph;
-        }
-    }
-    lap("inflate + windows + bytes");
-    if (trace) fprintf(stderr, "[ginflate] %u segments, %zu members\n", n_segments, members.size());
-    if (rr) {
-        // (every piece was checked as it was made; the owner of the last slice has compared CRC-32 and length with the trailer
-        //  and seen the stream end where the trailer begins)
-        if (!rr->mine.empty() && rr->mine.back() + 1 == rr->n_slices && (!ended || (last_end_bit + 7) / 8 != in_n - 8))
-            return no("stream end (range mode)", (long long)((last_end_bit + 7) / 8));
-        cleanup(true);
-        g_handled++;
-        g_range_files++;
-        g_range_pieces += rr->pieces->size();
-        *text_dev = (char *)d_text;
-        *len = total;
-        *lease = A;
         return true;
     }
-    // the stream must end where the last trailer begins (after padding to a byte)
-    if (!ended || members.empty() || members.back().open || (last_end_bit + 7) / 8 != in_n - 8) return no("stream end", (long long)((last_end_bit + 7) / 8));
-    // CRC-32 by segments of 4 KB from every member's first byte, combined on the host with ONE precomputed operator
-    constexpr int SEG_LOG2 = 12;
-    const uint64_t seg = 1ull << SEG_LOG2;
-    std::vector<CrcMember> cm;
-    uint64_t nseg = 0;
-    for (const Member &m : members) {
-        if (!m.len) continue;                                  // (an empty member has no segment: its CRC is that of nothing)
-        cm.push_back(CrcMember{m.at, m.len, nseg});
-        nseg += (m.len + seg - 1) >> SEG_LOG2;
-    }
-    GI(hipMallocAsync((void **)&d_tab, std::max<size_t>(16, cm.size() * sizeof(CrcMember)), st));      // (the member table)
-    GI(hipMallocAsync((void **)&d_crc, std::max<uint64_t>(1, nseg) * 4, st));
-    std::vector<uint32_t> crcs(std::max<uint64_t>(1, nseg));
-    if (nseg) {
-        GB(h2d(d_tab, cm.data(), cm.size() * sizeof(CrcMember)));
-        hipLaunchKernelGGL(crc_members_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, st, d_text, reinterpret_cast<const CrcMember *>(d_tab), (uint32_t)cm.size(), nseg,
-                           SEG_LOG2, d_crc);
-        GB(d2h(crcs.data(), d_crc, nseg * 4));
-    }
-    bool crc_ok = true;
+
+    // ---- verification: CRC-32 of the text ranges (at, len), by segments of 4 KB from every range's first byte, combined on the host
+    // with ONE precomputed operator.  (All members of a file at its end; range mode: every member's part in one slice -- a
+    // bgzip slice holds thousands.)
+    bool text_crcs(const std::vector<std::pair<uint64_t, uint64_t>> &items, std::vector<uint32_t> &out)
     {
+        constexpr int SEG_LOG2 = 12;
+        const uint64_t seg = 1ull << SEG_LOG2;
+        std::vector<CrcMember> cm;
+        uint64_t nseg = 0;
+        for (const auto &it : items) {
+            if (!it.second) continue;                              // (an empty range has no segment: its CRC is that of nothing)
+            cm.push_back(CrcMember{it.first, it.second, nseg});
+            nseg += (it.second + seg - 1) >> SEG_LOG2;
+        }
+        if (d_tab) { hipFreeAsync(d_tab, st); d_tab = nullptr; }      // (range mode: the slice before's)
+        if (d_crc) { hipFreeAsync(d_crc, st); d_crc = nullptr; }
+        GI(hipMallocAsync((void **)&d_tab, std::max<size_t>(16, cm.size() * sizeof(CrcMember)), st));      // (the member table)
+        GI(hipMallocAsync((void **)&d_crc, std::max<uint64_t>(1, nseg) * 4, st));
+        std::vector<uint32_t> crcs(std::max<uint64_t>(1, nseg));
+        if (nseg) {
+            GB(h2d(d_tab, cm.data(), cm.size() * sizeof(CrcMember)));
+            hipLaunchKernelGGL(crc_members_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, st, d_text, (const CrcMember *)d_tab, (uint32_t)cm.size(), nseg, SEG_LOG2,
+                               d_crc);
+            GB(d2h(crcs.data(), d_crc, nseg * 4));
+        }
         uint32_t op[32];
         crc_zero_operator(op, SEG_LOG2);
         // the operator as four byte-indexed tables: one application = four lookups (there are 250 segments per MB)
         std::vector<uint32_t> opt(4 * 256);
         for (int byte = 0; byte < 4; byte++)
             for (uint32_t v = 0; v < 256; v++) opt[(size_t)byte * 256 + v] = gf2_times(op, v << (8 * byte));
+        out.clear();
         uint64_t si = 0;
-        for (const Member &m : members) {
+        for (const auto &it : items) {
             uint32_t crc = (uint32_t)crc32(0L, Z_NULL, 0);
-            for (uint64_t a0 = 0; a0 < m.len; a0 += seg, si++) {
-                const uint64_t l = std::min<uint64_t>(seg, m.len - a0);
+            for (uint64_t a0 = 0; a0 < it.second; a0 += seg, si++) {
+                const uint64_t l = std::min<uint64_t>(seg, it.second - a0);
                 if (l == seg) crc = opt[crc & 0xFF] ^ opt[256 + ((crc >> 8) & 0xFF)] ^ opt[512 + ((crc >> 16) & 0xFF)] ^ opt[768 + (crc >> 24)] ^ crcs[si];
                 else crc = (uint32_t)crc32_combine(crc, crcs[si], (z_off_t)l);
             }
-            crc_ok = crc_ok && crc == m.crc;
+            out.push_back(crc);
         }
+        return true;
     }
-    lap("crc");
+    // the whole-file path: every member against its trailer
+    bool verify_members()
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> items;
+        for (const Member &m : members) items.emplace_back(m.at, m.len);
+        std::vector<uint32_t> crc;
+        if (!text_crcs(items, crc)) return false;
+        bool crc_ok = true;
+        for (size_t mi = 0; mi < members.size(); mi++) crc_ok = crc_ok && crc[mi] == members[mi].crc;
+        lap("crc");
+#ifdef SS_GZ_DEBUG_SKIPCRC           // diagnostic builds only (scripts/dev): hand out the text although it is wrong
+        if (!crc_ok) fprintf(stderr, "[ginflate] CRC MISMATCH (debug build: text returned)\n");
+        return true;
+#else
+        return crc_ok ? true : no("crc");
+#endif
+    }
+
+    // ---- range mode: what lies in front of this slice comes down the chain now (the symbols are ready: the ranks did that
+    //      part at the same time); the slice must begin exactly where the one before ended
+    bool slice_receive(const Segment &s, const Seg &sg, ChainIn &before)
+    {
+        if (s.consumed_ph || s.ch.empty()) return no("range: entries dropped at the slice edge", sg.slice);
+        if (sg.slice > 0) {
+            if (!rr->recv_for(sg.slice)) return no("chain receive", sg.slice);
+            if (rr->msg.status < 0) return no("chain: a rank before this one declined", sg.slice);
+            if (rr->msg.end_bit != (!bgzf.empty() ? sg.hdr_bit : s.ch[0].start) || rr->msg.carry_len > CARRY_MAX)
+                return no("range: the slice before ends elsewhere", sg.slice);
+            GB(h2d(A->prev, rr->msg.window, WSIZE));
+            have_prev = true;
+            before.nl = rr->msg.nl; before.len = rr->msg.len; before.crc = rr->msg.crc;
+            before.carry.assign(rr->msg.carry, rr->msg.carry + rr->msg.carry_len);
+        } else {
+            have_prev = false;
+        }
+        // the member that is open at the cut goes on in this slice (several members -- lanes joined with cat -- are followed
+        // as in the whole-file path: a member that ends inside the slice is checked against its trailer here, the next one
+        // starts with nothing in front of it; CRC-32 and length of the open member travel down the chain)
+        if (!s.ch[0].fresh) members.push_back(Member{total, 0, 0, 0, true, before.crc, before.len});
+        return true;
+    }
+    // ---- this slice's piece: CRC, newlines, the bytes behind its last complete record; then the chain goes on
+    bool slice_piece(const Segment &s, const Seg &sg, const ChainIn &before)
+    {
+        const uint32_t my_slice = sg.slice;
+        const uint64_t p_at = s.text_off[0], p_len = total - s.text_off[0];
+        if (p_len < WSIZE && my_slice + 1 < rr->n_slices) return no("range: a slice with less text than a window", my_slice);      // (the window it hands on would reach into another piece)
+        // CRC-32 of every member's part in this slice: a member that ended here against its trailer, the open one goes on
+        uint32_t crc_now = (uint32_t)crc32(0L, Z_NULL, 0);
+        uint64_t len_now = 0;
+        std::vector<std::pair<uint64_t, uint64_t>> m_items;
+        for (size_t mi = s.m_first; mi < members.size(); mi++) m_items.emplace_back(members[mi].at, members[mi].len);
+        std::vector<uint32_t> m_crc;
+        if (!text_crcs(m_items, m_crc)) return false;
+        for (size_t mi = s.m_first; mi < members.size(); mi++) {
+            const Member &m = members[mi];
+            const uint32_t c = m.len ? (uint32_t)crc32_combine(m.crc0, m_crc[mi - s.m_first], (z_off_t)m.len) : m.crc0;
+            if (!m.open) { if (c != m.crc) return no("crc (range mode)", (long long)mi); }
+            else if (mi + 1 == members.size()) { crc_now = c; len_now = m.len0 + m.len; }
+            else return no("member left open", (long long)mi);
+        }
+        unsigned long long p_nl = 0;
+        GI(hipMemsetAsync(d_entry, 0, 8, st));                   // (the entries are on the host by now: a free device word)
+        hipLaunchKernelGGL(count_nl_kernel, dim3(1024), dim3(256), 0, st, d_text + p_at, p_len, reinterpret_cast<unsigned long long *>(d_entry));
+        GB(d2h(&p_nl, d_entry, 8));
+        uint64_t keep = p_len;                                   // bytes of the piece up to the end of its last complete record
+        if (my_slice + 1 < rr->n_slices) {
+            // records end at newlines whose number in the file is a multiple of four: the last such newline of this piece is
+            // among its last four; the tail of the piece is looked at on the host
+            const uint64_t drop = (before.nl + p_nl) % 4;        // newlines behind the last complete record
+            if (p_nl < drop + 1) return no("range: a slice without a complete record", my_slice);
+            const uint64_t tail = std::min<uint64_t>(p_len, (uint64_t)CARRY_MAX + 1);
+            std::vector<uint8_t> tb(tail);
+            GB(d2h(tb.data(), d_text + p_at + (p_len - tail), tail));
+            uint64_t seen = 0, q = tail;
+            while (q > 0) {                                      // q - 1: the newline that ends the last complete record
+                if (tb[q - 1] == '\n') { if (seen == drop) break; seen++; }
+                q--;
+            }
+            if (q == 0) return no("range: a record longer than the chain carries", my_slice);
+            keep = p_len - tail + q;
+            rr->msg.status = 0;
+            rr->msg.crc = crc_now;
+            rr->msg.len = len_now;
+            rr->msg.nl = before.nl + p_nl;
+            rr->msg.end_bit = !bgzf.empty() ? (s.ch.back().trailer + 8) * 8 : s.ch.back().end;      // (bgzip: the next member's header)
+            rr->msg.carry_len = (uint32_t)(p_len - keep);
+            memcpy(rr->msg.carry, tb.data() + q, p_len - keep);
+            GB(d2h(rr->msg.window, A->prev, WSIZE));
+            if (!rr->send_from(my_slice)) return no("chain send", my_slice);
+        } else if (members.empty() || members.back().open) {
+            return no("the last member is not closed (range mode)");     // (every closed member was checked against its trailer above)
+        }
+        rr->pieces->push_back(GzPiece{p_at, p_len, keep, before.carry});
+        rr->duty++;
+        rr->received = false;
+        return true;
+    }
+
+    // ---- the call, step by step.  false: `why` is set, and the caller leaves through declined()
+    bool inflate_file()
+    {
+        if (!plan()) return false;
+        scratch_ahead();
+        bgzf = bgzf_members(in, in_n);
+        {
+            std::vector<uint64_t> entry;
+            if (!stage_image() || !search(entry) || !chunk_list(entry)) return false;
+        }
+        if (!enter_blocks() || !no_lonely_stretch() || !take_scratch()) return false;
+        size_t seg_i = 0;
+        for (size_t gi = 0; gi < G.size(); seg_i++) {
+            Segment s;
+            s.gi = gi;
+            if (!inflate_segment(s, seg_i)) return false;
+            if (rr) {
+                ChainIn before;
+                if (!slice_receive(s, segs[seg_i], before) || !segment_text(s) || !slice_piece(s, segs[seg_i], before)) return false;
+                gi = seg_i + 1 < segs.size() ? segs[seg_i + 1].gi : G.size();
+            } else {
+                if (!segment_text(s)) return false;
+                gi = s.gj + s.consumed_ph;
+            }
+        }
+        lap("inflate + windows + bytes");
+        if (trace) fprintf(stderr, "[ginflate] %u segments, %zu members\n", n_segments, members.size());
+        if (rr) {
+            // (every piece was checked as it was made; the owner of the last slice has compared CRC-32 and length with the trailer
+            //  and seen the stream end where the trailer begins)
+            if (!rr->mine.empty() && rr->mine.back() + 1 == rr->n_slices && (!ended || (last_end_bit + 7) / 8 != in_n - 8))
+                return no("stream end (range mode)", (long long)((last_end_bit + 7) / 8));
+            return true;
+        }
+        // the stream must end where the last trailer begins (after padding to a byte)
+        if (!ended || members.empty() || members.back().open || (last_end_bit + 7) / 8 != in_n - 8) return no("stream end", (long long)((last_end_bit + 7) / 8));
+        return verify_members();
+    }
+};
 #undef GI
 #undef GB
-#ifdef SS_GZ_DEBUG_SKIPCRC           // diagnostic builds only (scripts/dev): hand out the text although it is wrong
-    if (!crc_ok) fprintf(stderr, "[ginflate] CRC MISMATCH (debug build: text returned)\n");
-#else
-    if (!crc_ok) return no("crc");
-#endif
-    cleanup(true);
-    g_handled++;
-    *text_dev = (char *)d_text;
-    *len = total;
-    *lease = A;
+
+}  // namespace
+
+static bool gpu_gunzip_impl(const uint8_t *in, uint64_t in_n, char **text_dev, uint64_t *len, void **lease, int fd, RangeRun *rr)
+{
+    Gunzip g(in, in_n, fd, rr);
+    if (!g.inflate_file()) return g.declined();
+    g.hand_out(text_dev, len, lease);
     return true;
 }
 
