@@ -35,6 +35,15 @@
 // 20 M reads against ~80 ms of parsing and PCIe for the same reads, and every scan of the set is then 0-35 % faster
 // depending on the coverage of the sample (profiles/r03_locality_sweep.json).
 //
+// THE DRIVER (ss::order_flat_dev) is the sequence of its steps: probe_one_length (the slab's head: is it a candidate for the
+// one-length paths, with which L and n_rec) -> Scratch::take (one block, laid out in one place) -> one of three PATHS:
+//   bin_sorted    one length, the product: NewSlab::alloc, key_fixed, the sort, gather_fixed (packed; again ASCII when a byte
+//                 is outside the alphabet)
+//   bin_counted   one length under ss_test_hook 6 = 1: count_fixed, prefix_and_tail, NewSlab::alloc, place_fixed(_packed)
+//   bin_general   ragged records: count, prefix_and_tail, NewSlab::alloc, place (+ place_again for tiles beyond the table)
+// A one-length path that meets a shorter or longer record says "not of one length" and the general passes run.  Every path
+// reports its own three timing figures; the driver stores them, counts the slab and hands the scratch on to the next call.
+//
 // PACKED slabs.  A slab of one-length records whose every byte is A C G T or N (the gather checks the alphabet beside the
 // layout) is placed as 2-bit codes + invalid flags, 3 bytes per 8 positions (ss_scan_dev.h IN_PACKED): 57 bytes per 150-base
 // read instead of 152.  Positions, slots, bins and tiles are those of the ASCII slab; packed group g is exactly encode16 of its
@@ -56,14 +65,11 @@
 
 namespace {
 
-#ifndef SS_ORDER_CH
-#define SS_ORDER_CH 64
-#endif
-constexpr int CH = SS_ORDER_CH;             // bytes of a slab owned by one lane (64 or 128): that many / 16 loads in flight
+constexpr int CH = 64;                      // bytes of a slab owned by one lane: that many / 16 loads in flight
 constexpr int RB = 256 * CH;                // ... and by one workgroup (16 KB: what bounds these passes is the chain of dependent
                                             // round trips of a workgroup -- load, neighbours, key bytes, atomic -- not its instructions)
 constexpr int HALO = 512;                   // bytes behind the tile searched (in parallel) for the end of its last record
-static_assert(22 <= 23, "a table entry has 24 bits for the bin; order_bits stays at or below 22");
+constexpr int MAX_ORDER_BITS = 22;          // widest binning key (order_bits): 4 M bins + the one for records without a first k-mer
 constexpr uint32_t NO_NL = 0xFFFFFFFFu;     // "no newline" as a tile-relative position
 constexpr int TCAP = 2 * CH;                // record starts per tile that the record table holds (reads of ~125 bases and more)
 
@@ -153,9 +159,10 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane)
 // nor keys anything): entry = start in the tile (14 bits) | length (26 bits) | bin (24 bits); a tile with more than
 // TCAP record starts (reads shorter than ~125 bases), or a record of 64 MB, says T_OVERFLOW and is discovered again.
 constexpr uint32_t T_OVERFLOW = 0xFFFFFFFFu;
-constexpr int START_BITS = CH == 64 ? 14 : 15, LEN_BITS = 40 - START_BITS;
+constexpr int START_BITS = 14, LEN_BITS = 26, BIN_BITS = 64 - START_BITS - LEN_BITS;
 constexpr uint32_t LEN_LIMIT = 1u << LEN_BITS;
 static_assert(RB == 1 << START_BITS, "a table entry holds the start within the tile in START_BITS bits");
+static_assert((1ull << MAX_ORDER_BITS) < (1ull << BIN_BITS), "a table entry holds every bin, 1 << bits (no first k-mer) included, in BIN_BITS bits");
 
 struct TileLds {
     uint32_t first[5];                      // first newline (tile-relative) of waves 0..3 and of the halo
@@ -165,13 +172,8 @@ struct TileLds {
     uint32_t len[256], bin[256], pend[256]; // length, bin, inclusive count of 16-byte pieces
 };
 
-#if SS_ORDER_CH == 128
-typedef unsigned __int128 mask_t;           // one bit per byte of the lane's chunk
-__device__ __forceinline__ uint32_t mask_ctz(mask_t m) { const uint64_t lo = (uint64_t)m; return lo ? (uint32_t)__builtin_ctzll(lo) : 64u + (uint32_t)__builtin_ctzll((uint64_t)(m >> 64)); }
-#else
-typedef uint64_t mask_t;
+typedef uint64_t mask_t;                    // one bit per byte of the lane's chunk
 __device__ __forceinline__ uint32_t mask_ctz(mask_t m) { return (uint32_t)__builtin_ctzll(m); }
-#endif
 struct TileState { mask_t nl, st; uint32_t later; uint64_t tile0, i0; };
 
 // loads the lane's 64 bytes, finds the record starts in them and the first newline behind them (tile + halo)
@@ -263,10 +265,7 @@ __device__ __forceinline__ uint32_t tile_round(const char *__restrict__ b, uint6
     return cnt;
 }
 
-#ifndef SS_SLOT_ALIGN
-#define SS_SLOT_ALIGN 8u
-#endif
-__host__ __device__ __forceinline__ uint32_t slot_of(uint32_t len) { return (len + 1u + (SS_SLOT_ALIGN - 1u)) & ~(SS_SLOT_ALIGN - 1u); }     // record + '\n', padded to 8 bytes
+__host__ __device__ __forceinline__ uint32_t slot_of(uint32_t len) { return (len + 1u + 7u) & ~7u; }     // record + '\n', padded to 8 bytes
 
 // ---- pass 1: bytes per bin, and the tile's record table -----------------------------------------------------------------
 __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) void count_kernel(const char *__restrict__ b, uint64_t n, int bits, unsigned long long *__restrict__ hist,
@@ -310,6 +309,42 @@ __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) void c
 // The workgroup copies its records together: their 16-byte pieces are numbered across the workgroup (prefix sum of the
 // piece counts), every lane finds the record of its piece by binary search in LDS, loads 16 unaligned bytes, pads behind
 // the record's end with '\n' and stores them aligned (slots are multiples of 8 bytes).
+
+// the piece at offset c of a record of rlen bytes: its record bytes stay, '\n' behind them
+__device__ __forceinline__ void pad_piece(uint32_t (&w)[4], uint32_t rlen, uint32_t c)
+{
+    const int keep = (int)min(16u, rlen > c ? rlen - c : 0u);              // record bytes in this piece
+    if (keep < 16) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int k = keep - 4 * d;
+            if (k <= 0) w[d] = 0x0A0A0A0Au;
+            else if (k < 4) { const uint32_t m = (1u << (8 * k)) - 1u; w[d] = (w[d] & m) | (0x0A0A0A0Au & ~m); }
+        }
+    }
+}
+
+// the record of piece p: the first of the round's cnt records whose inclusive piece count (L.pend) exceeds p
+__device__ __forceinline__ int piece_record(const TileLds &L, uint32_t cnt, uint32_t p)
+{
+    int lo = 0, hi = (int)cnt - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (L.pend[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// one piece: the record's bytes from `v`, '\n' behind its end, stored aligned (slots are multiples of 8 bytes)
+__device__ __forceinline__ void store_piece(char *__restrict__ dst, uint64_t out, uint4 v, uint32_t rlen, uint32_t rslot, uint32_t c)
+{
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    pad_piece(w, rlen, c);
+    char *o8 = static_cast<char *>(__builtin_assume_aligned(dst + out, 8));
+    if (c + 16 <= rslot) __builtin_memcpy(o8, w, 16);
+    else __builtin_memcpy(o8, w, 8);
+}
+
 __device__ __forceinline__ void copy_round(const char *__restrict__ b, uint64_t n, char *__restrict__ dst, TileLds &L, uint32_t cnt)
 {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -322,57 +357,11 @@ __device__ __forceinline__ void copy_round(const char *__restrict__ b, uint64_t 
     if ((uint32_t)t < cnt) L.pend[t] = pend;
     __syncthreads();
     for (uint32_t p = (uint32_t)t; p < total; p += 256) {
-        int lo = 0, hi = (int)cnt - 1;                                     // first record whose inclusive piece count exceeds p
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (L.pend[mid] <= p) lo = mid + 1; else hi = mid;
-        }
-        const uint32_t rlen = L.len[lo], rslot = slot_of(rlen);
-        const uint32_t c = (p - (L.pend[lo] - ((rslot + 15u) >> 4))) * 16u;
-        const uint64_t src = L.src[lo] + c, out = L.dst[lo] + c;
-        uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-        const int keep = (int)min(16u, rlen > c ? rlen - c : 0u);          // record bytes in this piece
-        if (keep > 0) {
-            const uint4 v = load16_nl(b, src, n);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            if (keep < 16) {
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    const int k = keep - 4 * d;
-                    if (k <= 0) w[d] = 0x0A0A0A0Au;
-                    else if (k < 4) { const uint32_t m = (1u << (8 * k)) - 1u; w[d] = (w[d] & m) | (0x0A0A0A0Au & ~m); }
-                }
-            }
-        }
-        char *o8 = static_cast<char *>(__builtin_assume_aligned(dst + out, 8));
-        if (c + 16 <= rslot) __builtin_memcpy(o8, w, 16);
-        else __builtin_memcpy(o8, w, 8);
+        const int lo = piece_record(L, cnt, p);
+        const uint32_t rlen = L.len[lo], rslot = slot_of(rlen), c = (p - (L.pend[lo] - ((rslot + 15u) >> 4))) * 16u;
+        const uint4 x = rlen > c ? load16_nl(b, L.src[lo] + c, n) : make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
+        store_piece(dst, L.dst[lo] + c, x, rlen, rslot, c);
     }
-}
-
-// one piece: the record's bytes from `v`, '\n' behind its end, stored aligned (slots are multiples of 8 bytes)
-__device__ __forceinline__ void store_piece(char *__restrict__ dst, uint64_t out, uint4 v, uint32_t rlen, uint32_t rslot, uint32_t c)
-{
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    const int keep = (int)min(16u, rlen > c ? rlen - c : 0u);              // record bytes in this piece
-    if (keep < 16) {
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const int k = keep - 4 * d;
-            if (k <= 0) w[d] = 0x0A0A0A0Au;
-            else if (k < 4) { const uint32_t m = (1u << (8 * k)) - 1u; w[d] = (w[d] & m) | (0x0A0A0A0Au & ~m); }
-        }
-    }
-    char *o8 = static_cast<char *>(__builtin_assume_aligned(dst + out, 8));
-#ifdef SS_PLACE_NT      // (A/B builds: the slab is written once and read by a later kernel -- stores that do not allocate in L2)
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    typedef u32x2 u32x2_a8 __attribute__((aligned(8)));
-    __builtin_nontemporal_store((u32x2){w[0], w[1]}, reinterpret_cast<u32x2_a8 *>(o8));
-    if (c + 16 <= rslot) __builtin_nontemporal_store((u32x2){w[2], w[3]}, reinterpret_cast<u32x2_a8 *>(o8 + 8));
-#else
-    if (c + 16 <= rslot) __builtin_memcpy(o8, w, 16);
-    else __builtin_memcpy(o8, w, 8);
-#endif
 }
 
 // the usual tile: everything is in the table.  The chain of dependent round trips is what bounds this pass, so it is kept
@@ -414,11 +403,7 @@ __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) void p
         rec[r] = 0; off[r] = 0;
         v[r] = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
         if (p < total) {
-            int lo = 0, hi = (int)known - 1;                               // first record whose inclusive piece count exceeds p
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (L.pend[mid] <= p) lo = mid + 1; else hi = mid;
-            }
+            const int lo = piece_record(L, known, p);
             const uint32_t rlen = L.len[lo], c = (p - (L.pend[lo] - ((slot_of(rlen) + 15u) >> 4))) * 16u;
             rec[r] = (uint32_t)lo; off[r] = c;
             if (rlen > c) v[r] = load16_nl(b, L.src[lo] + c, n);
@@ -435,11 +420,7 @@ __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) void p
         }
     }
     for (uint32_t p = (uint32_t)t + 256u * PRE; p < total; p += 256) {    // long records: the rest, piece by piece
-        int lo = 0, hi = (int)known - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (L.pend[mid] <= p) lo = mid + 1; else hi = mid;
-        }
+        const int lo = piece_record(L, known, p);
         const uint32_t rlen = L.len[lo], rslot = slot_of(rlen), c = (p - (L.pend[lo] - ((rslot + 15u) >> 4))) * 16u;
         const uint4 x = rlen > c ? load16_nl(b, L.src[lo] + c, n) : make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
         store_piece(dst, L.dst[lo] + c, x, rlen, rslot, c);
@@ -506,7 +487,6 @@ __global__ __launch_bounds__(256, 8) void count_fixed_kernel(const char *__restr
     const uint64_t base = r0 * L1;
     bool bad = false;
     uint32_t alpha = 0;
-#ifndef SS_COUNT_NOVERIFY          // (A/B builds only: what the count pass costs when it reads each record's first bytes and nothing else)
     for (uint32_t off = (uint32_t)lane * 16u; off < span; off += 1024u) {
         const uint4 v = load16_nl(b, base + off, n);
         const uint32_t m = nl_mask16(v);
@@ -516,9 +496,6 @@ __global__ __launch_bounds__(256, 8) void count_fixed_kernel(const char *__restr
         bad |= ((m ^ want) & valid) != 0u;
         alpha |= not_packable4(v.x) | not_packable4(v.y) | not_packable4(v.z) | not_packable4(v.w);      // (bytes past the span: the
     }                                                                      // next wave's records, or padding that must be '\n')
-#else
-    alpha = 1u;
-#endif
     if (r0 + nr == n_rec) {                                                // behind the last record: newlines only (padding)
         for (uint64_t i = base + span + (uint32_t)lane; i < n; i += 64) bad |= b[i] != '\n';
     }
@@ -542,13 +519,7 @@ __global__ __launch_bounds__(256, 8) void place_fixed_kernel(const char *__restr
     const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), slot = slot_of(L), P = (slot + 15u) >> 4, total = nr * P;
     const uint64_t base = r0 * L1;
     unsigned long long d0 = 0;
-#if defined(SS_PLACE_SEQ)          // (A/B builds, results unbinned: what the pass costs as a plain copy -- no atomics, sequential destinations)
-    if ((uint32_t)lane < nr) d0 = (r0 + (uint64_t)lane) * slot;
-#elif defined(SS_PLACE_HASH)       // (A/B builds, results WRONG: scattered like the real thing, no atomics)
-    if ((uint32_t)lane < nr) d0 = ((((r0 + (uint64_t)lane) * 0x9E3779B97F4A7C15ull) >> 20) % n_rec) * slot;
-#else
     if ((uint32_t)lane < nr) d0 = atomicAdd(&cursor[bins[r0 + lane]], (unsigned long long)slot);      // (answer needed at the stores)
-#endif
     for (uint32_t p0 = 0; p0 < total; p0 += 64u * FPRE) {
         uint4 v[FPRE];
         uint32_t rec[FPRE], off[FPRE];
@@ -610,15 +581,7 @@ __global__ __launch_bounds__(256, 6) void place_fixed_packed_kernel(const char *
                 const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
                 if (p >= total) continue;
                 uint32_t w[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
-                const int keep = (int)min(16u, L > off ? L - off : 0u);      // record bytes in this piece, '\n' behind them
-                if (keep < 16) {
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const int k = keep - 4 * d;
-                        if (k <= 0) w[d] = 0x0A0A0A0Au;
-                        else if (k < 4) { const uint32_t m = (1u << (8 * k)) - 1u; w[d] = (w[d] & m) | (0x0A0A0A0Au & ~m); }
-                    }
-                }
+                pad_piece(w, L, off);
                 uint32_t code, inv;
                 ss::dev::encode16(w, code, inv);
                 // the group's 6 bytes: code[0..15] inv[0..7] code[16..31] inv[8..15] (2-byte aligned in LDS)
@@ -740,8 +703,8 @@ __global__ __launch_bounds__(256, 7) void gather_fixed_kernel(const char *__rest
                     const uint32_t want = e < 16u ? 1u << e : 0u, valid = e < 16u ? (2u << e) - 1u : 0xFFFFu;
                     bad |= ((m ^ want) & valid) != 0u;
                 }
-                const int keep = (int)min(16u, L > off ? L - off : 0u);      // record bytes in this piece, '\n' behind them
-                if (keep < 16) {
+                const int keep = (int)min(16u, L > off ? L - off : 0u);      // record bytes in this piece, '\n' behind them (pad_piece,
+                if (keep < 16) {                                             // written out: the helper costs this kernel two SGPRs)
 #pragma unroll
                     for (int d = 0; d < 4; d++) {
                         const int k = keep - 4 * d;
@@ -842,11 +805,11 @@ __global__ __launch_bounds__(1024) void scan_apply_kernel(unsigned long long *__
 }
 
 // bin width: about four records per bin for the block at hand (reads that share their first minimizer then sit in the
-// same scan tile or the next), 12 bits at least, 22 at most (4 M counters = 32 MB)
+// same scan tile or the next), 12 bits at least, MAX_ORDER_BITS at most (4 M counters = 32 MB)
 int order_bits(uint64_t n_bytes)
 {
     int bits = 12;
-    while (bits < 22 && (n_bytes / 152) >> (bits + 2)) bits++;
+    while (bits < MAX_ORDER_BITS && (n_bytes / 152) >> (bits + 2)) bits++;
     return bits;
 }
 
@@ -856,12 +819,318 @@ namespace ss {
 
 static std::mutex g_scr_mu;
 static uint64_t g_order_n[2] = {0, 0};        // slabs binned by the one-length passes / by the general ones (ss_reads_order_counters)
-static double g_order_ms[3] = {0, 0, 0};      // the last order_flat_dev: count + prefix, allocation of the new slab, place
+static double g_order_ms[3] = {0, 0, 0};      // the last order_flat_dev, as its path reported them (reorder_timing in ss_common.h)
 static char *g_scr = nullptr;            // the scratch of the last call (bin cursors, per-tile record tables), kept for the next
 static uint64_t g_scr_cap = 0;
 
 std::atomic<long long> g_hook_ascii_slabs{0};      // ss_test_hook(5, ...): 1 = binned slabs of one length stay ASCII
 std::atomic<long long> g_hook_atomic_binning{0};   // ss_test_hook(6, ...): 1 = slabs of one length go through the count + atomic placement
+
+namespace {
+
+// ---- order_flat_dev, step by step ------------------------------------------------------------------------------------------
+// probe_one_length -> Scratch::take -> one of bin_sorted / bin_counted (slabs of one length; either may answer "not of one
+// length after all") -> bin_general -> timing, counters, *out.  Every path takes its new slab through NewSlab::alloc and, but
+// for the sorted one, its cursors through prefix_and_tail; nothing else is shared between them.
+typedef std::chrono::steady_clock Clock;
+inline double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+enum class Binned { done, not_one_length, failed };
+enum { T_TOTAL = 0, T_FLAG = 1, T_ALPHA = 2 };      // the tail words behind the bin sizes: positions of the new slab; tiles that did not
+                                                    // fit the table (general) / "not of one length"; a byte other than A C G T N
+
+inline bool hip_ok(hipError_t e, const char *what, int line)
+{
+    if (e != hipSuccess) ss::set_last_error(what, __FILE__, line, hipGetLastError());
+    return e == hipSuccess;
+}
+#define SS_R(call) do { if (!hip_ok((call), #call, __LINE__)) return Binned::failed; } while (0)
+struct Owner { Owner() = default; Owner(const Owner &) = delete; Owner &operator=(const Owner &) = delete; };      // of device memory, of events
+
+// what a call knows before anything runs
+struct Call {
+    const char *src;
+    uint64_t n;
+    int bits;
+    uint32_t n_bins;
+    unsigned nb, nsb;                          // tiles of the general passes; workgroups of the prefix
+    Clock::time_point t_begin = Clock::now();
+    Call(const char *src_, uint64_t n_) : src(src_), n(n_), bits(order_bits(n_)), n_bins((1u << bits) + 1u), nb((unsigned)((n_ + RB - 1) / RB)),
+                                          nsb((n_bins + SCAN_PER - 1) / SCAN_PER) {}
+    void lap(const char *what) const
+    {
+        static const bool trace = getenv("SS_INGEST_TRACE") != nullptr;
+        if (!trace) return;
+        hipDeviceSynchronize();
+        fprintf(stderr, "[reorder] %-22s at %.4f s\n", what, std::chrono::duration<double>(Clock::now() - t_begin).count());
+    }
+    // the end of a path that placed its records: everything has run
+    hipError_t finish(Clock::time_point *t_end) const
+    {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        lap("place");
+        *t_end = Clock::now();
+        return e;
+    }
+};
+
+// records of one length: the first newline says which (L = 0: not a candidate); the passes check every record against it
+struct OneLength { uint32_t L = 0; uint64_t n_rec = 0; };
+
+hipError_t probe_one_length(const char *src, uint64_t n, OneLength *one)
+{
+    *one = OneLength();
+    static const bool fixed_allowed = [] { const char *e = getenv("SS_ORDER_FIXED"); return !(e && !strcmp(e, "0")); }();
+    if (!fixed_allowed || n < 64) return hipSuccess;
+    char head[FIX_MAX_L + 2];
+    const size_t hn = (size_t)std::min<uint64_t>(n, sizeof(head));
+    const hipError_t e = hipMemcpy(head, src, hn, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    const void *nl = memchr(head, '\n', hn);
+    if (!nl) return hipSuccess;
+    const uint32_t L = (uint32_t)((const char *)nl - head);
+    // (fewer than 64 bytes behind the last record: what key_fixed_kernel's one lane checks for '\n')
+    if (L >= FIX_MIN_L && L <= FIX_MAX_L && n / (L + 1) >= 1 && n - (n / (L + 1)) * (L + 1) < 64) { one->L = L; one->n_rec = n / (L + 1); }
+    return hipSuccess;
+}
+
+// The scratch of a call, one allocation: bin sizes / cursors + the three tail words, block sums of the prefix, per-tile record
+// counts, and a region that is the record table of the general passes, or the 4-byte bins of the count + atomic placement, or
+// the sort's keys, values (twice each) and temporary storage -- sized for whichever of those the call may come to use.
+// The scratch of the call before is kept (0.35 GB for 20 M reads: two driver calls fewer per sample); keep() hands the larger
+// of the two blocks on to the next call.  A call that fails frees its block.
+class Scratch : Owner {
+public:
+    struct Sort { uint32_t *k0, *k1, *v0, *v1; void *temp; size_t temp_bytes; };
+    ~Scratch() { if (d_) hipFree(d_); }
+
+    hipError_t take(const Call &c, const OneLength &one, bool for_sort)
+    {
+        n_bins_ = c.n_bins;
+        if (for_sort) {
+            hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
+            const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tb_, k, v, (int)one.n_rec, 0, c.bits + 1);
+            if (e != hipSuccess) return e;
+        }
+        a4_ = (one.n_rec * 4 + 255) & ~255ull;
+        o_sums_ = ((uint64_t)c.n_bins + 3) * 8;
+        o_cnt_ = o_sums_ + ((uint64_t)c.nsb + 1) * 8;
+        o_region_ = (o_cnt_ + (uint64_t)c.nb * 4 + 255) & ~255ull;
+        const uint64_t bytes = o_region_ + std::max<uint64_t>((uint64_t)c.nb * TCAP * 8, for_sort ? 4 * a4_ + ((sort_tb_ + 255) & ~255ull) : a4_);
+        {
+            std::lock_guard<std::mutex> g(g_scr_mu);
+            if (g_scr && g_scr_cap >= bytes) { d_ = g_scr; cap_ = g_scr_cap; g_scr = nullptr; g_scr_cap = 0; }
+        }
+        if (d_) return hipSuccess;
+        cap_ = bytes;
+        return hipMalloc((void **)&d_, bytes);
+    }
+    void keep()
+    {
+        {
+            std::lock_guard<std::mutex> g(g_scr_mu);
+            if (!g_scr || g_scr_cap < cap_) { std::swap(g_scr, d_); std::swap(g_scr_cap, cap_); }
+        }
+        if (d_) hipFree(d_);
+        d_ = nullptr;
+    }
+
+    unsigned long long *hist() const { return (unsigned long long *)d_; }             // n_bins bin sizes, then cursors
+    unsigned long long *tail() const { return hist() + n_bins_; }                      // T_TOTAL, T_FLAG, T_ALPHA
+    uint64_t hist_bytes() const { return o_sums_; }                                    // ... what a count pass zeroes: both
+    unsigned long long *sums() const { return (unsigned long long *)(d_ + o_sums_); }
+    uint32_t *tile_counts() const { return (uint32_t *)(d_ + o_cnt_); }
+    unsigned long long *table() const { return (unsigned long long *)(d_ + o_region_); }
+    uint32_t *bins() const { return (uint32_t *)(d_ + o_region_); }
+    Sort sort() const
+    {
+        uint32_t *a = (uint32_t *)(d_ + o_region_);
+        return Sort{a, a + a4_ / 4, a + 2 * (a4_ / 4), a + 3 * (a4_ / 4), d_ + o_region_ + 4 * a4_, sort_tb_};
+    }
+
+private:
+    char *d_ = nullptr;
+    uint64_t cap_ = 0, o_sums_ = 0, o_cnt_ = 0, o_region_ = 0, a4_ = 0;       // a4_: one per-record array of 4-byte entries
+    uint32_t n_bins_ = 0;
+    size_t sort_tb_ = 0;
+};
+
+// The new slab: `total` positions of records, `cap` positions in all (a multiple of 16), in a block of real_cap bytes (a kept
+// block may be larger).  Freed unless a path hands it out (release) or back (put_back).
+struct NewSlab : Owner {
+    char *d = nullptr;
+    uint64_t total = 0, cap = 0, real_cap = 0;
+    bool packed = false;
+    Clock::time_point t_alloc;
+    ~NewSlab() { if (d) hipFree(d); }
+
+    hipError_t alloc(const Call &c, bool pk, uint64_t total_)
+    {
+        total = total_; packed = pk;
+        cap = std::max<uint64_t>((total + 15) & ~15ull, 16);
+        const hipError_t e = get_block();
+        t_alloc = Clock::now();
+        c.lap("new slab");
+        return e;
+    }
+    // the packed gather met a byte other than A C G T N: an ASCII slab instead, in this block if it holds one
+    hipError_t make_ascii()
+    {
+        packed = false;
+        if (real_cap >= cap) return hipSuccess;
+        put_back();
+        return get_block();
+    }
+    // behind the records: packed, '\n' (code 1, invalid) up to the 16-position boundary -- at most one 3-byte unit (slots are
+    // multiples of 8) --, then the slack behind the last group (not the rest of a larger block); ASCII, '\n' up to the boundary
+    hipError_t fill_tail() const
+    {
+        hipError_t e = hipSuccess;
+        if (packed) {
+            const uint64_t t0 = total / 8u * 3u, t1 = ss::dev::in_bytes(true, cap) + 8;
+            e = hipMemsetAsync(d + t0, 0xFF, t1 - t0, 0);
+            if (e == hipSuccess && cap > total) e = hipMemsetAsync(d + t0, 0x55, 2, 0);
+        } else if (cap > total) {
+            e = hipMemsetAsync(d + total, '\n', cap - total, 0);
+        }
+        return e;
+    }
+    void put_back() { ss::big_put(d, real_cap); d = nullptr; }
+    char *release() { char *p = d; d = nullptr; return p; }
+
+private:
+    // packed: 6 bytes per 16 positions, and 8 bytes behind them that the scans' 8-byte loads may touch (IN_PACKED).  A slab whose
+    // ASCII form would be a block the process keeps (ss::big_put) still takes a block of that size: destroyed, it goes back to
+    // the kept blocks and must serve what comes next -- the next sample's file-order slab, or its binning -- which a block of the
+    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones.
+    hipError_t get_block()
+    {
+        const uint64_t bytes = packed ? std::max<uint64_t>(ss::dev::in_bytes(true, cap) + 8, cap >= ss::BIG_KEEP_MIN ? cap : 0) : cap;
+        return ss::big_malloc((void **)&d, bytes, &real_cap);
+    }
+};
+
+struct EventPair : Owner {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~EventPair() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+    hipError_t create() { const hipError_t e = hipEventCreate(&ev[0]); return e == hipSuccess ? hipEventCreate(&ev[1]) : e; }
+};
+
+// bin sizes -> exclusive prefix (the bins' cursors) -> the first n_tail tail words on the host
+hipError_t prefix_and_tail(const Call &c, const Scratch &scr, unsigned long long *tail, int n_tail)
+{
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(c.nsb), dim3(1024), 0, 0, scr.hist(), c.n_bins, scr.sums());
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, 0, scr.sums(), c.nsb, scr.tail());
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(c.nsb), dim3(1024), 0, 0, scr.hist(), c.n_bins, scr.sums());
+    return hipMemcpy(tail, scr.tail(), 8 * (size_t)n_tail, hipMemcpyDeviceToHost);
+}
+
+// the figures of a path that counts, allocates and places (ss_reads_order_timing): from the call's start, so a one-length
+// attempt that failed before is in the first
+hipError_t finish_counted(const Call &c, Clock::time_point t_counted, const NewSlab &slab, double ms[3])
+{
+    Clock::time_point t_end;
+    const hipError_t e = c.finish(&t_end);
+    ms[0] = ms_between(c.t_begin, t_counted); ms[1] = ms_between(t_counted, slab.t_alloc); ms[2] = ms_between(slab.t_alloc, t_end);
+    return e;
+}
+
+// One length, sorted: the new slab's size is known before anything runs (n_rec slots), so its block is taken first, and the
+// flags are read once, after the gather.  Figures: key + sort (on the device), allocation (from the call's start), gather +
+// tail -- the first and the last add up to the kernels' wall time.
+Binned bin_sorted(const Call &c, const OneLength &one, const Scratch &scr, NewSlab &slab, double ms[3])
+{
+    const uint32_t slot = ::slot_of(one.L), P = (slot + 15u) >> 4;
+    const unsigned nbf = (unsigned)((one.n_rec + 255) / 256);
+    SS_R(slab.alloc(c, g_hook_ascii_slabs.load() == 0, one.n_rec * slot));
+    const Scratch::Sort s = scr.sort();
+    unsigned long long *flags = scr.tail();
+    EventPair t;
+    SS_R(t.create());
+    auto gather = [&](const uint32_t *perm) {
+        const uint32_t G = gather_rows(slab.packed, one.L), R = slab.packed ? slot / 8u * 3u : slot;
+        auto kern = slab.packed ? gather_fixed_kernel<true> : gather_fixed_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(nbf), dim3(256), 4u * G * R, 0, c.src, c.n, one.n_rec, one.L, P, (uint32_t)(((1ull << 32) + P - 1) / P), G,
+                           perm, (uint8_t *)slab.d, flags + T_FLAG, flags + T_ALPHA);
+    };
+    unsigned long long tail[3] = {0, 0, 0};
+    SS_R(hipMemsetAsync(flags, 0, 24, 0));
+    SS_R(hipEventRecord(t.ev[0], 0));
+    hipLaunchKernelGGL(key_fixed_kernel, dim3(nbf), dim3(256), 0, 0, c.src, c.n, one.n_rec, one.L, c.bits, s.k0, s.v0, flags + T_FLAG);
+    hipcub::DoubleBuffer<uint32_t> dk(s.k0, s.k1), dv(s.v0, s.v1);
+    size_t temp_bytes = s.temp_bytes;
+    SS_R(hipcub::DeviceRadixSort::SortPairs(s.temp, temp_bytes, dk, dv, (int)one.n_rec, 0, c.bits + 1, 0));
+    SS_R(hipEventRecord(t.ev[1], 0));
+    const uint32_t *perm = dv.Current();
+    gather(perm);
+    SS_R(slab.fill_tail());
+    SS_R(hipMemcpy(tail + T_FLAG, flags + T_FLAG, 16, hipMemcpyDeviceToHost));
+    if (tail[T_FLAG] == 0 && slab.packed && tail[T_ALPHA]) {        // a byte other than A C G T N: the same order, ASCII
+        SS_R(slab.make_ascii());
+        gather(perm);
+        SS_R(slab.fill_tail());
+        // (the packed gather's waves stop once the slab is known not packable: the layout is checked by the ASCII one)
+        SS_R(hipMemcpy(tail + T_FLAG, flags + T_FLAG, 8, hipMemcpyDeviceToHost));
+    }
+    SS_R(hipGetLastError());
+    if (tail[T_FLAG]) { slab.put_back(); return Binned::not_one_length; }       // some record is shorter or longer after all
+    float ms_key_sort = -1.f;
+    SS_R(hipEventElapsedTime(&ms_key_sort, t.ev[0], t.ev[1]));
+    Clock::time_point t_end;
+    SS_R(c.finish(&t_end));
+    ms[0] = ms_key_sort; ms[1] = ms_between(c.t_begin, slab.t_alloc); ms[2] = ms_between(slab.t_alloc, t_end) - ms_key_sort;
+    return Binned::done;
+}
+
+// One length, ss_test_hook 6: the count + atomic placement (count_fixed checks the layout and the alphabet)
+Binned bin_counted(const Call &c, const OneLength &one, const Scratch &scr, NewSlab &slab, double ms[3])
+{
+    const uint32_t L1 = one.L + 1u, slot = ::slot_of(one.L), P = (slot + 15u) >> 4;
+    const unsigned nbf = (unsigned)((one.n_rec + 255) / 256);
+    unsigned long long tail[3] = {0, 0, 0};
+    SS_R(hipMemsetAsync(scr.hist(), 0, scr.hist_bytes(), 0));
+    hipLaunchKernelGGL(count_fixed_kernel, dim3(nbf), dim3(256), 0, 0, c.src, c.n, one.n_rec, one.L, (uint32_t)(((1ull << 32) + L1 - 1) / L1), c.bits,
+                       scr.hist(), scr.bins(), scr.tail() + T_FLAG, scr.tail() + T_ALPHA);
+    SS_R(prefix_and_tail(c, scr, tail, 3));
+    if (tail[T_FLAG]) return Binned::not_one_length;                 // some record is shorter or longer after all
+    c.lap("count + prefix");
+    const Clock::time_point t_counted = Clock::now();
+    SS_R(slab.alloc(c, tail[T_ALPHA] == 0 && g_hook_ascii_slabs.load() == 0, tail[T_TOTAL]));
+    if (slab.packed) {
+        // a record's LDS area: 4 bytes in front (a span's first dword may begin before it), its groups, 4 behind
+        const uint32_t B = slot / 8u * 3u, A = (6u * P + 8u + 3u) & ~3u;
+        const uint32_t G = std::min<uint32_t>(64u, PK_LDS / A), ND = ((B + 2u) >> 2) + 1u;      // records per round; dwords a span touches
+        hipLaunchKernelGGL(place_fixed_packed_kernel, dim3(nbf), dim3(256), 0, 0, c.src, c.n, one.n_rec, one.L, P, (uint32_t)(((1ull << 32) + P - 1) / P),
+                           A, G, ND, (uint32_t)(((1ull << 32) + ND - 1) / ND), scr.hist(), (const uint32_t *)scr.bins(), (uint8_t *)slab.d);
+    } else {
+        hipLaunchKernelGGL(place_fixed_kernel, dim3(nbf), dim3(256), 0, 0, c.src, c.n, one.n_rec, one.L, (uint32_t)(((1ull << 32) + P - 1) / P),
+                           scr.hist(), (const uint32_t *)scr.bins(), slab.d);
+    }
+    SS_R(slab.fill_tail());
+    SS_R(finish_counted(c, t_counted, slab, ms));
+    return Binned::done;
+}
+
+// The general passes: ragged records, or a slab that was not of one length after all
+Binned bin_general(const Call &c, const Scratch &scr, NewSlab &slab, double ms[3])
+{
+    unsigned long long tail[2] = {0, 0};
+    SS_R(hipMemsetAsync(scr.hist(), 0, scr.hist_bytes(), 0));
+    hipLaunchKernelGGL(count_kernel, dim3(c.nb), dim3(256), 0, 0, c.src, c.n, c.bits, scr.hist(), scr.tile_counts(), scr.table(), scr.tail() + T_FLAG);
+    SS_R(prefix_and_tail(c, scr, tail, 2));
+    c.lap("count + prefix");
+    const Clock::time_point t_counted = Clock::now();
+    SS_R(slab.alloc(c, false, tail[T_TOTAL]));
+    hipLaunchKernelGGL(place_kernel, dim3(c.nb), dim3(256), 0, 0, c.src, c.n, scr.hist(), scr.tile_counts(), scr.table(), slab.d);
+    if (tail[T_FLAG]) hipLaunchKernelGGL(place_again_kernel, dim3(c.nb), dim3(256), 0, 0, c.src, c.n, c.bits, scr.hist(), scr.tile_counts(), slab.d);
+    SS_R(slab.fill_tail());
+    SS_R(finish_counted(c, t_counted, slab, ms));
+    return Binned::done;
+}
+#undef SS_R
+
+}  // namespace
 
 // src[0, n) (a flat base block on the device) -> a new slab with the records binned: out->d (hipMalloc'ed or a kept block),
 // out->cap; an ASCII slab of out->used bytes (a multiple of 16, '\n' padded), or -- records of one length, every byte of them
@@ -869,205 +1138,32 @@ std::atomic<long long> g_hook_atomic_binning{0};   // ss_test_hook(6, ...): 1 = 
 int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
 {
     *out = ss_reads::Slab();
-    const int bits = order_bits(n);
-    const uint32_t n_bins = (1u << bits) + 1u;
-    static const bool trace = getenv("SS_INGEST_TRACE") != nullptr;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace) return;
-        hipDeviceSynchronize();
-        fprintf(stderr, "[reorder] %-22s at %.4f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
-    };
-    const unsigned nb = (unsigned)((n + RB - 1) / RB), nsb = (n_bins + SCAN_PER - 1) / SCAN_PER;
-    // one allocation for the scratch: bin sizes / cursors (+ total), block sums of the prefix, per-tile record counts and table
-    const uint64_t o_sums = ((uint64_t)n_bins + 3) * 8, o_cnt = o_sums + (((uint64_t)nsb + 1) * 8), o_tab = (o_cnt + (uint64_t)nb * 4 + 255) & ~255ull;
-    // records of one length: the first newline says which; the count pass checks every record against it
-    uint32_t fix_L = 0;
-    uint64_t n_rec = 0;
-    static const bool fixed_allowed = [] { const char *e = getenv("SS_ORDER_FIXED"); return !(e && !strcmp(e, "0")); }();
-    if (fixed_allowed && n >= 64) {
-        char head[FIX_MAX_L + 2];
-        const size_t hn = (size_t)std::min<uint64_t>(n, sizeof(head));
-        if (hipMemcpy(head, src, hn, hipMemcpyDeviceToHost) != hipSuccess) { ss::set_last_error("hipMemcpy", __FILE__, __LINE__, hipGetLastError()); return SS_EHIP; }
-        const void *nl = memchr(head, '\n', hn);
-        if (nl) {
-            const uint32_t L = (uint32_t)((const char *)nl - head);
-            if (L >= FIX_MIN_L && L <= FIX_MAX_L && n / (L + 1) >= 1 && n - (n / (L + 1)) * (L + 1) < 64) { fix_L = L; n_rec = n / (L + 1); }
-        }
-    }
+    const Call c(src, n);
+    OneLength one;
+    if (!hip_ok(probe_one_length(src, n, &one), "hipMemcpy", __LINE__)) return SS_EHIP;
     // the sorted one-length path (ss_test_hook 6 = 1: the count + atomic placement instead); hipcub counts its items in an int
-    const bool sorted = fix_L && g_hook_atomic_binning.load() == 0 && n_rec < (1ull << 31);
-    const uint64_t a4 = (n_rec * 4 + 255) & ~255ull;    // one per-record array of 4-byte entries
-    size_t sort_tb = 0;
-    if (sorted) {
-        hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
-        if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tb, k, v, (int)n_rec, 0, bits + 1) != hipSuccess) {
-            ss::set_last_error("hipcub::DeviceRadixSort::SortPairs", __FILE__, __LINE__, hipGetLastError()); return SS_EHIP;
-        }
-    }
-    // (the record table of the general passes, the 4-byte bins of the count + atomic placement, and the sort's keys, values (twice)
-    //  and temporary storage share a region: whichever is larger)
-    const uint64_t scratch = o_tab + std::max<uint64_t>((uint64_t)nb * TCAP * 8, sorted ? 4 * a4 + ((sort_tb + 255) & ~255ull) : a4);
-    char *d_scr = nullptr, *d_new = nullptr;
-#define SS_R(call) do { if ((call) != hipSuccess) { ss::set_last_error(#call, __FILE__, __LINE__, hipGetLastError()); hipFree(d_scr); hipFree(d_new); return SS_EHIP; } } while (0)
-    // (the scratch of the call before is kept -- 0.35 GB for 20 M reads --: two driver calls fewer per sample)
-    uint64_t scr_cap = 0;
-    {
-        std::lock_guard<std::mutex> g(g_scr_mu);
-        if (g_scr && g_scr_cap >= scratch) { d_scr = g_scr; scr_cap = g_scr_cap; g_scr = nullptr; g_scr_cap = 0; }
-    }
-    if (!d_scr) { SS_R(hipMalloc((void **)&d_scr, scratch)); scr_cap = scratch; }
-    unsigned long long *d_hist = (unsigned long long *)d_scr, *d_sums = (unsigned long long *)(d_scr + o_sums);
-    uint32_t *d_cnt = (uint32_t *)(d_scr + o_cnt);
-    unsigned long long *d_tab = (unsigned long long *)(d_scr + o_tab);
-    constexpr unsigned pad1 = 0, pad2 = 0;
-    unsigned long long tail[3] = {0, 0, 0};              // positions of the new slab; tiles that did not fit the table / "not of one
-    bool fixed = false, packed = false;                  // length"; a byte other than A C G T N in the records
-    uint64_t cap = 0, real_cap = 0;                      // positions of the new slab; bytes of its block (a kept block may be larger)
-    auto t_counted = t_begin, t_alloc = t_begin;
-    float ms_key_sort = -1.f;                            // (the sorted path: key pass + sort, timed on the device)
-    // packed: 6 bytes per 16 positions, and 8 bytes behind them that the scans' 8-byte loads may touch (IN_PACKED).  A slab whose
-    // ASCII form would be a block the process keeps (ss::big_put) still takes a block of that size: destroyed, it goes back to
-    // the kept blocks and must serve what comes next -- the next sample's file-order slab, or its binning -- which a block of the
-    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones.
-    auto block_bytes = [](bool pk, uint64_t c) { return pk ? std::max<uint64_t>(ss::dev::in_bytes(true, c) + 8, c >= ss::BIG_KEEP_MIN ? c : 0) : c; };
-    // behind the records: packed, '\n' (code 1, invalid) up to the 16-position boundary -- at most one 3-byte unit (slots are
-    // multiples of 8) --, then the slack behind the last group (not the rest of a larger block); ASCII, '\n' up to the boundary
-    auto fill_tail = [&](bool pk, uint64_t total) -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (pk) {
-            const uint64_t t0 = total / 8u * 3u, t1 = ss::dev::in_bytes(true, cap) + 8;
-            e = hipMemsetAsync(d_new + t0, 0xFF, t1 - t0, 0);
-            if (e == hipSuccess && cap > total) e = hipMemsetAsync(d_new + t0, 0x55, 2, 0);
-        } else if (cap > total) {
-            e = hipMemsetAsync(d_new + total, '\n', cap - total, 0);
-        }
-        return e;
-    };
-    if (sorted) {
-        // one length: the new slab's size is known before anything runs (n_rec slots), so its block is taken first, and the
-        // flags are read once, after the gather
-        const uint32_t slot = ::slot_of(fix_L), P = (slot + 15u) >> 4;
-        const uint64_t total = n_rec * slot;
-        cap = std::max<uint64_t>((total + 15) & ~15ull, 16);
-        const bool want_packed = g_hook_ascii_slabs.load() == 0;
-        SS_R(ss::big_malloc((void **)&d_new, block_bytes(want_packed, cap), &real_cap));
-        t_alloc = std::chrono::steady_clock::now();
-        lap("new slab");
-        uint32_t *k0 = (uint32_t *)(d_scr + o_tab), *k1 = (uint32_t *)(d_scr + o_tab + a4), *v0 = (uint32_t *)(d_scr + o_tab + 2 * a4),
-                 *v1 = (uint32_t *)(d_scr + o_tab + 3 * a4);
-        void *d_temp = d_scr + o_tab + 4 * a4;
-        unsigned long long *flags = d_hist + n_bins;     // [1] not of one length, [2] not packable
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        SS_R(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) { hipEventDestroy(ev[0]); SS_R(hipErrorOutOfMemory); }
-        auto gather = [&](bool pk, const uint32_t *perm) {
-            const uint32_t G = gather_rows(pk, fix_L), R = pk ? slot / 8u * 3u : slot;
-            auto kern = pk ? gather_fixed_kernel<true> : gather_fixed_kernel<false>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 4u * G * R, 0, src, n, n_rec, fix_L, P,
-                               (uint32_t)(((1ull << 32) + P - 1) / P), G, perm, (uint8_t *)d_new, flags + 1, flags + 2);
-        };
-        hipError_t e = hipMemsetAsync(flags, 0, 24, 0);
-        if (e == hipSuccess) e = hipEventRecord(ev[0], 0);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(key_fixed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, bits, k0, v0, flags + 1);
-            hipcub::DoubleBuffer<uint32_t> dk(k0, k1), dv(v0, v1);
-            e = hipcub::DeviceRadixSort::SortPairs(d_temp, sort_tb, dk, dv, (int)n_rec, 0, bits + 1, 0);
-            if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
-            const uint32_t *perm = dv.Current();
-            if (e == hipSuccess) { gather(want_packed, perm); e = fill_tail(want_packed, total); }
-            if (e == hipSuccess) e = hipMemcpy(tail + 1, flags + 1, 16, hipMemcpyDeviceToHost);
-            fixed = tail[1] == 0;
-            if (e == hipSuccess && fixed && want_packed && tail[2]) {         // a byte other than A C G T N: the same order, ASCII
-                if (real_cap < cap) {
-                    ss::big_put(d_new, real_cap); d_new = nullptr;
-                    e = ss::big_malloc((void **)&d_new, cap, &real_cap);
-                }
-                if (e == hipSuccess) { gather(false, perm); e = fill_tail(false, total); }
-                // (the packed gather's waves stop once the slab is known not packable: the layout is checked by the ASCII one)
-                if (e == hipSuccess) e = hipMemcpy(tail + 1, flags + 1, 8, hipMemcpyDeviceToHost);
-                fixed = tail[1] == 0;
-            }
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess && fixed) e = hipEventElapsedTime(&ms_key_sort, ev[0], ev[1]);
-        hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
-        SS_R(e);
-        packed = fixed && want_packed && tail[2] == 0;
-        tail[0] = total;
-        if (!fixed) { ss::big_put(d_new, real_cap); d_new = nullptr; }      // (else: some record is shorter or longer after all)
-    } else if (fix_L) {
-        // ss_test_hook 6: the count + atomic placement
-        const uint32_t L1 = fix_L + 1u;
-        const unsigned nbf = (unsigned)((n_rec + 255) / 256);
-        SS_R(hipMemsetAsync(d_hist, 0, o_sums, 0));
-        hipLaunchKernelGGL(count_fixed_kernel, dim3(nbf), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + L1 - 1) / L1), bits, d_hist,
-                           (uint32_t *)d_tab, d_hist + n_bins + 1, d_hist + n_bins + 2);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(nsb), dim3(1024), 0, 0, d_hist, n_bins, d_sums);
-        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, 0, d_sums, nsb, d_hist + n_bins);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(1024), 0, 0, d_hist, n_bins, d_sums);
-        SS_R(hipMemcpy(tail, d_hist + n_bins, 24, hipMemcpyDeviceToHost));
-        fixed = tail[1] == 0;                            // (else: some record is shorter or longer after all -- the general passes)
-        packed = fixed && tail[2] == 0 && g_hook_ascii_slabs.load() == 0;
-    }
-    if (!fixed) {
-        SS_R(hipMemsetAsync(d_hist, 0, o_sums, 0));
-        hipLaunchKernelGGL(count_kernel, dim3(nb), dim3(256), pad1, 0, src, n, bits, d_hist, d_cnt, d_tab, d_hist + n_bins + 1);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(nsb), dim3(1024), 0, 0, d_hist, n_bins, d_sums);
-        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, 0, d_sums, nsb, d_hist + n_bins);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(1024), 0, 0, d_hist, n_bins, d_sums);
-        SS_R(hipMemcpy(tail, d_hist + n_bins, 16, hipMemcpyDeviceToHost));
-    }
-    const unsigned long long total = tail[0];
-    if (!(sorted && fixed)) {
-        lap("count + prefix");
-        t_counted = std::chrono::steady_clock::now();
-        cap = std::max<uint64_t>((total + 15) & ~15ull, 16);      // positions
-        SS_R(ss::big_malloc((void **)&d_new, block_bytes(packed, cap), &real_cap));
-        t_alloc = std::chrono::steady_clock::now();
-        lap("new slab");
-        if (packed) {
-            // a record's LDS area: 4 bytes in front (a span's first dword may begin before it), its groups, 4 behind
-            const uint32_t P = (::slot_of(fix_L) + 15u) >> 4, B = ::slot_of(fix_L) / 8u * 3u, A = (6u * P + 8u + 3u) & ~3u;
-            const uint32_t G = std::min<uint32_t>(64u, PK_LDS / A), ND = ((B + 2u) >> 2) + 1u;      // records per round; dwords a span touches
-            hipLaunchKernelGGL(place_fixed_packed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, P,
-                               (uint32_t)(((1ull << 32) + P - 1) / P), A, G, ND, (uint32_t)(((1ull << 32) + ND - 1) / ND), d_hist,
-                               (const uint32_t *)d_tab, (uint8_t *)d_new);
-        } else if (fixed) {
-            const uint32_t P = (::slot_of(fix_L) + 15u) >> 4;
-            hipLaunchKernelGGL(place_fixed_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, 0, src, n, n_rec, fix_L, (uint32_t)(((1ull << 32) + P - 1) / P),
-                               d_hist, (const uint32_t *)d_tab, d_new);
-        } else {
-            hipLaunchKernelGGL(place_kernel, dim3(nb), dim3(256), pad2, 0, src, n, d_hist, d_cnt, d_tab, d_new);
-            if (tail[1]) hipLaunchKernelGGL(place_again_kernel, dim3(nb), dim3(256), 0, 0, src, n, bits, d_hist, d_cnt, d_new);
-        }
-        SS_R(fill_tail(packed, total));
-    }
-    SS_R(hipGetLastError());
-    SS_R(hipDeviceSynchronize());
-    lap("place");
+    const bool sorted = one.L && g_hook_atomic_binning.load() == 0 && one.n_rec < (1ull << 31);
+    Scratch scr;
+    if (!hip_ok(scr.take(c, one, sorted), "Scratch::take", __LINE__)) return SS_EHIP;
+    NewSlab slab;
+    double ms[3] = {0, 0, 0};
+    Binned r = Binned::not_one_length;
+    if (one.L) r = sorted ? bin_sorted(c, one, scr, slab, ms) : bin_counted(c, one, scr, slab, ms);
+    const bool fixed = r == Binned::done;
+    if (r == Binned::not_one_length) r = bin_general(c, scr, slab, ms);
+    if (r != Binned::done) return SS_EHIP;
     {
         // where the call's time went (ss_reads_order_timing): the driver's allocation of the new slab is not the kernels' time,
         // and on some boxes a fresh 3 GB allocation takes 60-90 ms
-        const auto t_end = std::chrono::steady_clock::now();
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::lock_guard<std::mutex> g(g_scr_mu);
-        if (sorted && fixed) {                           // key + sort, allocation, gather + tail (the first and the last add up to the kernels' wall time)
-            g_order_ms[0] = ms_key_sort; g_order_ms[1] = ms(t_begin, t_alloc); g_order_ms[2] = ms(t_alloc, t_end) - ms_key_sort;
-        } else {                                         // count + prefix, allocation, place
-            g_order_ms[0] = ms(t_begin, t_counted); g_order_ms[1] = ms(t_counted, t_alloc); g_order_ms[2] = ms(t_alloc, t_end);
-        }
+        for (int i = 0; i < 3; i++) g_order_ms[i] = ms[i];
         g_order_n[fixed ? 0 : 1]++;
     }
-#undef SS_R
-    {
-        std::lock_guard<std::mutex> g(g_scr_mu);
-        if (!g_scr || g_scr_cap < scr_cap) { std::swap(g_scr, d_scr); std::swap(g_scr_cap, scr_cap); }
-    }
-    if (d_scr) hipFree(d_scr);
-    out->d = d_new; out->cap = real_cap; out->binned = true;
-    out->used = packed ? ss::dev::in_bytes(true, cap) : cap;
-    if (packed) { out->packed = true; out->n_pos = cap; out->L = fix_L; out->slot = ::slot_of(fix_L); }
+    scr.keep();
+    out->cap = slab.real_cap; out->binned = true;
+    out->used = slab.packed ? ss::dev::in_bytes(true, slab.cap) : slab.cap;
+    if (slab.packed) { out->packed = true; out->n_pos = slab.cap; out->L = one.L; out->slot = ::slot_of(one.L); }
+    out->d = slab.release();
     return SS_OK;
 }
 

@@ -1,7 +1,9 @@
 """Binning of records of one length by sorting (ss_reorder.hip key_fixed_kernel, a stable radix sort, gather_fixed_kernel): the
 binned slab holds the records in bin order and, inside a bin, in FILE order -- so two binnings of one input read back byte for
 byte the same.  ss_test_hook 6 = 1 bins through the count + atomic placement instead: the same records per bin, the same counts.
-Bytes other than A C G T N keep the slab ASCII; a slab that is not of one length after all takes the general passes."""
+Bytes other than A C G T N keep the slab ASCII; a slab that is not of one length after all takes the general passes -- from
+either one-length path.  The scratch block is one allocation that each path lays out its own way and that is kept from call to
+call: one process takes it through every layout."""
 import ctypes as C
 
 import numpy as np
@@ -78,16 +80,41 @@ def _kdb(L, g):
     return L.KmerDB.from_text(kfa, 31, True)
 
 
-def _bin_once(L, block, hook6=0):
+def _one_length_candidate(block):
+    """(L, n_rec) when order_flat_dev takes the block for the one-length paths, else None: the first newline says L, within
+    FIX_MIN_L..FIX_MAX_L, at least 64 bytes (`qualifies` of test_binning_of_records_of_one_length), fewer than 64 bytes behind
+    the last whole record."""
+    n, length = len(block), block[:1025].find(b"\n")
+    if n < 64 or not 32 <= length <= 1023 or n % (length + 1) >= 64:
+        return None
+    return length, n // (length + 1)
+
+
+def _ragged_block(seed, n_rec, g):
+    """n_rec reads of 100..200 bases cut from g, some with an N: no one-length candidate (checked)."""
+    rs = np.random.RandomState(seed)
+    lens = rs.randint(100, 201, size=n_rec)
+    starts = rs.randint(0, len(g) - 200, size=n_rec)
+    recs = [g[s:s + n].tobytes() for s, n in zip(starts, lens)]
+    for i in range(3, n_rec, 97):
+        recs[i] = recs[i][:40] + b"N" + recs[i][41:]
+    block = b"\n".join(recs) + b"\n"
+    assert _one_length_candidate(block) is None
+    return recs, block
+
+
+def _bin_once(L, block, hook6=0, hook5=0):
     import torch
     d = torch.frombuffer(bytearray(block), dtype=torch.uint8).cuda()
     L.check(L.lib().ss_test_hook(6, hook6), "ss_test_hook")
+    L.check(L.lib().ss_test_hook(5, hook5), "ss_test_hook")
     try:
         f0, g0 = _order_counters(L)
         rset = L.ReadSet.from_flat_dev(d.data_ptr(), d.numel(), order=True)
         f1, g1 = _order_counters(L)
     finally:
         L.lib().ss_test_hook(6, 0)
+        L.lib().ss_test_hook(5, 0)
     L.check(L.lib().ss_device_sync(), "sync")
     return rset, (f1 - f0, g1 - g0)
 
@@ -140,13 +167,19 @@ def test_sorted_binning_keeps_file_order_inside_a_bin(L, length, n_rec, pad, low
     db.close()
 
 
-@pytest.mark.parametrize("length,n_rec,lower", [(150, 30000, False), (150, 30000, True), (77, 5001, False)])
+@pytest.mark.parametrize("length,n_rec,lower", [(150, 30000, False), (150, 30000, True), (77, 5001, False), (151, 4097, False),
+                                                (151, 4097, True), (1023, 700, False), (1023, 700, True), (33, 64, False),
+                                                (33, 64, True), (32, 65, False), (32, 65, True), (100, 1, False)])
 def test_hook6_atomic_placement_agrees_with_the_sort(L, length, n_rec, lower):
     """ss_test_hook 6 = 1 (count + atomic placement) and 0 (key + sort + gather) on one input: the same records in every bin,
-    the same layout, bit-identical counters after a scan."""
+    the same layout, bit-identical counters after a scan.  Slots of 8 x odd positions with a partial last wave (151 x 4097),
+    several LDS rounds per wave (1023), the shortest lengths with one wave and one record more, a single record; packed
+    (place_fixed_packed_kernel) and, lower case in some first k-mers, ASCII (place_fixed_kernel)."""
     g = _genome(91 + length, 40000 + length)
     recs = _records(17 + n_rec, length, n_rec, g, lower_first=lower)
     block = b"\n".join(recs) + b"\n"
+    assert _one_length_candidate(block) == (length, n_rec)
+    assert not lower or n_rec > 5                               # (_records puts the lower case into record 5, 508, ...)
     bits = _order_bits(len(block))
     db = _kdb(L, g)
     got = {}
@@ -192,11 +225,8 @@ def test_bytes_outside_the_alphabet_give_an_ascii_slab(L, letter):
     db.close()
 
 
-@pytest.mark.parametrize("variant", ["inner_newline", "one_base_short", "inner_newline_last"])
-def test_not_one_length_takes_the_general_passes(L, variant):
-    """An internal newline (the byte count still divides: only the gather's check sees it) and a record one base short (the
-    records behind it shifted: the key pass sees it) each go through the general passes, with the same counts as the flat scan."""
-    g = _genome(9, 50150)
+def _broken_block(variant, g):
+    """9 000 x 150 bases that the probe takes for records of one length and that are not."""
     recs = _records(31, 150, 9000, g)
     if variant == "inner_newline":
         recs[4000] = recs[4000][:75] + b"\n" + recs[4000][76:]
@@ -206,14 +236,107 @@ def test_not_one_length_takes_the_general_passes(L, variant):
         recs[2500] = recs[2500][:-1]
         recs[6000] = recs[6000] + b"A"
     block = b"\n".join(recs) + b"\n"
+    assert _one_length_candidate(block) == (150, 9000)
+    return recs, block
+
+
+def _check_fallback(L, variant, hook6):
+    g = _genome(9, 50150)
+    recs, block = _broken_block(variant, g)
     db = _kdb(L, g)
     db.reset()
     db.scan_flat(block)
     want = db.counts_rows().copy()
-    rset, used = _bin_once(L, block)
+    rset, used = _bin_once(L, block, hook6=hook6)
     assert used == (0, 1), variant
     assert np.array_equal(_counts(L, db, rset), want)
     back = [r for r in rset.read_back().split(b"\n") if r]
     assert sorted(back) == sorted(r for chunk in recs for r in chunk.split(b"\n") if r)
     rset.close()
+    db.close()
+
+
+@pytest.mark.parametrize("variant", ["inner_newline", "one_base_short", "inner_newline_last"])
+def test_not_one_length_takes_the_general_passes(L, variant):
+    """An internal newline (the byte count still divides: only the gather's check sees it) and a record one base short (the
+    records behind it shifted: the key pass sees it) each go through the general passes, with the same counts as the flat scan."""
+    _check_fallback(L, variant, 0)
+
+
+@pytest.mark.parametrize("variant", ["inner_newline", "one_base_short"])
+def test_not_one_length_under_hook6_takes_the_general_passes(L, variant):
+    """The same from the count + atomic placement (ss_test_hook 6 = 1): count_fixed_kernel sees the newline in the middle of a
+    record, and the record a base short (a later one a base long), and the general passes bin the slab."""
+    _check_fallback(L, variant, 1)
+
+
+@pytest.mark.parametrize("hook6", [0, 1])
+def test_timing_after_a_fallback(L, hook6):
+    """ss_reads_order_timing after a one-length attempt that fell back: count + prefix (the failed attempt in it), allocation,
+    place."""
+    recs, block = _broken_block("inner_newline", _genome(9, 50150))
+    rset, used = _bin_once(L, block, hook6=hook6)
+    assert used == (0, 1)
+    timing = np.zeros(3)
+    L.check(L.lib().ss_reads_order_timing(L.ptr(timing)), "ss_reads_order_timing")
+    assert timing[0] > 0 and timing[1] >= 0 and timing[2] > 0
+    rset.close()
+
+
+def test_hooks_5_and_6_together(L):
+    """The count + atomic placement with ASCII slabs asked for: an all-ACGT slab of one length stays ASCII, with correct counts;
+    packed again once hook 5 is back at 0."""
+    g = _genome(41, 30150)
+    starts = np.random.RandomState(43).randint(0, len(g) - 150, size=6000)
+    recs = [a.tobytes() for a in g[starts[:, None] + np.arange(150)[None, :]]]
+    block = b"\n".join(recs) + b"\n"
+    assert _one_length_candidate(block) == (150, 6000) and set(block) <= set(b"ACGT\n")
+    db = _kdb(L, g)
+    db.reset()
+    db.scan_flat(block)
+    want = db.counts_rows().copy()
+    for hook5, packed in ((1, 0), (0, 1)):
+        rset, used = _bin_once(L, block, hook6=1, hook5=hook5)
+        assert used == (1, 0)
+        assert rset.packed_slabs() == packed
+        assert np.array_equal(_counts(L, db, rset), want)
+        assert sorted(r for r in rset.read_back().split(b"\n") if r) == sorted(recs)
+        rset.close()
+    db.close()
+
+
+def test_one_scratch_block_through_every_layout(L):
+    """One process, one kept scratch block: the record table of the general passes (a ragged slab of ~2 MB), the sort's arrays
+    (one length, ~0.3 MB, in the larger kept block), the per-record bins (the same under hook 6), a larger record table (~6 MB
+    ragged: the kept block is replaced), the sort's arrays again; then the kept block is released and a slab binned afresh."""
+    g = _genome(77, 60000)
+    db = _kdb(L, g)
+    ragged_2mb, ragged_6mb = _ragged_block(1, 13000, g), _ragged_block(2, 40000, g)
+    fixed = _records(5, 150, 2000, g)
+    one_len = (fixed, b"\n".join(fixed) + b"\n")
+    assert _one_length_candidate(one_len[1]) == (150, 2000)
+    assert 1.8e6 < len(ragged_2mb[1]) < 2.2e6 and 5.5e6 < len(ragged_6mb[1]) < 6.5e6 and 0.28e6 < len(one_len[1]) < 0.32e6
+    want = {}
+    for recs, block in (ragged_2mb, ragged_6mb, one_len):
+        db.reset()
+        db.scan_flat(block)
+        want[id(block)] = db.counts_rows().copy()
+
+    def step(what, hook6, expect):
+        recs, block = what
+        rset, used = _bin_once(L, block, hook6=hook6)
+        assert used == expect
+        assert np.array_equal(_counts(L, db, rset), want[id(block)])
+        assert sorted(r for r in rset.read_back().split(b"\n") if r) == sorted(recs)
+        rset.close()
+
+    step(ragged_2mb, 0, (0, 1))
+    step(one_len, 0, (1, 0))
+    step(one_len, 1, (1, 0))
+    step(ragged_6mb, 0, (0, 1))
+    step(one_len, 0, (1, 0))
+    release = getattr(L.lib(), "ss_gz_gpu_release", None)
+    if release is not None:
+        L.check(release(), "ss_gz_gpu_release")
+        step(one_len, 0, (1, 0))
     db.close()
