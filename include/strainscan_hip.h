@@ -301,6 +301,15 @@ int ss_scan_reads_multi(ss_db *const *dbs, int n_dbs, const ss_reads *r, void *s
 /* Launches of the several-tables kernel so far in this process, per filter kind of the tables it took (diagnostics):
  * out[0] tables behind their own Bloom filters (tree tables), out[1] tables announced with ss_db_expect_hits, out[2] neither. */
 int ss_scan_multi_launches(uint64_t out[3]);
+/* How many records of a resident set carry k-mers of a table (`--read_support`).  A record is a maximal run of bytes other than
+ * '\n' in the set (a read; a record longer than a block counts as its pieces); a hit of a record is a k-mer start position in it at
+ * which ss_scan_reads would add 1 to a counter of the table.
+ * hist[b], b < n_bins-1: records of the set with exactly b hits against db; hist[n_bins-1]: records with >= n_bins-1.
+ * *hits: the hits of all records.  sum(hist) = the set's non-empty records.  Reads the table's index, never its counters
+ * (a scan's accumulated counts are the same before and after).  Synchronous.  Page-index tables (17 <= k <= 31) only:
+ * SS_ERANGE for a flat table; SS_EINVAL for n_bins < 2, a NULL argument, a table and a set on different devices. */
+int ss_reads_support(const ss_db *db, const ss_reads *r, uint32_t n_bins, uint64_t *hist, uint64_t *hits);
+int ss_reads_support_calls(uint64_t *n);   /* calls so far in this process (diagnostics; tests use it to show "flag off = not run") */
 
 /* --------------------------------------------------------------------------------------------
  * Host FASTA/FASTQ -> flat base block (what jellyfish's sequence parser feeds its counter).

@@ -15,7 +15,9 @@ and says where the time goes (SS_CLI_TRACE milestones: interpreter + imports, tr
 cluster scans, per-cluster solve, reports).  The reference itself re-runs jellyfish over ALL reads once per identified
 cluster and solves the clusters one after the other.
 
-    bench_cli_l2.py [n_reads = 20000000] [clusters = 5000000x300,2000000x120,1000000x60] [text|gz[-LEVEL]] [leaves = 202]
+    bench_cli_l2.py [n_reads = 20000000] [clusters = 5000000x300,2000000x120,1000000x60] [text|gz[-LEVEL]] [leaves = 202] [flags]
+
+(flags: further flags for every `strainscan` run, one argument, e.g. "--read_support": profiles/r11_read_support.md)
 
 all_kid.pkl (a 5 M-entry dict k-mer -> id that the reference unpickles, Vote_...:348) is NOT written: this implementation never
 reads it (row r of all_kmer.fasta is k-mer id r + 1, Build_kmer_sets_..._sp.py:397-399,409-410)."""
@@ -138,10 +140,11 @@ def main():
     shapes = [tuple(int(x) for x in c.split("x")) for c in (sys.argv[2] if len(sys.argv) > 2 else "5000000x300,2000000x120,1000000x60").split(",")]
     mode = sys.argv[3] if len(sys.argv) > 3 else "text"
     C = int(sys.argv[4]) if len(sys.argv) > 4 else 202
-    print(json.dumps(run(n_reads, shapes, mode, C)))
+    flags = sys.argv[5].split() if len(sys.argv) > 5 else []
+    print(json.dumps(run(n_reads, shapes, mode, C, cli_flags=flags)))
 
 
-def run(n_reads, shapes, mode="text", C=202, per_cluster=True):
+def run(n_reads, shapes, mode="text", C=202, per_cluster=True, cli_flags=()):
     """-> the dict main() prints (bench.py calls this with a reduced configuration for its `cli_e2e` block)."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -204,7 +207,9 @@ def run(n_reads, shapes, mode="text", C=202, per_cluster=True):
                    setup_s=round(time.perf_counter() - t0, 1))
 
         odir = os.path.join(base, "out")
-        args = ["-i", fq[0], "-j", fq[1], "-d", base, "-o", odir]
+        args = ["-i", fq[0], "-j", fq[1], "-d", base, "-o", odir] + list(cli_flags)
+        if cli_flags:
+            out["cli_flags"] = list(cli_flags)
         runs = []
         for label in ("nothing_cached", "images_cached", "images_cached_again"):
             shutil.rmtree(odir, ignore_errors=True)

@@ -1,8 +1,8 @@
 """`strainscan` command line -- drop-in for the identification CLI StrainScan.py:113-271.
 
 Same flags (-i -j -d -o -k -l -b -p -r -e -s), same cutoff ladder, same output files
-(final_report.txt, C<id>/StrainVote.report, strain_prob.txt).  One flag of its own: -q Q masks bases of Phred quality below Q
-(`jellyfish count -Q`; off by default).  Plasmid mode (-p 1/2) rebuilds a
+(final_report.txt, C<id>/StrainVote.report, strain_prob.txt).  Two flags of its own: -q Q masks bases of Phred quality below Q
+(`jellyfish count -Q`; off by default); --read_support also writes read_support.tsv (reads that carry each table's k-mers).  Plasmid mode (-p 1/2) rebuilds a
 database with the reference's offline builder (StrainScan.py:235) and is out of scope here.
 """
 import argparse
@@ -111,6 +111,10 @@ def add_arguments(ap, multi=False):
                          "chr(33+Q), as `jellyfish count -Q`; BAM: qual < Q, records without qualities are left alone) "
                          "becomes N before k-mers are counted; FASTA input is untouched.  An integer in 0..93 "
                          "(default: 0, no masking)")
+    ap.add_argument("--read_support", dest="read_support", action="store_true",
+                    help="Also write read_support.tsv: for the tree's table and for every cluster table scanned at layer 2, how "
+                         "many reads of the sample carry at least 1, 2, 4, ... 64 of its k-mers (needs the sample resident on "
+                         "the device and k >= 17)")
 
 
 def min_base_qual_arg(text):
@@ -131,6 +135,13 @@ def apply_min_base_qual(q):
     from . import _lib, db
     _lib.set_min_base_qual(q)               # (0 as well: the command line states the setting of its run)
     db.MASK_REPORT.update(on=bool(q), done=False)
+
+
+def apply_read_support(on):
+    """--read_support (strainscan_amd.set_read_support): the tables scanned from here on leave a row each with db.READ_SUPPORT;
+    the command writes them to read_support.tsv when it ends.  stdout and the other report files are untouched."""
+    from . import db
+    db.read_support_reset(on)
 
 
 def settings(args):
@@ -223,7 +234,13 @@ def main(argv=None):
     from . import dist
     rank, world = dist.init_from_env()      # torchrun: one process per GPU, reads shard across ranks
     out_dir = rank_output_dir(out_dir, rank)
-    identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
+    apply_read_support(args.read_support)
+    try:
+        identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
+    finally:
+        from . import db
+        db.write_read_support(out_dir)      # (in a finally: the reference's own early exit()s come through here as SystemExit)
+        db.read_support_reset()
 
 
 def cli(main_fn=None):

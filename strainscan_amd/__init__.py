@@ -13,6 +13,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.StrainScan.main                            (StrainScan.py:113, the `strainscan` CLI)
 
     strainscan_amd.set_min_base_qual / get_min_base_qual      (the base-quality mask of `strainscan -q`; process-wide, off by default)
+    strainscan_amd.set_read_support                           (`strainscan --read_support`: rows of reads per table, db.READ_SUPPORT)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -26,6 +27,15 @@ def set_min_base_qual(q):
     cutoff), ...) stay as they are: this is the one setting they read."""
     from . import _lib
     _lib.set_min_base_qual(q)
+
+
+def set_read_support(on):
+    """`strainscan --read_support` for callers of the functions above: from here on the tree scan of identify_cluster and the
+    cluster scans of vote_strain_L2_batch each leave a row in strainscan_amd.db.READ_SUPPORT["rows"][None] -- (table, distinct
+    k-mers, reads, hits, 65-bin histogram of hits per read) -- and db.write_read_support(out_dir) writes them as
+    read_support.tsv.  set_read_support(False) turns it off and drops the rows.  Off by default; nothing runs while it is off."""
+    from . import db
+    db.read_support_reset(bool(on))
 
 
 def get_min_base_qual():

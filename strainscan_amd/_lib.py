@@ -106,6 +106,8 @@ SIGNATURES = {
     "ss_db_probe_info": (i32, [vp, vp]),
     "ss_scan_reads_multi": (i32, [vp, i32, vp, vp]),
     "ss_scan_multi_launches": (i32, [P(u64)]),
+    "ss_reads_support": (i32, [vp, vp, u32, vp, P(u64)]),
+    "ss_reads_support_calls": (i32, [P(u64)]),
     "ss_scan_reset": (i32, [vp, vp]),
     "ss_scan_flat_dev": (i32, [vp, vp, u64, vp]),
     "ss_scan_flat_host": (i32, [vp, cp, u64]),
@@ -472,6 +474,21 @@ class ReadSet:
 
     def scan_into(self, kdb, stream=None):
         check(lib().ss_scan_reads(kdb.handle, self._h, stream), "ss_scan_reads")
+
+    def support(self, kdb, n_bins=65):
+        """(hist, hits): hist[b] = records of the set with exactly b k-mer hits against `kdb` (the last bin: that many or more),
+        np.uint64[n_bins]; hits = the hits of all records (ss_reads_support).  The table's counters are left alone."""
+        hist = np.zeros(max(int(n_bins), 1), np.uint64)
+        hits = C.c_uint64()
+        check(lib().ss_reads_support(kdb.handle, self._h, int(n_bins), ptr(hist), C.byref(hits)), "ss_reads_support")
+        return hist, int(hits.value)
+
+
+def support_calls():
+    """Calls of ss_reads_support so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_support_calls(C.byref(n)), "ss_reads_support_calls")
+    return n.value
 
 
 def scan_multi_launches():

@@ -280,6 +280,15 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
                      bool packed = false);
 int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned,
                            bool packed = false);
+// ss_reads_support (ss_support.hip): the lookups of one slab with the per-record sink of scan_minik_kernel (ss_mini.hip).  A found
+// k-mer adds 1 to rec_hits[rec_base + record of its start position]; records at or beyond rec_limit are never written.
+struct SupportArgs {
+    uint32_t *rec_hits;             // [rec_limit] hits per record of the set
+    const uint32_t *tile_base;      // ASCII slab: record ends before each 1024-position tile of the slab; packed: unused
+    uint64_t rec_base, rec_limit;   // records of the slabs before this one; records of the set
+    uint32_t slot;                  // packed slab: positions per record
+};
+int launch_support_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, hipStream_t stream);
 // the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster
 // table: the combining variant under binned reads), or none at all.  One launch takes tables of one kind (ss_scan_multi_launches).
 enum { MULTI_BLOOM = 0, MULTI_EXPECT = 1, MULTI_PLAIN = 2 };

@@ -1325,19 +1325,43 @@ struct KShared {
     uint2 q[KQ];                                              // position | minimizer offset << 10, h
 };
 
+// Where a found k-mer goes (the SINK of scan_minik_kernel).  CountSink: 1 to its counter in the table -- the scan.  SupportSink
+// (ss_reads_support, ss_support.hip): the bit of its start position in a bitmap of the tile in LDS; the tile's tail walks the
+// bitmap beside the record boundaries and adds the hits to rec_hits, one atomic per (lane, record).  The lookup itself -- the
+// one statement of the page format with k at run time -- is the same code for both.
+struct CountSink {
+    static constexpr bool SUPPORT = false;
+    uint32_t *__restrict__ counts;
+    uint32_t cbase;
+    __device__ __forceinline__ void bucket(uint32_t slot, uint32_t *, uint32_t) const { atomicAdd(&counts[slot], 1u); }
+    __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *, uint32_t) const { atomicAdd(&counts[cbase + page_slot], 1u); }
+};
+struct SupportSink {
+    static constexpr bool SUPPORT = true;
+    ss::SupportArgs a;
+    __device__ __forceinline__ void bucket(uint32_t, uint32_t *bits, uint32_t p) const { atomicOr(&bits[p >> 5], 1u << (p & 31u)); }
+    __device__ __forceinline__ void inline_slot(uint32_t, uint32_t *bits, uint32_t p) const { atomicOr(&bits[p >> 5], 1u << (p & 31u)); }
+};
+// the tile's LDS: the support variant adds the hit bitmap and the '\n' flags of the tile's bytes (nl[0]: bit 15 = the byte before the tile)
+template <bool SUPPORT> struct KSharedT : KShared { __device__ __forceinline__ uint32_t *bits() { return nullptr; } };
+template <> struct KSharedT<true> : KShared {
+    uint32_t hit[KPOS / 32];
+    uint16_t nl[KT + 2];
+    __device__ __forceinline__ uint32_t *bits() { return hit; }
+};
+
 // How the time of a first version went (4 M reads, k = 25, profiles/r06_ab_log.md): one lane per position, four positions of a
 // thread one after the other: 4.0 ms -- 1.9 of it the minimizers (a loop of k - 14 dependent LDS reads per position at five waves
 // per SIMD), 0.2 the page sectors, 2.4 the slots: 4 % of the positions hit, so nearly every wave walked the whole hit path, four
 // times per tile.  Hence: a lane owns FOUR ADJACENT positions and reads their k - 11 keys once, as five 16-byte LDS loads (the
 // four windows share all but three keys on either side); the four page heads are in flight together; positions whose page shows
 // their tag (or is full) are compacted into an LDS queue with ballots and settled ONCE per tile, one candidate per lane.
-template <int IN, bool BLOOM>
+template <int IN, bool BLOOM, class SINK>
 __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restrict__ bases, uint64_t n, uint64_t n_tiles, int k,
                                                         const uint64_t *__restrict__ mkeys, const uint4 *__restrict__ pages, uint32_t n_pages,
-                                                        uint32_t *__restrict__ counts, uint32_t cbase, const uint32_t *__restrict__ bloom,
-                                                        uint32_t bloom_shift)
+                                                        const SINK sink, const uint32_t *__restrict__ bloom, uint32_t bloom_shift)
 {
-    __shared__ KShared S;
+    __shared__ KSharedT<SINK::SUPPORT> S;
     const int t = threadIdx.x;
     const uint32_t W = (uint32_t)(k - ss::MINI_M + 1), F = W - 1u;      // m-mers per k-mer (3..17), flank bases
     const uint64_t kmask = (1ull << (2 * k)) - 1ull, vmask = (1ull << k) - 1ull;
@@ -1367,17 +1391,17 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
                     bool found = false;
                     if ((mask >> o) & 1u) {
                         const uint32_t cpos = bstart + 1u + (uint32_t)__popc(mask & ((1u << o) - 1u));
-                        if (mkeys[cpos] == key) { atomicAdd(&counts[cpos], 1u); found = true; }
+                        if (mkeys[cpos] == key) { sink.bucket(cpos, S.bits(), p); found = true; }
                     }
                     if (!found && (l32 >> 31)) {                                // several k-mers per offset: look through the bucket
                         const uint32_t cnt = (uint32_t)(mkeys[bstart] >> 32);
                         for (uint32_t c = 0; c < cnt; c++)
-                            if (mkeys[bstart + 1u + c] == key) { atomicAdd(&counts[bstart + 1u + c], 1u); break; }
+                            if (mkeys[bstart + 1u + c] == key) { sink.bucket(bstart + 1u + c, S.bits(), p); break; }
                     }
                 } else if ((hi8 & 31u) == F - o) {                              // an inline k-mer with this minimizer offset
                     const uint32_t mid = reinterpret_cast<const uint16_t *>(pb + 48)[sl];
                     if ((mid >> 4) == ((h >> 8) & 0xFFFu) && reinterpret_cast<const uint32_t *>(pb + 16)[sl] == ss::flank_of_key_k(key, o, k))
-                        atomicAdd(&counts[cbase + page * 8u + sl], 1u);
+                        sink.inline_slot(page * 8u + sl, S.bits(), p);
                 }
             }
             full = (tg.w >> 24) != (uint32_t)ss::PG_EMPTY_HI;
@@ -1394,6 +1418,13 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
             decode_in<IN>(w, code, inv);
             S.code[t] = code;
             S.inv[t] = (uint16_t)inv;
+            if constexpr (SINK::SUPPORT) {
+                if (t < KPOS / 32) S.hit[t] = 0u;
+                if (IN != IN_PACKED) {
+                    S.nl[t + 1] = (uint16_t)newline_mask16(w);
+                    if (t == 0) S.nl[0] = (b0 == 0 || bases[b0 - 1] == 0x0Au) ? 0x8000u : 0u;      // (a slab begins behind a boundary)
+                }
+            }
             if (t < 3) {
                 load_in<IN>(bases, b0 + (uint64_t)(KT + t) * 16, n, w);
                 decode_in<IN>(w, code, inv);
@@ -1465,7 +1496,7 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
                 page_[j] = ss::page_of(h_[j], n_pages);
             }
 #if defined(SS_KSTOP) && SS_KSTOP == 1      // (debug builds: the time of the phases up to here; results are then of course wrong)
-            { uint32_t acc = 0; for (int r = 0; r < 4; r++) acc ^= h_[r] ^ m_[r] ^ (uint32_t)go_[r]; if (acc == 0x12345678u) atomicAdd(&counts[0], 1u); continue; }
+            { uint32_t acc = 0; for (int r = 0; r < 4; r++) acc ^= h_[r] ^ m_[r] ^ (uint32_t)go_[r]; if (acc == 0x12345678u) atomicAdd(&sink.counts[0], 1u); continue; }
 #endif
             if (BLOOM) {
                 uint32_t bw[4];
@@ -1480,7 +1511,7 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
                 if (go_[j]) tg_[j] = pages[(uint64_t)page_[j] * 4u];
             }
 #if defined(SS_KSTOP) && SS_KSTOP == 2
-            { uint32_t acc = 0; for (int r = 0; r < 4; r++) acc ^= tg_[r].x ^ tg_[r].w ^ m_[r]; if (acc == 0x12345678u) atomicAdd(&counts[0], 1u); continue; }
+            { uint32_t acc = 0; for (int r = 0; r < 4; r++) acc ^= tg_[r].x ^ tg_[r].w ^ m_[r]; if (acc == 0x12345678u) atomicAdd(&sink.counts[0], 1u); continue; }
 #endif
             bool cand_[4];
 #pragma unroll
@@ -1512,7 +1543,7 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
             }
             }
 #if defined(SS_KSTOP) && SS_KSTOP == 3
-            if (nq == 0x12345678u) atomicAdd(&counts[0], S.q[t].x);
+            if (nq == 0x12345678u) atomicAdd(&sink.counts[0], S.q[t].x);
             nq = 0;
             continue;
 #endif
@@ -1527,6 +1558,37 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
                 nq = 0;
             }
         }
+        // ---- support: the tile's hit bits to the records.  A lane takes the 16 positions it decoded: `bnd` has a bit where the record
+        // index steps up (ASCII: a record end, a '\n' behind a byte that is none -- no k-mer starts there; packed: the first
+        // position of a slot), r is the record of its first position: the tile's base + the boundaries of the lanes before (a wave
+        // prefix sum), or position / slot.  One atomic per (lane, record) with hits: neighbouring lanes, neighbouring words.
+        if constexpr (SINK::SUPPORT) {
+            const ss::SupportArgs &A = sink.a;
+            const uint32_t hits = (S.hit[t >> 1] >> (16 * (t & 1))) & 0xFFFFu;
+            uint32_t bnd = 0;
+            uint64_t r = A.rec_base;
+            if (IN == IN_PACKED) {
+                const uint64_t q = b0 / A.slot;
+                const uint32_t rem0 = (uint32_t)(b0 - q * A.slot) + 16u * (uint32_t)t;
+                uint32_t rem = rem0 % A.slot;
+                r += q + rem0 / A.slot;
+#pragma unroll
+                for (int i = 1; i < 16; i++)
+                    if (++rem == A.slot) { rem = 0; bnd |= 1u << i; }
+            } else {
+                const uint32_t nl = S.nl[t + 1];
+                bnd = nl & ~((nl << 1) | (uint32_t)(S.nl[t] >> 15)) & 0xFFFFu;
+                const uint32_t mine = (uint32_t)__popc(bnd);
+                r += A.tile_base[tile] + wave_inclusive_sum(mine) - mine;
+            }
+            for (uint32_t h = hits, b = bnd; h; r++) {
+                const uint32_t nb = b ? (b & (0u - b)) : 0x10000u, below = nb - 1u;      // the positions before the next boundary
+                const uint32_t c = (uint32_t)__popc(h & below);
+                if (c && r < A.rec_limit) atomicAdd(&A.rec_hits[r], c);
+                h &= ~below;
+                b &= ~nb;
+            }
+        }
     }
 }
 
@@ -1538,8 +1600,27 @@ static int launch_scan_minik(ss_db *db, const uint8_t *b, uint64_t n, hipStream_
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)256 * 32 * 16);
     with_input_layout(b, packed, [&](auto in) {
         with_bool(multi_kind(db) == MULTI_BLOOM, [&](auto bloom) {
-            hipLaunchKernelGGL((scan_minik_kernel<decltype(in)::value, decltype(bloom)::value>), dim3(blocks), dim3(KT), 0, stream, b, n, n_tiles, db->k, db->d_mkeys,
-                               reinterpret_cast<const uint4 *>(db->d_dir), db->n_dir, db->d_counts, (uint32_t)db->n_mslots, db->d_bloom,
+            hipLaunchKernelGGL((scan_minik_kernel<decltype(in)::value, decltype(bloom)::value, CountSink>), dim3(blocks), dim3(KT), 0, stream, b, n, n_tiles,
+                               db->k, db->d_mkeys, reinterpret_cast<const uint4 *>(db->d_dir), db->n_dir, CountSink{db->d_counts, (uint32_t)db->n_mslots},
+                               db->d_bloom, 30u - db->bloom_bits);
+        });
+    });
+    SS_HIP(hipGetLastError());
+    return SS_OK;
+}
+
+// the same lookups for ss_reads_support: every k from 17 to 31 goes through the per-position kernel, whose sink marks positions
+// instead of counting k-mers; the table's counters are not touched
+int launch_support_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, hipStream_t stream)
+{
+    const uint8_t *b = (const uint8_t *)bases_dev;
+    const uint64_t n_tiles = (n + KPOS - 1) / KPOS;
+    if (!n_tiles || db->layout != 1 || (packed ? a.slot == 0 : a.tile_base == nullptr)) return SS_EINVAL;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)256 * 32 * 16);
+    with_input_layout(b, packed, [&](auto in) {
+        with_bool(multi_kind(db) == MULTI_BLOOM, [&](auto bloom) {
+            hipLaunchKernelGGL((scan_minik_kernel<decltype(in)::value, decltype(bloom)::value, SupportSink>), dim3(blocks), dim3(KT), 0, stream, b, n, n_tiles,
+                               db->k, db->d_mkeys, reinterpret_cast<const uint4 *>(db->d_dir), db->n_dir, SupportSink{a}, db->d_bloom,
                                30u - db->bloom_bits);
         });
     });

@@ -140,6 +140,20 @@ __device__ __forceinline__ void encode16(const uint32_t w[4], uint32_t &code, ui
     inv = (lo | (hi << 8)) >> 7;                                                    // sums are 128 x the flag masks
 }
 
+// 16 ASCII bytes (4 dwords) -> bit i set where byte i is '\n' (the record boundaries of ss_reads_support: the invalid flags of
+// encode16 do not tell '\n' from N)
+__device__ __forceinline__ uint32_t newline_mask16(const uint32_t w[4])
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const uint32_t x = w[d] ^ 0x0A0A0A0Au;
+        const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;     // 0x80 where the byte is '\n'
+        m |= __builtin_amdgcn_udot4(z, 0x08040201u, 0u, false) >> 7 << (4 * d);
+    }
+    return m;
+}
+
 // 16 bytes at `off` of the base stream; bytes at or beyond n read as '\n'.
 template <bool ALIGNED>
 __device__ __forceinline__ void load16(const uint8_t *__restrict__ bases, uint64_t off, uint64_t n,

@@ -1,0 +1,195 @@
+// ss_reads_support: how many records of a resident read set carry k-mers of a table (`--read_support`).
+//
+// The scans add a hit to the counter of its k-mer and forget the read it came from; this is the other projection: hits per RECORD,
+// reduced on the device to a histogram (records with exactly b hits) and the total.  A record is a maximal run of bytes other
+// than '\n' in a slab (a slot's L bases in a packed slab); a hit is a start position at which ss_scan_reads would count.  Nothing
+// here depends on the order of the records, so the result is the same for a set in file order, binned, or packed.
+//
+// Three passes, each a plain launch (no device-wide barrier inside a kernel):
+//   1. record_ends_kernel (ASCII slabs only): record ends per 1024-position tile, from the raw bytes -- a record end is a '\n'
+//      behind a byte that is none; a slab that does not end in '\n' ends its last record all the same.  hipcub's ExclusiveSum
+//      turns them into the record index at which every tile begins.  A packed slab needs neither: record = position / slot.
+//   2. scan_minik_kernel<.., SupportSink> (ss_mini.hip): the lookups of the per-position scan kernel, k at run time, all three
+//      input layouts, behind the table's Bloom filter where it has one.  A found k-mer sets the bit of its position in a bitmap
+//      of the tile in LDS; the tile's tail adds the bits up per record and issues one atomicAdd per (lane, record) into
+//      rec_hits[] -- about two per lane for 150-base reads, neighbouring lanes on neighbouring words.  Records that straddle
+//      tiles, or span many, meet in that array; record indices run on from slab to slab.
+//   3. support_hist_kernel: rec_hits -> bins in LDS per workgroup -> a few global 64-bit atomics.
+// The scratch (4 bytes per record, 4 per tile) comes from the stream-ordered pool and goes back before the call returns.
+#include "ss_scan_dev.h"
+
+#include <hipcub/hipcub.hpp>
+
+using namespace ss::dev;
+
+namespace {
+
+constexpr int SUP_TILE = 1024;      // positions per tile: KPOS of scan_minik_kernel (ss_mini.hip), one wave each
+
+// one wave per tile, 16 bytes per lane; tile_ends[tile] = record ends at positions [tile * 1024, tile * 1024 + 1024) below n, and
+// in the tile of byte n - 1 one more if that byte is not '\n'
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void record_ends_kernel(const uint8_t *__restrict__ bases, uint64_t n, uint64_t n_tiles,
+                                                          uint32_t *__restrict__ tile_ends)
+{
+    const uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= n_tiles) return;                                        // (the same for the whole wave)
+    const uint64_t off = tile * (uint64_t)SUP_TILE + (uint64_t)(threadIdx.x & 63u) * 16u;
+    uint32_t c = 0;
+    if (off < n) {
+        uint32_t w[4];
+        load16<ALIGNED>(bases, off, n, w);
+        const uint32_t nl = newline_mask16(w);
+        const uint32_t prev = (off == 0 || bases[off - 1] == 0x0Au) ? 1u : 0u;
+        uint32_t ends = nl & ~((nl << 1) | prev) & 0xFFFFu;
+        if (n - off < 16u) ends &= (1u << (uint32_t)(n - off)) - 1u;    // positions below n only
+        c = (uint32_t)__popc(ends);
+        if (n - off <= 16u) c += ((nl >> (uint32_t)(n - 1u - off)) & 1u) ^ 1u;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63u) == 0) tile_ends[tile] = c;
+}
+
+constexpr uint32_t HIST_LDS = 1024;      // bins a workgroup adds up in LDS; higher bins (n_bins above that) go to global memory
+
+// out[b], b < n_bins: records with min(hits, n_bins - 1) == b; out[n_bins]: the hits of all records
+__global__ __launch_bounds__(256) void support_hist_kernel(const uint32_t *__restrict__ rec_hits, uint64_t n_rec, uint32_t n_bins,
+                                                           unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t bins[HIST_LDS];
+    for (uint32_t b = threadIdx.x; b < HIST_LDS; b += 256u) bins[b] = 0u;
+    __syncthreads();
+    unsigned long long sum = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t h = rec_hits[i], b = min(h, n_bins - 1u);
+        sum += h;
+        if (b < HIST_LDS) atomicAdd(&bins[b], 1u);
+        else atomicAdd(&out[b], 1ull);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < min(n_bins, HIST_LDS); b += 256u)
+        if (bins[b]) atomicAdd(&out[b], (unsigned long long)bins[b]);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&out[n_bins], sum);
+}
+
+// pool allocations of one call, given back on every way out
+struct Scratch {
+    std::vector<void *> p;
+    hipError_t get(void **q, size_t bytes)
+    {
+        const hipError_t e = ss::l2s::dmalloc(q, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) p.push_back(*q);
+        return e;
+    }
+    ~Scratch()
+    {
+        for (void *q : p) (void)ss::l2s::dfree(q);
+        if (!p.empty()) (void)ss::l2s::sync();
+    }
+};
+
+std::atomic<uint64_t> g_support_calls{0};
+
+}  // namespace
+
+extern "C" {
+
+int ss_reads_support_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_support_calls.load();
+    return SS_OK;
+}
+
+int ss_reads_support(const ss_db *db, const ss_reads *R, uint32_t n_bins, uint64_t *hist, uint64_t *hits)
+{
+    if (!db || !R || !hist || !hits || n_bins < 2) return SS_EINVAL;
+    if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
+    if (R->has_cut_record && db->k != 31) return SS_ERANGE;         // cut records carry a 30-base overlap (as ss_scan_reads)
+    struct Part { const ss_reads::Slab *sl; uint64_t n, n_tiles, tile_off, n_rec; };
+    std::vector<Part> parts;
+    uint64_t tiles_total = 0;
+    for (const auto &sl : R->slabs) {
+        if (!sl.used || !sl.positions()) continue;
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, sl.d) != hipSuccess || at.device != db->device) { (void)hipGetLastError(); return SS_EINVAL; }
+        Part pt{&sl, sl.positions(), 0, tiles_total, 0};
+        pt.n_tiles = (pt.n + SUP_TILE - 1) / SUP_TILE;
+        if (sl.packed) {
+            if (!sl.slot) return SS_EINVAL;
+            pt.n_rec = pt.n / sl.slot;
+        } else {
+            if (pt.n_tiles + 1 > 0x7FFFFFFFull) return SS_ERANGE;   // hipcub counts its items in an int
+            tiles_total += pt.n_tiles + 1;
+        }
+        parts.push_back(pt);
+    }
+    g_support_calls++;
+    const hipStream_t st = ss::l2s::stream();
+    Scratch scratch;
+    uint32_t *d_ends = nullptr, *d_base = nullptr, *d_rec = nullptr;
+    unsigned long long *d_out = nullptr;
+    // 1. ASCII slabs: record ends per tile -> the record index at which each tile begins; [n_tiles] of a slab = its records
+    if (tiles_total) {
+        SS_HIP(scratch.get((void **)&d_ends, tiles_total * 4));
+        SS_HIP(scratch.get((void **)&d_base, tiles_total * 4));
+        SS_HIP(ss::l2s::set(d_ends, 0, tiles_total * 4));
+        size_t tmp_bytes = 0;
+        for (const Part &pt : parts)
+            if (!pt.sl->packed) {
+                size_t tb = 0;
+                SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_ends, d_base, (int)(pt.n_tiles + 1), st));
+                tmp_bytes = std::max(tmp_bytes, tb);
+            }
+        void *d_tmp = nullptr;
+        SS_HIP(scratch.get(&d_tmp, tmp_bytes));
+        std::vector<uint32_t> n_rec(parts.size(), 0);
+        for (size_t i = 0; i < parts.size(); i++) {
+            const Part &pt = parts[i];
+            if (pt.sl->packed) continue;
+            const uint8_t *b = (const uint8_t *)pt.sl->d;
+            const dim3 grid((unsigned)((pt.n_tiles + 3) / 4));
+            if ((((uintptr_t)b) & 15) == 0) hipLaunchKernelGGL(record_ends_kernel<true>, grid, dim3(256), 0, st, b, pt.n, pt.n_tiles, d_ends + pt.tile_off);
+            else hipLaunchKernelGGL(record_ends_kernel<false>, grid, dim3(256), 0, st, b, pt.n, pt.n_tiles, d_ends + pt.tile_off);
+            SS_HIP(hipGetLastError());
+            size_t tb = tmp_bytes;
+            SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_ends + pt.tile_off, d_base + pt.tile_off, (int)(pt.n_tiles + 1), st));
+            SS_HIP(hipMemcpyAsync(&n_rec[i], d_base + pt.tile_off + pt.n_tiles, 4, hipMemcpyDeviceToHost, st));
+        }
+        SS_HIP(ss::l2s::sync());
+        for (size_t i = 0; i < parts.size(); i++)
+            if (!parts[i].sl->packed) parts[i].n_rec = n_rec[i];
+    }
+    uint64_t rec_total = 0;
+    for (const Part &pt : parts) rec_total += pt.n_rec;
+    // 2. hits per record
+    SS_HIP(scratch.get((void **)&d_rec, rec_total * 4));
+    SS_HIP(scratch.get((void **)&d_out, ((size_t)n_bins + 1) * 8));
+    SS_HIP(ss::l2s::set(d_rec, 0, std::max<uint64_t>(rec_total * 4, 16)));
+    SS_HIP(ss::l2s::set(d_out, 0, ((size_t)n_bins + 1) * 8));
+    uint64_t rec_base = 0;
+    for (const Part &pt : parts) {
+        if (pt.n >= (uint64_t)db->k && pt.n_rec) {
+            const ss::SupportArgs a{d_rec, pt.sl->packed ? nullptr : d_base + pt.tile_off, rec_base, rec_total, pt.sl->packed ? pt.sl->slot : 0u};
+            const int rc = ss::launch_support_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, st);
+            if (rc) return rc;
+        }
+        rec_base += pt.n_rec;
+    }
+    // 3. histogram and total
+    if (rec_total) {
+        const unsigned blocks = (unsigned)std::min<uint64_t>((rec_total + 256 * 8 - 1) / (256 * 8), 2048);
+        hipLaunchKernelGGL(support_hist_kernel, dim3(blocks), dim3(256), 0, st, d_rec, rec_total, n_bins, d_out);
+        SS_HIP(hipGetLastError());
+    }
+    std::vector<unsigned long long> out((size_t)n_bins + 1);
+    SS_HIP(ss::l2s::copy(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t b = 0; b < n_bins; b++) hist[b] = out[b];
+    *hits = out[n_bins];
+    return SS_OK;
+}
+
+}  // extern "C"

@@ -95,6 +95,78 @@ def report_mask(masked=None, no_qual=None, bases=None):
     sys.stderr.flush()
 
 
+# --read_support (StrainScan.apply_read_support turns it on): how many reads carry k-mers of each table the run scans.  Rows are
+# collected while the tables are open -- the tree's after the tree scan (TreeImage), a cluster's in cluster_counts /
+# cluster_counts_many -- under the scope of the database at work (strainscan-multi: its label), and written by the command when
+# it ends.  "skipped": why nothing is written (said once on stderr).
+READ_SUPPORT = {"on": False, "scope": None, "rows": {}, "skipped": None}
+READ_SUPPORT_FILE = "read_support.tsv"
+READ_SUPPORT_BINS = 65
+READ_SUPPORT_GE = (1, 2, 4, 8, 16, 32, 64)
+_READ_SUPPORT_LOCK = threading.Lock()
+
+
+def read_support_reset(on=False):
+    READ_SUPPORT.update(on=bool(on), scope=None, rows={}, skipped=None)
+
+
+def read_support_ge(hist):
+    """A 65-bin histogram (hist[b]: records with exactly b hits, hist[64]: 64 and more) -> records with >= 1, 2, 4, ... 64 hits."""
+    h = [int(v) for v in hist]
+    assert len(h) == READ_SUPPORT_BINS
+    return [sum(h[t:]) for t in READ_SUPPORT_GE]
+
+
+def read_support_text(rows):
+    """The text of read_support.tsv for rows of (table, kmers, reads, hits, hist)."""
+    out = ["table\tkmers\treads\thits\t" + "\t".join("ge%d" % t for t in READ_SUPPORT_GE) + "\n"]
+    for table, kmers, reads, hits, hist in rows:
+        out.append("\t".join([table] + [str(int(v)) for v in [kmers, reads, hits] + read_support_ge(hist)]) + "\n")
+    return "".join(out)
+
+
+def _read_support_skip(why):
+    import sys
+    if READ_SUPPORT["skipped"] is None:
+        READ_SUPPORT["skipped"] = why
+        print("read_support: %s and was not computed" % why, file=sys.stderr)
+        sys.stderr.flush()
+
+
+def collect_read_support(table, kdb, paths):
+    """One row of read_support.tsv: the resident reads of `paths` against `kdb` (ReadSet.support), summed over the ranks.  A no-op
+    unless --read_support is on; a table that already has its row under the current scope keeps it.  Every rank calls this at the
+    same point (it holds a collective)."""
+    if not READ_SUPPORT["on"] or READ_SUPPORT["skipped"] is not None:
+        return
+    with _READ_SUPPORT_LOCK:
+        rows = READ_SUPPORT["rows"].setdefault(READ_SUPPORT["scope"], {})
+        if table in rows:
+            return
+        if kdb.k < 17:
+            return _read_support_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % kdb.k)
+        rs = resident_reads(paths)
+        if rs is None:
+            return _read_support_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
+        hist, hits = rs.support(kdb, READ_SUPPORT_BINS)
+        v = np.concatenate([hist.astype(np.int64), np.array([hits, rs.info()["n_records"]], np.int64)])
+        from . import dist
+        if dist.is_distributed():
+            v = dist.allreduce_int64(v)
+        rows[table] = (table, kdb.info()["n_distinct"], int(v[-1]), int(v[-2]), [int(x) for x in v[:-2]])
+
+
+def write_read_support(out_dir, scope=None):
+    """out_dir/read_support.tsv from the rows collected under `scope`; nothing without the flag, without rows, or after a skip."""
+    rows = READ_SUPPORT["rows"].get(scope)
+    if not READ_SUPPORT["on"] or READ_SUPPORT["skipped"] is not None or not rows:
+        return None
+    path = os.path.join(out_dir, READ_SUPPORT_FILE)
+    with open(path, "w") as f:
+        f.write(read_support_text(rows.values()))
+    return path
+
+
 def resident_reads(paths):
     """The sample's reads as flat base blocks in HBM (parsed and copied over PCIe once), or None
     when they would not fit the budget (then every scan streams the files again).  Under

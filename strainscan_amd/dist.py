@@ -59,6 +59,19 @@ def allreduce_counts(t, group=None):
     return t
 
 
+def allreduce_int64(v, group=None):
+    """Sum over the ranks of a short vector of non-negative integers below 2^63 (numpy) -> np.int64 array.  The values travel
+    through allreduce_counts as four 16-bit digits each: an int32 sum of digits cannot wrap with fewer than 32 768 ranks."""
+    import numpy as np
+    import torch
+    v = np.asarray(v, np.int64)
+    digits = np.stack([(v >> s) & 0xFFFF for s in (0, 16, 32, 48)]).astype(np.int32)
+    t = torch.from_numpy(digits).to(device=exchange_device()).contiguous()
+    allreduce_counts(t, group)
+    d = t.to("cpu").numpy().astype(np.int64)
+    return d[0] + (d[1] << 16) + (d[2] << 32) + (d[3] << 48)
+
+
 class _NodeExchange:
     """What exchange_touched needs from a node set: the touched flags out and in, the touched nodes' segments packed
     and unpacked (device pointers; strainscan_amd._lib.NodeSet over ss_nodes_*; tests substitute a numpy double)."""
