@@ -132,6 +132,13 @@ def enet_cv_fit(img, cols, vec, trace=None, split=None):
 
     p = len(cols)
     n = vec.n_keep
+    # what ElasticNetCV.fit raises at :437-442 -- check_array for no row at all, ShuffleSplit(test_size=0.5) for one (its
+    # training half would be empty); without it Q = 0 gives a model of zeros with an error, and no row 0 / 0
+    if n == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=(0, %d)) while a minimum of 1 is required." % p)
+    if n - int(np.ceil(TEST_SIZE * n)) == 0:
+        raise ValueError("With n_samples=%d, test_size=%s and train_size=None, the resulting train set will be empty. "
+                         "Adjust any of the aforementioned parameters." % (n, TEST_SIZE))
     y_dev = vec.ykeep
     fold = None
     if split is not None:                     # started in detect_core: the host walks the word stream, the device does the swaps

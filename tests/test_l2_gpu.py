@@ -856,6 +856,10 @@ def _l2_branch_scenarios(tmp_path, monkeypatch, golden_l2):
     test_detect_strains("three", golden_l2)
     test_detect_strains("many", golden_l2)
     monkeypatch.undo()
+    # no kept row, one kept row: ElasticNetCV's ValueErrors (tests/test_l2_solver_gpu.py)
+    from tests import test_l2_solver_gpu as solver
+    for n_keep in (0, 1):
+        solver.test_enet_cv_fit_refuses_an_empty_training_half(n_keep)
     for name in sc.L2_BATCH_CASES:
         d = tmp_path / ("batch_" + name)
         d.mkdir()
