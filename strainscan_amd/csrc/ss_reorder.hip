@@ -37,21 +37,23 @@
 //
 // THE DRIVER (ss::order_flat_dev) is the sequence of its steps: probe_one_length (the slab's head: is it a candidate for the
 // one-length paths, with which L and n_rec) -> Scratch::take (one block, laid out in one place) -> one of three PATHS:
-//   bin_sorted    one length, the product: NewSlab::alloc, key_fixed, the sort, gather_fixed (packed; again ASCII when a byte
-//                 is outside the alphabet)
+//   bin_sorted    one length, the product: NewSlab::alloc, pack_key_fixed (the one read of the ASCII slab: checks, keys, a packed
+//                 file-order intermediate), the sort, gather_packed; gather_fixed (ASCII, from the source, in the same order) when
+//                 a byte is outside the alphabet; ss_test_hook 5 = 1: key_fixed, the sort, gather_fixed
 //   bin_counted   one length under ss_test_hook 6 = 1: count_fixed, prefix_and_tail, NewSlab::alloc, place_fixed(_packed)
 //   bin_general   ragged records: count, prefix_and_tail, NewSlab::alloc, place (+ place_again for tiles beyond the table)
 // A one-length path that meets a shorter or longer record says "not of one length" and the general passes run.  Every path
 // reports its own three timing figures; the driver stores them, counts the slab and hands the scratch on to the next call.
 //
-// PACKED slabs.  A slab of one-length records whose every byte is A C G T or N (the gather checks the alphabet beside the
+// PACKED slabs.  A slab of one-length records whose every byte is A C G T or N (the pack pass checks the alphabet beside the
 // layout) is placed as 2-bit codes + invalid flags, 3 bytes per 8 positions (ss_scan_dev.h IN_PACKED): 57 bytes per 150-base
 // read instead of 152.  Positions, slots, bins and tiles are those of the ASCII slab; packed group g is exactly encode16 of its
 // bytes [16g, 16g + 16), so every scan kernel sees bit-identical codes and flags, without its encode phase.  The placement is
 // meant to gain from the random sectors its scattered writes touch (~3.3 per record ASCII, ~1.9 packed); it gains less: place
 // 2.06 -> 1.93 ms per 20 M reads (profiles/r07_packed_ab.md: it also encodes, at 6 waves per SIMD, with byte stores at the edges);
-// the sorted path writes the packed slab in order instead (profiles/r08_binning_gather_ab.md).  Any other byte (lower case, IUPAC,
-// '\r'): the gather runs again with ASCII output, in the same order; ragged records, or ss_test_hook 5 = 1: ASCII.
+// the sorted path writes the packed slab in order instead (profiles/r08_binning_gather_ab.md), from records it packed in file order
+// while it keyed them (profiles/r15_binning_pack_ab.md).  Any other byte (lower case, IUPAC, '\r'): the ASCII gather runs, in the same
+// order; ragged records, or ss_test_hook 5 = 1: ASCII.
 #include "ss_common.h"
 
 #include <mutex>
@@ -465,7 +467,7 @@ __global__ __launch_bounds__(256) void place_again_kernel(const char *__restrict
 //   place_fixed   the returning atomicAdd on the bin's cursor is issued first; while it is on its way the lanes load the
 //                 span's pieces (numbered across the wave: consecutive lanes, consecutive 16 bytes); the destination of
 //                 a piece's record comes from the owning lane by a wave shuffle; aligned stores, padded with '\n'
-// These two (and place_fixed_packed) are what ss_test_hook 6 = 1 runs; the product sorts instead (key_fixed, gather_fixed below).
+// These two (and place_fixed_packed) are what ss_test_hook 6 = 1 runs; the product sorts instead (pack_key_fixed, gather_packed below).
 constexpr uint32_t FIX_MIN_L = 32, FIX_MAX_L = 1023;
 
 // non-zero unless every byte of w is 'A' 'C' 'G' 'T' 'N' or '\n' -- upper case only: a packed slab reads back as exactly these
@@ -624,16 +626,30 @@ __global__ __launch_bounds__(256, 6) void place_fixed_packed_kernel(const char *
 // The two passes above pay for random-address atomics (one per record on the bin counters, one returning one on the cursors) and
 // for scattered partial writes.  With every slot of one size, the output position of a record is its RANK in bin order, times the
 // slot: so the records' keys are sorted instead, and the copy reads at random and writes in order.
-//   key_fixed     one lane per record, no atomics: key[i] = its bin (record_bin, from its first 32 bytes), val[i] = i.  A cheap
-//                 check beside it: the byte in front of every record start, and the last record's newline and the padding behind
-//                 it, must be '\n' (what a shorter, longer or empty record shifts); else not_fixed, and the gather does nothing
+// The ASCII slab is read ONCE, in order, by the pass that does everything its bytes are needed for; what is moved at random
+// afterwards is the packed record, one aligned 64-byte sector per 150-base read instead of ~3.4 sectors of ASCII.
+//   pack_key_fixed  a wave owns 64 consecutive SOURCE records, one contiguous span, streamed in 16-byte pieces numbered across the
+//                 wave.  Every piece is CHECKED (a newline at offset L of its record and none before it; only newlines behind the
+//                 last record; A C G T N only), padded with '\n', encoded (encode16) and put into LDS, record r at r Rt
+//                 (R = slot / 8 x 3 bytes packed, 57 for 150 bases; Rt = R rounded up to 16: 64); the wave's nr Rt bytes go out
+//                 as whole aligned 16-byte stores to the file-order INTERMEDIATE at r0 Rt (bytes R .. Rt - 1 of a record are
+//                 never read).  Then every lane keys its own record from its first 32 ASCII bytes (in cache by then): key[i] =
+//                 its bin (record_bin), val[i] = i; no atomics but the flags, set only while still clear (atomics on ONE address
+//                 from every wave queue up for ms).  A wave that finds not_packable set stops encoding and only keys -- a
+//                 lower-case slab costs what key_fixed costs --; one that finds not_fixed set returns
 //   (sort)        hipcub::DeviceRadixSort::SortPairs over the key bits [0, bits + 1): stable, so a bin keeps its records in file
 //                 order and a binned slab is the same byte for byte from run to run
-//   gather_fixed  a wave owns 64 consecutive OUTPUT records; output record j is source record perm[j] at byte j R of the new slab
-//                 (R = slot / 8 x 3 packed: 57 bytes for 150 bases; R = slot ASCII).  The pieces of the wave's records (16 bytes of
-//                 a source record each, numbered across the wave) are loaded, CHECKED (a newline at offset L and none before it;
-//                 packed: A C G T N only), padded with '\n', encoded and put into LDS in output layout; then the wave's span goes
-//                 out as aligned 16-byte stores (rounds of G records, G R a multiple of 16: every round's span starts aligned).
+//   gather_packed a wave owns 64 consecutive OUTPUT records; output record j is record perm[j] of the intermediate: Rt / 16
+//                 aligned 16-byte loads, all of the wave's in flight at once (4 per lane for 150 bases), into LDS at stride Rt;
+//                 the round's span of G R bytes is read back at stride R (dword by dword, alignbyte) and goes out as aligned
+//                 16-byte stores (rounds of G records, G R a multiple of 16: every round's span starts aligned).  No checks, no
+//                 encode; nothing to do once either flag is set
+//   key_fixed     (ss_test_hook 5 = 1: an ASCII slab wanted) one lane per record: key and val as above.  A cheap check beside
+//                 it: the byte in front of every record start, and the last record's newline and the padding behind it, must be
+//                 '\n' (what a shorter, longer or empty record shifts); else not_fixed, and the gather does nothing
+//   gather_fixed  the ASCII gather FROM THE SOURCE, for hook 5 and for a slab with a byte outside the alphabet (same perm): the
+//                 pieces of the wave's 64 output records are loaded at random, CHECKED (a newline at offset L and none before
+//                 it), padded with '\n' and put into LDS in output layout; then the span goes out as aligned 16-byte stores
 __global__ __launch_bounds__(256) void key_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L, int bits,
                                                         uint32_t *__restrict__ key, uint32_t *__restrict__ val,
                                                         unsigned long long *__restrict__ not_fixed)
@@ -652,35 +668,202 @@ __global__ __launch_bounds__(256) void key_fixed_kernel(const char *__restrict__
 }
 
 constexpr uint32_t GX_LDS_PK = 6144, GX_LDS_ASCII = 8192;    // LDS a wave may take: 16 records of the longest slot (1024 positions)
-constexpr int GPK = 3;                      // pieces a lane has in flight (70 VGPRs: seven waves per SIMD, no scratch; more pieces spill)
+constexpr int GPK = 3;                      // pieces a lane of the ASCII gather has in flight (62 VGPRs, no scratch)
+constexpr int PKP = 2;                      // ... of the pack pass (63 VGPRs: eight waves per SIMD, no scratch; 3 pieces: as fast;
+                                            // 4 at six waves: 8 spilled, slower)
+constexpr int GQ = 4;                       // ... of the packed gather: 64 lanes x 4 = the 256 pieces of 64 packed records of 150 bases
 
-// records per round of the gather: G <= 64, G R a multiple of 16 and within the wave's LDS (the launch takes 4 G R bytes)
+// bytes of a packed record (3 per 8 positions), and its stride in the file-order intermediate: whole 16-byte pieces
+__host__ __device__ __forceinline__ uint32_t packed_row(uint32_t slot) { return slot / 8u * 3u; }
+__host__ __device__ __forceinline__ uint32_t packed_stride(uint32_t slot) { return (packed_row(slot) + 15u) & ~15u; }
+
+// records per round of a gather: G <= 64, G R a multiple of 16 (every round's span starts aligned) and at most lim bytes.  The
+// ASCII gather's LDS is those G R bytes per wave; the packed gather holds the round at stride Rt <= R + 15, G Rt + 16 bytes per
+// wave (7.1 KB at most, 28.5 KB per workgroup)
 inline uint32_t gather_rows(bool pk, uint32_t L)
 {
-    const uint32_t slot = slot_of(L), R = pk ? slot / 8u * 3u : slot, lim = pk ? GX_LDS_PK : GX_LDS_ASCII;
+    const uint32_t slot = slot_of(L), R = pk ? packed_row(slot) : slot, lim = pk ? GX_LDS_PK : GX_LDS_ASCII;
     uint32_t G = 64;
     while (G > 1 && (G * R > lim || (G * R) % 16u)) G--;
     return G;
 }
+// records per round of the pack pass: G Rt within the wave's LDS (Rt is a multiple of 16 already)
+inline uint32_t pack_rows(uint32_t L) { return std::min<uint32_t>(64u, GX_LDS_PK / packed_stride(slot_of(L))); }
 
-template <bool PK>
-__global__ __launch_bounds__(256, 7) void gather_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L,
+// 16 aligned bytes that are touched once -- the intermediate's 1.28 GB per 20 M reads, written, read back at random, and the
+// new slab's 1.14 GB: marked non-temporal, they do not push what is still to be read out of the caches (pack + key + sort 1.73 ->
+// 1.53 ms, packed gather + tail 0.75 -> 0.70 ms per 20 M reads of 150 bases; the same mark on the pack pass's reads of the source
+// costs 0.3 ms: profiles/r15_binning_pack_ab.md)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 load16_once(const void *p)
+{
+    const u32x4 x = __builtin_nontemporal_load(static_cast<const u32x4 *>(__builtin_assume_aligned(p, 16)));
+    return make_uint4(x.x, x.y, x.z, x.w);
+}
+__device__ __forceinline__ void store16_once(void *p, const uint4 v)
+{
+    const u32x4 x = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(x, static_cast<u32x4 *>(__builtin_assume_aligned(p, 16)));
+}
+
+// the pack + key pass: see "records of one length, SORTED" above.  A wave that sees not_packable set only keys (and checks the
+// padding behind the last record: the ASCII gather checks every record, not what follows them); one that sees not_fixed returns.
+// Bytes R .. Rt - 1 of a record are indeterminate by design: nobody writes them in LDS, they travel to the intermediate and into
+// the gather's LDS as they are, and the gather's read at stride R never takes them (its `keep` mask and the record's wrap).
+__global__ __launch_bounds__(256, 8) void pack_key_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L, uint32_t P,
+                                                                uint32_t magic_p, uint32_t G, int bits, uint32_t *__restrict__ key,
+                                                                uint32_t *__restrict__ val, uint8_t *__restrict__ inter,
+                                                                unsigned long long *__restrict__ not_fixed, unsigned long long *__restrict__ not_packable)
+{
+    extern __shared__ uint4 gx_lds[];       // 4 waves x G Rt bytes
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave) * 64u;
+    if (r0 >= n_rec || __ballot(*(volatile unsigned long long *)not_fixed != 0ull)) return;
+    const bool pack = __ballot(*(volatile unsigned long long *)not_packable != 0ull) == 0ull;
+    const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), slot = slot_of(L), Rt = packed_stride(slot);
+    const uint64_t base = r0 * L1;
+    uint4 *W = gx_lds + (size_t)wave * (G * Rt / 16u);
+    uint8_t *W8 = reinterpret_cast<uint8_t *>(W);
+    bool bad = false;
+    uint32_t alpha = 0;
+    for (uint32_t c0 = 0; pack && c0 < nr; c0 += G) {
+        const uint32_t nc = min(G, nr - c0), total = nc * P;
+        for (uint32_t p0 = 0; p0 < total; p0 += 64u * PKP) {
+            uint4 v[PKP];                                                  // (piece, record and offset are worked out twice: registers)
+#pragma unroll
+            for (int r = 0; r < PKP; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
+                v[r] = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
+                if (p < total && L >= off) v[r] = load16_clamped(b, base + (uint64_t)(c0 + rec) * L1 + off, n);      // (the piece of byte L is
+                                                                    // loaded too; bytes behind byte L < n are neither checked nor kept)
+            }
+#pragma unroll
+            for (int r = 0; r < PKP; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(__umulhi(p, magic_p), nc - 1u), off = (p - rec * P) * 16u;
+                if (p >= total) continue;
+                uint32_t w[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+                if (L >= off) {                                             // a newline at byte L, none before it
+                    const uint32_t m = nl_mask16(v[r]), e = L - off;
+                    const uint32_t want = e < 16u ? 1u << e : 0u, valid = e < 16u ? (2u << e) - 1u : 0xFFFFu;
+                    bad |= ((m ^ want) & valid) != 0u;
+                }
+                pad_piece(w, L, off);
+                alpha |= not_packable4(w[0]) | not_packable4(w[1]) | not_packable4(w[2]) | not_packable4(w[3]);
+                uint32_t code, inv;
+                ss::dev::encode16(w, code, inv);
+                // the group's 6 bytes: code[0..15] inv[0..7] code[16..31] inv[8..15] (2-byte aligned in LDS); the last piece of a
+                // slot of 8 x odd positions has only its first 3 (the byte behind them is one of R .. Rt - 1: never read)
+                uint16_t *q = reinterpret_cast<uint16_t *>(W8 + rec * Rt + (off >> 4) * 6u);
+                q[0] = (uint16_t)code;
+                q[1] = (uint16_t)((inv & 0xFFu) | ((code >> 8) & 0xFF00u));
+                if (off + 16u <= slot) q[2] = (uint16_t)((code >> 24) | (inv & 0xFF00u));
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // the round's records: nc Rt bytes at (r0 + c0) Rt of the intermediate, whole aligned 16-byte stores
+        uint8_t *out = inter + (r0 + c0) * Rt;
+        for (uint32_t q = (uint32_t)lane * 16u; q < nc * Rt; q += 1024u) store16_once(out + q, W[q >> 4]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // (the next round's LDS writes come behind these reads)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (r0 + nr == n_rec) {                                                // behind the last record: newlines only (padding)
+        for (uint64_t i = base + (uint64_t)nr * L1 + (uint32_t)lane; i < n; i += 64) bad |= b[i] != '\n';
+    }
+    if (__ballot(bad)) { if (lane == 0 && !*(volatile unsigned long long *)not_fixed) atomicOr(not_fixed, 1ull); return; }
+    if (__ballot(alpha != 0u) && lane == 0 && !*(volatile unsigned long long *)not_packable) atomicOr(not_packable, 1ull);
+    if ((uint32_t)lane < nr) {
+        key[r0 + lane] = record_bin(b, base + (uint64_t)lane * L1, L, bits);      // (from the ASCII bytes, in cache by now; s + 32 <= s + L + 1 <= n)
+        val[r0 + lane] = (uint32_t)(r0 + lane);
+    }
+}
+
+// the packed gather: output record j of the wave is record perm[r0 + j] of the intermediate, Rt / 16 aligned pieces; they land in
+// LDS at stride Rt (piece p of the round at W[p]) and the round's span is read back at stride R, dword by dword
+__global__ __launch_bounds__(256, 8) void gather_packed_kernel(const uint8_t *__restrict__ inter, uint64_t n_rec, uint32_t R, uint32_t magic_r,
+                                                               uint32_t Q, uint32_t magic_q, uint32_t G, const uint32_t *__restrict__ perm,
+                                                               uint8_t *__restrict__ dst, const unsigned long long *__restrict__ not_fixed,
+                                                               const unsigned long long *__restrict__ not_packable)
+{
+    extern __shared__ uint4 gx_lds[];       // 4 waves x (G Rt + 16) bytes (+16: the second dword of the last record's last read)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave) * 64u;
+    // nothing to do once the slab is known not to be of one length, or not packable: the general passes, or the ASCII gather, come next
+    if (r0 >= n_rec || *(volatile const unsigned long long *)not_fixed || *(volatile const unsigned long long *)not_packable) return;
+    const uint32_t nr = (uint32_t)min((uint64_t)64, n_rec - r0), Rt = Q * 16u;
+    uint4 *W = gx_lds + (size_t)wave * (G * Q + 1u);
+    const uint32_t *W32 = reinterpret_cast<const uint32_t *>(W);
+    const uint8_t *W8 = reinterpret_cast<const uint8_t *>(W);
+    const uint32_t mine = (uint32_t)lane < nr ? min(perm[r0 + lane], (uint32_t)(n_rec - 1u)) : 0u;      // source of the wave's output record `lane`
+    for (uint32_t c0 = 0; c0 < nr; c0 += G) {
+        const uint32_t nc = min(G, nr - c0), total = nc * Q;
+        for (uint32_t p0 = 0; p0 < total; p0 += 64u * GQ) {                 // (uniform trip count: every lane takes part in the shuffles;
+            uint4 v[GQ];                                                    // Q = 1 has no 32-bit reciprocal)
+#pragma unroll
+            for (int r = 0; r < GQ; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r, rec = min(Q == 1u ? p : __umulhi(p, magic_q), nc - 1u), k = p - rec * Q;
+                const uint32_t s = (uint32_t)__shfl((int)mine, (int)(c0 + rec), 64);
+                v[r] = make_uint4(0u, 0u, 0u, 0u);
+                if (p < total) v[r] = load16_once(inter + (uint64_t)s * Rt + k * 16u);
+            }
+#pragma unroll
+            for (int r = 0; r < GQ; r++) {
+                const uint32_t p = p0 + (uint32_t)lane + 64u * r;
+                if (p < total) W[p] = v[r];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // the round's span: nc R bytes at (r0 + c0) R -- 16-byte aligned, whole 16-byte stores but at the slab's very end
+        const uint32_t span = nc * R;
+        uint8_t *out = dst + (r0 + c0) * R;
+        for (uint32_t q = (uint32_t)lane * 16u; q < span; q += 1024u) {
+            uint32_t rec = __umulhi(q, magic_r), o = q - rec * R;           // span byte q = byte o of the round's record rec
+            if (q + 16u <= span) {
+                uint32_t w[4];
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    const uint32_t x = rec * Rt + o;
+                    w[d] = __builtin_amdgcn_alignbyte(W32[(x >> 2) + 1u], W32[x >> 2], x & 3u);
+                    if (o + 4u > R) {                                       // the record's last 1 to 3 bytes, then the next record's first
+                        const uint32_t keep = 8u * (R - o);                 // (R >= 15: a dword touches two records at most)
+                        w[d] = (w[d] & ((1u << keep) - 1u)) | (W32[((rec + 1u) * Rt) >> 2] << keep);
+                    }
+                    o += 4u;
+                    if (o >= R) { o -= R; rec++; }
+                }
+                store16_once(out + q, make_uint4(w[0], w[1], w[2], w[3]));
+            } else {
+                for (uint32_t k = q; k < span; k++) {
+                    out[k] = W8[rec * Rt + o];
+                    if (++o == R) { o = 0; rec++; }
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // (the next round's LDS writes come behind these reads)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+// the ASCII gather, from the source: hook 5, or a slab with a byte outside the alphabet
+__global__ __launch_bounds__(256, 8) void gather_fixed_kernel(const char *__restrict__ b, uint64_t n, uint64_t n_rec, uint32_t L,
                                                               uint32_t P, uint32_t magic_p, uint32_t G, const uint32_t *__restrict__ perm,
-                                                              uint8_t *__restrict__ dst, unsigned long long *__restrict__ not_fixed,
-                                                              unsigned long long *__restrict__ not_packable)
+                                                              uint8_t *__restrict__ dst, unsigned long long *__restrict__ not_fixed)
 {
     extern __shared__ uint4 gx_lds[];       // 4 waves x G R bytes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave) * 64u;
-    // nothing to do once the slab is known not to be of one length, or (packed) not packable: the general passes, or the ASCII
-    // gather -- which checks the layout again -- come next
-    if (r0 >= n_rec || *(volatile unsigned long long *)not_fixed || (PK && *(volatile unsigned long long *)not_packable)) return;
-    const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), slot = slot_of(L), R = PK ? slot / 8u * 3u : slot;
+    // nothing to do once the slab is known not to be of one length: the general passes come next
+    if (r0 >= n_rec || *(volatile unsigned long long *)not_fixed) return;
+    const uint32_t L1 = L + 1u, nr = (uint32_t)min((uint64_t)64, n_rec - r0), slot = slot_of(L), R = slot;
     uint4 *W = gx_lds + (size_t)wave * (G * R / 16u);
     uint8_t *W8 = reinterpret_cast<uint8_t *>(W);
     const uint32_t mine = (uint32_t)lane < nr ? perm[r0 + lane] : 0u;      // source of the wave's output record `lane`
     bool bad = false;
-    uint32_t alpha = 0;
     for (uint32_t c0 = 0; c0 < nr; c0 += G) {
         const uint32_t nc = min(G, nr - c0), total = nc * P;
         for (uint32_t p0 = 0; p0 < total; p0 += 64u * GPK) {                // (uniform trip count: every lane takes part in the shuffles)
@@ -703,29 +886,10 @@ __global__ __launch_bounds__(256, 7) void gather_fixed_kernel(const char *__rest
                     const uint32_t want = e < 16u ? 1u << e : 0u, valid = e < 16u ? (2u << e) - 1u : 0xFFFFu;
                     bad |= ((m ^ want) & valid) != 0u;
                 }
-                const int keep = (int)min(16u, L > off ? L - off : 0u);      // record bytes in this piece, '\n' behind them (pad_piece,
-                if (keep < 16) {                                             // written out: the helper costs this kernel two SGPRs)
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        const int k = keep - 4 * d;
-                        if (k <= 0) w[d] = 0x0A0A0A0Au;
-                        else if (k < 4) { const uint32_t mk = (1u << (8 * k)) - 1u; w[d] = (w[d] & mk) | (0x0A0A0A0Au & ~mk); }
-                    }
-                }
-                if (PK) {
-                    alpha |= not_packable4(w[0]) | not_packable4(w[1]) | not_packable4(w[2]) | not_packable4(w[3]);
-                    uint32_t code, inv;
-                    ss::dev::encode16(w, code, inv);
-                    // the group's 6 bytes: code[0..15] inv[0..7] code[16..31] inv[8..15]; the last piece of a slot of 8 x odd
-                    // positions has only its first 3 (the next record's bytes follow)
-                    uint8_t *q = W8 + rec * R + (off >> 4) * 6u;
-                    q[0] = (uint8_t)code; q[1] = (uint8_t)(code >> 8); q[2] = (uint8_t)inv;
-                    if (off + 16u <= slot) { q[3] = (uint8_t)(code >> 16); q[4] = (uint8_t)(code >> 24); q[5] = (uint8_t)(inv >> 8); }
-                } else {
-                    uint64_t *q = reinterpret_cast<uint64_t *>(W8 + rec * R + off);      // (8-byte aligned: slots are multiples of 8)
-                    q[0] = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-                    if (off + 16u <= slot) q[1] = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-                }
+                pad_piece(w, L, off);
+                uint64_t *q = reinterpret_cast<uint64_t *>(W8 + rec * R + off);      // (8-byte aligned: slots are multiples of 8)
+                q[0] = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+                if (off + 16u <= slot) q[1] = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -743,7 +907,6 @@ __global__ __launch_bounds__(256, 7) void gather_fixed_kernel(const char *__rest
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     if (__ballot(bad) && lane == 0 && !*(volatile unsigned long long *)not_fixed) atomicOr(not_fixed, 1ull);
-    if (PK && __ballot(alpha != 0u) && lane == 0 && !*(volatile unsigned long long *)not_packable) atomicOr(not_packable, 1ull);
 }
 
 // ---- exclusive prefix over the bin sizes (up to 4 M of them): block sums, their prefix, local prefixes ----------------------
@@ -895,9 +1058,33 @@ hipError_t probe_one_length(const char *src, uint64_t n, OneLength *one)
     return hipSuccess;
 }
 
+// The file-order intermediate of the sorted path (pack_key_fixed_kernel writes it, gather_packed_kernel reads it): n_rec records
+// at stride Rt.  A large packed slab takes a block of its ASCII size (NewSlab::get_block) and uses 3/8 of it: the intermediate
+// lives in the unused tail of that block when it fits (150 bases: 1.14 + 1.28 GB in 3.04 GB), else -- every slab below
+// BIG_KEEP_MIN, and the few lengths whose Rt is more than 5/8 of the slot (slot 48: R = 18, Rt = 32) -- in the call's scratch
+// (which, grown for a large slab, is not kept for the next call); no intermediate under ss_test_hook 5 = 1.
+// A function of n_rec and L alone, worked out here and nowhere else, before anything is allocated.
+inline uint64_t slab_positions(uint64_t total) { return std::max<uint64_t>((total + 15) & ~15ull, 16); }
+inline uint64_t packed_block_bytes(uint64_t cap) { return std::max<uint64_t>(ss::dev::in_bytes(true, cap) + 8, cap >= ss::BIG_KEEP_MIN ? cap : 0); }
+struct PackPlan {
+    uint64_t bytes = 0, slab_off = 0;          // of the intermediate; where it begins in the new slab's block (in_slab)
+    bool in_slab = false, large = false;       // large: the slab takes a kept block (BIG_KEEP_MIN and more)
+    uint64_t scratch_bytes() const { return in_slab ? 0 : bytes; }
+    explicit PackPlan(const OneLength &one)
+    {
+        if (!one.L) return;
+        const uint64_t cap = slab_positions(one.n_rec * ::slot_of(one.L));
+        bytes = one.n_rec * packed_stride(::slot_of(one.L));
+        slab_off = (ss::dev::in_bytes(true, cap) + 8 + 255) & ~255ull;
+        in_slab = slab_off + bytes <= packed_block_bytes(cap);
+        large = cap >= ss::BIG_KEEP_MIN;
+    }
+};
+
 // The scratch of a call, one allocation: bin sizes / cursors + the three tail words, block sums of the prefix, per-tile record
 // counts, and a region that is the record table of the general passes, or the 4-byte bins of the count + atomic placement, or
-// the sort's keys, values (twice each) and temporary storage -- sized for whichever of those the call may come to use.
+// the sort's keys, values (twice each) and temporary storage, and behind them the file-order intermediate where the new slab's
+// block does not hold it (PackPlan) -- sized for whichever of those the call may come to use.
 // The scratch of the call before is kept (0.35 GB for 20 M reads: two driver calls fewer per sample); keep() hands the larger
 // of the two blocks on to the next call.  A call that fails frees its block.
 class Scratch : Owner {
@@ -905,7 +1092,7 @@ public:
     struct Sort { uint32_t *k0, *k1, *v0, *v1; void *temp; size_t temp_bytes; };
     ~Scratch() { if (d_) hipFree(d_); }
 
-    hipError_t take(const Call &c, const OneLength &one, bool for_sort)
+    hipError_t take(const Call &c, const OneLength &one, bool for_sort, uint64_t inter_bytes, bool inter_of_large_slab)
     {
         n_bins_ = c.n_bins;
         if (for_sort) {
@@ -917,7 +1104,11 @@ public:
         o_sums_ = ((uint64_t)c.n_bins + 3) * 8;
         o_cnt_ = o_sums_ + ((uint64_t)c.nsb + 1) * 8;
         o_region_ = (o_cnt_ + (uint64_t)c.nb * 4 + 255) & ~255ull;
-        const uint64_t bytes = o_region_ + std::max<uint64_t>((uint64_t)c.nb * TCAP * 8, for_sort ? 4 * a4_ + ((sort_tb_ + 255) & ~255ull) : a4_);
+        o_inter_ = o_region_ + 4 * a4_ + ((sort_tb_ + 255) & ~255ull);
+        const uint64_t bytes = std::max<uint64_t>(o_region_ + std::max<uint64_t>((uint64_t)c.nb * TCAP * 8, a4_), for_sort ? o_inter_ + inter_bytes : 0);
+        // a LARGE slab's intermediate that does not fit its block (PackPlan) makes this block 0.64 GB per 20 M reads, for one call:
+        // it is not handed on (a slab below BIG_KEEP_MIN adds 171 MB at most, to a block that is kept as before)
+        transient_ = for_sort && inter_bytes && inter_of_large_slab;
         {
             std::lock_guard<std::mutex> g(g_scr_mu);
             if (g_scr && g_scr_cap >= bytes) { d_ = g_scr; cap_ = g_scr_cap; g_scr = nullptr; g_scr_cap = 0; }
@@ -928,7 +1119,7 @@ public:
     }
     void keep()
     {
-        {
+        if (!transient_) {
             std::lock_guard<std::mutex> g(g_scr_mu);
             if (!g_scr || g_scr_cap < cap_) { std::swap(g_scr, d_); std::swap(g_scr_cap, cap_); }
         }
@@ -948,12 +1139,14 @@ public:
         uint32_t *a = (uint32_t *)(d_ + o_region_);
         return Sort{a, a + a4_ / 4, a + 2 * (a4_ / 4), a + 3 * (a4_ / 4), d_ + o_region_ + 4 * a4_, sort_tb_};
     }
+    uint8_t *intermediate() const { return (uint8_t *)(d_ + o_inter_); }               // (a sorting call whose plan is not in_slab)
 
 private:
     char *d_ = nullptr;
-    uint64_t cap_ = 0, o_sums_ = 0, o_cnt_ = 0, o_region_ = 0, a4_ = 0;       // a4_: one per-record array of 4-byte entries
+    uint64_t cap_ = 0, o_sums_ = 0, o_cnt_ = 0, o_region_ = 0, o_inter_ = 0, a4_ = 0;       // a4_: one per-record array of 4-byte entries
     uint32_t n_bins_ = 0;
     size_t sort_tb_ = 0;
+    bool transient_ = false;
 };
 
 // The new slab: `total` positions of records, `cap` positions in all (a multiple of 16), in a block of real_cap bytes (a kept
@@ -968,7 +1161,7 @@ struct NewSlab : Owner {
     hipError_t alloc(const Call &c, bool pk, uint64_t total_)
     {
         total = total_; packed = pk;
-        cap = std::max<uint64_t>((total + 15) & ~15ull, 16);
+        cap = slab_positions(total);
         const hipError_t e = get_block();
         t_alloc = Clock::now();
         c.lap("new slab");
@@ -1003,10 +1196,11 @@ private:
     // packed: 6 bytes per 16 positions, and 8 bytes behind them that the scans' 8-byte loads may touch (IN_PACKED).  A slab whose
     // ASCII form would be a block the process keeps (ss::big_put) still takes a block of that size: destroyed, it goes back to
     // the kept blocks and must serve what comes next -- the next sample's file-order slab, or its binning -- which a block of the
-    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones.
+    // packed size cannot (a fresh 3 GB from the driver: ~60 ms against 0.02).  The bytes written and scanned are the packed ones;
+    // the sorted path keeps its file-order intermediate in the rest while it runs (PackPlan).
     hipError_t get_block()
     {
-        const uint64_t bytes = packed ? std::max<uint64_t>(ss::dev::in_bytes(true, cap) + 8, cap >= ss::BIG_KEEP_MIN ? cap : 0) : cap;
+        const uint64_t bytes = packed ? packed_block_bytes(cap) : cap;
         return ss::big_malloc((void **)&d, bytes, &real_cap);
     }
 };
@@ -1037,40 +1231,55 @@ hipError_t finish_counted(const Call &c, Clock::time_point t_counted, const NewS
 }
 
 // One length, sorted: the new slab's size is known before anything runs (n_rec slots), so its block is taken first, and the
-// flags are read once, after the gather.  Figures: key + sort (on the device), allocation (from the call's start), gather +
+// flags are read once, after the gather.  Packed slab wanted: pack + key, sort, packed gather; a byte outside the alphabet (seen
+// by the pack pass): the ASCII gather from the source, in the same order, and a second look at the layout flag.  ss_test_hook
+// 5 = 1: key, sort, ASCII gather.  Figures: pack / key + sort (on the device), allocation (from the call's start), gather +
 // tail -- the first and the last add up to the kernels' wall time.
-Binned bin_sorted(const Call &c, const OneLength &one, const Scratch &scr, NewSlab &slab, double ms[3])
+Binned bin_sorted(const Call &c, const OneLength &one, bool want_packed, const PackPlan &plan, const Scratch &scr, NewSlab &slab, double ms[3])
 {
-    const uint32_t slot = ::slot_of(one.L), P = (slot + 15u) >> 4;
+    const uint32_t slot = ::slot_of(one.L), P = (slot + 15u) >> 4, magic_p = (uint32_t)(((1ull << 32) + P - 1) / P);
     const unsigned nbf = (unsigned)((one.n_rec + 255) / 256);
-    SS_R(slab.alloc(c, g_hook_ascii_slabs.load() == 0, one.n_rec * slot));
+    SS_R(slab.alloc(c, want_packed, one.n_rec * slot));
     const Scratch::Sort s = scr.sort();
     unsigned long long *flags = scr.tail();
     EventPair t;
     SS_R(t.create());
-    auto gather = [&](const uint32_t *perm) {
-        const uint32_t G = gather_rows(slab.packed, one.L), R = slab.packed ? slot / 8u * 3u : slot;
-        auto kern = slab.packed ? gather_fixed_kernel<true> : gather_fixed_kernel<false>;
-        hipLaunchKernelGGL(kern, dim3(nbf), dim3(256), 4u * G * R, 0, c.src, c.n, one.n_rec, one.L, P, (uint32_t)(((1ull << 32) + P - 1) / P), G,
-                           perm, (uint8_t *)slab.d, flags + T_FLAG, flags + T_ALPHA);
+    auto gather_ascii = [&](const uint32_t *perm) {
+        const uint32_t G = gather_rows(false, one.L);
+        hipLaunchKernelGGL(gather_fixed_kernel, dim3(nbf), dim3(256), 4u * G * slot, 0, c.src, c.n, one.n_rec, one.L, P, magic_p, G, perm,
+                           (uint8_t *)slab.d, flags + T_FLAG);
     };
+    const bool packing = slab.packed;
+    uint8_t *inter = !packing ? nullptr : plan.in_slab ? (uint8_t *)slab.d + plan.slab_off : scr.intermediate();
     unsigned long long tail[3] = {0, 0, 0};
     SS_R(hipMemsetAsync(flags, 0, 24, 0));
     SS_R(hipEventRecord(t.ev[0], 0));
-    hipLaunchKernelGGL(key_fixed_kernel, dim3(nbf), dim3(256), 0, 0, c.src, c.n, one.n_rec, one.L, c.bits, s.k0, s.v0, flags + T_FLAG);
+    if (packing) {
+        const uint32_t G = pack_rows(one.L);
+        hipLaunchKernelGGL(pack_key_fixed_kernel, dim3(nbf), dim3(256), 4u * G * packed_stride(slot), 0, c.src, c.n, one.n_rec, one.L, P, magic_p, G,
+                           c.bits, s.k0, s.v0, inter, flags + T_FLAG, flags + T_ALPHA);
+    } else {
+        hipLaunchKernelGGL(key_fixed_kernel, dim3(nbf), dim3(256), 0, 0, c.src, c.n, one.n_rec, one.L, c.bits, s.k0, s.v0, flags + T_FLAG);
+    }
     hipcub::DoubleBuffer<uint32_t> dk(s.k0, s.k1), dv(s.v0, s.v1);
     size_t temp_bytes = s.temp_bytes;
     SS_R(hipcub::DeviceRadixSort::SortPairs(s.temp, temp_bytes, dk, dv, (int)one.n_rec, 0, c.bits + 1, 0));
     SS_R(hipEventRecord(t.ev[1], 0));
     const uint32_t *perm = dv.Current();
-    gather(perm);
+    if (packing) {
+        const uint32_t G = gather_rows(true, one.L), R = packed_row(slot), Q = packed_stride(slot) / 16u;
+        hipLaunchKernelGGL(gather_packed_kernel, dim3(nbf), dim3(256), 4u * (G * Q + 1u) * 16u, 0, inter, one.n_rec, R, (uint32_t)(((1ull << 32) + R - 1) / R),
+                           Q, (uint32_t)(((1ull << 32) + Q - 1) / Q), G, perm, (uint8_t *)slab.d, flags + T_FLAG, flags + T_ALPHA);
+    } else {
+        gather_ascii(perm);
+    }
     SS_R(slab.fill_tail());
     SS_R(hipMemcpy(tail + T_FLAG, flags + T_FLAG, 16, hipMemcpyDeviceToHost));
-    if (tail[T_FLAG] == 0 && slab.packed && tail[T_ALPHA]) {        // a byte other than A C G T N: the same order, ASCII
+    if (tail[T_FLAG] == 0 && packing && tail[T_ALPHA]) {            // a byte other than A C G T N: the same order, ASCII
         SS_R(slab.make_ascii());
-        gather(perm);
+        gather_ascii(perm);
         SS_R(slab.fill_tail());
-        // (the packed gather's waves stop once the slab is known not packable: the layout is checked by the ASCII one)
+        // (the pack pass's waves stop checking once the slab is known not packable: the layout is checked by the ASCII gather)
         SS_R(hipMemcpy(tail + T_FLAG, flags + T_FLAG, 8, hipMemcpyDeviceToHost));
     }
     SS_R(hipGetLastError());
@@ -1143,12 +1352,14 @@ int order_flat_dev(const char *src, uint64_t n, ss_reads::Slab *out)
     if (!hip_ok(probe_one_length(src, n, &one), "hipMemcpy", __LINE__)) return SS_EHIP;
     // the sorted one-length path (ss_test_hook 6 = 1: the count + atomic placement instead); hipcub counts its items in an int
     const bool sorted = one.L && g_hook_atomic_binning.load() == 0 && one.n_rec < (1ull << 31);
+    const bool want_packed = g_hook_ascii_slabs.load() == 0;       // (ss_test_hook 5 = 1: no pack pass, no intermediate)
+    const PackPlan plan(one);
     Scratch scr;
-    if (!hip_ok(scr.take(c, one, sorted), "Scratch::take", __LINE__)) return SS_EHIP;
+    if (!hip_ok(scr.take(c, one, sorted, sorted && want_packed ? plan.scratch_bytes() : 0, plan.large), "Scratch::take", __LINE__)) return SS_EHIP;
     NewSlab slab;
     double ms[3] = {0, 0, 0};
     Binned r = Binned::not_one_length;
-    if (one.L) r = sorted ? bin_sorted(c, one, scr, slab, ms) : bin_counted(c, one, scr, slab, ms);
+    if (one.L) r = sorted ? bin_sorted(c, one, want_packed, plan, scr, slab, ms) : bin_counted(c, one, scr, slab, ms);
     const bool fixed = r == Binned::done;
     if (r == Binned::not_one_length) r = bin_general(c, scr, slab, ms);
     if (r != Binned::done) return SS_EHIP;
@@ -1190,12 +1401,12 @@ void reorder_release()
     if (d) hipFree(d);
 }
 
-// Policy: ALWAYS, unless SS_READS_ORDER=file.  Binning 20 M one-length reads costs ~2.5 ms of kernel time once per sample
-// (sorted path; ragged reads ~3.6); a tree scan of
+// Policy: ALWAYS, unless SS_READS_ORDER=file.  Binning 20 M one-length reads costs ~2.2 ms of kernel time once per sample
+// (sorted path: pack + key 1.0, sort 0.5, packed gather 0.7; ragged reads ~3.6); a tree scan of
 // the binned set is 1.8 ms faster than in file order on sampled node sets (5.6 -> 3.8 ms), 0.7 ms on contiguous ones, a
 // cluster scan 6 ms (16.8 -> 10.6: the hits of a locus' reads are added up in LDS).  So it pays from the SECOND scan of a sample
 // on -- the tree scan + one cluster's scan, or the two scans of -b -- and a sample that is scanned exactly once (every
-// identified cluster single-strain) loses ~0.7 ms per 20 M one-length reads, beside ~80 ms of text ingest for the same reads.  The
+// identified cluster single-strain) loses ~0.4 ms per 20 M one-length reads, beside ~80 ms of text ingest for the same reads.  The
 // loader cannot know which it will be: the clusters are identified by the first scan.
 bool reads_order_wanted()
 {
