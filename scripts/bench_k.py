@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cluster-table scans at k != 31 (`-k`, StrainScan.py:136,266-271; Vote_Strain_L2_Lasso_new_sp.py:359-371): the minimizer-paged
-index (ss_mini.hip) serves 17 <= k <= 31 (k = 31 through the tuned kernel, the others through scan_minik_kernel; round 6), the flat
+index (ss_mini.hip) serves 17 <= k <= 31 (k = 31 through the tuned kernel, the others through scan_minik_kernel of ss_minik.hip; round 6), the flat
 open-address table (ss_scan.hip) what is below -- and every k under SS_LAYOUT=flat (the A/B leg).
     bench_k.py [rows] [reads]      -> one JSON line per k: index build time from a k-mer FASTA, scan kernel time, reads/s
 Table: `rows` k-mers cut from random genomes (every 20th position, both orientations as the builder writes them);

@@ -1,6 +1,6 @@
 // ss_build_dev.hip -- the minimizer-paged index of ss_mini.hip built ON THE DEVICE.
 //
-// The host build (ss_mini.hip build_mini: minimizers, partition + sort, buckets + items, page placement) takes ~0.9 s for
+// The host build (ss_mini_build.hip build_mini: minimizers, partition + sort, buckets + items, page placement) takes ~0.9 s for
 // the 25 M rows of an E. coli tree on the 16 CPUs a GPU box grants -- most of the first call on a new database (the
 // image is cached afterwards, strainscan_amd/db.py).  The same index, byte for byte (tests hash the exported images of
 // both builds), from sorts, prefix sums and a handful of streaming kernels:
@@ -424,7 +424,7 @@ int build_mini_dev(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64
         bool ok = n_spill <= SPILL_CAP;
         if (ok && n_spill) {
             // the items that left their partition's pages: placed serially, in item order, at or behind the next partition's
-            // first page (or their home page if that lies further on) -- ss_mini.hip's spill pass
+            // first page (or their home page if that lies further on) -- ss_mini_build.hip's spill pass
             std::vector<uint32_t> sp(n_spill), sh(n_spill);
             std::vector<uint64_t> spos(n_spill);
             ok = hipMemcpy(sp.data(), d_spill, (uint64_t)n_spill * 4, hipMemcpyDeviceToHost) == hipSuccess;

@@ -190,10 +190,11 @@ extern std::atomic<long long> g_hook_atomic_binning;   // ss_test_hook 6 (ss_reo
 void reorder_release();
 void reorder_counters(uint64_t out[2]);      // slabs binned by the one-length passes / by the general ones, in this process
 void reorder_timing(double out[3]);      // the last binning call (ms): key + sort, slab allocation, gather + tail (the sorted one-length path); else count + prefix, slab allocation, place      // the binning scratch kept between calls goes back to the device (ss_gz_gpu_release)
+// the page index built on the host (ss_mini_build.hip), after the device build has had its turn
 int build_mini(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64_t n_rows, int upper_keys);
 // the same index built on the device (ss_build_dev.hip); anything but SS_OK / SS_EKEY: nothing was built, use the host build
 int build_mini_dev(ss_db *db, const uint64_t *keys, const uint8_t *flags, uint64_t n_rows, int upper_keys);
-int mark_solid(ss_db *db);      // PG_SOLID flags of the bucket references, after either build (ss_mini.hip)
+int mark_solid(ss_db *db);      // PG_SOLID flags of the bucket references, after either build (ss_mini_build.hip)
 struct InflatedText { char *p = nullptr; uint64_t n = 0; };
 bool inflate_whole(const char *path, uint64_t budget, char **text, uint64_t *len, int mode, unsigned threads);
 uint64_t inflate_budget_bytes();
@@ -280,7 +281,7 @@ int launch_scan_mini(ss_db *db, const void *bases_dev, uint64_t n, hipStream_t s
                      bool packed = false);
 int launch_scan_mini_multi(ss_db *const *dbs, int n_dbs, const void *bases_dev, uint64_t n, hipStream_t stream, bool binned,
                            bool packed = false);
-// ss_reads_support (ss_support.hip): the lookups of one slab with the per-record sink of scan_minik_kernel (ss_mini.hip).  A found
+// ss_reads_support (ss_support.hip): the lookups of one slab with the per-record sink of scan_minik_kernel (ss_minik.hip).  A found
 // k-mer adds 1 to rec_hits[rec_base + record of its start position]; records at or beyond rec_limit are never written.
 struct SupportArgs {
     uint32_t *rec_hits;             // [rec_limit] hits per record of the set
@@ -289,6 +290,8 @@ struct SupportArgs {
     uint32_t slot;                  // packed slab: positions per record
 };
 int launch_support_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, hipStream_t stream);
+// the scan of one table through the same kernel (ss_minik.hip): launch_scan_mini sends it the tables it does not take itself
+int launch_scan_minik(ss_db *db, const uint8_t *bases_dev, uint64_t n, hipStream_t stream, bool packed);
 // the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster
 // table: the combining variant under binned reads), or none at all.  One launch takes tables of one kind (ss_scan_multi_launches).
 enum { MULTI_BLOOM = 0, MULTI_EXPECT = 1, MULTI_PLAIN = 2 };

@@ -242,7 +242,7 @@ int ss_db_build(const uint64_t *keys, const uint8_t *flags, uint64_t n_rows, int
     db->n_slots = db->capacity;
     if (hipGetDevice(&db->device) != hipSuccess) { delete db; return SS_ENODEV; }
     // layout: minimizer pages for 17 <= k <= 31 (k = 31, the tree scan and the default layer-2 k, through the tuned kernel;
-    // the other k through the one-lane-per-position kernel, ss_mini.hip scan_minik_kernel), flat table below that;
+    // the other k through the one-lane-per-position kernel, ss_minik.hip scan_minik_kernel), flat table below that;
     // SS_LAYOUT=flat overrides for A/B measurements
     const char *lay = getenv("SS_LAYOUT");
     db->layout = (k >= ss::MINI_K_MIN && k <= 31) ? 1 : 0;

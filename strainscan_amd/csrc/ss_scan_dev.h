@@ -1,4 +1,4 @@
-// Device helpers shared by the scan kernels (flat table: ss_scan.hip, minimizer buckets: ss_mini.hip).
+// Device helpers shared by the scan kernels (flat table: ss_scan.hip; page index: ss_mini.hip, ss_minik.hip) and the index builds.
 #pragma once
 #include "ss_common.h"
 #include <stdlib.h>
@@ -45,7 +45,7 @@ __host__ __device__ __forceinline__ uint32_t mix30(uint32_t x)
     return h;
 }
 
-// ---- the page index of ss_mini.hip (built by ss_mini.hip on the host, by ss_build_dev.hip on the device) ----
+// ---- the page index of ss_mini.hip (built by ss_mini_build.hip on the host, by ss_build_dev.hip on the device) ----
 constexpr uint32_t HDR_MULTI = 1u << 17;
 __host__ __device__ __forceinline__ uint32_t page_of(uint32_t h, uint32_t n_pages) { return mulhi32(h << 2, n_pages); }
 constexpr uint32_t PG_SLOTS = 8;                          // slots per 64-byte page
@@ -222,6 +222,19 @@ __device__ __forceinline__ void decode_in(const uint32_t w[4], uint32_t &code, u
         code = __builtin_amdgcn_perm(w[1], w[0], 0x04030100u + w[2]);                 // bytes s, s+1, s+3, s+4
         inv = __builtin_amdgcn_perm(w[1], w[0], 0x0C0C0502u + (w[2] & 0xFFFFu));      // bytes s+2, s+5 (0x0C: zero)
     }
+}
+
+// inclusive prefix sum over the 64 lanes of a wave in the VALU (DPP row shifts + row broadcasts):
+// no LDS round trips (ds_bpermute) on the critical path of every tile (scan_mini_kernel, scan_minik_kernel)
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
+    return v;
 }
 
 // byte offset of position `pos` (a multiple of 16) in a block of the given layout

@@ -9,7 +9,7 @@
 //   1. record_ends_kernel (ASCII slabs only): record ends per 1024-position tile, from the raw bytes -- a record end is a '\n'
 //      behind a byte that is none; a slab that does not end in '\n' ends its last record all the same.  hipcub's ExclusiveSum
 //      turns them into the record index at which every tile begins.  A packed slab needs neither: record = position / slot.
-//   2. scan_minik_kernel<.., SupportSink> (ss_mini.hip): the lookups of the per-position scan kernel, k at run time, all three
+//   2. scan_minik_kernel<.., SupportSink> (ss_minik.hip): the lookups of the per-position scan kernel, k at run time, all three
 //      input layouts, behind the table's Bloom filter where it has one.  A found k-mer sets the bit of its position in a bitmap
 //      of the tile in LDS; the tile's tail adds the bits up per record and issues one atomicAdd per (lane, record) into
 //      rec_hits[] -- about two per lane for 150-base reads, neighbouring lanes on neighbouring words.  Records that straddle
@@ -24,7 +24,7 @@ using namespace ss::dev;
 
 namespace {
 
-constexpr int SUP_TILE = 1024;      // positions per tile: KPOS of scan_minik_kernel (ss_mini.hip), one wave each
+constexpr int SUP_TILE = 1024;      // positions per tile: KPOS of scan_minik_kernel (ss_minik.hip), one wave each
 
 // one wave per tile, 16 bytes per lane; tile_ends[tile] = record ends at positions [tile * 1024, tile * 1024 + 1024) below n, and
 // in the tile of byte n - 1 one more if that byte is not '\n'

@@ -684,3 +684,34 @@ def test_every_environment_variable_is_documented():
     assert read - listed == set(), "read but not documented: %s" % sorted((v, sorted(src[v])) for v in read - listed)
     assert listed - read == set(), "documented but no longer read: %s" % sorted(listed - read)
     assert len(read) <= 45
+
+
+def test_kernel_isa_diff_tool(tmp_path, capsys):
+    """scripts/kernel_isa_diff.py: a file's kernels split over two files, at other function ordinals, compare equal; a changed
+    instruction, a changed descriptor line and a missing kernel do not."""
+    from scripts import kernel_isa_diff as kd
+
+    def kernel(name, ordinal, insn="v_mov_b32_e32 v1, 0", vgprs=14):
+        return ("\t.globl\t%s\n%s:      ; @%s\n; %%bb.0:\n\t%s\n\ts_cbranch_execz .LBB%d_2\n.LBB%d_2:%s; in Loop: Header=BB%d_1\n"
+                "\ts_endpgm\n\t.amdhsa_kernel %s\n\t\t.amdhsa_next_free_vgpr %d\n\t.end_amdhsa_kernel\n.Lfunc_end%d:\n"
+                "\t.set __hip_cuid_%x, 0\n" % (name, name, name, insn, ordinal, ordinal, " " * (8 - len(str(ordinal))), ordinal,
+                                               name, vgprs, ordinal, ordinal))
+
+    def run(old, *new):
+        paths = []
+        for i, text in enumerate((old,) + new):
+            paths.append(str(tmp_path / ("f%d.s" % i)))
+            open(paths[-1], "w").write(text)
+        rc = kd.main(["kernel_isa_diff.py"] + paths)
+        return rc, capsys.readouterr().out
+
+    old = kernel("_Z1av", 0) + kernel("_Z1bv", 11)
+    assert run(old, kernel("_Z1bv", 0), kernel("_Z1av", 3))[0] == 0
+    rc, out = run(old, kernel("_Z1bv", 0), kernel("_Z1av", 3, insn="v_mov_b32_e32 v1, 1"))
+    assert rc == 1 and "differs: _Z1av" in out and "-v_mov_b32_e32 v1, 0" in out
+    rc, out = run(old, kernel("_Z1bv", 0, vgprs=15), kernel("_Z1av", 3))
+    assert rc == 1 and "differs: _Z1bv" in out
+    rc, out = run(old, kernel("_Z1av", 0))
+    assert rc == 1 and "only in OLD: _Z1bv" in out
+    rc, out = run(kernel("_Z1av", 0), old)
+    assert rc == 1 and "only in NEW: _Z1bv" in out

@@ -1131,7 +1131,7 @@ def test_index_image_independent_of_thread_count(L, tmp_path):
 
 @pytest.mark.parametrize("inline_max", ["2", "0", "8"])
 def test_device_index_build_equals_host_build(L, tmp_path, inline_max):
-    """ss_build_dev.hip (the default) and the host build of ss_mini.hip (SS_BUILD=host) must export the SAME image, byte
+    """ss_build_dev.hip (the default) and the host build of ss_mini_build.hip (SS_BUILD=host) must export the SAME image, byte
     for byte: a sampled database (nearly every k-mer alone under its minimizer: inline page slots), a contiguous one
     (nine k-mers per minimizer: buckets, offset masks, the Bloom filter), a FASTA with duplicate rows, lower-case rows,
     rows with N and short rows in the three key modes of the reference's modules (owner rows, row_valid, SS_EKEY), a
