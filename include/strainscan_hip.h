@@ -85,7 +85,7 @@ void ss_gz_free(char *text);
 /* The same text written to out_path (the threaded inflater writes through a shared mapping of the file): the ranks
  * of one node inflate a .gz sample ONCE into /dev/shm and each parses its share of the plain text. */
 int ss_gz_inflate_to_file(const char *path, const char *out_path, int threads, uint64_t *len);
-/* The same on the GPU (ss_ginflate.hip: the two-pass scheme with one wave per chunk of the deflate data, the
+/* The same on the GPU (ss_ginflate.hip, its kernels in ss_ginflate_dev.h: the two-pass scheme with one wave per chunk of the deflate data, the
  * text verified against CRC-32 and ISIZE of the trailer); *text is a host buffer released with ss_gz_free.  SS_ERANGE:
  * not handled on the device (a damaged file, data that expands beyond the symbol budget, ...): use ss_gz_inflate. */
 int ss_gz_inflate_gpu(const char *path, char **text, uint64_t *len);
@@ -95,7 +95,8 @@ int ss_gz_inflate_gpu(const char *path, char **text, uint64_t *len);
 int ss_gz_gpu_counters(uint64_t *handled, uint64_t *declined);
 /* The device inflater keeps its scratch (symbol streams, window maps, the text buffer: ~6-12 GB, at most two sets; its
  * pinned upload buffers) for the next call, the binning of resident reads its 0.2 GB -- large allocations are slow to come
- * by on this platform; this hands all of it back, and the large device blocks kept by ss_dev_big_blocks' stash. */
+ * by on this platform; this hands all of it back, and the large device blocks kept by ss_dev_big_blocks' stash
+ * (ss_gz_scratch.hip). */
 int ss_gz_gpu_release(void);
 /* Device blocks of 256 MB and more that a load is done with -- the text of a large .gz, the file-order slab that binning has
  * replaced, the slabs of a destroyed read set -- are kept (at most three, 24 GB) and handed to the next large request of this
@@ -108,7 +109,7 @@ int ss_dev_big_blocks(uint64_t out[3]);
 int ss_dev_big_release(void);
 /* The pinned upload buffers of n_files (<= 2) concurrent .gz inputs, made ahead of time (~40 ms a set; a command-line process
  * calls this on its warm-up thread): a file of 32 MB or more then travels through them (8 ms instead of 12-30 per 66 MB);
- * without them only files of 256 MB or more make their own. */
+ * without them only files of 256 MB or more make their own (ss_gz_scratch.hip). */
 int ss_gz_warm_up(int n_files);
 /* Who inflates the .gz inputs of the next ss_reads_load / ss_scan_files* calls of this process: 0 (default) the device, and
  * the host inflaters for whatever it declines; 1 the device or NOBODY -- a declined input makes the call return SS_EAGAIN
@@ -117,7 +118,7 @@ int ss_gz_warm_up(int n_files);
  * ranks of a sharded run must all take the same path for a file: they load under policy 1, all-reduce the outcome and,
  * if any of them was declined, all load again under policy 2 (strainscan_amd/dist.py load_agreed). */
 int ss_gz_set_policy(int mode);
-/* Several ranks SHARE the inflation of a gzip member (ss_ginflate.hip, range mode; the reference pipes one `zcat` per file,
+/* Several ranks SHARE the inflation of a gzip member (ss_gz_range.hip: the chain; ss_ginflate.hip: the slices; the reference pipes one `zcat` per file,
  * identify.py:81-84).  The deflate data is cut into slices, slice s belongs to rank s mod world: a rank finds the block
  * starts of its slices, inflates them to symbols (the expensive part, all ranks at once) and receives what lies in front
  * of each slice -- 32 KB of text, the count of newlines so far, the bytes of the record that straddles the cut, CRC-32 and
@@ -132,7 +133,7 @@ typedef int (*ss_gz_chain_fn)(void *msg, uint64_t bytes, int slice, int directio
 int ss_gz_set_range(int rank, int world, uint64_t slice_bytes, ss_gz_chain_fn chain, void *user);
 /* files this process has inflated its share of in range mode, and the slices that came to */
 int ss_gz_range_counters(uint64_t *files, uint64_t *pieces);
-/* Test hooks, switched by this call only (nothing in the environment does): which = 1: plant a wrong block entry in search
+/* Test hooks (ss_host.hip), switched by this call only (nothing in the environment does): which = 1: plant a wrong block entry in search
  * chunk `value` of every .gz inflated on the device (0 = off); 2: this process declines .gz inputs on the device (in range mode
  * it still serves the chain); 3: this rank leaves range mode WITHOUT serving the chain -- what a crashed peer looks like;
  * 4: which scan kernel of the page index a table goes through -- value 1: tables of k = 31 through the one-lane-per-position

@@ -179,7 +179,7 @@ def main():
     finally:
         shutil.rmtree(d, ignore_errors=True)
     out["note"] = ("ss_reads_load of one file -> resident read set (binned), page cache warm, median of alternating runs; bam = "
-                   "inflated on the device (ss_ginflate.hip) + ss_bam_dev.hip, fq_gz = the same reads as a bgzip-style FASTQ through "
+                   "inflated on the device (ss_ginflate.hip, ss_gz_scratch.hip) + ss_bam_dev.hip, fq_gz = the same reads as a bgzip-style FASTQ through "
                    "ss_ginflate.hip + ss_fastq_dev.hip, bam_host = SS_GZ_GPU=0: host inflaters + the host decoder")
     print(json.dumps(out))
 

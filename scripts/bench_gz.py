@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""gzip'ed FASTQ -> counts: rate of the sequential (inflate) reader, one thread per file."""
+"""gzip'ed FASTQ -> counts: rate of the sequential (inflate) reader, one thread per file.  The device legs go through
+ss_ginflate.hip (its kernels: ss_ginflate_dev.h; the pinned upload and the kept scratch: ss_gz_scratch.hip)."""
 import gzip, json, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

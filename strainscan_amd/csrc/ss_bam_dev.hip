@@ -6,7 +6,7 @@
 // reverse-complemented back to the read as sequenced, every 4-bit code becomes its letter of "=ACMGRSVTWYHKDBN".  The flat
 // block is each kept record's letters and a '\n': the flat block of the FASTQ made from the BAM, byte for byte.
 //
-// Device path (the stream already lies on the device, gpu_gunzip):
+// Device path (the stream already lies on the device, gpu_gunzip of ss_ginflate.hip):
 //   1  walk: one wave per segment of the stream (a BGZF member's text, or 64 KB); its 64 lanes test 64 candidate entries at a
 //      time for the guessed entry -- the first position at which a chain of well-formed records starts; htslib writers usually
 //      begin a member with a record, so that is the first candidate -- and lane 0 walks from there to the exit, the first record

@@ -198,6 +198,8 @@ int mark_solid(ss_db *db);      // PG_SOLID flags of the bucket references, afte
 struct InflatedText { char *p = nullptr; uint64_t n = 0; };
 bool inflate_whole(const char *path, uint64_t budget, char **text, uint64_t *len, int mode, unsigned threads);
 uint64_t inflate_budget_bytes();
+// gzip member header -> offset of the deflate data, 0 = not a header this code handles (ss_pgz.hip)
+uint64_t gzip_header_len(const uint8_t *p, uint64_t n);
 hipStream_t ingest_stream(unsigned i);   // a few process-wide non-blocking streams (creating one costs ~13 ms)
 void free_later(char *p);
 bool ingest_trace();                     // SS_INGEST_TRACE, read once: the "[ingest]" stage lines of ss_ingest.hip and ss_scan.hip
@@ -208,15 +210,15 @@ void inflate_gz_inputs(const char *const *paths, const std::vector<int> &gz, std
 bool gz_on_gpu();
 int gz_policy();                         // ss_gz_set_policy: 0 device then host, 1 device or SS_EAGAIN, 2 host
 bool gpu_gunzip(const uint8_t *in, uint64_t in_n, char **text_dev, uint64_t *len, void **lease, int fd);      // the text is lent until ...
-void gpu_gunzip_done(void *lease);
+void gpu_gunzip_done(void *lease);                          // (ss_gz_scratch.hip: the lease is the call's scratch arena)
 // a non-blocking stream for the length of a call, from a small pool (making and destroying one is ~0.6 ms); handed back synchronised
 hipStream_t call_stream_get();
 void call_stream_put(hipStream_t s);
-// range mode (ss_gz_set_range): this rank's slices of a member.  text[at, at + len) is a slice's text, its first `keep` bytes
+// range mode (ss_gz_set_range, ss_gz_range.hip): this rank's slices of a member.  text[at, at + len) is a slice's text, its first `keep` bytes
 // end with the last record that is complete in it, `carry` holds the bytes of the record that began in the slice before
 struct GzPiece { uint64_t at, len, keep; std::vector<uint8_t> carry; };
 bool gz_range_active();
-extern std::atomic<long long> g_hook_entry, g_hook_decline, g_hook_skip_chain;      // ss_test_hook (ss_ginflate.hip)
+extern std::atomic<long long> g_hook_entry, g_hook_decline, g_hook_skip_chain;      // ss_test_hook 1, 2 (ss_ginflate.hip), 3 (ss_gz_range.hip)
 // The files of a load go down the chain in the order of their paths (the messages of one pair of ranks are matched in order): a
 // file draws a ticket (in path order, before its thread starts), its first chain call waits for the files before it to have
 // finished THEIR chain traffic, and gz_range_pass hands the turn on (idempotent; waits for the turn itself if the file never
@@ -325,7 +327,7 @@ void *big_take(uint64_t bytes, uint64_t *cap = nullptr);      // *cap: what the 
 void big_put(void *p, uint64_t cap);
 void big_release();                                      // everything kept goes back to the driver (ss_gz_gpu_release)
 hipError_t big_malloc(void **p, uint64_t bytes, uint64_t *got);      // big_take, else hipMalloc (which, failing, is tried again after big_release); *got >= bytes
-// a whole file into device memory through the pinned upload buffers of the .gz path (ss_ginflate.hip)
+// a whole file into device memory through the pinned upload buffers of the .gz path (ss_gz_scratch.hip)
 bool upload_file_to_device(int fd, uint64_t n, uint8_t *d_dst);
 // ss_scan_flat_dev for a block whose records ss_reorder.hip has binned by locus (the scan may add hits up in LDS first)
 // (set_id: ss_reads::serial of the resident set the block belongs to, 0 = none)

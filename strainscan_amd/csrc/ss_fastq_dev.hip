@@ -318,7 +318,7 @@ int gz_fastq_to_flat_dev(const char *path, int shard_rank, int shard_world, char
 }
 
 // The same when several ranks share the file's inflation (range mode, ss_gz_set_range): this rank gets the text of ITS slices
-// (gpu_gunzip_range), every piece = the bytes of the record that straddles the cut in front of it + its own complete records;
+// (gpu_gunzip_range, ss_gz_range.hip), every piece = the bytes of the record that straddles the cut in front of it + its own complete records;
 // the sequence lines of each piece become a flat block handed to `flat`.  0 = done (every record that begins in this rank's
 // slices has been handed over), 1 = declined (nothing usable was handed over: the caller reports SS_EAGAIN and all ranks
 // settle for another path).

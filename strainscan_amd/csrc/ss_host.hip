@@ -232,6 +232,27 @@ const char *ss_strerror(int code)
 
 const char *ss_last_error(void) { return ss::g_last_error; }
 
+// Test hooks, switched by an explicit call only (never by the environment); each flag is defined beside the code that reads it
+// (ss_common.h).  1 = plant a wrong entry in search chunk `value` (0 = off; ss_ginflate.hip), 2 = this process declines .gz inputs
+// on the device (range mode: it still serves the chain), 3 = this rank leaves range mode without serving the chain (what a crashed
+// peer looks like: the others' bounded wait must end it; ss_gz_range.hip), 4 = which scan
+// kernel of the page index a table goes through (ss_mini.hip launch_scan_mini: 1 = k = 31 through the per-position kernel, 2 = every
+// k through it, 3 = every k through scan_mini_kernel; 0 = the product's choice): the kernels held to each other, 5 = binned slabs of
+// one length stay ASCII (1) or are packed where they can be (0, the product's choice; ss_reorder.hip order_flat_dev), 6 = one-length
+// slabs take the count + atomic placement (1; ss_reorder.hip).
+int ss_test_hook(int which, long long value)
+{
+    switch (which) {
+    case 1: ss::g_hook_entry = value; return SS_OK;
+    case 2: ss::g_hook_decline = value; return SS_OK;
+    case 3: ss::g_hook_skip_chain = value; return SS_OK;
+    case 4: ss::g_hook_generic_k = value; return SS_OK;
+    case 5: ss::g_hook_ascii_slabs = value; return SS_OK;
+    case 6: ss::g_hook_atomic_binning = value; return SS_OK;
+    default: return SS_EINVAL;
+    }
+}
+
 int ss_device_count(int *n)
 {
     if (!n) return SS_EINVAL;

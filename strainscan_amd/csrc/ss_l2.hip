@@ -695,7 +695,7 @@ int ss_l2_create(const int64_t *indptr, const int32_t *indices, uint64_t K, uint
 }
 
 /* the same with the column indices ALREADY on the device (the inflated `indices.npy` member of all_strains_re.npz,
- * ss_npz_member_dev: 2.5 GB for a 5 M x 300 cluster that neither visits the host nor crosses PCIe uncompressed) */
+ * ss_npz_member_dev in ss_npz_dev.hip: 2.5 GB for a 5 M x 300 cluster that neither visits the host nor crosses PCIe uncompressed) */
 int ss_l2_create_dev(const int64_t *indptr, const int32_t *indices_dev, uint64_t K, uint32_t S, ss_l2 **out)
 {
     if (indices_dev && (((uintptr_t)indices_dev) & 3u)) return SS_EINVAL;
@@ -806,7 +806,7 @@ int ss_l2_destroy(ss_l2 *h)
 
 // The cluster image file of strainscan_amd (identify_strains_L2_Enet_Pscan_new_sp.py _write_l2_cache: bit planes, then the
 // overlap matrix's CSR arrays, each at a 64-byte boundary of the file) straight to the device: the whole file travels through
-// the pinned upload buffers of the .gz path (ss_ginflate.hip upload_file: four threads, ~40 GB/s from the page cache) into ONE
+// the pinned upload buffers of the .gz path (ss_gz_scratch.hip upload_file: four threads, ~40 GB/s from the page cache) into ONE
 // allocation, and the handle's pointers point into it.  Through a memory map and pageable copies the 253 MB of a 5 M x 300
 // cluster took 25 ms of the 70 its vote takes; this way ~7.  The caller gives the layout it read from the file's header;
 // everything the other constructors check is checked here too (padding bits of the planes, row pointers, sizes).

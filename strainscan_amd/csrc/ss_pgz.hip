@@ -333,7 +333,10 @@ int inflate_block(Bits &b, Out &o, bool known_window)
 #undef PGZ_RET
 }
 
-// gzip member header -> offset of the deflate data, 0 = not a header this code handles
+}  // namespace
+
+namespace ss {
+// (ss_common.h; the device gunzip, ss_ginflate.hip, reads its headers with it too)
 uint64_t gzip_header_len(const uint8_t *p, uint64_t n)
 {
     if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8) return 0;
@@ -350,9 +353,6 @@ uint64_t gzip_header_len(const uint8_t *p, uint64_t n)
     return pos + 8 < n ? pos : 0;
 }
 
-}  // namespace
-
-namespace ss {
 // where the text goes: by default 2 MB aligned heap memory released with free(); ss_gz_inflate_to_file maps a file
 struct TextAlloc {
     void *(*alloc)(uint64_t cap, void *ctx) = nullptr;

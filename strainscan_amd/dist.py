@@ -215,7 +215,7 @@ def scan_files_sharded(kdb, paths, allreduce=True):
 
 
 def _gz_chain(rank, world):
-    """The callback of ss_gz_set_range: direction 1 = send the message to the owner of the next slice, 0 = receive the one
+    """The callback of ss_gz_set_range (ss_gz_range.hip: RangeRun calls it): direction 1 = send the message to the owner of the next slice, 0 = receive the one
     for `slice` from the owner of the slice before (slice s belongs to rank s mod world).  Called on the loader's worker
     thread while this thread waits inside the library.  NCCL moves device tensors, gloo host tensors."""
     import ctypes as C

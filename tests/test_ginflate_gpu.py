@@ -1,4 +1,5 @@
-"""The device gzip inflater (strainscan_amd/csrc/ss_ginflate.hip) against Python's gzip module.
+"""The device gzip inflater (strainscan_amd/csrc/ss_ginflate.hip, with ss_ginflate_dev.h, ss_gz_scratch.hip and ss_gz_range.hip)
+against Python's gzip module.
 
 The reference reads .gz samples through gzip.open (library/identify.py:100-108 via jellyfish's input pipe); here the
 member is inflated on the GPU when SS_GZ_GPU=1.  Contract under test: whatever ss_gz_inflate_gpu returns with SS_OK
