@@ -311,6 +311,39 @@ int ss_scan_multi_launches(uint64_t out[3]);
  * SS_ERANGE for a flat table; SS_EINVAL for n_bins < 2, a NULL argument, a table and a set on different devices. */
 int ss_reads_support(const ss_db *db, const ss_reads *r, uint32_t n_bins, uint64_t *hist, uint64_t *hits);
 int ss_reads_support_calls(uint64_t *n);   /* calls so far in this process (diagnostics; tests use it to show "flag off = not run") */
+/* The records of a resident set with at least min_hits hits against a table, as a NEW resident set (`--extract_reads`); a record
+ * and a hit are those of ss_reads_support.  *out is destroyed by the caller like any other set.  It holds exactly the selected
+ * records, in an unspecified order, as one ASCII, unbinned slab in the flat layout (each record's bytes and '\n', the block padded
+ * with '\n'); nothing selected: a valid set of 0 records.  From an ASCII slab the bytes are copied as they are (lower case, IUPAC
+ * codes, '\r'); from a packed slab a base is the letter ss_reads_read_back writes.  ss_reads_read_back, ss_reads_info (n_records
+ * and n_bases exact), ss_scan_reads and ss_reads_support work on *out unchanged.  Synchronous.  Reads the table's index, never its
+ * counters.  SS_ERANGE: a flat table (k below 17); a set with a cut record, at any k (a cut piece is not a read); more records
+ * than hipcub's int item count holds.  SS_EINVAL: a NULL argument, min_hits == 0, a table and a set on different devices. */
+int ss_reads_select(const ss_db *db, const ss_reads *r, uint32_t min_hits, ss_reads **out);
+int ss_reads_select_calls(uint64_t *n);    /* calls so far in this process (diagnostics; "flag off = not run") */
+
+/* --------------------------------------------------------------------------------------------
+ * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input
+ * files BY CONTENT: a record is named by a 128-bit digest of its flat form -- two independent 64-bit hashes over its bytes and
+ * its length: FNV-1a (64-bit) and a multiply-rotate hash over 8-byte words with a splitmix64 finish, each closed with the
+ * length.  A record that was not selected is written only if BOTH hashes collide with a selected one's: a false positive needs
+ * a 128-bit collision.  Reads with the same flat form share a digest and a fate.
+ * ss_flat_record_keys: keys[2 i], keys[2 i + 1] = the digest of the i-th non-empty record ('\n'-separated) of a flat block;
+ *   *n_records = how many there are; SS_ERANGE (and *n_records set) when cap (in records) is too small; keys = NULL counts.
+ *   The flat block is taken as the loader made it: with the base-quality mask on, it is the masked form.
+ * ss_extract_write: reads the n_in (1 or 2) input files again -- plain text mapped, .gz through the host inflater -- walks them
+ *   record by record with the grammar of ss_fastx_to_flat (four-line and multi-line FASTQ, FASTA of any wrapping, CRLF; the
+ *   base-quality mask applied), and writes the ORIGINAL TEXT of every record whose flat form's digest is among the n_keys
+ *   digests of `keys`, byte for byte, to out_paths[i].  Two inputs are walked in lockstep and record i of both files is
+ *   written when EITHER mate is selected.  A record with an empty sequence has no digest and is never selected (in a pair it
+ *   goes along with a selected mate, so that the two files stay in step).
+ *   counters[0] records read, all inputs together, [1] records written, all outputs together, [2] pairs written because of
+ *   mate 1 only, [3] because of mate 2 only.  SS_EIO: an unreadable input, unequal record counts; SS_EINVAL: a BAM or CRAM input, a bad
+ *   argument.  On any error no output file is left behind (the text goes to <name>.tmp, renamed at the end).
+ * ------------------------------------------------------------------------------------------ */
+int ss_flat_record_keys(const char *flat, uint64_t len, uint64_t *keys, uint64_t cap, uint64_t *n_records);
+int ss_extract_write(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys,
+                     const char *const *out_paths, uint64_t counters[4]);
 
 /* --------------------------------------------------------------------------------------------
  * Host FASTA/FASTQ -> flat base block (what jellyfish's sequence parser feeds its counter).

@@ -115,6 +115,11 @@ def add_arguments(ap, multi=False):
                     help="Also write read_support.tsv: for the tree's table and for every cluster table scanned at layer 2, how "
                          "many reads of the sample carry at least 1, 2, 4, ... 64 of its k-mers (needs the sample resident on "
                          "the device and k >= 17)")
+    ap.add_argument("-x", "--extract_reads", dest="extract_reads", type=extract_reads_arg, default=0, metavar="N",
+                    help="Also write the reads that carry at least N k-mers of a table to OUT/extracted/<table>_1.<ext> (and _2 "
+                         "with -j; a pair when either mate does), for the tree's table and every cluster table scanned at "
+                         "layer 2.  An integer >= 1; read_support.tsv's geN columns say how many reads a given N keeps.  Needs "
+                         "the sample resident on the device, k >= 17, FASTA/FASTQ input and one rank (default: off)")
 
 
 def min_base_qual_arg(text):
@@ -126,6 +131,17 @@ def min_base_qual_arg(text):
     if not 0 <= q <= 93:
         raise argparse.ArgumentTypeError("%d is outside 0..93" % q)
     return q
+
+
+def extract_reads_arg(text):
+    """-x's value: an integer of at least 1, or the parser's error (exit status 2, before any input is opened)."""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer >= 1" % text)
+    if n < 1 or n > 0xFFFFFFFF:
+        raise argparse.ArgumentTypeError("%d is outside 1..%d" % (n, 0xFFFFFFFF))
+    return n
 
 
 def apply_min_base_qual(q):
@@ -142,6 +158,13 @@ def apply_read_support(on):
     the command writes them to read_support.tsv when it ends.  stdout and the other report files are untouched."""
     from . import db
     db.read_support_reset(on)
+
+
+def apply_extract_reads(n, out_dir=None):
+    """-x N (strainscan_amd.set_extract_reads): the tables scanned from here on leave their reads in out_dir/extracted/ (db.
+    collect_extract_reads).  stdout and the report files are untouched; 0 turns it off."""
+    from . import db
+    db.extract_reads_reset(n, out_dir)
 
 
 def settings(args):
@@ -235,12 +258,14 @@ def main(argv=None):
     rank, world = dist.init_from_env()      # torchrun: one process per GPU, reads shard across ranks
     out_dir = rank_output_dir(out_dir, rank)
     apply_read_support(args.read_support)
+    apply_extract_reads(args.extract_reads, out_dir)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:
         from . import db
         db.write_read_support(out_dir)      # (in a finally: the reference's own early exit()s come through here as SystemExit)
         db.read_support_reset()
+        db.extract_reads_reset()
 
 
 def cli(main_fn=None):

@@ -14,6 +14,7 @@ host-side mirror of the reference's Python interface for that path:
 
     strainscan_amd.set_min_base_qual / get_min_base_qual      (the base-quality mask of `strainscan -q`; process-wide, off by default)
     strainscan_amd.set_read_support                           (`strainscan --read_support`: rows of reads per table, db.READ_SUPPORT)
+    strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, db.EXTRACT_READS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -36,6 +37,17 @@ def set_read_support(on):
     read_support.tsv.  set_read_support(False) turns it off and drops the rows.  Off by default; nothing runs while it is off."""
     from . import db
     db.read_support_reset(bool(on))
+
+
+def set_extract_reads(n, out_dir=None):
+    """`strainscan -x N` for callers of the functions above: from here on the tree scan of identify_cluster and the cluster
+    scans of vote_strain_L2_batch each write the reads with at least `n` k-mer hits against their table to
+    out_dir/extracted/<table>_1.<ext> (and _2 for a pair, written when either mate has them); out_dir defaults to the current
+    directory.  n is an integer of at least 1; 0 (or None) turns it off.  Off by default; nothing runs while it is off."""
+    if n and (isinstance(n, bool) or not isinstance(n, int) or n < 1):
+        raise ValueError("extract_reads must be an integer >= 1 (or 0 for off), not %r" % (n,))
+    from . import db
+    db.extract_reads_reset(n or 0, out_dir)
 
 
 def get_min_base_qual():

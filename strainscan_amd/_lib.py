@@ -108,6 +108,10 @@ SIGNATURES = {
     "ss_scan_multi_launches": (i32, [P(u64)]),
     "ss_reads_support": (i32, [vp, vp, u32, vp, P(u64)]),
     "ss_reads_support_calls": (i32, [P(u64)]),
+    "ss_reads_select": (i32, [vp, vp, u32, P(vp)]),
+    "ss_reads_select_calls": (i32, [P(u64)]),
+    "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
+    "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
     "ss_scan_reset": (i32, [vp, vp]),
     "ss_scan_flat_dev": (i32, [vp, vp, u64, vp]),
     "ss_scan_flat_host": (i32, [vp, cp, u64]),
@@ -482,6 +486,48 @@ class ReadSet:
         hits = C.c_uint64()
         check(lib().ss_reads_support(kdb.handle, self._h, int(n_bins), ptr(hist), C.byref(hits)), "ss_reads_support")
         return hist, int(hits.value)
+
+    def select(self, kdb, min_hits):
+        """A new ReadSet: the records of this one with at least `min_hits` k-mer hits against `kdb` (ss_reads_select), as one
+        ASCII, unbinned block in an unspecified order.  The caller closes it.  The table's counters are left alone."""
+        h = C.c_void_p()
+        check(lib().ss_reads_select(kdb.handle, self._h, int(min_hits), C.byref(h)), "ss_reads_select")
+        sub = ReadSet.__new__(ReadSet)
+        sub._h = h
+        return sub
+
+
+def select_calls():
+    """Calls of ss_reads_select so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_select_calls(C.byref(n)), "ss_reads_select_calls")
+    return n.value
+
+
+def flat_record_keys(flat):
+    """np.uint64[n, 2]: the 128-bit digest of every non-empty record of a flat block (bytes), in order (ss_flat_record_keys)."""
+    flat = bytes(flat)
+    n = C.c_uint64()
+    check(lib().ss_flat_record_keys(flat, len(flat), None, 0, C.byref(n)), "ss_flat_record_keys")
+    keys = np.zeros((n.value, 2), np.uint64)
+    if n.value:
+        check(lib().ss_flat_record_keys(flat, len(flat), ptr(keys), n.value, C.byref(n)), "ss_flat_record_keys")
+    return keys
+
+
+def extract_write(in_paths, keys, out_paths):
+    """Every record of the input files (one, or a pair walked in lockstep) whose flat form has a digest among `keys`
+    (np.uint64[n, 2]) goes to out_paths, original text byte for byte; a pair when either mate is selected (ss_extract_write).
+    -> dict(read=, written=, mate1_only=, mate2_only=).  No output file is left behind when it fails (SSError)."""
+    ins = [os.fsencode(p) for p in in_paths]
+    outs = [os.fsencode(p) for p in out_paths]
+    if len(ins) != len(outs):
+        raise ValueError("one output path per input path")
+    keys = np.ascontiguousarray(keys, np.uint64).reshape(-1, 2)
+    c = (C.c_uint64 * 4)()
+    check(lib().ss_extract_write((C.c_char_p * len(ins))(*ins), len(ins), ptr(keys) if keys.size else None, keys.shape[0],
+                                 (C.c_char_p * len(outs))(*outs), c), "ss_extract_write")
+    return dict(zip(("read", "written", "mate1_only", "mate2_only"), (int(v) for v in c)))
 
 
 def support_calls():

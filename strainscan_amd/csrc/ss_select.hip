@@ -1,0 +1,283 @@
+// ss_reads_select: the records of a resident read set with at least min_hits hits against a table, as a new resident set
+// (`--extract_reads`).
+//
+// ss_reads_support reduces rec_hits[] to a histogram and throws it away; this keeps it and acts on it.  A record and a hit mean
+// what they mean there, so the selection depends on a record's bytes only: the same records are chosen from a set in file
+// order, binned or packed, and the caller finds them in the input files again BY CONTENT (ss_extract.hip) -- nothing here knows
+// where a record stood in a file.
+//
+// Four passes, each a plain launch; the scratch comes from the stream-ordered pool and goes back before the call returns:
+//   1. rec_hits_of (ss_support.hip): the record base of every tile and rec_hits[], exactly as ss_reads_support makes them.
+//   2. record_spans_kernel (ASCII slabs): start[rec] and end[rec].  A lane takes 16 bytes; a record START is a byte other than
+//      '\n' behind a '\n' (or at the slab's first byte), a record END a '\n' behind a byte that is none (and the slab's end behind
+//      such a byte).  Starts and ends alternate, so the record a start belongs to is the number of ends before it: the tile's
+//      base + the ends of the lanes before (a wave prefix sum of popcounts) + the ends below it in the lane.  A record that spans
+//      tiles gets its start from the tile where it begins and its end from the tile where it ends; empty lines between records
+//      belong to no record.  A packed slab needs no kernel: start = rec * slot, length = L.
+//   3. select_len_kernel: out_len[rec] = hits >= min_hits ? length + 1 : 0, the selected records counted on the way; hipcub's
+//      64-bit ExclusiveSum turns the lengths into byte offsets in the new slab, which is allocated once (ss::big_malloc).
+//   4. gather_kernel: sixteen lanes per selected record copy its bytes and a '\n' to its offset.  Source and destination are
+//      unaligned in general.  The lanes walk the 16-byte ALIGNED pieces of the destination that the record touches: a piece that
+//      is all the record's is one 16-byte load (any alignment) and one aligned 16-byte store; the piece at either end, which
+//      the record shares with its neighbours, is the same one load and then byte stores of the record's own bytes -- no lane
+//      ever writes a byte that is not its record's.  From a packed slab a piece is three 3-byte units turned back into letters
+//      ("ACTG"[code], 'N' where invalid: what ss_reads_read_back writes).  All offsets are 64-bit.
+#include "ss_scan_dev.h"
+#include "ss_support.h"
+
+#include <hipcub/hipcub.hpp>
+
+using namespace ss::dev;
+using ss::SUP_TILE;
+
+namespace {
+
+// one wave per tile, 16 bytes per lane (the shape of record_ends_kernel, ss_support.hip); records at or beyond rec_limit are
+// never written
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void record_spans_kernel(const uint8_t *__restrict__ bases, uint64_t n, uint64_t n_tiles,
+                                                           const uint32_t *__restrict__ tile_base, uint64_t rec_base, uint64_t rec_limit,
+                                                           unsigned long long *__restrict__ start, unsigned long long *__restrict__ end)
+{
+    const uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= n_tiles) return;                                        // (the same for the whole wave)
+    const uint64_t off = tile * (uint64_t)SUP_TILE + (uint64_t)(threadIdx.x & 63u) * 16u;
+    uint32_t ends = 0, starts = 0, last = 0;
+    if (off < n) {
+        uint32_t w[4];
+        load16<ALIGNED>(bases, off, n, w);
+        const uint32_t nl = newline_mask16(w);
+        const uint32_t prev = (off == 0 || bases[off - 1] == 0x0Au) ? 1u : 0u;
+        const uint32_t behind_nl = (nl << 1) | prev;                    // bit i: the byte before byte i is '\n'
+        ends = nl & ~behind_nl & 0xFFFFu;
+        starts = ~nl & behind_nl & 0xFFFFu;
+        if (n - off < 16u) {                                            // positions below n only
+            const uint32_t m = (1u << (uint32_t)(n - off)) - 1u;
+            ends &= m;
+            starts &= m;
+        }
+        if (n - off <= 16u) last = ((nl >> (uint32_t)(n - 1u - off)) & 1u) ^ 1u;      // the slab ends inside a record
+    }
+    const uint32_t mine = (uint32_t)__popc(ends) + last;
+    uint64_t r = rec_base + tile_base[tile] + wave_inclusive_sum(mine) - mine;
+    for (uint32_t ev = starts | ends; ev; ev &= ev - 1u) {
+        const uint32_t b = (uint32_t)__ffs(ev) - 1u;
+        if ((starts >> b) & 1u) {
+            if (r < rec_limit) start[r] = off + b;
+        } else {
+            if (r < rec_limit) end[r] = off + b;
+            r++;
+        }
+    }
+    if (last && r < rec_limit) end[r] = n;
+}
+
+// records [rec0, rec0 + n_rec) of one slab: out_len = the bytes a record takes in the new slab (its length + '\n', 0 when it is
+// not selected); tot[0] += selected records, tot[1] += their bytes.  fixed_len != 0: a packed slab, every record that long.
+// A span that does not lie inside the slab's n positions (none should: start[] and end[] come filled with ~0) selects nothing,
+// so that the gather never reads outside the slab.
+__global__ __launch_bounds__(256) void select_len_kernel(const uint32_t *__restrict__ rec_hits, const unsigned long long *__restrict__ start,
+                                                         const unsigned long long *__restrict__ end, uint64_t rec0, uint64_t n_rec, uint64_t n,
+                                                         uint32_t fixed_len, uint32_t min_hits, unsigned long long *__restrict__ out_len,
+                                                         unsigned long long *__restrict__ tot)
+{
+    unsigned long long cnt = 0, bytes = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
+        const uint64_t r = rec0 + i;
+        unsigned long long len = 0;
+        if (rec_hits[r] >= min_hits) {
+            bool ok = true;
+            if (fixed_len) len = fixed_len;
+            else {
+                const unsigned long long s = start[r], e = end[r];
+                ok = s < e && e <= n;
+                len = e - s;
+            }
+            if (ok) { len += 1ull; cnt++; bytes += len; }
+            else len = 0;
+        }
+        out_len[r] = len;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); bytes += __shfl_xor(bytes, d, 64); }
+    if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
+}
+
+// positions [s, s + 16) of a packed slab (s + 16 <= its positions) as the 16 letters its ASCII form holds inside a record: the
+// three 3-byte units around them, fetched as twelve bytes from the first unit on (a packed slab has 8 readable bytes behind its
+// last group, ss_scan_dev.h IN_PACKED, and its last unit but one begins 6 bytes before the end)
+__device__ __forceinline__ uint4 packed_letters16(const uint8_t *__restrict__ pk, uint64_t s)
+{
+    uint32_t t[3];
+    __builtin_memcpy(t, pk + (s >> 3) * 3u, 12);
+    const uint32_t sh = (uint32_t)s & 7u;
+    const uint64_t lo = (uint64_t)t[0] | ((uint64_t)t[1] << 32);
+    uint64_t code = (lo & 0xFFFFull) | (((lo >> 24) & 0xFFFFull) << 16) | ((lo >> 48) << 32);      // bytes 0 1, 3 4, 6 7
+    uint32_t inv = (uint32_t)((lo >> 16) & 0xFFull) | (uint32_t)(((lo >> 40) & 0xFFull) << 8) | ((t[2] & 0xFFu) << 16);      // bytes 2, 5, 8
+    code >>= 2u * sh;
+    inv >>= sh;
+    uint32_t w[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int i = 4 * d + b;
+            const uint32_t c = (uint32_t)(code >> (2 * i)) & 3u;
+            const uint32_t ch = ((inv >> i) & 1u) ? (uint32_t)'N' : (0x47544341u >> (8u * c)) & 0xFFu;      // "ACTG"[code]
+            x |= ch << (8 * b);
+        }
+        w[d] = x;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// Sixteen lanes per record of one slab of n >= 16 positions (records [rec0, rec0 + n_rec)); dst is 16-byte aligned.  PACKED: src
+// is a packed slab, record r - rec0 at position (r - rec0) * slot; else src is an ASCII slab and start[] says where.
+// A lane takes one aligned 16-byte piece of the destination at a time.  The source bytes that belong there begin at `base`, any
+// alignment, and at an edge piece partly outside the record -- even outside the slab: so the 16 bytes are fetched from `base`
+// clamped into the slab, ONE load, and moved to their places with a 128-bit shift (every byte the piece needs lies in what was
+// fetched, because the record lies in the slab).  A piece that is all the record's (its '\n' included) is one aligned 16-byte
+// store; a piece it shares with a neighbour stores its own bytes one by one, and not a byte more.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void gather_kernel(const uint8_t *__restrict__ src, uint64_t n, const unsigned long long *__restrict__ start,
+                                                     const unsigned long long *__restrict__ out_len, const unsigned long long *__restrict__ out_off,
+                                                     uint64_t rec0, uint64_t n_rec, uint32_t slot, uint8_t *__restrict__ dst)
+{
+    const uint64_t g = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 4;
+    if (g >= n_rec) return;
+    const uint64_t r = rec0 + g;
+    const uint64_t ol = out_len[r];
+    if (!ol) return;                                                    // not selected
+    const uint64_t len = ol - 1u, D = out_off[r], S = PACKED ? g * (uint64_t)slot : (uint64_t)start[r];
+    const uint64_t A0 = D & ~15ull, n_pieces = (D + ol - A0 + 15u) >> 4;
+    for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
+        const uint64_t a = A0 + 16u * c;
+        const uint64_t lo = a > D ? a : D, hi = a + 16u < D + ol ? a + 16u : D + ol;      // the record's bytes of this piece: [lo, hi)
+        const int64_t base = (int64_t)S + ((int64_t)a - (int64_t)D);    // source position of the piece's byte 0
+        const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
+        uint4 v;
+        if (PACKED) v = packed_letters16(src, (uint64_t)q);
+        else __builtin_memcpy(&v, src + q, 16);
+        unsigned __int128 x;
+        __builtin_memcpy(&x, &v, 16);
+        const int shift = (int)(base - q);                              // byte j of the piece is byte j + shift of what was fetched
+        if (shift >= 16) x = 0;                                         // (only the '\n' behind a record that ends with the slab)
+        else if (shift > 0) x >>= 8 * shift;
+        else if (shift < 0) x <<= 8 * -shift;
+        if (D + len < a + 16u) {                                        // the byte behind the record
+            const uint32_t j = (uint32_t)(D + len - a);
+            x = (x & ~((unsigned __int128)0xFFu << (8u * j))) | ((unsigned __int128)0x0Au << (8u * j));
+        }
+        if (lo == a && hi == a + 16u) {
+            __builtin_memcpy(&v, &x, 16);
+            *reinterpret_cast<uint4 *>(dst + a) = v;
+        } else {
+            const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
+#pragma unroll
+            for (uint32_t j = 0; j < 16u; j++)
+                if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
+        }
+    }
+}
+
+std::atomic<uint64_t> g_select_calls{0};
+
+}  // namespace
+
+extern "C" {
+
+int ss_reads_select_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_select_calls.load();
+    return SS_OK;
+}
+
+int ss_reads_select(const ss_db *db, const ss_reads *R, uint32_t min_hits, ss_reads **out)
+{
+    if (!db || !R || !out || min_hits == 0) return SS_EINVAL;
+    if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
+    if (R->has_cut_record) return SS_ERANGE;                        // at any k: a cut piece is not a read
+    ss::RecHits rh;
+    // 1. hits per record
+    int rc = ss::rec_hits_of(db, R, &rh, &g_select_calls);
+    if (rc) return rc;
+    if (rh.rec_total > 0x7FFFFFFFull) return SS_ERANGE;             // hipcub counts its items in an int
+    const hipStream_t st = ss::l2s::stream();
+    const uint64_t rec_total = rh.rec_total;
+    unsigned long long *d_start = nullptr, *d_end = nullptr, *d_len = nullptr, *d_off = nullptr, *d_tot = nullptr;
+    unsigned long long tot[2] = {0, 0};
+    bool any_ascii = false;
+    for (const auto &pt : rh.parts) any_ascii = any_ascii || (!pt.sl->packed && pt.n_rec);
+    if (rec_total) {
+        // 2. record spans
+        if (any_ascii) {
+            SS_HIP(rh.scratch.get((void **)&d_start, rec_total * 8));
+            SS_HIP(rh.scratch.get((void **)&d_end, rec_total * 8));
+            SS_HIP(ss::l2s::set(d_start, 0xFF, rec_total * 8));
+            SS_HIP(ss::l2s::set(d_end, 0xFF, rec_total * 8));
+        }
+        for (const auto &pt : rh.parts) {
+            if (pt.sl->packed || !pt.n_rec) continue;
+            const uint8_t *b = (const uint8_t *)pt.sl->d;
+            const dim3 grid((unsigned)((pt.n_tiles + 3) / 4));
+            with_bool((((uintptr_t)b) & 15) == 0, [&](auto aligned) {
+                hipLaunchKernelGGL(record_spans_kernel<decltype(aligned)::value>, grid, dim3(256), 0, st, b, pt.n, pt.n_tiles,
+                                   rh.d_tile_base + pt.tile_off, pt.rec_base, pt.rec_base + pt.n_rec, d_start, d_end);
+            });
+            SS_HIP(hipGetLastError());
+        }
+        // 3. select: bytes per record, their exclusive sum
+        SS_HIP(rh.scratch.get((void **)&d_len, rec_total * 8));
+        SS_HIP(rh.scratch.get((void **)&d_off, rec_total * 8));
+        SS_HIP(rh.scratch.get((void **)&d_tot, 16));
+        SS_HIP(ss::l2s::set(d_tot, 0, 16));
+        for (const auto &pt : rh.parts) {
+            if (!pt.n_rec) continue;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 4096);
+            hipLaunchKernelGGL(select_len_kernel, dim3(blocks), dim3(256), 0, st, rh.d_rec_hits, d_start, d_end, pt.rec_base, pt.n_rec, pt.n,
+                               pt.sl->packed ? pt.sl->L : 0u, min_hits, d_len, d_tot);
+            SS_HIP(hipGetLastError());
+        }
+        size_t tmp_bytes = 0;
+        SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_off, (int)rec_total, st));
+        void *d_tmp = nullptr;
+        SS_HIP(rh.scratch.get(&d_tmp, tmp_bytes));
+        SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_len, d_off, (int)rec_total, st));
+        SS_HIP(ss::l2s::copy(tot, d_tot, 16, hipMemcpyDeviceToHost));
+    }
+    ss_reads *S = new (std::nothrow) ss_reads();
+    if (!S) return SS_ENOMEM;
+    S->n_records = tot[0];
+    S->n_bases = tot[1] - tot[0];
+    if (tot[1]) {
+        // the new slab, allocated once from the total
+        ss_reads::Slab sl;
+        sl.used = ss_reads::padded(tot[1]);
+        if (ss::big_malloc((void **)&sl.d, sl.used, &sl.cap) != hipSuccess) { delete S; return SS_ENOMEM; }
+        S->slabs.push_back(sl);
+        S->device_bytes = sl.cap;
+        S->n_blocks = 1;
+        S->first_slab = sl.cap;
+        // 4. gather
+        auto fail = [&](hipError_t e) { if (e != hipSuccess) ss::set_last_error("ss_reads_select", __FILE__, __LINE__, e); return e != hipSuccess; };
+        bool bad = fail(ss::l2s::set(sl.d + tot[1], '\n', sl.used - tot[1]));
+        for (const auto &pt : rh.parts) {
+            if (bad || !pt.n_rec) continue;
+            if (pt.n < 16) { bad = fail(hipErrorInvalidValue); continue; }      // (a slab is padded to a multiple of 16)
+            const dim3 grid((unsigned)((pt.n_rec * 16u + 255u) / 256u));
+            with_bool(pt.sl->packed, [&](auto packed) {
+                hipLaunchKernelGGL(gather_kernel<decltype(packed)::value>, grid, dim3(256), 0, st, (const uint8_t *)pt.sl->d, pt.n, d_start, d_len, d_off,
+                                   pt.rec_base, pt.n_rec, pt.sl->slot, (uint8_t *)sl.d);
+            });
+            bad = fail(hipGetLastError());
+        }
+        bad = fail(ss::l2s::sync()) || bad;
+        if (bad) { ss_reads_destroy(S); return SS_EHIP; }
+    }
+    *out = S;
+    return SS_OK;
+}
+
+}  // extern "C"

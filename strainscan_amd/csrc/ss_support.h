@@ -1,0 +1,43 @@
+// The first two passes of ss_reads_support (ss_support.hip), shared with ss_reads_select (ss_select.hip): the hits of every record
+// of a resident set against a page-index table, left on the device.  Not part of the C ABI.
+#pragma once
+#include "ss_common.h"
+
+#include <algorithm>
+
+namespace ss {
+
+constexpr int SUP_TILE = 1024;      // positions per tile: KPOS of scan_minik_kernel (ss_minik.hip), one wave each
+
+// pool allocations of one call, given back on every way out
+struct PoolScratch {
+    std::vector<void *> p;
+    hipError_t get(void **q, size_t bytes)
+    {
+        const hipError_t e = ss::l2s::dmalloc(q, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) p.push_back(*q);
+        return e;
+    }
+    ~PoolScratch()
+    {
+        for (void *q : p) (void)ss::l2s::dfree(q);
+        if (!p.empty()) (void)ss::l2s::sync();
+    }
+};
+
+// What rec_hits_of leaves behind.  The records of the set are numbered slab after slab (a slab's records from rec_base on, in
+// the order of their ends); rec_hits[i] = hits of record i.  An ASCII slab's tiles begin at tile_base[tile_off + tile]: the
+// record ends before the tile, and tile_base[tile_off + n_tiles] = the slab's records.  Everything lives in `scratch` and is
+// enqueued on ss::l2s::stream() when the call returns.
+struct RecHits {
+    struct Part { const ss_reads::Slab *sl; uint64_t n, n_tiles, tile_off, n_rec, rec_base; };
+    std::vector<Part> parts;             // the set's slabs that hold positions
+    uint64_t tiles_total = 0, rec_total = 0;
+    uint32_t *d_tile_base = nullptr;     // [tiles_total], ASCII slabs only
+    uint32_t *d_rec_hits = nullptr;      // [rec_total]
+    PoolScratch scratch;
+};
+// SS_ERANGE / SS_EINVAL as ss_reads_support states them; *calls is counted once the arguments have passed
+int rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls);
+
+}  // namespace ss

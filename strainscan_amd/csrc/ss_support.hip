@@ -16,15 +16,16 @@
 //      tiles, or span many, meet in that array; record indices run on from slab to slab.
 //   3. support_hist_kernel: rec_hits -> bins in LDS per workgroup -> a few global 64-bit atomics.
 // The scratch (4 bytes per record, 4 per tile) comes from the stream-ordered pool and goes back before the call returns.
+// Passes 1 and 2 are rec_hits_of (ss_support.h), which ss_reads_select (ss_select.hip) calls too.
 #include "ss_scan_dev.h"
+#include "ss_support.h"
 
 #include <hipcub/hipcub.hpp>
 
 using namespace ss::dev;
+using ss::SUP_TILE;
 
 namespace {
-
-constexpr int SUP_TILE = 1024;      // positions per tile: KPOS of scan_minik_kernel (ss_minik.hip), one wave each
 
 // one wave per tile, 16 bytes per lane; tile_ends[tile] = record ends at positions [tile * 1024, tile * 1024 + 1024) below n, and
 // in the tile of byte n - 1 one more if that byte is not '\n'
@@ -75,48 +76,23 @@ __global__ __launch_bounds__(256) void support_hist_kernel(const uint32_t *__res
     if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&out[n_bins], sum);
 }
 
-// pool allocations of one call, given back on every way out
-struct Scratch {
-    std::vector<void *> p;
-    hipError_t get(void **q, size_t bytes)
-    {
-        const hipError_t e = ss::l2s::dmalloc(q, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) p.push_back(*q);
-        return e;
-    }
-    ~Scratch()
-    {
-        for (void *q : p) (void)ss::l2s::dfree(q);
-        if (!p.empty()) (void)ss::l2s::sync();
-    }
-};
-
 std::atomic<uint64_t> g_support_calls{0};
 
 }  // namespace
 
-extern "C" {
-
-int ss_reads_support_calls(uint64_t *n)
+// passes 1 and 2 (ss_support.h): ss_reads_support reduces rec_hits to a histogram, ss_reads_select (ss_select.hip) acts on it
+int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls)
 {
-    if (!n) return SS_EINVAL;
-    *n = g_support_calls.load();
-    return SS_OK;
-}
-
-int ss_reads_support(const ss_db *db, const ss_reads *R, uint32_t n_bins, uint64_t *hist, uint64_t *hits)
-{
-    if (!db || !R || !hist || !hits || n_bins < 2) return SS_EINVAL;
     if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
     if (R->has_cut_record && db->k != 31) return SS_ERANGE;         // cut records carry a 30-base overlap (as ss_scan_reads)
-    struct Part { const ss_reads::Slab *sl; uint64_t n, n_tiles, tile_off, n_rec; };
-    std::vector<Part> parts;
+    using Part = RecHits::Part;
+    std::vector<Part> &parts = out->parts;
     uint64_t tiles_total = 0;
     for (const auto &sl : R->slabs) {
         if (!sl.used || !sl.positions()) continue;
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, sl.d) != hipSuccess || at.device != db->device) { (void)hipGetLastError(); return SS_EINVAL; }
-        Part pt{&sl, sl.positions(), 0, tiles_total, 0};
+        Part pt{&sl, sl.positions(), 0, tiles_total, 0, 0};
         pt.n_tiles = (pt.n + SUP_TILE - 1) / SUP_TILE;
         if (sl.packed) {
             if (!sl.slot) return SS_EINVAL;
@@ -127,11 +103,10 @@ int ss_reads_support(const ss_db *db, const ss_reads *R, uint32_t n_bins, uint64
         }
         parts.push_back(pt);
     }
-    g_support_calls++;
+    if (calls) (*calls)++;
     const hipStream_t st = ss::l2s::stream();
-    Scratch scratch;
+    PoolScratch &scratch = out->scratch;
     uint32_t *d_ends = nullptr, *d_base = nullptr, *d_rec = nullptr;
-    unsigned long long *d_out = nullptr;
     // 1. ASCII slabs: record ends per tile -> the record index at which each tile begins; [n_tiles] of a slab = its records
     if (tiles_total) {
         SS_HIP(scratch.get((void **)&d_ends, tiles_total * 4));
@@ -164,21 +139,45 @@ int ss_reads_support(const ss_db *db, const ss_reads *R, uint32_t n_bins, uint64
             if (!parts[i].sl->packed) parts[i].n_rec = n_rec[i];
     }
     uint64_t rec_total = 0;
-    for (const Part &pt : parts) rec_total += pt.n_rec;
+    for (Part &pt : parts) { pt.rec_base = rec_total; rec_total += pt.n_rec; }
     // 2. hits per record
     SS_HIP(scratch.get((void **)&d_rec, rec_total * 4));
-    SS_HIP(scratch.get((void **)&d_out, ((size_t)n_bins + 1) * 8));
     SS_HIP(ss::l2s::set(d_rec, 0, std::max<uint64_t>(rec_total * 4, 16)));
-    SS_HIP(ss::l2s::set(d_out, 0, ((size_t)n_bins + 1) * 8));
-    uint64_t rec_base = 0;
     for (const Part &pt : parts) {
         if (pt.n >= (uint64_t)db->k && pt.n_rec) {
-            const ss::SupportArgs a{d_rec, pt.sl->packed ? nullptr : d_base + pt.tile_off, rec_base, rec_total, pt.sl->packed ? pt.sl->slot : 0u};
+            const ss::SupportArgs a{d_rec, pt.sl->packed ? nullptr : d_base + pt.tile_off, pt.rec_base, rec_total, pt.sl->packed ? pt.sl->slot : 0u};
             const int rc = ss::launch_support_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, st);
             if (rc) return rc;
         }
-        rec_base += pt.n_rec;
     }
+    out->tiles_total = tiles_total;
+    out->rec_total = rec_total;
+    out->d_tile_base = d_base;
+    out->d_rec_hits = d_rec;
+    return SS_OK;
+}
+
+extern "C" {
+
+int ss_reads_support_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_support_calls.load();
+    return SS_OK;
+}
+
+int ss_reads_support(const ss_db *db, const ss_reads *R, uint32_t n_bins, uint64_t *hist, uint64_t *hits)
+{
+    if (!db || !R || !hist || !hits || n_bins < 2) return SS_EINVAL;
+    ss::RecHits rh;
+    const int rc = ss::rec_hits_of(db, R, &rh, &g_support_calls);
+    if (rc) return rc;
+    const hipStream_t st = ss::l2s::stream();
+    const uint64_t rec_total = rh.rec_total;
+    const uint32_t *d_rec = rh.d_rec_hits;
+    unsigned long long *d_out = nullptr;
+    SS_HIP(rh.scratch.get((void **)&d_out, ((size_t)n_bins + 1) * 8));
+    SS_HIP(ss::l2s::set(d_out, 0, ((size_t)n_bins + 1) * 8));
     // 3. histogram and total
     if (rec_total) {
         const unsigned blocks = (unsigned)std::min<uint64_t>((rec_total + 256 * 8 - 1) / (256 * 8), 2048);

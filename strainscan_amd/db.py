@@ -167,6 +167,95 @@ def write_read_support(out_dir, scope=None):
     return path
 
 
+# -x N / --extract_reads N (StrainScan.apply_extract_reads turns it on): the reads that carry at least N k-mers of a table, written
+# beside the reports as `dir`/extracted/<table>_1.<ext> (and _2 with a second mate), at the points where --read_support collects
+# its rows and while the table is open.  The device selects the records (ReadSet.select); they are found in the input files again
+# by the digest of their sequence, not by position -- a resident set keeps no map back to file order.  "done": the tables written
+# under each scope (strainscan-multi: a database's label, with `dir` = its report directory); "skipped": why nothing is written.
+# "files": what this run has written so far (a skip takes them away again: after a skip the run leaves no extracted/ of its own).
+EXTRACT_READS = {"n": 0, "scope": None, "dir": None, "done": {}, "skipped": None, "files": []}
+EXTRACT_READS_DIR = "extracted"
+_EXTRACT_READS_LOCK = threading.Lock()
+
+
+def extract_reads_reset(n=0, out_dir=None):
+    EXTRACT_READS.update(n=int(n or 0), scope=None, dir=out_dir, done={}, skipped=None, files=[])
+
+
+def _extract_reads_skip(why):
+    import sys
+    from . import dist
+    if EXTRACT_READS["skipped"] is None:
+        EXTRACT_READS["skipped"] = why
+        for f in EXTRACT_READS["files"]:
+            try:
+                os.remove(f)
+                os.rmdir(os.path.dirname(f))      # (once it is empty)
+            except OSError:
+                pass
+        EXTRACT_READS["files"] = []
+        if dist.rank_world()[0] == 0:
+            print("extract_reads: %s and nothing was extracted" % why, file=sys.stderr)
+            sys.stderr.flush()
+
+
+def fastx_record_type(path):
+    """'fasta' or 'fastq': the record type of a FASTA/FASTQ file, plain or gzip, by its first record's marker."""
+    import gzip
+    with open(path, "rb") as f:
+        head = f.read(2)
+    with (gzip.open(path, "rb") if head == b"\x1f\x8b" else open(path, "rb")) as f:
+        for line in f:
+            if line.strip():
+                return "fasta" if line.startswith(b">") else "fastq"
+    return "fastq"
+
+
+def collect_extract_reads(table, kdb, paths):
+    """extracted/<table>_1.<ext> (and _2): every read of `paths` with at least N k-mer hits against `kdb`, a pair when either
+    mate has them.  A no-op unless -x is on; a table that was written under the current scope is not written again."""
+    n = EXTRACT_READS["n"]
+    if not n or EXTRACT_READS["skipped"] is not None:
+        return
+    import sys
+    from . import dist
+    with _EXTRACT_READS_LOCK:
+        done = EXTRACT_READS["done"].setdefault(EXTRACT_READS["scope"], set())
+        if table in done:
+            return
+        if dist.is_distributed():
+            return _extract_reads_skip("runs on one rank only (this run has several)")
+        if kdb.k < 17:
+            return _extract_reads_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % kdb.k)
+        ps = [p for p in paths if p]
+        if any(_lib.input_kind(p) == "bam" for p in ps):
+            return _extract_reads_skip("reads FASTA and FASTQ input only (an input is a BAM)")
+        rs = resident_reads(paths)
+        if rs is None:
+            return _extract_reads_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
+        try:
+            sub = rs.select(kdb, n)
+        except _lib.SSError as e:
+            if e.code != _lib.SS_ERANGE:
+                raise
+            return _extract_reads_skip("cannot name the reads of a sample with a record longer than a block (it was cut)")
+        try:
+            selected = sub.info()["n_records"]
+            flat = sub.read_back()
+        finally:
+            sub.close()
+        keys = _lib.flat_record_keys(flat)
+        del flat
+        out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
+        os.makedirs(out_dir, exist_ok=True)
+        outs = [os.path.join(out_dir, "%s_%d.%s" % (table, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
+        c = _lib.extract_write(ps, keys, outs)
+        done.add(table)
+        EXTRACT_READS["files"].extend(outs)
+        print("extract_reads: %s\tN=%d\tselected on the device %d\twritten %d" % (table, n, selected, c["written"]), file=sys.stderr)
+        sys.stderr.flush()
+
+
 def resident_reads(paths):
     """The sample's reads as flat base blocks in HBM (parsed and copied over PCIe once), or None
     when they would not fit the budget (then every scan streams the files again).  Under

@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -129,6 +129,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
                 before_each(i)
             stage = "layer1"
             dbm.READ_SUPPORT["scope"] = label       # (--read_support: this database's rows, OUT/<label>/read_support.tsv)
+            dbm.EXTRACT_READS.update(scope=label, dir=od)      # (-x: OUT/<label>/extracted/)
             try:
                 cls_dict, l2 = StrainScan.identify_layer1(fq1, fq2, d, od, ldep, sprob)
                 stage = "layer2"
@@ -149,6 +150,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
             finally:
                 dbm.write_read_support(od, label)
                 dbm.READ_SUPPORT["scope"] = None
+                dbm.EXTRACT_READS.update(scope=None, dir=None)
             rows.append((label, d, status))
     if rank == 0:
         write_table(os.path.join(out_dir, TSV), rows)
@@ -165,11 +167,13 @@ def main(argv=None):
     rank, _ = dist.init_from_env()
     out_dir = StrainScan.rank_output_dir(out_dir, rank)
     StrainScan.apply_read_support(args.read_support)
+    StrainScan.apply_extract_reads(args.extract_reads)
     try:
         rows = identify_databases((args.input_fq, args.input_fq2 or ""), dbs, out_dir, ksize=opts["ksize"], ldep=opts["ldep"],
                                   sprob=opts["sprob"], emode=opts["emode"], msn=opts["msn"], pmode=opts["pmode"], rank=rank)
     finally:
         StrainScan.apply_read_support(False)
+        StrainScan.apply_extract_reads(0)
     return 1 if any(st.startswith("error:") for _, _, st in rows) else 0
 
 

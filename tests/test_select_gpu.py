@@ -1,0 +1,318 @@
+"""ss_reads_select (ss_select.hip): the records of a resident set with at least min_hits hits against a table, compacted into a new
+resident set.  For every (table, read set) below and min_hits in {1, 16, 10**9} the subset holds exactly the records the model of
+tests/rs_model.py selects (as a multiset of lines: the order is unspecified), its counts are exact, it scans and supports like any
+other set, and the call leaves the source set and the table's counters alone."""
+import gzip
+import os
+
+import numpy as np
+import pytest
+
+from tests import rs_model
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def L():
+    from strainscan_amd import _lib
+    _lib.require_gpu()
+    return _lib
+
+
+def _rand(rs, n):
+    return np.frombuffer(b"ACGT", np.uint8)[rs.randint(0, 4, size=n)].tobytes()
+
+
+def _distinct(kmers):
+    return list(dict.fromkeys(kmers))
+
+
+def _kfa(kmers):
+    return b"".join(b">1\n" + km + b"\n" for km in kmers)
+
+
+def _all_kmers(g, k, step=1):
+    return [g[i:i + k] for i in range(0, len(g) - k + 1, step)]
+
+
+@pytest.fixture(scope="module")
+def material():
+    """The genome g, the repeat genome, and `src`: what the reads are cut from (both, so that every table is hit)."""
+    rs = np.random.RandomState(2024)
+    g = _rand(rs, 70000)
+    stretch = _rand(rs, 60)
+    rep = b"".join(_rand(rs, 1128) + stretch for _ in range(5))
+    rep += _rand(rs, 6000 - len(rep))
+    junk = _rand(rs, 30000)                    # (shares no 17-mer with the tables worth mentioning: most reads cut here have no hit)
+    src = g + rep + junk
+    return dict(g=g, rep=rep, src=src, junk=junk)
+
+
+TABLES = ["k31_sampled", "k31_dense", "k31_repeat", "k25", "k17"]
+
+
+@pytest.fixture(scope="module")
+def tables(L, material):
+    """name -> (KmerDB, k, model keys)"""
+    g = material["g"]
+    spec = {
+        "k31_sampled": (31, _all_kmers(g, 31, 7), False),                 # inline slots, a Bloom filter
+        "k31_dense": (31, _all_kmers(g[:20000], 31), True),               # solid buckets; expects hits
+        "k31_repeat": (31, _all_kmers(material["rep"], 31), False),       # several k-mers per minimizer offset
+        "k25": (25, _all_kmers(g, 25, 3), False),
+        "k17": (17, _all_kmers(g[:30000], 17), False),                    # three m-mers per k-mer
+    }
+    out = {}
+    for name, (k, kmers, expect) in spec.items():
+        kmers = _distinct(kmers)
+        db = L.KmerDB.from_text(_kfa(kmers), k, True)
+        if expect:
+            db.expect_hits(True)
+        out[name] = (db, k, rs_model.encode_kmers(kmers, k))
+    yield out
+    for db, _, _ in out.values():
+        db.close()
+
+
+def _one_length_block(material):
+    rs = np.random.RandomState(7)
+    src = np.frombuffer(material["src"], np.uint8)
+    starts = rs.randint(0, src.size - 150, size=3000)
+    arr = src[starts[:, None] + np.arange(150)[None, :]].copy()
+    arr[::53, :][np.arange(len(arr[::53])), rs.randint(0, 150, size=len(arr[::53]))] = ord("N")
+    arr[5::211, 0] = ord("N")
+    arr[9::223, 149] = ord("N")
+    return b"".join(a.tobytes() + b"\n" for a in arr)
+
+
+def _ragged_block(material, tail_mod):
+    """Lengths 1, 30, 31, 32 and 150, two long records, lower case, N inside and at the ends, an empty record; the block's length
+    is tail_mod modulo 1024 (its last record is sized for that)."""
+    rs = np.random.RandomState(11)
+    g, src = material["g"], material["src"]
+    recs = []
+    for i in range(2400):
+        ln = (1, 30, 31, 32, 150, 150, 150, 150)[i % 8]
+        s = rs.randint(0, len(src) - ln)
+        r = bytearray(src[s:s + ln])
+        if i % 17 == 0 and ln > 40:
+            a = rs.randint(0, ln - 35)
+            r[a:a + 35] = bytes(r[a:a + 35]).lower()
+        if i % 19 == 0:
+            r[rs.randint(0, ln)] = ord("N")
+        if i % 41 == 0:
+            r[0] = ord("N")
+        if i % 43 == 0:
+            r[-1] = ord("n")
+        recs.append(bytes(r))
+    recs.insert(700, g[1000:3500])             # spans three tiles
+    recs.insert(1500, g[5000:10000].lower()[:2500] + g[7500:10000])
+    block = b"\n".join(recs[:1000]) + b"\n\n" + b"\n".join(recs[1000:]) + b"\n"      # (two '\n' in a row: an empty record)
+    last = (tail_mod - len(block) - 1) % 1024
+    if last < 40:
+        last += 1024
+    block += src[300:300 + last] + b"\n"
+    assert len(block) % 1024 == tail_mod
+    return block
+
+
+def _dense_block(material):
+    """531 reads of 150 bases cut from g[:20000], no N: every one has 120 hits against k31_dense"""
+    rs = np.random.RandomState(5)
+    g = material["g"]
+    return b"".join(g[s:s + 150] + b"\n" for s in rs.randint(0, 20000 - 150, size=531))
+
+
+def _edges_block(material):
+    """the first and the last record of the slab come from g[:20000]; the 300 between them (lengths 1 .. 200) from the junk"""
+    rs = np.random.RandomState(6)
+    g, junk = material["g"], material["junk"]
+    mid = []
+    for _ in range(300):
+        ln = int(rs.randint(1, 201))
+        s = int(rs.randint(0, len(junk) - ln))
+        mid.append(junk[s:s + ln])
+    return g[100:250] + b"\n" + b"\n".join(mid) + b"\n" + g[300:437] + b"\n"
+
+
+def _fastq_gz(path, block, seed):
+    rs = np.random.RandomState(seed)
+    qa = np.frombuffer(b"0123456789BCDEFGHIJ", np.uint8)
+    out = []
+    for i, r in enumerate(block.split(b"\n")):
+        if r:
+            out.append(b"@r%d\n%s\n+\n%s\n" % (i, r, qa[rs.randint(0, qa.size, size=len(r))].tobytes()))
+    with open(path, "wb") as f:
+        f.write(gzip.compress(b"".join(out), 1))
+    assert os.path.getsize(path) >= 1 << 20
+    return path
+
+
+SETS = ["packed", "ascii_binned", "file_order", "ragged_binned", "ragged_1024", "ragged_1025", "gz_pair", "all_dense", "edges"]
+
+
+@pytest.fixture(scope="module")
+def read_sets(L, material, tmp_path_factory):
+    """name -> (ReadSet, its bytes read back)"""
+    import torch
+    keep, out = [], {}
+
+    def flat(block, order, ascii_slabs=False):
+        d = torch.frombuffer(bytearray(block), dtype=torch.uint8).cuda()
+        keep.append(d)
+        L.check(L.lib().ss_test_hook(5, 1 if ascii_slabs else 0), "ss_test_hook")
+        try:
+            rset = L.ReadSet.from_flat_dev(d.data_ptr(), d.numel(), order=order)
+        finally:
+            L.lib().ss_test_hook(5, 0)
+        L.check(L.lib().ss_device_sync(), "sync")
+        return rset
+
+    one = _one_length_block(material)
+    out["packed"] = flat(one, True)
+    assert out["packed"].packed_slabs() >= 1
+    out["ascii_binned"] = flat(one, True, ascii_slabs=True)
+    assert out["ascii_binned"].packed_slabs() == 0
+    out["file_order"] = flat(one, False)
+    out["ragged_binned"] = flat(_ragged_block(material, 0), True)
+    out["ragged_1024"] = flat(_ragged_block(material, 0), False)
+    out["ragged_1025"] = flat(_ragged_block(material, 1), False)
+    out["all_dense"] = flat(_dense_block(material), False)
+    out["edges"] = flat(_edges_block(material), False)
+    # two .fastq.gz files of 1 MB and more: the device path gives each a slab of its own -- record indices run on across slabs
+    rs = np.random.RandomState(13)
+    src = np.frombuffer(material["src"], np.uint8)
+    root = str(tmp_path_factory.mktemp("sel_gz"))
+    paths = []
+    for m in range(2):
+        starts = rs.randint(0, src.size - 150, size=11000)
+        arr = src[starts[:, None] + np.arange(150)[None, :]]
+        paths.append(_fastq_gz(os.path.join(root, "r%d.fastq.gz" % (m + 1)), b"".join(a.tobytes() + b"\n" for a in arr), 100 + m))
+    out["gz_pair"] = L.ReadSet(paths)
+    sets = {name: (r, r.read_back()) for name, r in out.items()}
+    yield sets
+    for r in out.values():
+        r.close()
+
+
+_MODEL = {}
+
+
+def _model(tables, read_sets, tname, sname):
+    """(records, per-record hits of the model), computed once per (table, set)"""
+    if (tname, sname) not in _MODEL:
+        _, k, keys = tables[tname]
+        text = read_sets[sname][1]
+        _MODEL[tname, sname] = ([p for p in text.split(b"\n") if p], rs_model.hits_per_record(text, keys, k))
+    return _MODEL[tname, sname]
+
+
+@pytest.mark.parametrize("min_hits", [1, 16, 10 ** 9])
+@pytest.mark.parametrize("sname", SETS)
+@pytest.mark.parametrize("tname", TABLES)
+def test_select_equals_model(L, tables, read_sets, tname, sname, min_hits):
+    db, k, _ = tables[tname]
+    rset, text = read_sets[sname]
+    recs, per = _model(tables, read_sets, tname, sname)
+    assert per.size == len(recs)
+    want = sorted(r for r, h in zip(recs, per) if h >= min_hits)
+    want_hits = int(per[per >= min_hits].sum())
+    # the scan of the same pair: its counters are what select() must leave alone
+    db.reset()
+    rset.scan_into(db)
+    L.check(L.lib().ss_device_sync(), "sync")
+    before = db.counts_rows().copy()
+    calls = L.select_calls()
+    sub = rset.select(db, min_hits)
+    try:
+        assert L.select_calls() == calls + 1
+        assert (db.counts_rows() == before).all()
+        assert rset.read_back() == text
+        got_text = sub.read_back()
+        got = sorted(p for p in got_text.split(b"\n") if p)
+        info = sub.info()
+        print(tname, sname, min_hits, "records", len(recs), "selected", len(want), "bases", sum(map(len, want)), "device", info["n_records"],
+              info["n_bases"])
+        assert len(got_text) % 16 == 0 and (not got_text or got_text.endswith(b"\n"))
+        assert got == want
+        assert info["n_records"] == len(want) and info["n_bases"] == sum(map(len, want))
+        assert sub.packed_slabs() == 0
+        if not want:
+            assert got_text.replace(b"\n", b"") == b""
+        # the subset is a read set like any other: scanned against the same table it gives the selected records' hits ...
+        db.reset()
+        sub.scan_into(db)
+        L.check(L.lib().ss_device_sync(), "sync")
+        assert int(db.counts_rows().astype(np.uint64).sum()) == want_hits
+        # ... and its support has nothing below min_hits
+        hist, hits = sub.support(db)
+        assert hits == want_hits and int(hist.sum()) == len(want)
+        assert int(hist[:min(min_hits, 64)].sum()) == 0
+        assert (hist == rs_model.histogram(per[per >= min_hits], 65)).all()
+    finally:
+        sub.close()
+
+
+def test_everything_is_selected(L, tables, read_sets):
+    """reads cut from g[:20000] against the dense table at min_hits 1: the whole set, first and last record included"""
+    recs, per = _model(tables, read_sets, "k31_dense", "all_dense")
+    assert len(recs) == 531 and (per == 120).all()
+    sub = read_sets["all_dense"][0].select(tables["k31_dense"][0], 1)
+    try:
+        assert sorted(p for p in sub.read_back().split(b"\n") if p) == sorted(recs)
+        assert sub.info()["n_records"] == 531 and sub.info()["n_bases"] == 531 * 150
+    finally:
+        sub.close()
+
+
+def test_first_and_last_record_of_a_slab(L, tables, read_sets):
+    recs, per = _model(tables, read_sets, "k31_dense", "edges")
+    sel = np.nonzero(per >= 16)[0].tolist()
+    assert sel == [0, len(recs) - 1], sel
+    sub = read_sets["edges"][0].select(tables["k31_dense"][0], 16)
+    try:
+        assert sorted(p for p in sub.read_back().split(b"\n") if p) == sorted([recs[0], recs[-1]])
+    finally:
+        sub.close()
+
+
+def test_lower_case_survives_the_copy(L, tables, read_sets):
+    """from an ASCII slab the copy is byte-exact: the half-lower-case 5 000-base record comes out as it went in"""
+    recs, per = _model(tables, read_sets, "k31_dense", "ragged_1025")
+    long_rec = max(recs, key=len)
+    assert len(long_rec) == 5000 and long_rec[:2500].islower() and per[recs.index(long_rec)] >= 16
+    sub = read_sets["ragged_1025"][0].select(tables["k31_dense"][0], 16)
+    try:
+        assert long_rec in sub.read_back().split(b"\n")
+    finally:
+        sub.close()
+
+
+def test_errors(L, material, tables, read_sets):
+    rset = read_sets["packed"][0]
+    before = L.select_calls()
+    with pytest.raises(L.SSError) as e:
+        rset.select(tables["k25"][0], 0)
+    assert e.value.code == L.SS_EINVAL
+    k15 = L.KmerDB.from_text(_kfa(_distinct(_all_kmers(material["g"][:5000], 15, 5))), 15, True)
+    try:
+        with pytest.raises(L.SSError) as e:
+            rset.select(k15, 1)
+        assert e.value.code == L.SS_ERANGE
+    finally:
+        k15.close()
+    assert L.select_calls() == before
+
+
+def test_nothing_selected_is_a_valid_empty_set(L, tables, read_sets):
+    sub = read_sets["ragged_binned"][0].select(tables["k17"][0], 10 ** 9)
+    try:
+        assert sub.info()["n_records"] == 0 and sub.info()["n_bases"] == 0
+        assert sub.read_back().replace(b"\n", b"") == b""
+        hist, hits = sub.support(tables["k17"][0])
+        assert hits == 0 and int(hist.sum()) == 0
+        sub2 = sub.select(tables["k17"][0], 1)
+        sub2.close()
+    finally:
+        sub.close()
