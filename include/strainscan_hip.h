@@ -321,6 +321,22 @@ int ss_reads_support_calls(uint64_t *n);   /* calls so far in this process (diag
  * than hipcub's int item count holds.  SS_EINVAL: a NULL argument, min_hits == 0, a table and a set on different devices. */
 int ss_reads_select(const ss_db *db, const ss_reads *r, uint32_t min_hits, ss_reads **out);
 int ss_reads_select_calls(uint64_t *n);    /* calls so far in this process (diagnostics; "flag off = not run") */
+/* The same two questions per LABEL of the table's rows (`--by_strain`: a cluster table holds the k-mers of all its strains; the
+ * caller labels the rows that only one of the called strains has).  row_labels[i], i < the table's rows (host memory): 0 = the row
+ * counts for nobody, j in 1..n_labels = it counts for label j.  Rows that share a slot (the same k-mer listed twice) keep their
+ * common label; where they disagree the k-mer counts for nobody.  A hit of label j is a hit of ss_reads_support whose k-mer has
+ * label j, so label j's results are those of ss_reads_support / ss_reads_select against a table of label j's k-mers alone.
+ * ss_reads_support_labeled: hist[(j-1) * n_bins + b] and hits[j-1] as ss_reads_support defines them, kmers[j-1] = the distinct
+ *   k-mers (slots) of label j.  Each label's histogram sums to the set's records.
+ * ss_reads_select_labeled: ss_reads_select on the hits of `label`.
+ * Both are synchronous and read the table's index, never its counters.  SS_ERANGE: as the unlabelled call states it.  SS_EINVAL:
+ * as there, and n_labels outside 1..SS_LABELS_MAX, a row label above n_labels, `label` outside 1..n_labels. */
+#define SS_LABELS_MAX 15
+int ss_reads_support_labeled(const ss_db *db, const ss_reads *r, const uint8_t *row_labels, uint32_t n_labels, uint32_t n_bins,
+                             uint64_t *hist, uint64_t *hits, uint64_t *kmers);
+int ss_reads_select_labeled(const ss_db *db, const ss_reads *r, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                            uint32_t min_hits, ss_reads **out);
+int ss_reads_labeled_calls(uint64_t *n);   /* calls of either so far in this process (diagnostics; "flag off = not run") */
 
 /* --------------------------------------------------------------------------------------------
  * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input

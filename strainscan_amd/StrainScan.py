@@ -122,6 +122,21 @@ def add_arguments(ap, multi=False):
                          "the sample resident on the device, k >= 17, FASTA/FASTQ input and one rank (default: off)")
 
 
+    ap.add_argument("--by_strain", dest="by_strain", action="store_true",
+                    help="With --read_support and/or -x N: attribute reads to the strains called in each multi-strain cluster.  "
+                         "A k-mer counts for a called strain when no other called strain of the cluster has it.  Writes "
+                         "strain_support.tsv (rows C<id>.<n>, n = the strain's number in C<id>/StrainVote.report) and "
+                         "OUT/extracted/C<id>.<n>_1.<ext>; reads that only carry k-mers shared between called strains are in "
+                         "C<id>'s files and in no strain's (default: off)")
+
+
+def refuse_by_strain_alone(ap, args):
+    """--by_strain without --read_support or -x has nothing to write: the parser's error (exit status 2, before any input is
+    opened)."""
+    if args.by_strain and not (args.read_support or args.extract_reads):
+        ap.error("--by_strain needs --read_support and/or -x N")
+
+
 def min_base_qual_arg(text):
     """-q's value: an integer in 0..93, or the parser's error (exit status 2, before any input is opened)."""
     try:
@@ -165,6 +180,13 @@ def apply_extract_reads(n, out_dir=None):
     collect_extract_reads).  stdout and the report files are untouched; 0 turns it off."""
     from . import db
     db.extract_reads_reset(n, out_dir)
+
+
+def apply_by_strain(on):
+    """--by_strain (strainscan_amd.set_by_strain): the multi-strain clusters solved from here on attribute their reads to the called
+    strains (db.collect_by_strain).  stdout, the reports, read_support.tsv and extracted/C<id>_* are untouched."""
+    from . import db
+    db.by_strain_reset(on)
 
 
 def settings(args):
@@ -243,6 +265,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="StrainScan.py", description=usage)
     add_arguments(ap)
     args = ap.parse_args(argv)
+    refuse_by_strain_alone(ap, args)
 
     fq_dir = args.input_fq
     fq2 = args.input_fq2 or ""
@@ -259,13 +282,16 @@ def main(argv=None):
     out_dir = rank_output_dir(out_dir, rank)
     apply_read_support(args.read_support)
     apply_extract_reads(args.extract_reads, out_dir)
+    apply_by_strain(args.by_strain)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:
         from . import db
         db.write_read_support(out_dir)      # (in a finally: the reference's own early exit()s come through here as SystemExit)
+        db.write_strain_support(out_dir)
         db.read_support_reset()
         db.extract_reads_reset()
+        db.by_strain_reset()
 
 
 def cli(main_fn=None):

@@ -199,6 +199,8 @@ def vote_strain_L2(item, counts=None):
                 o.write(str(c) + "\t" + name + " (With_ExtraRegion_covered)" + body + "\t\n")
             else:
                 o.write(str(c) + "\t" + name + body + "\t\n")
+    from .db import collect_by_strain
+    collect_by_strain(cls, db_dir, out_dir + "/StrainVote.report", ksize, [input_fq, fq2])      # (--by_strain)
 
 
 def vote_strain_L2_batch(input_fq, fq2, db_dir, out_dir, ksize, res, l2, msn, pmode, emode):

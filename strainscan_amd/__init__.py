@@ -15,6 +15,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_min_base_qual / get_min_base_qual      (the base-quality mask of `strainscan -q`; process-wide, off by default)
     strainscan_amd.set_read_support                           (`strainscan --read_support`: rows of reads per table, db.READ_SUPPORT)
     strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, db.EXTRACT_READS)
+    strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, db.BY_STRAIN)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -48,6 +49,16 @@ def set_extract_reads(n, out_dir=None):
         raise ValueError("extract_reads must be an integer >= 1 (or 0 for off), not %r" % (n,))
     from . import db
     db.extract_reads_reset(n or 0, out_dir)
+
+
+def set_by_strain(on):
+    """`strainscan --by_strain` for callers of the functions above: from here on vote_strain_L2_batch, after a multi-strain
+    cluster has written its StrainVote.report, attributes reads to the called strains -- with set_read_support on, rows for
+    db.write_strain_support(out_dir) (strain_support.tsv); with set_extract_reads on, extracted/C<id>.<n>_1.<ext>.  A k-mer
+    counts for a called strain when no other called strain of the cluster has it.  Off by default; nothing runs while it is
+    off, or while both of the other two are off."""
+    from . import db
+    db.by_strain_reset(bool(on))
 
 
 def get_min_base_qual():

@@ -110,6 +110,9 @@ SIGNATURES = {
     "ss_reads_support_calls": (i32, [P(u64)]),
     "ss_reads_select": (i32, [vp, vp, u32, P(vp)]),
     "ss_reads_select_calls": (i32, [P(u64)]),
+    "ss_reads_support_labeled": (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
+    "ss_reads_select_labeled": (i32, [vp, vp, vp, u32, u32, u32, P(vp)]),
+    "ss_reads_labeled_calls": (i32, [P(u64)]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
     "ss_scan_reset": (i32, [vp, vp]),
@@ -495,6 +498,47 @@ class ReadSet:
         sub = ReadSet.__new__(ReadSet)
         sub._h = h
         return sub
+
+    def support_labeled(self, kdb, row_labels, n_labels, n_bins=65):
+        """support() per label of the table's rows (ss_reads_support_labeled): row_labels[i] in 0..n_labels for row i of the
+        table, 0 = counts for nobody.  -> (hist np.uint64[n_labels, n_bins], hits np.uint64[n_labels], kmers np.uint64[n_labels]:
+        the distinct k-mers of each label).  Rows that share a k-mer under different labels count for nobody."""
+        lab = _row_labels(kdb, row_labels)
+        nl = max(int(n_labels), 0)
+        hist = np.zeros((max(nl, 1), max(int(n_bins), 1)), np.uint64)
+        hits = np.zeros(max(nl, 1), np.uint64)
+        kmers = np.zeros(max(nl, 1), np.uint64)
+        check(lib().ss_reads_support_labeled(kdb.handle, self._h, ptr(lab), nl, int(n_bins), ptr(hist), ptr(hits), ptr(kmers)),
+              "ss_reads_support_labeled")
+        return hist, hits, kmers
+
+    def select_labeled(self, kdb, row_labels, n_labels, label, min_hits):
+        """select() on the hits of one label (ss_reads_select_labeled): the records with at least `min_hits` hits whose k-mer has
+        label `label`, as a new ReadSet.  The caller closes it."""
+        lab = _row_labels(kdb, row_labels)
+        h = C.c_void_p()
+        check(lib().ss_reads_select_labeled(kdb.handle, self._h, ptr(lab), max(int(n_labels), 0), max(int(label), 0), int(min_hits),
+                                            C.byref(h)), "ss_reads_select_labeled")
+        sub = ReadSet.__new__(ReadSet)
+        sub._h = h
+        return sub
+
+
+LABELS_MAX = 15      # SS_LABELS_MAX (strainscan_hip.h): labels per call of the labelled forms
+
+
+def _row_labels(kdb, row_labels):
+    lab = np.ascontiguousarray(row_labels, np.uint8)
+    if lab.ndim != 1 or lab.size != kdb.n_rows:
+        raise ValueError("one label per row of the table (%d), not %r" % (kdb.n_rows, lab.shape))
+    return lab if lab.size else np.zeros(1, np.uint8)
+
+
+def labeled_calls():
+    """Calls of ss_reads_support_labeled and ss_reads_select_labeled so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_labeled_calls(C.byref(n)), "ss_reads_labeled_calls")
+    return n.value
 
 
 def select_calls():

@@ -292,6 +292,10 @@ struct SupportArgs {
     uint32_t slot;                  // packed slab: positions per record
 };
 int launch_support_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, hipStream_t stream);
+// ss_reads_support_labeled (ss_label.hip): the same with the label sink.  slot_label[n_slots] (indexed like d_counts) is 0 or
+// 1..n_labels; a found k-mer of label j adds 1 to a.rec_hits[(j - 1) * a.rec_limit + record]; label 0 counts nowhere.
+int launch_label_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, const uint8_t *slot_label,
+                       uint32_t n_labels, hipStream_t stream);
 // the scan of one table through the same kernel (ss_minik.hip): launch_scan_mini sends it the tables it does not take itself
 int launch_scan_minik(ss_db *db, const uint8_t *bases_dev, uint64_t n, hipStream_t stream, bool packed);
 // the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster

@@ -33,28 +33,67 @@ struct KShared {
 
 // Where a found k-mer goes (the SINK of scan_minik_kernel).  CountSink: 1 to its counter in the table -- the scan.  SupportSink
 // (ss_reads_support, ss_support.hip): the bit of its start position in a bitmap of the tile in LDS; the tile's tail walks the
-// bitmap beside the record boundaries and adds the hits to rec_hits, one atomic per (lane, record).  The lookup itself -- the
-// one statement of the page format with k at run time -- is the same code for both.
+// bitmap beside the record boundaries and adds the hits to rec_hits, one atomic per (lane, record).  LabelSink
+// (ss_reads_support_labeled, ss_label.hip): the LABEL of its slot (slot_label[], indexed like the counters; 0 = none) in a 4-bit
+// field per position; the tail does the same walk once per label the lane's 16 positions hold, into that label's slice of
+// rec_hits.  The lookup itself -- the one statement of the page format with k at run time -- is the same code for all three.
+// PER_POS: the bits a position has in the tile's LDS (0: none, no tail).
 struct CountSink {
-    static constexpr bool SUPPORT = false;
+    static constexpr int PER_POS = 0;
     uint32_t *__restrict__ counts;
     uint32_t cbase;
     __device__ __forceinline__ void bucket(uint32_t slot, uint32_t *, uint32_t) const { atomicAdd(&counts[slot], 1u); }
     __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *, uint32_t) const { atomicAdd(&counts[cbase + page_slot], 1u); }
 };
 struct SupportSink {
-    static constexpr bool SUPPORT = true;
+    static constexpr int PER_POS = 1;
     ss::SupportArgs a;
     __device__ __forceinline__ void bucket(uint32_t, uint32_t *bits, uint32_t p) const { atomicOr(&bits[p >> 5], 1u << (p & 31u)); }
     __device__ __forceinline__ void inline_slot(uint32_t, uint32_t *bits, uint32_t p) const { atomicOr(&bits[p >> 5], 1u << (p & 31u)); }
 };
-// the tile's LDS: the support variant adds the hit bitmap and the '\n' flags of the tile's bytes (nl[0]: bit 15 = the byte before the tile)
-template <bool SUPPORT> struct KSharedT : KShared { __device__ __forceinline__ uint32_t *bits() { return nullptr; } };
-template <> struct KSharedT<true> : KShared {
-    uint32_t hit[KPOS / 32];
+struct LabelSink {
+    static constexpr int PER_POS = 4;
+    ss::SupportArgs a;                          // rec_hits: [n_labels][rec_limit]
+    const uint8_t *__restrict__ slot_label;     // [n_slots] 0 or 1..n_labels
+    uint32_t cbase, n_labels;
+    __device__ __forceinline__ void mark(uint32_t l, uint32_t *bits, uint32_t p) const { if (l) atomicOr(&bits[p >> 3], l << (4u * (p & 7u))); }
+    __device__ __forceinline__ void bucket(uint32_t slot, uint32_t *bits, uint32_t p) const { mark(slot_label[slot], bits, p); }
+    __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *bits, uint32_t p) const { mark(slot_label[cbase + page_slot], bits, p); }
+};
+static_assert(SS_LABELS_MAX <= 15, "a position's label is a 4-bit field");
+// the tile's LDS: the sinks with a tail add the positions' bits and the '\n' flags of the tile's bytes (nl[0]: bit 15 = the byte before the tile)
+// (LEAN: no '\n' flags -- the label sink over a packed slab, which has no '\n': the 132 bytes are what keeps the 21st one-wave
+// workgroup on a CU)
+template <int PER_POS, bool LEAN> struct KSharedT : KShared {
+    static constexpr int HIT_WORDS = KPOS * PER_POS / 32;
+    uint32_t hit[HIT_WORDS];
     uint16_t nl[KT + 2];
     __device__ __forceinline__ uint32_t *bits() { return hit; }
 };
+template <> struct KSharedT<4, true> : KShared {
+    static constexpr int HIT_WORDS = KPOS * 4 / 32;
+    uint32_t hit[HIT_WORDS];
+    __device__ __forceinline__ uint32_t *bits() { return hit; }
+};
+template <bool LEAN> struct KSharedT<0, LEAN> : KShared { __device__ __forceinline__ uint32_t *bits() { return nullptr; } };
+
+// The hits of a lane's 16 positions to their records: h has PER bits per position (the lowest one set where there is a hit), bnd
+// a bit per position where the record index steps up, r is the record of the first position.  add(record, hits) once per record
+// with hits.
+template <int PER, class T, class ADD>
+__device__ __forceinline__ void hits_to_records(T h, uint32_t bnd, uint64_t r, const ADD &add)
+{
+    for (uint32_t b = bnd; h; r++) {
+        const uint32_t nb = b ? (b & (0u - b)) : 0x10000u;      // the positions before the next boundary
+        T below;
+        if constexpr (PER == 1) below = nb - 1u;
+        else below = b ? ((T)1 << (PER * ((uint32_t)__ffs(b) - 1u))) - (T)1 : ~(T)0;
+        const uint32_t c = sizeof(T) == 8 ? (uint32_t)__popcll(h & below) : (uint32_t)__popc((uint32_t)(h & below));
+        if (c) add(r, c);
+        h &= ~below;
+        b &= ~nb;
+    }
+}
 
 // How the time of a first version went (4 M reads, k = 25, profiles/r06_ab_log.md): one lane per position, four positions of a
 // thread one after the other: 4.0 ms -- 1.9 of it the minimizers (a loop of k - 14 dependent LDS reads per position at five waves
@@ -67,7 +106,7 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
                                                         const uint64_t *__restrict__ mkeys, const uint4 *__restrict__ pages, uint32_t n_pages,
                                                         const SINK sink, const uint32_t *__restrict__ bloom, uint32_t bloom_shift)
 {
-    __shared__ KSharedT<SINK::SUPPORT> S;
+    __shared__ KSharedT<SINK::PER_POS, SINK::PER_POS == 4 && IN == IN_PACKED> S;
     const int t = threadIdx.x;
     const uint32_t W = (uint32_t)(k - ss::MINI_M + 1), F = W - 1u;      // m-mers per k-mer (3..17), flank bases
     const uint64_t kmask = (1ull << (2 * k)) - 1ull, vmask = (1ull << k) - 1ull;
@@ -124,9 +163,9 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
             decode_in<IN>(w, code, inv);
             S.code[t] = code;
             S.inv[t] = (uint16_t)inv;
-            if constexpr (SINK::SUPPORT) {
-                if (t < KPOS / 32) S.hit[t] = 0u;
-                if (IN != IN_PACKED) {
+            if constexpr (SINK::PER_POS != 0) {
+                for (int i = t; i < S.HIT_WORDS; i += KT) S.hit[i] = 0u;
+                if constexpr (IN != IN_PACKED) {
                     S.nl[t + 1] = (uint16_t)newline_mask16(w);
                     if (t == 0) S.nl[0] = (b0 == 0 || bases[b0 - 1] == 0x0Au) ? 0x8000u : 0u;      // (a slab begins behind a boundary)
                 }
@@ -257,12 +296,11 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
         // index steps up (ASCII: a record end, a '\n' behind a byte that is none -- no k-mer starts there; packed: the first
         // position of a slot), r is the record of its first position: the tile's base + the boundaries of the lanes before (a wave
         // prefix sum), or position / slot.  One atomic per (lane, record) with hits: neighbouring lanes, neighbouring words.
-        if constexpr (SINK::SUPPORT) {
+        if constexpr (SINK::PER_POS != 0) {
             const ss::SupportArgs &A = sink.a;
-            const uint32_t hits = (S.hit[t >> 1] >> (16 * (t & 1))) & 0xFFFFu;
             uint32_t bnd = 0;
             uint64_t r = A.rec_base;
-            if (IN == IN_PACKED) {
+            if constexpr (IN == IN_PACKED) {
                 const uint64_t q = b0 / A.slot;
                 const uint32_t rem0 = (uint32_t)(b0 - q * A.slot) + 16u * (uint32_t)t;
                 uint32_t rem = rem0 % A.slot;
@@ -276,12 +314,22 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
                 const uint32_t mine = (uint32_t)__popc(bnd);
                 r += A.tile_base[tile] + wave_inclusive_sum(mine) - mine;
             }
-            for (uint32_t h = hits, b = bnd; h; r++) {
-                const uint32_t nb = b ? (b & (0u - b)) : 0x10000u, below = nb - 1u;      // the positions before the next boundary
-                const uint32_t c = (uint32_t)__popc(h & below);
-                if (c && r < A.rec_limit) atomicAdd(&A.rec_hits[r], c);
-                h &= ~below;
-                b &= ~nb;
+            if constexpr (SINK::PER_POS == 1) {
+                const uint32_t hits = (S.hit[t >> 1] >> (16 * (t & 1))) & 0xFFFFu;
+                hits_to_records<1>(hits, bnd, r, [&](uint64_t rec, uint32_t c) { if (rec < A.rec_limit) atomicAdd(&A.rec_hits[rec], c); });
+            } else {
+                // the lane's sixteen 4-bit labels; label by label (mostly none, or one): the positions that carry it, walked as above
+                uint64_t v = (uint64_t)S.hit[2 * t] | ((uint64_t)S.hit[2 * t + 1] << 32);
+                while (v) {
+                    const uint32_t j = (uint32_t)(v >> (((uint32_t)__ffsll((unsigned long long)v) - 1u) & ~3u)) & 15u;
+                    const uint64_t x = v ^ ((uint64_t)j * 0x1111111111111111ull);
+                    const uint64_t z = ~(x | (x >> 1) | (x >> 2) | (x >> 3)) & 0x1111111111111111ull;      // bit 4 i: position i has label j
+                    if (j <= sink.n_labels) {
+                        uint32_t *__restrict__ rh = A.rec_hits + (uint64_t)(j - 1u) * A.rec_limit;
+                        hits_to_records<4>(z, bnd, r, [&](uint64_t rec, uint32_t c) { if (rec < A.rec_limit) atomicAdd(&rh[rec], c); });
+                    }
+                    v &= ~(z * 15ull);
+                }
             }
         }
     }
@@ -316,6 +364,16 @@ int launch_support_minik(const ss_db *db, const void *bases_dev, uint64_t n, boo
 {
     if (!n || db->layout != 1 || (packed ? a.slot == 0 : a.tile_base == nullptr)) return SS_EINVAL;
     return launch_minik(db, (const uint8_t *)bases_dev, n, packed, SupportSink{a}, stream);
+}
+
+// ... and for ss_reads_support_labeled (ss_label.hip): a found k-mer counts for the label of its slot, in that label's slice of
+// a.rec_hits ([n_labels][a.rec_limit]); slot_label is indexed like the table's counters
+int launch_label_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, const uint8_t *slot_label,
+                       uint32_t n_labels, hipStream_t stream)
+{
+    if (!n || db->layout != 1 || (packed ? a.slot == 0 : a.tile_base == nullptr)) return SS_EINVAL;
+    if (!slot_label || n_labels < 1 || n_labels > SS_LABELS_MAX) return SS_EINVAL;
+    return launch_minik(db, (const uint8_t *)bases_dev, n, packed, LabelSink{a, slot_label, (uint32_t)db->n_mslots, n_labels}, stream);
 }
 
 }  // namespace ss

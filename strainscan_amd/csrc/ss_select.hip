@@ -8,6 +8,8 @@
 //
 // Four passes, each a plain launch; the scratch comes from the stream-ordered pool and goes back before the call returns:
 //   1. rec_hits_of (ss_support.hip): the record base of every tile and rec_hits[], exactly as ss_reads_support makes them.
+//      Passes 2-4 are select_records, which works on whichever slice of rec_hits[] it is given: ss_reads_select_labeled
+//      (ss_label.hip) hands it the hits of one label.
 //   2. record_spans_kernel (ASCII slabs): start[rec] and end[rec].  A lane takes 16 bytes; a record START is a byte other than
 //      '\n' behind a '\n' (or at the slab's first byte), a record END a '\n' behind a byte that is none (and the slab's end behind
 //      such a byte).  Starts and ends alternate, so the record a start belongs to is the number of ends before it: the tile's
@@ -201,8 +203,16 @@ int ss_reads_select(const ss_db *db, const ss_reads *R, uint32_t min_hits, ss_re
     if (R->has_cut_record) return SS_ERANGE;                        // at any k: a cut piece is not a read
     ss::RecHits rh;
     // 1. hits per record
-    int rc = ss::rec_hits_of(db, R, &rh, &g_select_calls);
+    const int rc = ss::rec_hits_of(db, R, &rh, &g_select_calls);
     if (rc) return rc;
+    return ss::select_records(&rh, rh.d_rec_hits, min_hits, out);
+}
+
+}  // extern "C"
+
+int ss::select_records(RecHits *rhp, const uint32_t *d_rec_hits, uint32_t min_hits, ss_reads **out)
+{
+    RecHits &rh = *rhp;
     if (rh.rec_total > 0x7FFFFFFFull) return SS_ERANGE;             // hipcub counts its items in an int
     const hipStream_t st = ss::l2s::stream();
     const uint64_t rec_total = rh.rec_total;
@@ -236,7 +246,7 @@ int ss_reads_select(const ss_db *db, const ss_reads *R, uint32_t min_hits, ss_re
         for (const auto &pt : rh.parts) {
             if (!pt.n_rec) continue;
             const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 4096);
-            hipLaunchKernelGGL(select_len_kernel, dim3(blocks), dim3(256), 0, st, rh.d_rec_hits, d_start, d_end, pt.rec_base, pt.n_rec, pt.n,
+            hipLaunchKernelGGL(select_len_kernel, dim3(blocks), dim3(256), 0, st, d_rec_hits, d_start, d_end, pt.rec_base, pt.n_rec, pt.n,
                                pt.sl->packed ? pt.sl->L : 0u, min_hits, d_len, d_tot);
             SS_HIP(hipGetLastError());
         }
@@ -279,5 +289,3 @@ int ss_reads_select(const ss_db *db, const ss_reads *R, uint32_t min_hits, ss_re
     *out = S;
     return SS_OK;
 }
-
-}  // extern "C"

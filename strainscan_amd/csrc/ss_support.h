@@ -34,10 +34,17 @@ struct RecHits {
     std::vector<Part> parts;             // the set's slabs that hold positions
     uint64_t tiles_total = 0, rec_total = 0;
     uint32_t *d_tile_base = nullptr;     // [tiles_total], ASCII slabs only
-    uint32_t *d_rec_hits = nullptr;      // [rec_total]
+    uint32_t *d_rec_hits = nullptr;      // [n_labels][rec_total] (the plain form: one slice)
     PoolScratch scratch;
 };
-// SS_ERANGE / SS_EINVAL as ss_reads_support states them; *calls is counted once the arguments have passed
-int rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls);
+// SS_ERANGE / SS_EINVAL as ss_reads_support states them; *calls is counted once the arguments have passed.
+// The labelled form (d_slot_label != nullptr: [db->n_slots] labels 0..n_labels, ss_label.hip): slice j - 1 of d_rec_hits holds the
+// hits whose k-mer has label j.
+int rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls, const uint8_t *d_slot_label = nullptr,
+                uint32_t n_labels = 1);
+// pass 3 of ss_reads_support on one slice of rec_hits: hist[n_bins] and *hits (scratch from rh)
+int rec_hits_histogram(RecHits *rh, const uint32_t *d_rec_hits, uint32_t n_bins, uint64_t *hist, uint64_t *hits);
+// passes 2-4 of ss_reads_select (ss_select.hip) on one slice of rec_hits: the records with at least min_hits there, as a new set
+int select_records(RecHits *rh, const uint32_t *d_rec_hits, uint32_t min_hits, ss_reads **out);
 
 }  // namespace ss

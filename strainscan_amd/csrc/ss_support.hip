@@ -16,7 +16,8 @@
 //      tiles, or span many, meet in that array; record indices run on from slab to slab.
 //   3. support_hist_kernel: rec_hits -> bins in LDS per workgroup -> a few global 64-bit atomics.
 // The scratch (4 bytes per record, 4 per tile) comes from the stream-ordered pool and goes back before the call returns.
-// Passes 1 and 2 are rec_hits_of (ss_support.h), which ss_reads_select (ss_select.hip) calls too.
+// Passes 1 and 2 are rec_hits_of (ss_support.h), which ss_reads_select (ss_select.hip) calls too; with slot labels (ss_label.hip)
+// pass 2 runs the label sink and rec_hits[] has a slice per label.  Pass 3 is rec_hits_histogram, on one slice.
 #include "ss_scan_dev.h"
 #include "ss_support.h"
 
@@ -81,7 +82,7 @@ std::atomic<uint64_t> g_support_calls{0};
 }  // namespace
 
 // passes 1 and 2 (ss_support.h): ss_reads_support reduces rec_hits to a histogram, ss_reads_select (ss_select.hip) acts on it
-int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls)
+int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls, const uint8_t *d_slot_label, uint32_t n_labels)
 {
     if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
     if (R->has_cut_record && db->k != 31) return SS_ERANGE;         // cut records carry a 30-base overlap (as ss_scan_reads)
@@ -140,13 +141,14 @@ int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomi
     }
     uint64_t rec_total = 0;
     for (Part &pt : parts) { pt.rec_base = rec_total; rec_total += pt.n_rec; }
-    // 2. hits per record
-    SS_HIP(scratch.get((void **)&d_rec, rec_total * 4));
-    SS_HIP(ss::l2s::set(d_rec, 0, std::max<uint64_t>(rec_total * 4, 16)));
+    // 2. hits per record (the labelled form: a slice per label)
+    SS_HIP(scratch.get((void **)&d_rec, rec_total * 4 * n_labels));
+    SS_HIP(ss::l2s::set(d_rec, 0, std::max<uint64_t>(rec_total * 4 * n_labels, 16)));
     for (const Part &pt : parts) {
         if (pt.n >= (uint64_t)db->k && pt.n_rec) {
             const ss::SupportArgs a{d_rec, pt.sl->packed ? nullptr : d_base + pt.tile_off, pt.rec_base, rec_total, pt.sl->packed ? pt.sl->slot : 0u};
-            const int rc = ss::launch_support_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, st);
+            const int rc = d_slot_label ? ss::launch_label_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, d_slot_label, n_labels, st)
+                                        : ss::launch_support_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, st);
             if (rc) return rc;
         }
     }
@@ -154,6 +156,26 @@ int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomi
     out->rec_total = rec_total;
     out->d_tile_base = d_base;
     out->d_rec_hits = d_rec;
+    return SS_OK;
+}
+
+// 3. histogram and total
+int ss::rec_hits_histogram(RecHits *rh, const uint32_t *d_rec, uint32_t n_bins, uint64_t *hist, uint64_t *hits)
+{
+    const hipStream_t st = ss::l2s::stream();
+    const uint64_t rec_total = rh->rec_total;
+    unsigned long long *d_out = nullptr;
+    SS_HIP(rh->scratch.get((void **)&d_out, ((size_t)n_bins + 1) * 8));
+    SS_HIP(ss::l2s::set(d_out, 0, ((size_t)n_bins + 1) * 8));
+    if (rec_total) {
+        const unsigned blocks = (unsigned)std::min<uint64_t>((rec_total + 256 * 8 - 1) / (256 * 8), 2048);
+        hipLaunchKernelGGL(support_hist_kernel, dim3(blocks), dim3(256), 0, st, d_rec, rec_total, n_bins, d_out);
+        SS_HIP(hipGetLastError());
+    }
+    std::vector<unsigned long long> out((size_t)n_bins + 1);
+    SS_HIP(ss::l2s::copy(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t b = 0; b < n_bins; b++) hist[b] = out[b];
+    *hits = out[n_bins];
     return SS_OK;
 }
 
@@ -172,23 +194,7 @@ int ss_reads_support(const ss_db *db, const ss_reads *R, uint32_t n_bins, uint64
     ss::RecHits rh;
     const int rc = ss::rec_hits_of(db, R, &rh, &g_support_calls);
     if (rc) return rc;
-    const hipStream_t st = ss::l2s::stream();
-    const uint64_t rec_total = rh.rec_total;
-    const uint32_t *d_rec = rh.d_rec_hits;
-    unsigned long long *d_out = nullptr;
-    SS_HIP(rh.scratch.get((void **)&d_out, ((size_t)n_bins + 1) * 8));
-    SS_HIP(ss::l2s::set(d_out, 0, ((size_t)n_bins + 1) * 8));
-    // 3. histogram and total
-    if (rec_total) {
-        const unsigned blocks = (unsigned)std::min<uint64_t>((rec_total + 256 * 8 - 1) / (256 * 8), 2048);
-        hipLaunchKernelGGL(support_hist_kernel, dim3(blocks), dim3(256), 0, st, d_rec, rec_total, n_bins, d_out);
-        SS_HIP(hipGetLastError());
-    }
-    std::vector<unsigned long long> out((size_t)n_bins + 1);
-    SS_HIP(ss::l2s::copy(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost));
-    for (uint32_t b = 0; b < n_bins; b++) hist[b] = out[b];
-    *hits = out[n_bins];
-    return SS_OK;
+    return ss::rec_hits_histogram(&rh, rh.d_rec_hits, n_bins, hist, hits);
 }
 
 }  // extern "C"

@@ -217,7 +217,6 @@ def collect_extract_reads(table, kdb, paths):
     n = EXTRACT_READS["n"]
     if not n or EXTRACT_READS["skipped"] is not None:
         return
-    import sys
     from . import dist
     with _EXTRACT_READS_LOCK:
         done = EXTRACT_READS["done"].setdefault(EXTRACT_READS["scope"], set())
@@ -233,27 +232,195 @@ def collect_extract_reads(table, kdb, paths):
         rs = resident_reads(paths)
         if rs is None:
             return _extract_reads_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
+        _write_selected(table, lambda: rs.select(kdb, n), ps, n, done)
+
+
+def _write_selected(table, select, ps, n, done):
+    """select() -> the ReadSet of the selected records; read back, digested, found in the files `ps` again and written as
+    extracted/<table>_<mate>.<ext> (_EXTRACT_READS_LOCK held)."""
+    import sys
+    try:
+        sub = select()
+    except _lib.SSError as e:
+        if e.code != _lib.SS_ERANGE:
+            raise
+        return _extract_reads_skip("cannot name the reads of a sample with a record longer than a block (it was cut)")
+    try:
+        selected = sub.info()["n_records"]
+        flat = sub.read_back()
+    finally:
+        sub.close()
+    keys = _lib.flat_record_keys(flat)
+    del flat
+    out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
+    os.makedirs(out_dir, exist_ok=True)
+    outs = [os.path.join(out_dir, "%s_%d.%s" % (table, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
+    c = _lib.extract_write(ps, keys, outs)
+    done.add(table)
+    EXTRACT_READS["files"].extend(outs)
+    print("extract_reads: %s\tN=%d\tselected on the device %d\twritten %d" % (table, n, selected, c["written"]), file=sys.stderr)
+    sys.stderr.flush()
+
+
+# --by_strain (StrainScan.apply_by_strain turns it on; it needs --read_support and/or -x): a cluster table holds the k-mers of ALL
+# strains of its cluster, so its row of read_support.tsv and its extracted/C<id>_* are the cluster's reads.  After a cluster's
+# StrainVote.report has been written, collect_by_strain labels the table's rows by the called strain that alone has them
+# (strain_row_labels) and asks the device the same two questions per label (ReadSet.support_labeled / select_labeled): rows of
+# strain_support.tsv, and extracted/C<id>.<n>_1.<ext>.  Rows are kept per scope and cluster (READ_SUPPORT's scope: strainscan-multi
+# sets one per database) and written in the order the clusters were scanned.
+BY_STRAIN = {"on": False, "rows": {}}
+STRAIN_SUPPORT_FILE = "strain_support.tsv"
+_BY_STRAIN_LOCK = threading.Lock()
+EXTRA_REGION_MARK = " (With_ExtraRegion_covered)"      # what -e 1 appends to a strain's name in StrainVote.report
+
+
+def by_strain_reset(on=False):
+    BY_STRAIN.update(on=bool(on), rows={})
+
+
+def strain_support_text(rows):
+    """The text of strain_support.tsv for rows of (table, strain, kmers, reads, hits, hist)."""
+    out = ["table\tstrain\tkmers\treads\thits\t" + "\t".join("ge%d" % t for t in READ_SUPPORT_GE) + "\n"]
+    for table, strain, kmers, reads, hits, hist in rows:
+        out.append("\t".join([table, strain] + [str(int(v)) for v in [kmers, reads, hits] + read_support_ge(hist)]) + "\n")
+    return "".join(out)
+
+
+def called_strains(report_path):
+    """[(n, name)] of a StrainVote.report: its rows in order, n = column 1, name = column 2 without -e's mark."""
+    out = []
+    with open(report_path) as f:
+        f.readline()
+        for line in f:
+            ele = line.rstrip("\n").split("\t")
+            if len(ele) < 2 or not ele[0].strip():
+                break
+            name = ele[1][:-len(EXTRA_REGION_MARK)] if ele[1].endswith(EXTRA_REGION_MARK) else ele[1]
+            out.append((int(ele[0]), name))
+    return out
+
+
+def strain_row_labels(indptr, indices, data, n_rows, called_cols):
+    """np.uint8[n_rows] from a cluster's CSR matrix (row = k-mer, column = strain) and the called columns c_1 .. c_L: row r has
+    label j when it is non-zero in column c_j and in no other called column; every other row -- shared between called strains, or
+    in none of them -- has label 0.  Uncalled columns are not looked at."""
+    indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices)
+    n_mat = indptr.size - 1
+    n_cols = int(indices.max()) + 1 if indices.size else 0
+    col_label = np.zeros(max(n_cols, max(list(called_cols) + [0]) + 1), np.uint8)
+    for j, c in enumerate(called_cols, 1):
+        col_label[c] = j
+    lab = col_label[indices]                                         # the called columns only ...
+    if data is not None and not np.asarray(data).all():
+        lab = np.where(np.asarray(data) != 0, lab, 0).astype(np.uint8)
+    at = np.flatnonzero(lab)                                         # (a few of a cluster's many columns: short from here on)
+    rows = np.searchsorted(indptr, at, side="right") - 1
+    called = np.bincount(rows, minlength=n_mat)                      # ... a row sum over them ...
+    which = np.bincount(rows, weights=lab[at], minlength=n_mat).astype(np.int64)      # ... and, where it is 1, the arg-max
+    out = np.zeros(n_rows, np.uint8)
+    m = min(n_rows, n_mat)
+    out[:m] = np.where(called == 1, which, 0)[:m]
+    return out
+
+
+def cluster_csr_arrays(path):
+    """(indptr, indices, data) of a cluster's all_strains_re.npz.  Members that the archive stores without compression are
+    mapped, not read: np.load copies and checksums them (~7 ms per million non-zeros), and the solver has read and checked this
+    same file in this run already.  Anything else goes the solver's way (_load_npz_csr)."""
+    import zipfile
+    from .identify_strains_L2_Enet_Pscan_new_sp import _load_npz_csr, _npy_header, _npz_directory
+    try:
+        d = _npz_directory(path)
+        out = []
+        with open(path, "rb") as f:
+            for name in ("indptr", "indices", "data"):
+                off, _, _, usize, method = d[name + ".npy"]
+                if method != zipfile.ZIP_STORED:
+                    raise ValueError(name)
+                f.seek(off)
+                dtype, shape, _, hlen = _npy_header(f.read(min(usize, 4096)))
+                if len(shape) != 1 or dtype.hasobject or hlen + dtype.itemsize * shape[0] != usize:
+                    raise ValueError(name)
+                out.append(np.memmap(path, dtype=dtype, mode="r", offset=off + hlen, shape=shape) if shape[0] else np.zeros(0, dtype))
+        with np.load(path, allow_pickle=False) as z:
+            fmt = z["format"].item()
+        if (fmt.decode() if isinstance(fmt, bytes) else fmt) != "csr" or out[0].size < 1 or out[1].size != out[2].size:
+            raise ValueError("format")
+        return tuple(out)
+    except (OSError, KeyError, ValueError, zipfile.BadZipFile):
+        m = _load_npz_csr(path)
+        return m.indptr, m.indices, m.data
+
+
+def collect_by_strain(cls, cls_db_dir, report_path, ksize, paths):
+    """After cluster `cls` ('C<id>') has written report_path: its called strains' rows of strain_support.tsv (--read_support)
+    and their extracted/<cls>.<n>_* files (-x).  A no-op unless --by_strain is on.  Every rank calls this at the same point (it
+    holds collectives)."""
+    if not BY_STRAIN["on"] or not os.path.exists(report_path):
+        return
+    support = READ_SUPPORT["on"] and READ_SUPPORT["skipped"] is None
+    extract = bool(EXTRACT_READS["n"]) and EXTRACT_READS["skipped"] is None
+    if not (support or extract):
+        return
+    from . import dist
+    from .tree import load_plain_pkl
+    with _BY_STRAIN_LOCK:
+        scope = READ_SUPPORT["scope"]
+        rows = BY_STRAIN["rows"].setdefault(scope, {})
+        if cls in rows:
+            return
+        called = called_strains(report_path)
+        if not called:
+            return
+        sid = load_plain_pkl(os.path.join(cls_db_dir, "id2strain_re.pkl"))
+        col_of = {name: c for c, name in (sid.items() if isinstance(sid, dict) else enumerate(sid))}
+        indptr, indices, data = cluster_csr_arrays(os.path.join(cls_db_dir, "all_strains_re.npz"))
+        rs = resident_reads(paths)
+        if rs is None:                                               # (said by --read_support / -x already)
+            return
+        kdb = fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)
         try:
-            sub = rs.select(kdb, n)
-        except _lib.SSError as e:
-            if e.code != _lib.SS_ERANGE:
-                raise
-            return _extract_reads_skip("cannot name the reads of a sample with a record longer than a block (it was cut)")
-        try:
-            selected = sub.info()["n_records"]
-            flat = sub.read_back()
+            if kdb.k < 17:
+                return
+            labels = strain_row_labels(indptr, indices, data, kdb.n_rows, [col_of[name] for _, name in called])
+            n_reads = rs.info()["n_records"]
+            out = []
+            for j0 in range(0, len(called), _lib.LABELS_MAX):        # (more called strains than a call takes: several calls)
+                part = called[j0:j0 + _lib.LABELS_MAX]
+                lab = np.where((labels > j0) & (labels <= j0 + len(part)), labels - j0, 0).astype(np.uint8)
+                if support:
+                    hist, hits, kmers = rs.support_labeled(kdb, lab, len(part), READ_SUPPORT_BINS)
+                    v = np.concatenate([hist.astype(np.int64).ravel(), hits.astype(np.int64), [n_reads]])
+                    if dist.is_distributed():
+                        v = dist.allreduce_int64(v)
+                    hist = v[:hist.size].reshape(hist.shape)
+                    for i, (n, name) in enumerate(part):
+                        out.append(("%s.%d" % (cls, n), name, int(kmers[i]), int(v[-1]), int(v[hist.size + i]), [int(x) for x in hist[i]]))
+                if extract:
+                    with _EXTRACT_READS_LOCK:
+                        done = EXTRACT_READS["done"].setdefault(EXTRACT_READS["scope"], set())
+                        ps = [p for p in paths if p]
+                        for i, (n, name) in enumerate(part):
+                            if EXTRACT_READS["skipped"] is None and "%s.%d" % (cls, n) not in done:
+                                _write_selected("%s.%d" % (cls, n), lambda i=i: rs.select_labeled(kdb, lab, len(part), i + 1, EXTRACT_READS["n"]),
+                                                ps, EXTRACT_READS["n"], done)
+            rows[cls] = out
         finally:
-            sub.close()
-        keys = _lib.flat_record_keys(flat)
-        del flat
-        out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
-        os.makedirs(out_dir, exist_ok=True)
-        outs = [os.path.join(out_dir, "%s_%d.%s" % (table, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
-        c = _lib.extract_write(ps, keys, outs)
-        done.add(table)
-        EXTRACT_READS["files"].extend(outs)
-        print("extract_reads: %s\tN=%d\tselected on the device %d\twritten %d" % (table, n, selected, c["written"]), file=sys.stderr)
-        sys.stderr.flush()
+            kdb.close()
+
+
+def write_strain_support(out_dir, scope=None):
+    """out_dir/strain_support.tsv from the rows collected under `scope`, clusters in the order of read_support.tsv's rows;
+    nothing without --by_strain and --read_support, without rows, or after a skip."""
+    rows = BY_STRAIN["rows"].get(scope)
+    if not BY_STRAIN["on"] or not READ_SUPPORT["on"] or READ_SUPPORT["skipped"] is not None or not rows or not any(rows.values()):
+        return None
+    order = [t for t in READ_SUPPORT["rows"].get(scope, {}) if t in rows]
+    order += sorted(t for t in rows if t not in order)
+    path = os.path.join(out_dir, STRAIN_SUPPORT_FILE)
+    with open(path, "w") as f:
+        f.write(strain_support_text([r for t in order for r in sorted(rows[t], key=lambda r: int(r[0].rsplit(".", 1)[1]))]))
+    return path
 
 
 def resident_reads(paths):

@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -74,6 +74,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="strainscan-multi", description=usage)
     StrainScan.add_arguments(ap, multi=True)
     args = ap.parse_args(argv)
+    StrainScan.refuse_by_strain_alone(ap, args)
     try:
         opts = StrainScan.settings(args)
     except ValueError as e:
@@ -149,6 +150,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
                 status = "error:" + type(e).__name__
             finally:
                 dbm.write_read_support(od, label)
+                dbm.write_strain_support(od, label)     # (--by_strain: OUT/<label>/strain_support.tsv)
                 dbm.READ_SUPPORT["scope"] = None
                 dbm.EXTRACT_READS.update(scope=None, dir=None)
             rows.append((label, d, status))
@@ -168,12 +170,14 @@ def main(argv=None):
     out_dir = StrainScan.rank_output_dir(out_dir, rank)
     StrainScan.apply_read_support(args.read_support)
     StrainScan.apply_extract_reads(args.extract_reads)
+    StrainScan.apply_by_strain(args.by_strain)
     try:
         rows = identify_databases((args.input_fq, args.input_fq2 or ""), dbs, out_dir, ksize=opts["ksize"], ldep=opts["ldep"],
                                   sprob=opts["sprob"], emode=opts["emode"], msn=opts["msn"], pmode=opts["pmode"], rank=rank)
     finally:
         StrainScan.apply_read_support(False)
         StrainScan.apply_extract_reads(0)
+        StrainScan.apply_by_strain(False)
     return 1 if any(st.startswith("error:") for _, _, st in rows) else 0
 
 
