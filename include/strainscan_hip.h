@@ -143,7 +143,9 @@ int ss_gz_range_counters(uint64_t *files, uint64_t *pieces);
  * byte is A C G T or N; see ss_reads_packed_slabs) -- so that a test can hold the two layouts to each other on one read set;
  * 6: how binned slabs of records of one length are made -- value 1: the count pass + atomic placement (records in a bin in
  * no fixed order), 0: the product's choice (keys, a stable radix sort, a gather: records in a bin in file order) -- so that a
- * test or an A/B run can hold the two to each other in one process. */
+ * test or an A/B run can hold the two to each other in one process; 7: value 1: the device walk of a BAM stream declines, as
+ * after its re-walk rounds run out -- ss_reads_load decodes the BAM on the host, ss_bam_select / ss_bam_extract take the record
+ * starts from the host's walk. */
 int ss_test_hook(int which, long long value);
 
 /* The test sets of ShuffleSplit(n_splits, test_size, random_state=seed).split(range(n)) as scikit-learn 0.23
@@ -389,6 +391,42 @@ int ss_bam_decode(const void *stream, uint64_t n, int shard_rank, int shard_worl
 /* BAM inputs so far in this process: out[0] files decoded on the device, out[1] files decoded on the host, out[2] records
  * kept, out[3] records skipped (over all ranks' shares: every rank walks the whole stream).  Any thread. */
 int ss_bam_counters(uint64_t out[4]);
+/* --------------------------------------------------------------------------------------------
+ * Extracted reads from a BAM (`-x` / `--by_strain` on a BAM sample; ss_bam_extract.hip).  The output holds, in file order and
+ * byte for byte (block_size, name, flags, CIGAR, bases, qualities, every tag), every KEPT record of a selected TEMPLATE.  Kept is
+ * the loader's rule: neither 0x100 nor 0x800, l_seq != 0; a record that is not kept is never written, whatever its name.  A kept
+ * record is selected when the flat form the loader makes of it (reverse-complemented for 0x10, under the base-quality mask) has
+ * at least min_hits hits against the table, a hit being that of ss_reads_support -- with row_labels the hits of `label`, as
+ * ss_reads_select_labeled counts them.  A kept record is written when it is selected or when its read name (the bytes before the
+ * first NUL) equals that of a selected record of the same stream: mates, wherever they lie.  Names are compared through a 128-bit
+ * digest of their bytes and length (two independent 64-bit hashes): a true match is never missed, a record is written without one
+ * only on a 128-bit collision.  Needs the stream and the open table only -- no resident set; records of any length.
+ * ss_bam_select: stream = an inflated BAM stream in HOST memory (from "BAM\1").  row_labels == NULL: all hits; else as
+ *   ss_reads_select_labeled.  out: the written records, concatenated, in file order (no header); *out_len their bytes.
+ *   counters: [0] records of the stream, [1] kept, [2] selected by hits, [3] written.  SS_ERANGE with *out_len and the counters
+ *   set when cap is too small; SS_ERANGE for a flat table (k below 17); SS_EIO a damaged stream; SS_EINVAL as
+ *   ss_reads_select(_labeled) (a NULL argument, min_hits == 0, labels out of range).
+ * ss_bam_extract: one BAM file (BGZF, plain gzip or uncompressed) -> out_path, a BGZF BAM: the input's header from "BAM\1" to
+ *   the first record, byte for byte, then those records.  The file is inflated on the device where ss_reads_load would do that
+ *   (1 MB and more, not under SS_GZ_GPU=0), else on the host and uploaded; ss_bam_counters counts it under out[0] or out[1]
+ *   accordingly.  Written to <out_path>.tmp and renamed at the end; nothing is left on an error.  Members are compressed at zlib
+ *   level 1 (SS_BAM_OUT_LEVEL=0..9 changes it).  SS_EINVAL also for an input that is not a BAM.
+ * ss_bgzf_write (host only): head's bytes, then body's, as BGZF members of at most 0xff00 stream bytes each -- the "BC" extra
+ *   field, raw deflate at `level` (0..9), CRC-32, ISIZE -- and the 28-byte EOF block; a member never holds bytes of both.  The
+ *   members are compressed on up to min(16, SS_HOST_THREADS or the CPUs this process may use) threads.  SS_EIO (and no file)
+ *   when path cannot be written.
+ * ss_bam_extract_calls: calls of ss_bam_select and ss_bam_extract so far in this process ("flag off = not run").
+ * ss_bam_extract_timing: the last successful ss_bam_extract, host clock around its synchronised steps (ms): out[0] stream on the
+ *   device (inflate, or host inflate + upload), [1] walk + decode, [2] hits, [3] join, [4] gather, [5] download, [6] compress +
+ *   write, [7] the whole call.
+ * ------------------------------------------------------------------------------------------ */
+int ss_bam_select(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                  uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4]);
+int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                   uint32_t min_hits, const char *out_path, uint64_t counters[4]);
+int ss_bgzf_write(const char *path, const void *head, uint64_t head_n, const void *body, uint64_t body_n, int level);
+int ss_bam_extract_calls(uint64_t *n);
+int ss_bam_extract_timing(double out[8]);
 /* The base-quality mask (jellyfish count -Q; off by default).  With a threshold q in 1..93 every decoder that turns a file or a
  * text into bases -- ss_reads_load, ss_scan_files, ss_scan_files_shard, ss_reader_open / ss_reader_next (a reader keeps the
  * threshold it was opened under), ss_fastx_to_flat, ss_bam_decode -- writes 'N' for a base whose quality is below it:

@@ -119,7 +119,11 @@ def add_arguments(ap, multi=False):
                     help="Also write the reads that carry at least N k-mers of a table to OUT/extracted/<table>_1.<ext> (and _2 "
                          "with -j; a pair when either mate does), for the tree's table and every cluster table scanned at "
                          "layer 2.  An integer >= 1; read_support.tsv's geN columns say how many reads a given N keeps.  Needs "
-                         "the sample resident on the device, k >= 17, FASTA/FASTQ input and one rank (default: off)")
+                         "the sample resident on the device, k >= 17 and one rank.  BAM input (every input a BAM; the sample "
+                         "need not be resident) gives OUT/extracted/<table>_<i>.bam per input file: a BGZF BAM (zlib level 1) "
+                         "with the input's header and, byte for byte and in file order, every record of a template (read name) "
+                         "of which one record has N hits -- mates wherever they lie; secondary (0x100) and supplementary "
+                         "(0x800) records and records without bases are never written (default: off)")
 
 
     ap.add_argument("--by_strain", dest="by_strain", action="store_true",

@@ -140,6 +140,11 @@ SIGNATURES = {
     "ss_input_kind": (i32, [cp, P(i32)]),
     "ss_bam_decode": (i32, [vp, u64, i32, i32, vp, u64, P(u64), P(u64)]),
     "ss_bam_counters": (i32, [P(u64)]),
+    "ss_bam_select": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, u64, P(u64), P(u64)]),
+    "ss_bam_extract": (i32, [cp, vp, vp, u32, u32, u32, cp, P(u64)]),
+    "ss_bgzf_write": (i32, [cp, vp, u64, vp, u64, i32]),
+    "ss_bam_extract_calls": (i32, [P(u64)]),
+    "ss_bam_extract_timing": (i32, [P(C.c_double)]),
     "ss_set_min_base_qual": (i32, [i32]),
     "ss_get_min_base_qual": (i32, []),
     "ss_mask_counters": (i32, [P(u64)]),
@@ -764,6 +769,60 @@ def bam_counters():
     out = (C.c_uint64 * 4)()
     check(lib().ss_bam_counters(out), "ss_bam_counters")
     return dict(zip(("device", "host", "kept", "skipped"), (int(v) for v in out)))
+
+
+BAM_SELECT_COUNTERS = ("records", "kept", "selected", "written")
+
+
+def _label_args(kdb, labels, n_labels, label):
+    if labels is None:
+        return None, 0, 0
+    return ptr(_row_labels(kdb, labels)), max(int(n_labels), 0), max(int(label), 0)
+
+
+def bam_select(stream, kdb, min_hits, labels=None, n_labels=0, label=0):
+    """The kept records of the selected templates of an inflated BAM stream (bytes from b'BAM\\1'), concatenated in file order,
+    and dict(records=, kept=, selected=, written=) (ss_bam_select).  labels: one label per row of the table, the hits counted
+    are those of `label` (as ReadSet.select_labeled)."""
+    stream = bytes(stream)
+    lab, nl, lb = _label_args(kdb, labels, n_labels, label)
+    out = np.empty(max(len(stream), 1), np.uint8)                  # (the records written are records of the stream)
+    n, c = C.c_uint64(), (C.c_uint64 * 4)()
+    check(lib().ss_bam_select(stream, len(stream), kdb.handle, lab, nl, lb, int(min_hits), ptr(out), len(stream), C.byref(n), c),
+          "ss_bam_select")
+    return out[:n.value].tobytes(), dict(zip(BAM_SELECT_COUNTERS, (int(v) for v in c)))
+
+
+def bam_extract(in_path, kdb, min_hits, out_path, labels=None, n_labels=0, label=0):
+    """One BAM file -> out_path, a BGZF BAM of the input's header and the kept records of the selected templates
+    (ss_bam_extract) -> dict(records=, kept=, selected=, written=).  No file is left behind when it fails (SSError)."""
+    lab, nl, lb = _label_args(kdb, labels, n_labels, label)
+    c = (C.c_uint64 * 4)()
+    check(lib().ss_bam_extract(os.fsencode(in_path), kdb.handle, lab, nl, lb, int(min_hits), os.fsencode(out_path), c), "ss_bam_extract")
+    return dict(zip(BAM_SELECT_COUNTERS, (int(v) for v in c)))
+
+
+def bgzf_write(path, head, body, level=1):
+    """head + body as a BGZF file: members of at most 0xff00 bytes each and the EOF block (ss_bgzf_write; host only)."""
+    head, body = bytes(head), bytes(body)
+    check(lib().ss_bgzf_write(os.fsencode(path), head, len(head), body, len(body), int(level)), "ss_bgzf_write")
+
+
+def bam_extract_calls():
+    """Calls of ss_bam_select and ss_bam_extract so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_bam_extract_calls(C.byref(n)), "ss_bam_extract_calls")
+    return n.value
+
+
+BAM_EXTRACT_STEPS = ("stream", "walk_decode", "hits", "join", "gather", "download", "compress_write", "total")
+
+
+def bam_extract_timing():
+    """The last bam_extract in milliseconds, step by step (ss_bam_extract_timing)."""
+    out = (C.c_double * 8)()
+    check(lib().ss_bam_extract_timing(out), "ss_bam_extract_timing")
+    return dict(zip(BAM_EXTRACT_STEPS, (float(v) for v in out)))
 
 
 def set_min_base_qual(q):

@@ -34,6 +34,7 @@
 
 namespace ss {
 std::atomic<uint64_t> g_bam_dev_files{0}, g_bam_host_files{0}, g_bam_kept{0}, g_bam_skipped{0};
+std::atomic<long long> g_hook_bam_walk_decline{0};      // ss_test_hook 7: the device walk declines (as after MAX_ROUNDS)
 }
 
 namespace {
@@ -342,8 +343,10 @@ std::vector<uint64_t> bam_segments(const uint8_t *in, uint64_t in_n, uint64_t n)
 // The inflated stream on the device -> a new device buffer (big_malloc, padded like a block of ss_reads) with the flat block of
 // this rank's kept records.  0 = done, 1 = declined (too many re-walk rounds, too many records: the host decodes it), SS_EIO =
 // damaged, other < 0 = SS_E*.  `seg` are the segment starts of bam_segments.
+// `recs` (ss_bam_extract.hip): the record starts, kept flags and kept ordinals stay with the caller when the call returns 0; with
+// recs->host_rec the starts are the caller's (the host walk: nothing is walked here, and nothing declines but too many records).
 int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t> &seg_in, int shard_rank, int shard_world,
-                    char **d_flat, uint64_t *flat_len, uint64_t *flat_cap, uint64_t *n_records)
+                    char **d_flat, uint64_t *flat_len, uint64_t *flat_cap, uint64_t *n_records, BamRecords *recs)
 {
     hipStream_t st = call_stream_get();
     if (!st) return SS_EHIP;
@@ -356,7 +359,10 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     const int min_qual = min_base_qual();
     auto done = [&](int r) {
         void *scratch[] = {d_lo, d_entry, d_exit, d_base, d_rec, d_len1, d_off, d_count, d_which, d_keep, d_kidx, d_masked, d_tmp};
-        for (void *q : scratch) if (q) hipFreeAsync(q, st);
+        for (void *q : scratch) {
+            if (r == 0 && recs && q && (q == d_rec || q == d_keep || q == d_kidx)) continue;      // the caller's from here on
+            if (q) hipFreeAsync(q, st);
+        }
         hipStreamSynchronize(st);
         call_stream_put(st);
         if (r != 0 && flat) big_put(flat, *flat_cap);
@@ -385,7 +391,12 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     std::vector<uint64_t> entry(n_seg, 0), exit_(n_seg, 0);
     std::vector<uint32_t> count(n_seg, 0);
     uint64_t n_rec = 0;
-    if (hdr_end < n) {
+    const bool given = recs && recs->host_rec;
+    if (given) {
+        n_rec = recs->host_n_rec;
+        if (n_rec >= 0x7FFFFFF0ull) return done(1);
+    } else if (hdr_end < n) {
+        if (g_hook_bam_walk_decline.load()) return done(1);
         entry[0] = hdr_end;
         BM(hipMallocAsync((void **)&d_lo, (n_seg + 1) * 8, st));
         BM(hipMallocAsync((void **)&d_entry, n_seg * 8, st));
@@ -442,13 +453,16 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     }
     uint64_t total = 0, kept = 0;
     if (n_rec) {
-        BM(hipMallocAsync((void **)&d_base, n_seg * 8, st));
         BM(hipMallocAsync((void **)&d_rec, n_rec * 8, st));
         BM(hipMallocAsync((void **)&d_keep, (n_rec + 1) * 4, st));
         BM(hipMallocAsync((void **)&d_kidx, (n_rec + 1) * 4, st));
         BM(hipMallocAsync((void **)&d_len1, (n_rec + 1) * 8, st));
         BM(hipMallocAsync((void **)&d_off, (n_rec + 1) * 8, st));
-        {
+        if (given) {
+            BM(hipMemcpyAsync(d_rec, recs->host_rec, n_rec * 8, hipMemcpyHostToDevice, st));
+            BM(hipStreamSynchronize(st));
+        } else {
+            BM(hipMallocAsync((void **)&d_base, n_seg * 8, st));
             std::vector<uint64_t> base(n_seg);
             uint64_t b = 0;
             for (uint32_t m = 0; m < n_seg; m++) { base[m] = b; b += count[m]; }
@@ -456,9 +470,9 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
             BM(hipMemcpyAsync(d_entry, entry.data(), n_seg * 8, hipMemcpyHostToDevice, st));
             BM(hipMemcpyAsync(d_count, count.data(), n_seg * 4, hipMemcpyHostToDevice, st));
             BM(hipStreamSynchronize(st));                 // (the host vectors go out of scope)
+            hipLaunchKernelGGL(bam_list_kernel, dim3((n_seg + 63) / 64), dim3(64), 0, st, s, n, (const uint64_t *)d_entry, (const uint32_t *)d_count,
+                               (const uint64_t *)d_base, n_seg, d_rec);
         }
-        hipLaunchKernelGGL(bam_list_kernel, dim3((n_seg + 63) / 64), dim3(64), 0, st, s, n, (const uint64_t *)d_entry, (const uint32_t *)d_count,
-                           (const uint64_t *)d_base, n_seg, d_rec);
         const unsigned g = (unsigned)((n_rec + 1 + 255) / 256);
         hipLaunchKernelGGL(bam_keep_kernel, dim3(g), dim3(256), 0, st, s, (const uint64_t *)d_rec, n_rec, d_keep);
         BM(hipGetLastError());
@@ -507,6 +521,7 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     *n_records = own;
     g_bam_kept += kept;
     g_bam_skipped += n_rec - kept;
+    if (recs) { recs->d_rec = d_rec; recs->d_keep = d_keep; recs->d_kidx = d_kidx; recs->n_rec = n_rec; recs->kept = kept; recs->hdr_end = hdr_end; }
     return done(0);
 }
 
@@ -543,28 +558,31 @@ int gz_bam_to_flat_dev(const char *path, int shard_rank, int shard_world, char *
     return rc;
 }
 
-// The host path for one BAM file (INPUT_BAM_GZ or INPUT_BAM_RAW): the stream inflated on the host, decoded -> *flat (malloc, padded like a
-// block of ss_reads).  SS_OK, SS_EIO (damaged: a member's CRC or length, a record, the header), SS_ENOMEM.
-int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, char **flat, uint64_t *flat_len, uint64_t *n_records)
+// The inflated stream of one BAM file on the host (INPUT_BAM_GZ: the host inflaters; INPUT_BAM_RAW: the file mapped).  SS_OK,
+// SS_EIO (unreadable, a member's CRC or length), SS_ENOMEM.
+BamHostStream::~BamHostStream()
 {
-    char *text = nullptr;
-    uint64_t n = 0;
-    const uint8_t *s = nullptr;
-    void *map = nullptr;
-    uint64_t map_n = 0;
+    if (map) munmap(map, map_n);
+    free(text);
+}
+
+int bam_host_stream(const char *path, int kind, BamHostStream *out)
+{
+    char *&text = out->text;
+    uint64_t &n = out->n;
     if (kind == INPUT_BAM_RAW) {
         const int fd = open(path, O_RDONLY);
         if (fd < 0) return SS_EIO;
         struct stat sb;
         if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); return SS_EIO; }
-        map_n = (uint64_t)sb.st_size;
-        map = map_n ? mmap(nullptr, map_n, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+        out->map_n = (uint64_t)sb.st_size;
+        out->map = out->map_n ? mmap(nullptr, out->map_n, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
         close(fd);
-        if (map == MAP_FAILED) return SS_EIO;
-        s = (const uint8_t *)map;
-        n = map_n;
+        if (out->map == MAP_FAILED) { out->map = nullptr; return SS_EIO; }
+        out->s = (const uint8_t *)out->map;
+        n = out->map_n;
     } else if (inflate_whole(path, inflate_budget_bytes(), &text, &n, 0, 0)) {
-        s = (const uint8_t *)text;
+        out->s = (const uint8_t *)text;
     } else {
         // zlib: every member in turn, each checked against its CRC-32 and length (a missing BGZF EOF block is no error).  The whole
         // stream is held, within the same budget as the other host inflaters (SS_INFLATE_MAX_GB): a BAM whose stream is larger
@@ -591,9 +609,38 @@ int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, c
         int zerr = Z_OK;
         gzerror(g, &zerr);
         gzclose(g);
-        if (err != Z_OK || (zerr != Z_OK && zerr != Z_STREAM_END)) { free(text); return err == Z_MEM_ERROR ? SS_ENOMEM : SS_EIO; }
-        s = (const uint8_t *)text;
+        if (err != Z_OK || (zerr != Z_OK && zerr != Z_STREAM_END)) { free(text); text = nullptr; n = 0; return err == Z_MEM_ERROR ? SS_ENOMEM : SS_EIO; }
+        out->s = (const uint8_t *)text;
     }
+    return SS_OK;
+}
+
+// The record starts of a stream in one sequential walk (what the device walk settles on); *hdr_end = the first record's offset.
+// SS_EIO: damaged.
+int bam_host_records(const uint8_t *s, uint64_t n, std::vector<uint64_t> *rec, uint64_t *hdr_end)
+{
+    uint64_t p = 0;
+    int32_t n_ref = 0;
+    if (bam_header(s, n, n, &p, &n_ref) != 1) return SS_EIO;
+    *hdr_end = p;
+    while (p < n) {
+        const uint64_t l = rec_len(s, n, p);
+        if (!l) return SS_EIO;
+        rec->push_back(p);
+        p += l;
+    }
+    return SS_OK;
+}
+
+// The host path for one BAM file (INPUT_BAM_GZ or INPUT_BAM_RAW): the stream inflated on the host, decoded -> *flat (malloc, padded like a
+// block of ss_reads).  SS_OK, SS_EIO (damaged: a member's CRC or length, a record, the header), SS_ENOMEM.
+int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, char **flat, uint64_t *flat_len, uint64_t *n_records)
+{
+    BamHostStream hs;
+    const int src = bam_host_stream(path, kind, &hs);
+    if (src != SS_OK) return src;
+    const uint8_t *s = hs.s;
+    const uint64_t n = hs.n;
     uint64_t len = 0, own = 0, kept = 0, skipped = 0;
     int rc = bam_decode(s, n, shard_rank, shard_world, nullptr, &len, &own, &kept, &skipped);
     char *out = nullptr;
@@ -602,8 +649,6 @@ int bam_host_flat(const char *path, int kind, int shard_rank, int shard_world, c
         if (!out) rc = SS_ENOMEM;
         else rc = bam_decode(s, n, shard_rank, shard_world, out, &len, &own, &kept, &skipped);
     }
-    if (map) munmap(map, map_n);
-    free(text);
     if (rc != SS_OK) { free(out); return rc; }
     memset(out + len, '\n', ss_reads::padded(len) - len);
     *flat = out;

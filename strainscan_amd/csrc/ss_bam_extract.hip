@@ -1,0 +1,588 @@
+// ss_bam_extract.hip -- `-x` / `--by_strain` on a BAM sample: the records of the selected templates, copied out of the inflated
+// stream on the device, written as a BGZF BAM on the host.
+//
+// The FASTQ writer (ss_extract.hip) finds reads again by content because a resident set keeps no map back to file order.  A BAM
+// needs no such map: ss_bam_dev.hip leaves the start of every record (d_rec), the kept flag (d_keep) and the kept ordinal (d_kidx)
+// on the device, and its flat block holds kept record i as non-empty record i -- so the hits of rec_hits_of (ss_support.hip) on
+// that block are indexed by BAM record.  One path, for ss_bam_select (a stream in host memory) and ss_bam_extract (a file):
+//   1  the stream on the device (gpu_gunzip where the loader would use it; else the host inflaters and an upload)
+//   2  bam_to_flat_dev (shard_world 1) with BamRecords: walk, list, keep, length, decode; the record starts from the host walk
+//      when the device walk declines
+//   3  the flat block wrapped as a one-slab ASCII set -> rec_hits_of (with slot labels: the hits of one label), rec_total == kept
+//   4  name_digest_kernel: one lane per record; a kept record's read name (the bytes before the first NUL) -> two independent
+//      64-bit hashes over the bytes and the length, and sel[r] = hits >= N.  ExclusiveSum + compact_kernel + hipcub SortPairs: the
+//      digests of the selected records, sorted by the first hash.  template_len_kernel: a kept record is written when it is
+//      selected or a binary search finds its digest (both hashes) among them; out_len[r] = 4 + block_size, else 0
+//   5  a 64-bit ExclusiveSum of out_len -> offsets; record_gather_kernel: sixteen lanes per written record walk the 16-byte
+//      aligned pieces of the destination (the shape of gather_kernel, ss_select.hip): one load clamped into the stream, one
+//      aligned 16-byte store where the piece is all the record's, byte stores at the edges it shares with its neighbours
+//   6  the result to the host through two pinned buffers, chunk by chunk; ss_bgzf_write compresses the members on host threads.
+// Records that the loader does not keep (0x100, 0x800, no bases) are never written, whatever their name.
+// Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  No device-wide barrier inside a kernel.
+#include "ss_scan_dev.h"
+#include "ss_support.h"
+
+#include <hipcub/hipcub.hpp>
+#include <zlib.h>
+
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <cerrno>
+#include <chrono>
+#include <string>
+#include <thread>
+
+namespace {
+
+__device__ __forceinline__ uint32_t ld32d(const uint8_t *s, uint64_t p)
+{
+    return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24;
+}
+
+// One lane per record r <= n_rec (entry n_rec closes the sums).  A kept record: h1 = FNV-1a (64-bit) over the name's bytes and the
+// eight bytes of its length, h2 = a rotate-xor-multiply hash over the same bytes, closed with the length and the splitmix64
+// finisher; sel = its hits reach min_hits.  A record that is not kept: sel = 0 and a digest nobody asks for.
+__global__ __launch_bounds__(256) void name_digest_kernel(const uint8_t *__restrict__ s, const uint64_t *__restrict__ rec,
+                                                          const uint32_t *__restrict__ keep, const uint32_t *__restrict__ kidx,
+                                                          const uint32_t *__restrict__ hits, uint64_t n_rec, uint32_t min_hits,
+                                                          unsigned long long *__restrict__ h1, unsigned long long *__restrict__ h2,
+                                                          uint32_t *__restrict__ sel)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r > n_rec) return;
+    if (r == n_rec || !keep[r]) { sel[r] = 0u; return; }
+    const uint64_t p = rec[r];
+    const uint32_t lrn = s[p + 12];                                  // (>= 1, the bytes lie inside the record: rec_len)
+    unsigned long long a = 0xCBF29CE484222325ull, b = 0x243F6A8885A308D3ull;
+    uint32_t len = 0;
+    for (; len + 1u < lrn; len++) {
+        const uint32_t c = s[p + 36 + len];
+        if (!c) break;
+        a = (a ^ c) * 0x100000001B3ull;
+        b = (((b << 7) | (b >> 57)) ^ c) * 0x9E3779B97F4A7C15ull;
+    }
+    for (int i = 0; i < 8; i++) a = (a ^ (i == 0 ? len : 0u)) * 0x100000001B3ull;
+    b ^= (unsigned long long)len * 0xD6E8FEB86659FD93ull;
+    b = (b ^ (b >> 30)) * 0xBF58476D1CE4E5B9ull;
+    b = (b ^ (b >> 27)) * 0x94D049BB133111EBull;
+    b ^= b >> 31;
+    h1[r] = a;
+    h2[r] = b;
+    sel[r] = hits[kidx[r]] >= min_hits ? 1u : 0u;
+}
+
+// the digests of the selected records, in record order: (k1, k2)[sidx[r]]
+__global__ __launch_bounds__(256) void compact_kernel(const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sidx,
+                                                      const unsigned long long *__restrict__ h1, const unsigned long long *__restrict__ h2,
+                                                      uint64_t n_rec, unsigned long long *__restrict__ k1, unsigned long long *__restrict__ k2)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_rec || !sel[r]) return;
+    k1[sidx[r]] = h1[r];
+    k2[sidx[r]] = h2[r];
+}
+
+// out_len[r] (r <= n_rec; [n_rec] = 0) = 4 + block_size when kept record r is selected or shares its name's digest with a selected
+// record (k1 ascending, k2 beside it: every entry of the run of equal k1 is looked at, so a true match is never missed), else 0.
+// tot[0] += records written
+__global__ __launch_bounds__(256) void template_len_kernel(const uint8_t *__restrict__ s, const uint64_t *__restrict__ rec,
+                                                           const uint32_t *__restrict__ keep, const uint32_t *__restrict__ sel,
+                                                           const unsigned long long *__restrict__ h1, const unsigned long long *__restrict__ h2,
+                                                           uint64_t n_rec, const unsigned long long *__restrict__ k1,
+                                                           const unsigned long long *__restrict__ k2, uint32_t n_sel,
+                                                           unsigned long long *__restrict__ out_len, unsigned long long *__restrict__ tot)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    unsigned long long cnt = 0;
+    if (r <= n_rec) {
+        unsigned long long len = 0;
+        if (r < n_rec && keep[r]) {
+            bool w = sel[r] != 0u;
+            if (!w && n_sel) {
+                const unsigned long long a = h1[r], b = h2[r];
+                uint32_t lo = 0, hi = n_sel;
+                while (lo < hi) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    if (k1[mid] < a) lo = mid + 1u;
+                    else hi = mid;
+                }
+                for (; lo < n_sel && k1[lo] == a && !w; lo++) w = k2[lo] == b;
+            }
+            if (w) { len = 4ull + ld32d(s, rec[r]); cnt = 1; }
+        }
+        out_len[r] = len;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&tot[0], cnt);
+}
+
+// Sixteen lanes per record; src holds n >= 16 bytes and every written record lies inside them; dst is 16-byte aligned.  A lane takes
+// one aligned 16-byte piece of the destination at a time.  The source bytes that belong there begin at `base`, any alignment, and
+// at an edge piece partly outside the record, even outside the stream: so the 16 bytes are fetched from `base` clamped into the
+// stream, ONE load, and moved to their places with a 128-bit shift.  A piece that is all the record's is one aligned 16-byte store;
+// a piece it shares with a neighbour stores the record's own bytes one by one, and not a byte more.
+__global__ __launch_bounds__(256) void record_gather_kernel(const uint8_t *__restrict__ src, uint64_t n, const uint64_t *__restrict__ rec,
+                                                            const unsigned long long *__restrict__ out_len,
+                                                            const unsigned long long *__restrict__ out_off, uint64_t n_rec,
+                                                            uint8_t *__restrict__ dst)
+{
+    const uint64_t r = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 4;
+    if (r >= n_rec) return;
+    const uint64_t ol = out_len[r];
+    if (!ol) return;                                                    // not written
+    const uint64_t D = out_off[r], S = rec[r];
+    const uint64_t A0 = D & ~15ull, n_pieces = (D + ol - A0 + 15u) >> 4;
+    for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
+        const uint64_t a = A0 + 16u * c;
+        const uint64_t lo = a > D ? a : D, hi = a + 16u < D + ol ? a + 16u : D + ol;      // the record's bytes of this piece: [lo, hi)
+        const int64_t base = (int64_t)S + ((int64_t)a - (int64_t)D);    // source position of the piece's byte 0
+        const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
+        uint4 v;
+        __builtin_memcpy(&v, src + q, 16);
+        unsigned __int128 x;
+        __builtin_memcpy(&x, &v, 16);
+        const int shift = (int)(base - q);                              // byte j of the piece is byte j + shift of what was fetched
+        if (shift >= 16 || shift <= -16) x = 0;                         // (never: a byte of the record lies in the piece)
+        else if (shift > 0) x >>= 8 * shift;
+        else if (shift < 0) x <<= 8 * -shift;
+        if (lo == a && hi == a + 16u) {
+            __builtin_memcpy(&v, &x, 16);
+            *reinterpret_cast<uint4 *>(dst + a) = v;
+        } else {
+            const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
+#pragma unroll
+            for (uint32_t j = 0; j < 16u; j++)
+                if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
+        }
+    }
+}
+
+std::atomic<uint64_t> g_bam_extract_calls{0};
+std::mutex g_timing_mu;
+double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the last ss_bam_extract (ms): ss_bam_extract_timing
+
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+// What the selection leaves: the written records back to back in d_out (big_malloc'ed, out_cap; nullptr when nothing is written)
+struct Selection {
+    char *d_out = nullptr;
+    uint64_t out_cap = 0, total = 0, hdr_end = 0;
+    uint64_t counters[4] = {0, 0, 0, 0};
+    double ms[4] = {0, 0, 0, 0};                   // walk + decode, hits, join, gather
+    ~Selection() { if (d_out) ss::big_put(d_out, out_cap); }
+};
+
+// steps 2 to 5 on a stream that lies on the device (h_stream: the same bytes on the host, or nullptr)
+int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, const std::vector<uint64_t> &seg, const ss_db *db,
+                     const uint8_t *row_labels, uint32_t n_labels, uint32_t label, uint32_t min_hits, Selection *out)
+{
+    auto t0 = Clock::now();
+    // 2. records, kept flags, flat block
+    ss::BamRecords recs;
+    char *flat = nullptr;
+    uint64_t flat_len = 0, flat_cap = 0, n_own = 0;
+    std::vector<uint64_t> host_rec;
+    int rc = ss::bam_to_flat_dev(d_stream, n, seg, 0, 1, &flat, &flat_len, &flat_cap, &n_own, &recs);
+    if (rc == 1) {                                                      // the device walk declined: the host walks
+        std::vector<uint8_t> copy;
+        if (!h_stream) {
+            copy.resize(n);
+            SS_HIP(hipMemcpy(copy.data(), d_stream, n, hipMemcpyDeviceToHost));
+            h_stream = copy.data();
+        }
+        uint64_t hdr_end = 0;
+        rc = ss::bam_host_records(h_stream, n, &host_rec, &hdr_end);
+        if (rc) return rc;
+        recs.host_rec = host_rec.data();
+        recs.host_n_rec = host_rec.size();
+        rc = ss::bam_to_flat_dev(d_stream, n, seg, 0, 1, &flat, &flat_len, &flat_cap, &n_own, &recs);
+        if (rc == 1) return SS_ERANGE;                                  // more records than hipcub's int item count holds
+    }
+    if (rc) return rc;
+    const hipStream_t st = ss::l2s::stream();
+    struct Owned {                                                      // what bam_to_flat_dev handed over
+        ss::BamRecords &r; char *&flat; uint64_t &cap;
+        ~Owned()
+        {
+            for (void *q : {(void *)r.d_rec, (void *)r.d_keep, (void *)r.d_kidx}) if (q) (void)hipFreeAsync(q, ss::l2s::stream());
+            (void)ss::l2s::sync();
+            if (flat) ss::big_put(flat, cap);
+        }
+    } owned{recs, flat, flat_cap};
+    const uint64_t n_rec = recs.n_rec, kept = recs.kept;
+    out->hdr_end = recs.hdr_end;
+    out->counters[0] = n_rec;
+    out->counters[1] = kept;
+    out->ms[0] = ms_since(t0);
+    if (!kept) return SS_OK;
+    // 3. hits per kept record
+    t0 = Clock::now();
+    ss_reads R;
+    {
+        ss_reads::Slab sl;
+        sl.d = flat;
+        sl.cap = flat_cap;
+        sl.used = ss_reads::padded(flat_len);
+        R.slabs.push_back(sl);
+        R.n_records = kept;
+        R.n_bases = flat_len - kept;
+        R.n_blocks = 1;
+    }
+    ss::RecHits rh;
+    uint8_t *d_lab = nullptr;
+    if (row_labels) {
+        rc = ss::slot_labels_for(db, row_labels, n_labels, label, rh.scratch, &d_lab);
+        if (rc) return rc;
+    }
+    rc = ss::rec_hits_of(db, &R, &rh, nullptr, d_lab, 1);
+    if (rc) return rc;
+    SS_HIP(ss::l2s::sync());
+    if (rh.rec_total != kept) {
+        ss::set_last_error("ss_bam_select: the flat block's records are not the kept records", __FILE__, __LINE__, hipErrorUnknown);
+        return SS_EHIP;
+    }
+    out->ms[1] = ms_since(t0);
+    // 4. template join
+    t0 = Clock::now();
+    const uint8_t *s = reinterpret_cast<const uint8_t *>(d_stream);
+    ss::PoolScratch &scratch = rh.scratch;
+    unsigned long long *d_h1 = nullptr, *d_h2 = nullptr, *d_k1 = nullptr, *d_k2 = nullptr, *d_s1 = nullptr, *d_s2 = nullptr;
+    unsigned long long *d_len = nullptr, *d_off = nullptr, *d_tot = nullptr;
+    uint32_t *d_sel = nullptr, *d_sidx = nullptr;
+    void *d_tmp = nullptr;
+    const int items = (int)(n_rec + 1);                                 // (n_rec < 0x7FFFFFF0: bam_to_flat_dev)
+    const unsigned g1 = (unsigned)((n_rec + 1 + 255) / 256);
+    SS_HIP(scratch.get((void **)&d_h1, n_rec * 8));
+    SS_HIP(scratch.get((void **)&d_h2, n_rec * 8));
+    SS_HIP(scratch.get((void **)&d_sel, (n_rec + 1) * 4));
+    SS_HIP(scratch.get((void **)&d_sidx, (n_rec + 1) * 4));
+    SS_HIP(scratch.get((void **)&d_len, (n_rec + 1) * 8));
+    SS_HIP(scratch.get((void **)&d_off, (n_rec + 1) * 8));
+    SS_HIP(scratch.get((void **)&d_tot, 16));
+    SS_HIP(ss::l2s::set(d_tot, 0, 16));
+    hipLaunchKernelGGL(name_digest_kernel, dim3(g1), dim3(256), 0, st, s, (const uint64_t *)recs.d_rec, (const uint32_t *)recs.d_keep,
+                       (const uint32_t *)recs.d_kidx, (const uint32_t *)rh.d_rec_hits, n_rec, min_hits, d_h1, d_h2, d_sel);
+    SS_HIP(hipGetLastError());
+    size_t tb1 = 0, tb2 = 0;
+    SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, d_sel, d_sidx, items, st));
+    SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, d_len, d_off, items, st));
+    const size_t tmp_bytes = std::max(tb1, tb2);
+    SS_HIP(scratch.get(&d_tmp, tmp_bytes));
+    tb1 = tmp_bytes;
+    SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb1, d_sel, d_sidx, items, st));
+    uint32_t n_sel = 0;
+    SS_HIP(ss::l2s::copy(&n_sel, d_sidx + n_rec, 4, hipMemcpyDeviceToHost));
+    out->counters[2] = n_sel;
+    if (n_sel) {
+        SS_HIP(scratch.get((void **)&d_k1, (uint64_t)n_sel * 8));
+        SS_HIP(scratch.get((void **)&d_k2, (uint64_t)n_sel * 8));
+        SS_HIP(scratch.get((void **)&d_s1, (uint64_t)n_sel * 8));
+        SS_HIP(scratch.get((void **)&d_s2, (uint64_t)n_sel * 8));
+        hipLaunchKernelGGL(compact_kernel, dim3(g1), dim3(256), 0, st, (const uint32_t *)d_sel, (const uint32_t *)d_sidx,
+                           (const unsigned long long *)d_h1, (const unsigned long long *)d_h2, n_rec, d_k1, d_k2);
+        SS_HIP(hipGetLastError());
+        size_t sb = 0;
+        void *d_sort = nullptr;
+        SS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, d_k1, d_s1, d_k2, d_s2, (int)n_sel, 0, 64, st));
+        SS_HIP(scratch.get(&d_sort, sb));
+        SS_HIP(hipcub::DeviceRadixSort::SortPairs(d_sort, sb, d_k1, d_s1, d_k2, d_s2, (int)n_sel, 0, 64, st));
+    }
+    hipLaunchKernelGGL(template_len_kernel, dim3(g1), dim3(256), 0, st, s, (const uint64_t *)recs.d_rec, (const uint32_t *)recs.d_keep,
+                       (const uint32_t *)d_sel, (const unsigned long long *)d_h1, (const unsigned long long *)d_h2, n_rec,
+                       (const unsigned long long *)d_s1, (const unsigned long long *)d_s2, n_sel, d_len, d_tot);
+    SS_HIP(hipGetLastError());
+    // 5. offsets and copy
+    tb2 = tmp_bytes;
+    SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb2, d_len, d_off, items, st));
+    unsigned long long total = 0, tot[2] = {0, 0};
+    SS_HIP(hipMemcpyAsync(&total, d_off + n_rec, 8, hipMemcpyDeviceToHost, st));
+    SS_HIP(ss::l2s::copy(tot, d_tot, 16, hipMemcpyDeviceToHost));
+    out->counters[3] = tot[0];
+    out->total = total;
+    out->ms[2] = ms_since(t0);
+    if (!total) return SS_OK;
+    t0 = Clock::now();
+    if (n < 16 || total > n) return SS_EHIP;                            // (a record is 36 bytes and more; the records are the stream's)
+    if (ss::big_malloc((void **)&out->d_out, ss_reads::padded(total), &out->out_cap) != hipSuccess) { out->d_out = nullptr; return SS_ENOMEM; }
+    hipLaunchKernelGGL(record_gather_kernel, dim3((unsigned)((n_rec * 16u + 255u) / 256u)), dim3(256), 0, st, s, n, (const uint64_t *)recs.d_rec,
+                       (const unsigned long long *)d_len, (const unsigned long long *)d_off, n_rec, (uint8_t *)out->d_out);
+    SS_HIP(hipGetLastError());
+    SS_HIP(ss::l2s::sync());
+    out->ms[3] = ms_since(t0);
+    return SS_OK;
+}
+
+// d_src[0, total) -> dst (host, pageable) through two pinned buffers: the copy of a chunk runs beside the host's memcpy of the one before
+int download_chunks(const char *d_src, uint64_t total, char *dst)
+{
+    if (!total) return SS_OK;
+    const hipStream_t st = ss::l2s::stream();
+    const uint64_t CH = std::min<uint64_t>(total, 16ull << 20);
+    char *buf[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ok = true;
+    for (int i = 0; i < 2 && ok; i++)
+        ok = hipHostMalloc((void **)&buf[i], CH, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+    const uint64_t n_ch = (total + CH - 1) / CH;
+    for (uint64_t i = 0; i <= n_ch && ok; i++) {
+        if (i < n_ch) {
+            const uint64_t o = i * CH, l = std::min(CH, total - o);
+            ok = hipMemcpyAsync(buf[i & 1], d_src + o, l, hipMemcpyDeviceToHost, st) == hipSuccess && hipEventRecord(ev[i & 1], st) == hipSuccess;
+        }
+        if (i > 0 && ok) {
+            const uint64_t o = (i - 1) * CH, l = std::min(CH, total - o);
+            ok = hipEventSynchronize(ev[(i - 1) & 1]) == hipSuccess;
+            if (ok) memcpy(dst + o, buf[(i - 1) & 1], l);
+        }
+    }
+    (void)hipStreamSynchronize(st);
+    for (int i = 0; i < 2; i++) {
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+        if (buf[i]) (void)hipHostFree(buf[i]);
+    }
+    if (!ok) { (void)hipGetLastError(); return SS_EHIP; }
+    return SS_OK;
+}
+
+int check_args(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label, uint32_t min_hits)
+{
+    if (!db || min_hits == 0) return SS_EINVAL;
+    if (row_labels && (n_labels < 1 || n_labels > SS_LABELS_MAX || label < 1 || label > n_labels)) return SS_EINVAL;
+    if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
+    return SS_OK;
+}
+
+// a device copy of a host stream (big_malloc; at least 16 bytes)
+struct DeviceCopy {
+    char *d = nullptr;
+    uint64_t cap = 0;
+    int upload(const void *src, uint64_t n)
+    {
+        if (ss::big_malloc((void **)&d, ss_reads::padded(n), &cap) != hipSuccess) { d = nullptr; return SS_ENOMEM; }
+        if (n) SS_HIP(hipMemcpy(d, src, n, hipMemcpyHostToDevice));
+        return SS_OK;
+    }
+    ~DeviceCopy() { if (d) ss::big_put(d, cap); }
+};
+
+unsigned bgzf_threads()
+{
+    unsigned t = ss::host_cpus();
+    if (const char *e = getenv("SS_HOST_THREADS")) t = (unsigned)std::max(1, atoi(e));
+    return std::max(1u, std::min(16u, t));
+}
+
+constexpr uint32_t BGZF_BLOCK = 0xff00;
+const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// one member behind `out`: the 18-byte header with the "BC" field, raw deflate, CRC-32, ISIZE.  zs: a raw-deflate stream at the
+// caller's level; a member that would pass 64 KB (bytes that do not compress) is stored instead, as htslib does
+bool bgzf_member(z_stream *zs, const uint8_t *src, uint32_t len, std::vector<uint8_t> *out)
+{
+    const size_t at = out->size();
+    const size_t room = (size_t)len + (len >> 8) + 1024;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        out->resize(at + 18 + room + 8);
+        z_stream stored;
+        z_stream *z = zs;
+        if (attempt == 1) {
+            memset(&stored, 0, sizeof stored);
+            if (deflateInit2(&stored, 0, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+            z = &stored;
+        } else if (deflateReset(z) != Z_OK) return false;
+        z->next_in = const_cast<Bytef *>(src);
+        z->avail_in = len;
+        z->next_out = out->data() + at + 18;
+        z->avail_out = (uInt)room;
+        const int r = deflate(z, Z_FINISH);
+        const size_t clen = room - z->avail_out;
+        if (attempt == 1) deflateEnd(&stored);
+        if (r != Z_STREAM_END) return false;
+        const size_t bsize = 18 + clen + 8;
+        if (bsize > 65536) continue;
+        uint8_t *h = out->data() + at;
+        const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 'B', 'C', 0x02, 0};
+        memcpy(h, head, 16);
+        h[16] = (uint8_t)((bsize - 1) & 0xFF);
+        h[17] = (uint8_t)((bsize - 1) >> 8);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, len);
+        uint8_t *t = h + 18 + clen;
+        for (int i = 0; i < 4; i++) { t[i] = (uint8_t)(crc >> (8 * i)); t[4 + i] = (uint8_t)(len >> (8 * i)); }
+        out->resize(at + bsize);
+        return true;
+    }
+    return false;
+}
+
+bool write_all(int fd, const uint8_t *p, size_t n)
+{
+    while (n) {
+        const ssize_t w = write(fd, p, std::min<size_t>(n, 1u << 30));
+        if (w < 0) { if (errno == EINTR) continue; return false; }
+        p += w;
+        n -= (size_t)w;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ss_bam_extract_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_bam_extract_calls.load();
+    return SS_OK;
+}
+
+int ss_bam_extract_timing(double out[8])
+{
+    if (!out) return SS_EINVAL;
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    memcpy(out, g_timing, sizeof g_timing);
+    return SS_OK;
+}
+
+int ss_bgzf_write(const char *path, const void *head, uint64_t head_n, const void *body, uint64_t body_n, int level)
+{
+    if (!path || (!head && head_n) || (!body && body_n) || level < 0 || level > 9) return SS_EINVAL;
+    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) return SS_EIO;
+    // the members: the header's, then the body's (a member never holds bytes of both, so the first record starts a member)
+    struct Piece { const uint8_t *p; uint32_t n; };
+    std::vector<Piece> pieces;
+    for (uint64_t o = 0; o < head_n; o += BGZF_BLOCK) pieces.push_back({(const uint8_t *)head + o, (uint32_t)std::min<uint64_t>(BGZF_BLOCK, head_n - o)});
+    for (uint64_t o = 0; o < body_n; o += BGZF_BLOCK) pieces.push_back({(const uint8_t *)body + o, (uint32_t)std::min<uint64_t>(BGZF_BLOCK, body_n - o)});
+    const uint64_t M = pieces.size();
+    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(bgzf_threads(), (M + 63) / 64));
+    std::vector<std::vector<uint8_t>> outs(T);
+    std::vector<char> good(T, 1);
+    auto work = [&](unsigned t) {
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { good[t] = 0; return; }
+        try {
+            for (uint64_t m = M * t / T; m < M * (t + 1) / T && good[t]; m++)
+                if (!bgzf_member(&zs, pieces[m].p, pieces[m].n, &outs[t])) good[t] = 0;
+        } catch (const std::bad_alloc &) { good[t] = 0; }
+        deflateEnd(&zs);
+    };
+    if (T == 1) work(0);
+    else {
+        std::vector<std::thread> pool;
+        for (unsigned t = 0; t < T; t++) pool.emplace_back(work, t);
+        for (auto &th : pool) th.join();
+    }
+    bool ok = true;
+    for (unsigned t = 0; t < T; t++) ok = ok && good[t];
+    for (unsigned t = 0; t < T && ok; t++) ok = write_all(fd, outs[t].data(), outs[t].size());
+    ok = ok && write_all(fd, BGZF_EOF, sizeof BGZF_EOF);
+    ok = (close(fd) == 0) && ok;
+    if (!ok) { unlink(path); return SS_EIO; }
+    return SS_OK;
+}
+
+int ss_bam_select(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                  uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4])
+{
+    if ((!stream && n) || !out_len || !counters || (!out && cap)) return SS_EINVAL;
+    int rc = check_args(db, row_labels, n_labels, label, min_hits);
+    if (rc) return rc;
+    g_bam_extract_calls++;
+    DeviceCopy dc;
+    rc = dc.upload(stream, n);
+    if (rc) return rc;
+    Selection sel;
+    rc = select_on_device(dc.d, n, (const uint8_t *)stream, ss::bam_segments(nullptr, 0, n), db, row_labels, n_labels, label, min_hits, &sel);
+    if (rc) return rc;
+    memcpy(counters, sel.counters, sizeof sel.counters);
+    *out_len = sel.total;
+    if (sel.total > cap) return SS_ERANGE;
+    return download_chunks(sel.d_out, sel.total, (char *)out);
+}
+
+int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                   uint32_t min_hits, const char *out_path, uint64_t counters[4])
+{
+    if (!in_path || !out_path || !counters) return SS_EINVAL;
+    int rc = check_args(db, row_labels, n_labels, label, min_hits);
+    if (rc) return rc;
+    const int kind = ss::input_kind(in_path);
+    if (kind != ss::INPUT_BAM_GZ && kind != ss::INPUT_BAM_RAW) return SS_EINVAL;
+    g_bam_extract_calls++;
+    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const auto t_all = Clock::now();
+    auto t0 = t_all;
+    // 1. the stream on the device: inflated there where the loader would do that, else inflated on the host and uploaded
+    char *d_text = nullptr;
+    uint64_t n = 0;
+    void *lease = nullptr;
+    std::vector<uint64_t> seg;
+    if (kind == ss::INPUT_BAM_GZ && ss::gz_on_gpu() && !ss::g_hook_decline.load()) {
+        const int fd = open(in_path, O_RDONLY);
+        struct stat sb;
+        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= (1 << 20)) {
+            const uint64_t in_n = (uint64_t)sb.st_size;
+            const uint8_t *in = (const uint8_t *)mmap(nullptr, in_n, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (in != MAP_FAILED) {
+                if (in[0] == 0x1f && in[1] == 0x8b && ss::gpu_gunzip(in, in_n, &d_text, &n, &lease, fd)) seg = ss::bam_segments(in, in_n, n);
+                else d_text = nullptr;
+                munmap((void *)in, in_n);
+            }
+        }
+        if (fd >= 0) close(fd);
+    }
+    ss::BamHostStream hs;
+    DeviceCopy dc;
+    if (!d_text) {
+        rc = ss::bam_host_stream(in_path, kind, &hs);
+        if (rc) return rc;
+        n = hs.n;
+        rc = dc.upload(hs.s, n);
+        if (rc) return rc;
+        seg = ss::bam_segments(nullptr, 0, n);
+    }
+    ms[0] = ms_since(t0);
+    Selection sel;
+    rc = select_on_device(d_text ? d_text : dc.d, n, hs.s, seg, db, row_labels, n_labels, label, min_hits, &sel);
+    // 6. header and records to the host, then the file
+    std::vector<uint8_t> head;
+    char *body = nullptr;
+    t0 = Clock::now();
+    if (rc == SS_OK) {
+        try { head.resize(sel.hdr_end); } catch (const std::bad_alloc &) { rc = SS_ENOMEM; }
+        if (rc == SS_OK && sel.hdr_end && hipMemcpy(head.data(), d_text ? d_text : dc.d, sel.hdr_end, hipMemcpyDeviceToHost) != hipSuccess) rc = SS_EHIP;
+    }
+    if (rc == SS_OK && sel.total) {
+        body = (char *)malloc(sel.total);
+        rc = body ? download_chunks(sel.d_out, sel.total, body) : SS_ENOMEM;
+    }
+    if (lease) ss::gpu_gunzip_done(lease);
+    ms[5] = ms_since(t0);
+    if (rc == SS_OK) {
+        t0 = Clock::now();
+        int level = 1;
+        if (const char *e = getenv("SS_BAM_OUT_LEVEL")) level = std::max(0, std::min(9, atoi(e)));
+        const std::string tmp = std::string(out_path) + ".tmp";
+        rc = ss_bgzf_write(tmp.c_str(), head.data(), head.size(), body, sel.total, level);
+        if (rc == SS_OK && rename(tmp.c_str(), out_path) != 0) { unlink(tmp.c_str()); rc = SS_EIO; }
+        ms[6] = ms_since(t0);
+    }
+    free(body);
+    if (rc) return rc;
+    (d_text ? ss::g_bam_dev_files : ss::g_bam_host_files)++;
+    memcpy(counters, sel.counters, sizeof sel.counters);
+    for (int i = 0; i < 4; i++) ms[1 + i] = sel.ms[i];
+    ms[7] = ms_since(t_all);
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    memcpy(g_timing, ms, sizeof ms);
+    return SS_OK;
+}
+
+}  // extern "C"

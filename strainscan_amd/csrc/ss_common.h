@@ -249,6 +249,33 @@ int input_kind(const char *path);
 // it).  SS_EIO: damaged.
 int bam_input(const char *path, int kind, int shard_rank, int shard_world, const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &on_dev,
               const std::function<int(char *, uint64_t, uint64_t)> &on_host);
+// The steps of that path that ss_bam_extract.hip takes on its own (ss_bam_dev.hip).  BamRecords: what a caller of bam_to_flat_dev
+// may keep -- record r of the stream starts at d_rec[r] (n_rec of them), d_keep[r] says whether the loader keeps it and d_kidx[r] is
+// its ordinal among the kept ones, so kept record i is non-empty record i of the flat block (shard_world 1); the three come from
+// the stream-ordered pool (hipFreeAsync on any stream).  host_rec / host_n_rec (in): record starts from bam_host_records, for a
+// stream whose device walk declined.
+struct BamRecords {
+    uint64_t *d_rec = nullptr;
+    uint32_t *d_keep = nullptr, *d_kidx = nullptr;
+    uint64_t n_rec = 0, kept = 0, hdr_end = 0;
+    const uint64_t *host_rec = nullptr;
+    uint64_t host_n_rec = 0;
+};
+int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t> &seg, int shard_rank, int shard_world, char **d_flat,
+                    uint64_t *flat_len, uint64_t *flat_cap, uint64_t *n_records, BamRecords *recs = nullptr);
+std::vector<uint64_t> bam_segments(const uint8_t *in, uint64_t in_n, uint64_t n);      // in = NULL: 64 KB pieces
+struct BamHostStream {                   // the inflated stream on the host: s[0, n), released with the object
+    const uint8_t *s = nullptr;
+    uint64_t n = 0;
+    char *text = nullptr;
+    void *map = nullptr;
+    uint64_t map_n = 0;
+    ~BamHostStream();
+};
+int bam_host_stream(const char *path, int kind, BamHostStream *out);
+int bam_host_records(const uint8_t *s, uint64_t n, std::vector<uint64_t> *rec, uint64_t *hdr_end);
+extern std::atomic<uint64_t> g_bam_dev_files, g_bam_host_files;
+extern std::atomic<long long> g_hook_bam_walk_decline;      // ss_test_hook 7 (ss_bam_dev.hip)
 // What a consumer of input files does with their flat base blocks: ss_scan_files_shard scans them into a table, ss_reads_load
 // keeps them.  ingest_inputs sends every input down the ladder -- BAM, .gz on the device, .gz inflated on the host, the chunked
 // parse, the sequential reader -- and hands each block to the entry of the rung it came from.  `records` / `bases` add up what

@@ -239,7 +239,8 @@ const char *ss_last_error(void) { return ss::g_last_error; }
 // kernel of the page index a table goes through (ss_mini.hip launch_scan_mini: 1 = k = 31 through the per-position kernel, 2 = every
 // k through it, 3 = every k through scan_mini_kernel; 0 = the product's choice): the kernels held to each other, 5 = binned slabs of
 // one length stay ASCII (1) or are packed where they can be (0, the product's choice; ss_reorder.hip order_flat_dev), 6 = one-length
-// slabs take the count + atomic placement (1; ss_reorder.hip).
+// slabs take the count + atomic placement (1; ss_reorder.hip), 7 = the device walk of a BAM stream declines (as after its
+// re-walk rounds run out; ss_bam_dev.hip): the loader decodes on the host, ss_bam_select takes the record starts from the host walk.
 int ss_test_hook(int which, long long value)
 {
     switch (which) {
@@ -249,6 +250,7 @@ int ss_test_hook(int which, long long value)
     case 4: ss::g_hook_generic_k = value; return SS_OK;
     case 5: ss::g_hook_ascii_slabs = value; return SS_OK;
     case 6: ss::g_hook_atomic_binning = value; return SS_OK;
+    case 7: ss::g_hook_bam_walk_decline = value; return SS_OK;
     default: return SS_EINVAL;
     }
 }

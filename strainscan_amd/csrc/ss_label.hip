@@ -95,6 +95,12 @@ int slot_labels_of(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels
 
 }  // namespace
 
+// (ss_support.h: ss_bam_select obtains its slot labels here, as ss_reads_select_labeled does)
+int ss::slot_labels_for(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t only, PoolScratch &scratch, uint8_t **d_slot_label)
+{
+    return slot_labels_of(db, row_labels, n_labels, only, scratch, d_slot_label, nullptr);
+}
+
 extern "C" {
 
 int ss_reads_labeled_calls(uint64_t *n)

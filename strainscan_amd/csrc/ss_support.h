@@ -46,5 +46,8 @@ int rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<ui
 int rec_hits_histogram(RecHits *rh, const uint32_t *d_rec_hits, uint32_t n_bins, uint64_t *hist, uint64_t *hits);
 // passes 2-4 of ss_reads_select (ss_select.hip) on one slice of rec_hits: the records with at least min_hits there, as a new set
 int select_records(RecHits *rh, const uint32_t *d_rec_hits, uint32_t min_hits, ss_reads **out);
+// row labels (host, db->n_rows of them; only != 0: folded to 1 = `only`, 0 = the rest) -> *d_slot_label [db->n_slots] in `scratch`
+// (ss_label.hip); SS_EINVAL for a label above n_labels
+int slot_labels_for(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t only, PoolScratch &scratch, uint8_t **d_slot_label);
 
 }  // namespace ss

@@ -173,6 +173,8 @@ def write_read_support(out_dir, scope=None):
 # by the digest of their sequence, not by position -- a resident set keeps no map back to file order.  "done": the tables written
 # under each scope (strainscan-multi: a database's label, with `dir` = its report directory); "skipped": why nothing is written.
 # "files": what this run has written so far (a skip takes them away again: after a skip the run leaves no extracted/ of its own).
+# A BAM sample (every input a BAM) takes another way: ss_bam_extract per input file and table, from the file and the open table alone --
+# extracted/<table>_<i>.bam holds the input's header and the kept records of the selected templates (_write_selected_bam).
 EXTRACT_READS = {"n": 0, "scope": None, "dir": None, "done": {}, "skipped": None, "files": []}
 EXTRACT_READS_DIR = "extracted"
 _EXTRACT_READS_LOCK = threading.Lock()
@@ -227,12 +229,42 @@ def collect_extract_reads(table, kdb, paths):
         if kdb.k < 17:
             return _extract_reads_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % kdb.k)
         ps = [p for p in paths if p]
-        if any(_lib.input_kind(p) == "bam" for p in ps):
-            return _extract_reads_skip("reads FASTA and FASTQ input only (an input is a BAM)")
+        bam = _extract_inputs_bam(ps)
+        if bam is None:
+            return
+        if bam:
+            return _write_selected_bam(table, kdb, None, 0, 0, ps, n, done)
         rs = resident_reads(paths)
         if rs is None:
             return _extract_reads_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
         _write_selected(table, lambda: rs.select(kdb, n), ps, n, done)
+
+
+def _extract_inputs_bam(ps):
+    """True: every input is a BAM (-x writes BAM subsets, from the files and the open table alone); False: none is; None: a mix,
+    refused (_EXTRACT_READS_LOCK held)."""
+    bam = [_lib.input_kind(p) == "bam" for p in ps]
+    if any(bam) and not all(bam):
+        _extract_reads_skip("takes BAM inputs or FASTA/FASTQ inputs, not both (this run mixes them)")
+        return None
+    return bool(bam) and all(bam)
+
+
+def _write_selected_bam(table, kdb, labels, n_labels, label, ps, n, done):
+    """extracted/<table>_<i>.bam for each BAM input i: its header and the kept records of the templates with a record of at least
+    n hits against kdb (of `label` when labels are given), selected and copied on the device (_lib.bam_extract;
+    _EXTRACT_READS_LOCK held)."""
+    import sys
+    out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
+    os.makedirs(out_dir, exist_ok=True)
+    for i, p in enumerate(ps):
+        out = os.path.join(out_dir, "%s_%d.bam" % (table, i + 1))
+        c = _lib.bam_extract(p, kdb, n, out, labels, n_labels, label)
+        EXTRACT_READS["files"].append(out)
+        print("extract_reads: %s\tN=%d\tfile %d\tkept %d\tselected on the device %d\twritten %d" %
+              (table, n, i + 1, c["kept"], c["selected"], c["written"]), file=sys.stderr)
+    done.add(table)
+    sys.stderr.flush()
 
 
 def _write_selected(table, select, ps, n, done):
@@ -375,15 +407,19 @@ def collect_by_strain(cls, cls_db_dir, report_path, ksize, paths):
         sid = load_plain_pkl(os.path.join(cls_db_dir, "id2strain_re.pkl"))
         col_of = {name: c for c, name in (sid.items() if isinstance(sid, dict) else enumerate(sid))}
         indptr, indices, data = cluster_csr_arrays(os.path.join(cls_db_dir, "all_strains_re.npz"))
+        ps = [p for p in paths if p]
+        bam = extract and bool(ps) and all(_lib.input_kind(p) == "bam" for p in ps)      # (-x on a BAM needs no resident set)
         rs = resident_reads(paths)
         if rs is None:                                               # (said by --read_support / -x already)
-            return
+            support = False
+            if not bam:
+                return
         kdb = fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)
         try:
             if kdb.k < 17:
                 return
             labels = strain_row_labels(indptr, indices, data, kdb.n_rows, [col_of[name] for _, name in called])
-            n_reads = rs.info()["n_records"]
+            n_reads = rs.info()["n_records"] if support else 0
             out = []
             for j0 in range(0, len(called), _lib.LABELS_MAX):        # (more called strains than a call takes: several calls)
                 part = called[j0:j0 + _lib.LABELS_MAX]
@@ -399,11 +435,14 @@ def collect_by_strain(cls, cls_db_dir, report_path, ksize, paths):
                 if extract:
                     with _EXTRACT_READS_LOCK:
                         done = EXTRACT_READS["done"].setdefault(EXTRACT_READS["scope"], set())
-                        ps = [p for p in paths if p]
                         for i, (n, name) in enumerate(part):
-                            if EXTRACT_READS["skipped"] is None and "%s.%d" % (cls, n) not in done:
+                            if EXTRACT_READS["skipped"] is not None or "%s.%d" % (cls, n) in done:
+                                continue
+                            if bam:
+                                _write_selected_bam("%s.%d" % (cls, n), kdb, lab, len(part), i + 1, ps, EXTRACT_READS["n"], done)
+                            else:
                                 _write_selected("%s.%d" % (cls, n), lambda i=i: rs.select_labeled(kdb, lab, len(part), i + 1, EXTRACT_READS["n"]),
-                                                ps, EXTRACT_READS["n"], done)
+                                                    ps, EXTRACT_READS["n"], done)
             rows[cls] = out
         finally:
             kdb.close()
