@@ -271,6 +271,11 @@ int ss_ingest_threads(int *n);
 /* A resident read set from a flat base block that is already on the device (copied; order != 0: its records are put
  * in locality order, see below). */
 int ss_reads_from_flat_dev(const void *flat_dev, uint64_t n, int order, ss_reads **out);
+/* The records of a set that is in file order (ss_reads_from_flat_dev with order = 0, what ss_reads_select and ss_reads_resample
+ * return) put in locality order in place, whatever SS_READS_ORDER says: every slab that is not binned yet is replaced by its binned
+ * (where its records allow it: packed) copy; slabs below 64 bytes stay.  The records and every count are unchanged.  Waits for the
+ * device first (a scan in flight reads the slabs that are replaced).  SS_EINVAL: NULL. */
+int ss_reads_order(ss_reads *r);
 /* Where the last binning of a read set spent its time, in ms.  Records of one length (the sorted path): out[0] key pass + radix
  * sort (device time), out[1] the driver's allocation of the new slab (0.3 ms, or 60-90 ms for 3 GB on a box whose driver clears
  * the memory first), out[2] gather + tail (and the ASCII gather again where a byte is not A C G T N).  The general passes and
@@ -339,6 +344,22 @@ int ss_reads_support_labeled(const ss_db *db, const ss_reads *r, const uint8_t *
 int ss_reads_select_labeled(const ss_db *db, const ss_reads *r, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
                             uint32_t min_hits, ss_reads **out);
 int ss_reads_labeled_calls(uint64_t *n);   /* calls of either so far in this process (diagnostics; "flag off = not run") */
+/* A resident set resampled with replacement, as a NEW resident set (`--bootstrap`): every record of r (a record is that of
+ * ss_reads_support) appears in *out w times, w in 0..13, a Poisson(1) draw.  The layout of *out is that of ss_reads_select: one
+ * ASCII, unbinned slab, each copy's bytes and '\n', the block padded with '\n', letters from a packed slab as ss_reads_read_back
+ * writes them, n_records and n_bases of ss_reads_info exact, the order unspecified; nothing drawn: a valid set of 0 records.
+ * w depends on the record's BYTES only, so file order, binned ASCII, packed slabs and any sharding over ranks draw the same
+ * weight for the same read -- and identical reads share a weight.  It is, all arithmetic mod 2^64:
+ *   key = the second 64-bit half of the record's digest (keys[2i + 1] of ss_flat_record_keys) over its flat bytes; from a
+ *         packed slab these are the letters of its ASCII form
+ *   x = key + 0x9E3779B97F4A7C15 * (replicate + 1) + 0xD6E8FEB86659FD93 * seed
+ *   x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;  x ^= x >> 31;  u = x >> 32
+ *   w = the number of entries T_k <= u of T_k = floor(2^32 * e^-1 * sum_{i <= k} 1/i!), k = 0..12:
+ *       1580030168 3160060337 3950075421 4213413783 4279248373 4292415291 4294609777
+ *       4294923276 4294962463 4294966817 4294967252 4294967292 4294967295
+ * Synchronous.  SS_EINVAL: a NULL argument.  SS_ERANGE: a set with a cut record; more records than hipcub's int item count holds. */
+int ss_reads_resample(const ss_reads *r, uint64_t seed, uint32_t replicate, ss_reads **out);
+int ss_reads_resample_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
 
 /* --------------------------------------------------------------------------------------------
  * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input

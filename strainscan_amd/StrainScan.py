@@ -132,6 +132,16 @@ def add_arguments(ap, multi=False):
                          "strain_support.tsv (rows C<id>.<n>, n = the strain's number in C<id>/StrainVote.report) and "
                          "OUT/extracted/C<id>.<n>_1.<ext>; reads that only carry k-mers shared between called strains are in "
                          "C<id>'s files and in no strain's (default: off)")
+    ap.add_argument("--bootstrap", dest="bootstrap", type=bootstrap_arg, default=0, metavar="B",
+                    help="Also write strain_bootstrap.tsv: for every strain called in a multi-strain cluster, the 2.5 %% and 97.5 %% "
+                         "points of its depth and of its share of the cluster over B replicates, and in how many of them it is "
+                         "present.  A replicate resamples the reads with replacement on the device (a Poisson bootstrap over reads), "
+                         "re-counts the cluster's k-mers and solves again with the called strains and the penalty held fixed: the "
+                         "intervals are conditional on both and on the cluster's abundance, mates are resampled independently and "
+                         "identical reads together -- a lower bound on the real uncertainty.  An integer in 2..1000; needs the "
+                         "sample resident on the device and k >= 17 (default: off)")
+    ap.add_argument("--bootstrap_seed", dest="bootstrap_seed", type=bootstrap_seed_arg, default=1, metavar="S",
+                    help="The seed of --bootstrap's replicates: the same S gives the same file.  An integer in 0..2^63-1 (default: 1)")
 
 
 def refuse_by_strain_alone(ap, args):
@@ -163,6 +173,28 @@ def extract_reads_arg(text):
     return n
 
 
+def bootstrap_arg(text):
+    """--bootstrap's value: an integer in 2..1000, or the parser's error (exit status 2, before any input is opened)."""
+    try:
+        b = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer in 2..1000" % text)
+    if not 2 <= b <= 1000:
+        raise argparse.ArgumentTypeError("%d is outside 2..1000" % b)
+    return b
+
+
+def bootstrap_seed_arg(text):
+    """--bootstrap_seed's value: an integer in 0..2^63-1, or the parser's error (exit status 2, before any input is opened)."""
+    try:
+        s = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer in 0..2^63-1" % text)
+    if not 0 <= s <= (1 << 63) - 1:
+        raise argparse.ArgumentTypeError("%d is outside 0..2^63-1" % s)
+    return s
+
+
 def apply_min_base_qual(q):
     """-q Q: the process-wide threshold (strainscan_amd.set_min_base_qual); the load of the sample then writes ONE line to stderr
     (db.resident_reads: the threshold, bases masked / bases read and, if any, the BAM records that carried no qualities).
@@ -191,6 +223,14 @@ def apply_by_strain(on):
     strains (db.collect_by_strain).  stdout, the reports, read_support.tsv and extracted/C<id>_* are untouched."""
     from . import db
     db.by_strain_reset(on)
+
+
+def apply_bootstrap(b, seed=1):
+    """--bootstrap B --bootstrap_seed S (strainscan_amd.set_bootstrap): the multi-strain clusters solved from here on are solved
+    B more times on resampled reads (db.collect_bootstrap); the command writes strain_bootstrap.tsv when it ends.  stdout and
+    the other files are untouched; 0 turns it off."""
+    from . import db
+    db.bootstrap_reset(b, seed)
 
 
 def settings(args):
@@ -287,15 +327,18 @@ def main(argv=None):
     apply_read_support(args.read_support)
     apply_extract_reads(args.extract_reads, out_dir)
     apply_by_strain(args.by_strain)
+    apply_bootstrap(args.bootstrap, args.bootstrap_seed)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:
         from . import db
         db.write_read_support(out_dir)      # (in a finally: the reference's own early exit()s come through here as SystemExit)
         db.write_strain_support(out_dir)
+        db.write_bootstrap(out_dir)
         db.read_support_reset()
         db.extract_reads_reset()
         db.by_strain_reset()
+        db.bootstrap_reset()
 
 
 def cli(main_fn=None):

@@ -16,6 +16,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_read_support                           (`strainscan --read_support`: rows of reads per table, db.READ_SUPPORT)
     strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, db.EXTRACT_READS)
     strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, db.BY_STRAIN)
+    strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, db.BOOTSTRAP)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -59,6 +60,21 @@ def set_by_strain(on):
     off, or while both of the other two are off."""
     from . import db
     db.by_strain_reset(bool(on))
+
+
+def set_bootstrap(b, seed=1):
+    """`strainscan --bootstrap B --bootstrap_seed S` for callers of the functions above: from here on vote_strain_L2_batch, after
+    a multi-strain cluster has written its StrainVote.report, solves the cluster `b` more times, each on the reads resampled with
+    replacement on the device (ReadSet.resample(seed, replicate)), with the called strains and the penalty of the main solve held
+    fixed.  db.bootstrap_replicates() returns the replicate coefficients, db.write_bootstrap(out_dir) writes strain_bootstrap.tsv.
+    b is an integer in 2..1000 (0 or None turns it off), seed an integer in 0..2^63-1.  Off by default; nothing runs while it is
+    off."""
+    if b and (isinstance(b, bool) or not isinstance(b, int) or not 2 <= b <= 1000):
+        raise ValueError("bootstrap must be an integer in 2..1000 (or 0 for off), not %r" % (b,))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= (1 << 63) - 1:
+        raise ValueError("bootstrap seed must be an integer in 0..2^63-1, not %r" % (seed,))
+    from . import db
+    db.bootstrap_reset(b or 0, seed)
 
 
 def get_min_base_qual():

@@ -113,6 +113,9 @@ SIGNATURES = {
     "ss_reads_support_labeled": (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
     "ss_reads_select_labeled": (i32, [vp, vp, vp, u32, u32, u32, P(vp)]),
     "ss_reads_labeled_calls": (i32, [P(u64)]),
+    "ss_reads_resample": (i32, [vp, u64, u32, P(vp)]),
+    "ss_reads_resample_calls": (i32, [P(u64)]),
+    "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
     "ss_scan_reset": (i32, [vp, vp]),
@@ -528,8 +531,24 @@ class ReadSet:
         sub._h = h
         return sub
 
+    def order(self):
+        """Put the records of a set in file order (from_flat_dev(order=False), select(), resample()) in locality order, in place
+        (ss_reads_order): the records and every count stay, a scan of a cluster table gets faster.  -> self"""
+        check(lib().ss_reads_order(self._h), "ss_reads_order")
+        return self
 
-LABELS_MAX = 15      # SS_LABELS_MAX (strainscan_hip.h): labels per call of the labelled forms
+    def resample(self, seed, replicate):
+        """A new ReadSet: every record of this one w times, w in 0..13 a Poisson(1) draw that depends on the record's bytes,
+        `seed` and `replicate` alone (ss_reads_resample; tests/boot_model.py restates it) -- identical reads share a weight.  One
+        ASCII, unbinned block in an unspecified order.  The caller closes it."""
+        h = C.c_void_p()
+        check(lib().ss_reads_resample(self._h, int(seed), int(replicate), C.byref(h)), "ss_reads_resample")
+        sub = ReadSet.__new__(ReadSet)
+        sub._h = h
+        return sub
+
+
+LABELS_MAX = 15     # SS_LABELS_MAX (strainscan_hip.h): labels per call of the labelled forms
 
 
 def _row_labels(kdb, row_labels):
@@ -550,6 +569,13 @@ def select_calls():
     """Calls of ss_reads_select so far in this process."""
     n = C.c_uint64()
     check(lib().ss_reads_select_calls(C.byref(n)), "ss_reads_select_calls")
+    return n.value
+
+
+def resample_calls():
+    """Calls of ss_reads_resample so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_resample_calls(C.byref(n)), "ss_reads_resample_calls")
     return n.value
 
 

@@ -866,6 +866,30 @@ int ss_reads_from_flat_dev(const void *flat_dev, uint64_t n, int order, ss_reads
     return SS_OK;
 }
 
+int ss_reads_order(ss_reads *r)
+{
+    if (!r) return SS_EINVAL;
+    bool any = false;
+    for (const auto &sl : r->slabs) any = any || (!sl.binned && sl.used >= 64);
+    if (!any) return SS_OK;
+    if (hipDeviceSynchronize() != hipSuccess) return SS_EHIP;      // (a scan of the set in flight reads the slabs that are replaced)
+    std::lock_guard<std::mutex> g(r->mu);
+    uint64_t bytes = 0;
+    for (auto &sl : r->slabs) {
+        if (!sl.binned && sl.used >= 64) {
+            ss_reads::Slab nsl;
+            const int rc = ss::order_flat_dev(sl.d, sl.used, &nsl);
+            if (rc) return rc;
+            ss::big_put(sl.d, sl.cap);
+            sl = nsl;
+        }
+        bytes += sl.cap;
+    }
+    r->device_bytes = bytes;
+    r->serial = ss_reads::next_serial();                            // another set as far as a table's probe memory goes
+    return SS_OK;
+}
+
 int ss_reads_order_timing(double out_ms[3])
 {
     if (!out_ms) return SS_EINVAL;

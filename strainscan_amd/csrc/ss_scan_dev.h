@@ -237,6 +237,35 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v)
     return v;
 }
 
+// positions [s, s + 16) of a packed slab (s + 16 <= its positions) as the 16 letters its ASCII form holds inside a record: the
+// three 3-byte units around them, fetched as twelve bytes from the first unit on (a packed slab has 8 readable bytes behind its
+// last group, IN_PACKED, and its last unit but one begins 6 bytes before the end).  ss_select.hip's gather, ss_resample.hip's digest.
+__device__ __forceinline__ uint4 packed_letters16(const uint8_t *__restrict__ pk, uint64_t s)
+{
+    uint32_t t[3];
+    __builtin_memcpy(t, pk + (s >> 3) * 3u, 12);
+    const uint32_t sh = (uint32_t)s & 7u;
+    const uint64_t lo = (uint64_t)t[0] | ((uint64_t)t[1] << 32);
+    uint64_t code = (lo & 0xFFFFull) | (((lo >> 24) & 0xFFFFull) << 16) | ((lo >> 48) << 32);      // bytes 0 1, 3 4, 6 7
+    uint32_t inv = (uint32_t)((lo >> 16) & 0xFFull) | (uint32_t)(((lo >> 40) & 0xFFull) << 8) | ((t[2] & 0xFFu) << 16);      // bytes 2, 5, 8
+    code >>= 2u * sh;
+    inv >>= sh;
+    uint32_t w[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int i = 4 * d + b;
+            const uint32_t c = (uint32_t)(code >> (2 * i)) & 3u;
+            const uint32_t ch = ((inv >> i) & 1u) ? (uint32_t)'N' : (0x47544341u >> (8u * c)) & 0xFFu;      // "ACTG"[code]
+            x |= ch << (8 * b);
+        }
+        w[d] = x;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // byte offset of position `pos` (a multiple of 16) in a block of the given layout
 __host__ __device__ __forceinline__ uint64_t in_bytes(bool packed, uint64_t pos) { return packed ? (pos >> 4) * 6u : pos; }
 // the layout a launch instantiates for a block at `p`

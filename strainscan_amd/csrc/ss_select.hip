@@ -24,6 +24,10 @@
 //      the record shares with its neighbours, is the same one load and then byte stores of the record's own bytes -- no lane
 //      ever writes a byte that is not its record's.  From a packed slab a piece is three 3-byte units turned back into letters
 //      ("ACTG"[code], 'N' where invalid: what ss_reads_read_back writes).  All offsets are 64-bit.
+// select_records is three steps (ss_support.h): record_spans_of (pass 2 and the scratch of pass 3), the length pass, and
+// gather_records (the prefix sum, the new slab, pass 4).  out_len[rec] may be any multiple of length + 1: the gather writes that
+// many copies of the record back to back.  ss_reads_resample (ss_resample.hip) is the same three steps with its own length pass,
+// a Poisson multiplicity in the place of the 0/1 choice.
 #include "ss_scan_dev.h"
 #include "ss_support.h"
 
@@ -105,35 +109,6 @@ __global__ __launch_bounds__(256) void select_len_kernel(const uint32_t *__restr
     if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
 }
 
-// positions [s, s + 16) of a packed slab (s + 16 <= its positions) as the 16 letters its ASCII form holds inside a record: the
-// three 3-byte units around them, fetched as twelve bytes from the first unit on (a packed slab has 8 readable bytes behind its
-// last group, ss_scan_dev.h IN_PACKED, and its last unit but one begins 6 bytes before the end)
-__device__ __forceinline__ uint4 packed_letters16(const uint8_t *__restrict__ pk, uint64_t s)
-{
-    uint32_t t[3];
-    __builtin_memcpy(t, pk + (s >> 3) * 3u, 12);
-    const uint32_t sh = (uint32_t)s & 7u;
-    const uint64_t lo = (uint64_t)t[0] | ((uint64_t)t[1] << 32);
-    uint64_t code = (lo & 0xFFFFull) | (((lo >> 24) & 0xFFFFull) << 16) | ((lo >> 48) << 32);      // bytes 0 1, 3 4, 6 7
-    uint32_t inv = (uint32_t)((lo >> 16) & 0xFFull) | (uint32_t)(((lo >> 40) & 0xFFull) << 8) | ((t[2] & 0xFFu) << 16);      // bytes 2, 5, 8
-    code >>= 2u * sh;
-    inv >>= sh;
-    uint32_t w[4];
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        uint32_t x = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int i = 4 * d + b;
-            const uint32_t c = (uint32_t)(code >> (2 * i)) & 3u;
-            const uint32_t ch = ((inv >> i) & 1u) ? (uint32_t)'N' : (0x47544341u >> (8u * c)) & 0xFFu;      // "ACTG"[code]
-            x |= ch << (8 * b);
-        }
-        w[d] = x;
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // Sixteen lanes per record of one slab of n >= 16 positions (records [rec0, rec0 + n_rec)); dst is 16-byte aligned.  PACKED: src
 // is a packed slab, record r - rec0 at position (r - rec0) * slot; else src is an ASCII slab and start[] says where.
 // A lane takes one aligned 16-byte piece of the destination at a time.  The source bytes that belong there begin at `base`, any
@@ -141,44 +116,50 @@ __device__ __forceinline__ uint4 packed_letters16(const uint8_t *__restrict__ pk
 // clamped into the slab, ONE load, and moved to their places with a 128-bit shift (every byte the piece needs lies in what was
 // fetched, because the record lies in the slab).  A piece that is all the record's (its '\n' included) is one aligned 16-byte
 // store; a piece it shares with a neighbour stores its own bytes one by one, and not a byte more.
+// out_len[r] is a multiple of the record's length + 1: that many copies of it stand back to back from out_off[r] on (one for
+// ss_reads_select, 0..13 for ss_reads_resample), and the sixteen lanes write one after the other.
 template <bool PACKED>
 __global__ __launch_bounds__(256) void gather_kernel(const uint8_t *__restrict__ src, uint64_t n, const unsigned long long *__restrict__ start,
-                                                     const unsigned long long *__restrict__ out_len, const unsigned long long *__restrict__ out_off,
-                                                     uint64_t rec0, uint64_t n_rec, uint32_t slot, uint8_t *__restrict__ dst)
+                                                     const unsigned long long *__restrict__ end, const unsigned long long *__restrict__ out_len,
+                                                     const unsigned long long *__restrict__ out_off, uint64_t rec0, uint64_t n_rec, uint32_t slot,
+                                                     uint32_t fixed_len, uint8_t *__restrict__ dst)
 {
     const uint64_t g = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 4;
     if (g >= n_rec) return;
     const uint64_t r = rec0 + g;
-    const uint64_t ol = out_len[r];
-    if (!ol) return;                                                    // not selected
-    const uint64_t len = ol - 1u, D = out_off[r], S = PACKED ? g * (uint64_t)slot : (uint64_t)start[r];
-    const uint64_t A0 = D & ~15ull, n_pieces = (D + ol - A0 + 15u) >> 4;
-    for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
-        const uint64_t a = A0 + 16u * c;
-        const uint64_t lo = a > D ? a : D, hi = a + 16u < D + ol ? a + 16u : D + ol;      // the record's bytes of this piece: [lo, hi)
-        const int64_t base = (int64_t)S + ((int64_t)a - (int64_t)D);    // source position of the piece's byte 0
-        const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
-        uint4 v;
-        if (PACKED) v = packed_letters16(src, (uint64_t)q);
-        else __builtin_memcpy(&v, src + q, 16);
-        unsigned __int128 x;
-        __builtin_memcpy(&x, &v, 16);
-        const int shift = (int)(base - q);                              // byte j of the piece is byte j + shift of what was fetched
-        if (shift >= 16) x = 0;                                         // (only the '\n' behind a record that ends with the slab)
-        else if (shift > 0) x >>= 8 * shift;
-        else if (shift < 0) x <<= 8 * -shift;
-        if (D + len < a + 16u) {                                        // the byte behind the record
-            const uint32_t j = (uint32_t)(D + len - a);
-            x = (x & ~((unsigned __int128)0xFFu << (8u * j))) | ((unsigned __int128)0x0Au << (8u * j));
-        }
-        if (lo == a && hi == a + 16u) {
-            __builtin_memcpy(&v, &x, 16);
-            *reinterpret_cast<uint4 *>(dst + a) = v;
-        } else {
-            const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
+    const uint64_t all = out_len[r];
+    if (!all) return;                                                   // not selected
+    const uint64_t S = PACKED ? g * (uint64_t)slot : (uint64_t)start[r];
+    const uint64_t len = PACKED ? (uint64_t)fixed_len : (uint64_t)end[r] - S, ol = len + 1u, D_end = out_off[r] + all;
+    for (uint64_t D = out_off[r]; D + ol <= D_end; D += ol) {
+        const uint64_t A0 = D & ~15ull, n_pieces = (D + ol - A0 + 15u) >> 4;
+        for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
+            const uint64_t a = A0 + 16u * c;
+            const uint64_t lo = a > D ? a : D, hi = a + 16u < D + ol ? a + 16u : D + ol;      // the record's bytes of this piece: [lo, hi)
+            const int64_t base = (int64_t)S + ((int64_t)a - (int64_t)D);    // source position of the piece's byte 0
+            const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
+            uint4 v;
+            if (PACKED) v = packed_letters16(src, (uint64_t)q);
+            else __builtin_memcpy(&v, src + q, 16);
+            unsigned __int128 x;
+            __builtin_memcpy(&x, &v, 16);
+            const int shift = (int)(base - q);                              // byte j of the piece is byte j + shift of what was fetched
+            if (shift >= 16) x = 0;                                         // (only the '\n' behind a record that ends with the slab)
+            else if (shift > 0) x >>= 8 * shift;
+            else if (shift < 0) x <<= 8 * -shift;
+            if (D + len < a + 16u) {                                        // the byte behind the record
+                const uint32_t j = (uint32_t)(D + len - a);
+                x = (x & ~((unsigned __int128)0xFFu << (8u * j))) | ((unsigned __int128)0x0Au << (8u * j));
+            }
+            if (lo == a && hi == a + 16u) {
+                __builtin_memcpy(&v, &x, 16);
+                *reinterpret_cast<uint4 *>(dst + a) = v;
+            } else {
+                const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
 #pragma unroll
-            for (uint32_t j = 0; j < 16u; j++)
-                if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
+                for (uint32_t j = 0; j < 16u; j++)
+                    if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
+            }
         }
     }
 }
@@ -213,49 +194,68 @@ int ss_reads_select(const ss_db *db, const ss_reads *R, uint32_t min_hits, ss_re
 int ss::select_records(RecHits *rhp, const uint32_t *d_rec_hits, uint32_t min_hits, ss_reads **out)
 {
     RecHits &rh = *rhp;
+    RecSpans sp;
+    // 2. record spans
+    const int rc = ss::record_spans_of(&rh, &sp);
+    if (rc) return rc;
+    // 3. select: bytes per record
+    for (const auto &pt : rh.parts) {
+        if (!pt.n_rec) continue;
+        const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 4096);
+        hipLaunchKernelGGL(select_len_kernel, dim3(blocks), dim3(256), 0, ss::l2s::stream(), d_rec_hits, sp.d_start, sp.d_end, pt.rec_base, pt.n_rec,
+                           pt.n, pt.sl->packed ? pt.sl->L : 0u, min_hits, sp.d_len, sp.d_tot);
+        SS_HIP(hipGetLastError());
+    }
+    return ss::gather_records(&rh, sp, "ss_reads_select", out);
+}
+
+int ss::record_spans_of(RecHits *rhp, RecSpans *sp)
+{
+    RecHits &rh = *rhp;
     if (rh.rec_total > 0x7FFFFFFFull) return SS_ERANGE;             // hipcub counts its items in an int
     const hipStream_t st = ss::l2s::stream();
     const uint64_t rec_total = rh.rec_total;
-    unsigned long long *d_start = nullptr, *d_end = nullptr, *d_len = nullptr, *d_off = nullptr, *d_tot = nullptr;
-    unsigned long long tot[2] = {0, 0};
+    if (!rec_total) return SS_OK;
     bool any_ascii = false;
     for (const auto &pt : rh.parts) any_ascii = any_ascii || (!pt.sl->packed && pt.n_rec);
+    if (any_ascii) {
+        SS_HIP(rh.scratch.get((void **)&sp->d_start, rec_total * 8));
+        SS_HIP(rh.scratch.get((void **)&sp->d_end, rec_total * 8));
+        SS_HIP(ss::l2s::set(sp->d_start, 0xFF, rec_total * 8));
+        SS_HIP(ss::l2s::set(sp->d_end, 0xFF, rec_total * 8));
+    }
+    for (const auto &pt : rh.parts) {
+        if (pt.sl->packed || !pt.n_rec) continue;
+        const uint8_t *b = (const uint8_t *)pt.sl->d;
+        const dim3 grid((unsigned)((pt.n_tiles + 3) / 4));
+        with_bool((((uintptr_t)b) & 15) == 0, [&](auto aligned) {
+            hipLaunchKernelGGL(record_spans_kernel<decltype(aligned)::value>, grid, dim3(256), 0, st, b, pt.n, pt.n_tiles,
+                               rh.d_tile_base + pt.tile_off, pt.rec_base, pt.rec_base + pt.n_rec, sp->d_start, sp->d_end);
+        });
+        SS_HIP(hipGetLastError());
+    }
+    SS_HIP(rh.scratch.get((void **)&sp->d_len, rec_total * 8));
+    SS_HIP(rh.scratch.get((void **)&sp->d_tot, 16));
+    SS_HIP(ss::l2s::set(sp->d_tot, 0, 16));
+    return SS_OK;
+}
+
+int ss::gather_records(RecHits *rhp, const RecSpans &sp, const char *who, ss_reads **out)
+{
+    RecHits &rh = *rhp;
+    const hipStream_t st = ss::l2s::stream();
+    const uint64_t rec_total = rh.rec_total;
+    unsigned long long *d_off = nullptr;
+    unsigned long long tot[2] = {0, 0};
     if (rec_total) {
-        // 2. record spans
-        if (any_ascii) {
-            SS_HIP(rh.scratch.get((void **)&d_start, rec_total * 8));
-            SS_HIP(rh.scratch.get((void **)&d_end, rec_total * 8));
-            SS_HIP(ss::l2s::set(d_start, 0xFF, rec_total * 8));
-            SS_HIP(ss::l2s::set(d_end, 0xFF, rec_total * 8));
-        }
-        for (const auto &pt : rh.parts) {
-            if (pt.sl->packed || !pt.n_rec) continue;
-            const uint8_t *b = (const uint8_t *)pt.sl->d;
-            const dim3 grid((unsigned)((pt.n_tiles + 3) / 4));
-            with_bool((((uintptr_t)b) & 15) == 0, [&](auto aligned) {
-                hipLaunchKernelGGL(record_spans_kernel<decltype(aligned)::value>, grid, dim3(256), 0, st, b, pt.n, pt.n_tiles,
-                                   rh.d_tile_base + pt.tile_off, pt.rec_base, pt.rec_base + pt.n_rec, d_start, d_end);
-            });
-            SS_HIP(hipGetLastError());
-        }
-        // 3. select: bytes per record, their exclusive sum
-        SS_HIP(rh.scratch.get((void **)&d_len, rec_total * 8));
+        // the exclusive sum of the bytes per record: where each record's copies begin in the new slab
         SS_HIP(rh.scratch.get((void **)&d_off, rec_total * 8));
-        SS_HIP(rh.scratch.get((void **)&d_tot, 16));
-        SS_HIP(ss::l2s::set(d_tot, 0, 16));
-        for (const auto &pt : rh.parts) {
-            if (!pt.n_rec) continue;
-            const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 4096);
-            hipLaunchKernelGGL(select_len_kernel, dim3(blocks), dim3(256), 0, st, d_rec_hits, d_start, d_end, pt.rec_base, pt.n_rec, pt.n,
-                               pt.sl->packed ? pt.sl->L : 0u, min_hits, d_len, d_tot);
-            SS_HIP(hipGetLastError());
-        }
         size_t tmp_bytes = 0;
-        SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_off, (int)rec_total, st));
+        SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, sp.d_len, d_off, (int)rec_total, st));
         void *d_tmp = nullptr;
         SS_HIP(rh.scratch.get(&d_tmp, tmp_bytes));
-        SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_len, d_off, (int)rec_total, st));
-        SS_HIP(ss::l2s::copy(tot, d_tot, 16, hipMemcpyDeviceToHost));
+        SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, sp.d_len, d_off, (int)rec_total, st));
+        SS_HIP(ss::l2s::copy(tot, sp.d_tot, 16, hipMemcpyDeviceToHost));
     }
     ss_reads *S = new (std::nothrow) ss_reads();
     if (!S) return SS_ENOMEM;
@@ -271,15 +271,15 @@ int ss::select_records(RecHits *rhp, const uint32_t *d_rec_hits, uint32_t min_hi
         S->n_blocks = 1;
         S->first_slab = sl.cap;
         // 4. gather
-        auto fail = [&](hipError_t e) { if (e != hipSuccess) ss::set_last_error("ss_reads_select", __FILE__, __LINE__, e); return e != hipSuccess; };
+        auto fail = [&](hipError_t e) { if (e != hipSuccess) ss::set_last_error(who, __FILE__, __LINE__, e); return e != hipSuccess; };
         bool bad = fail(ss::l2s::set(sl.d + tot[1], '\n', sl.used - tot[1]));
         for (const auto &pt : rh.parts) {
             if (bad || !pt.n_rec) continue;
             if (pt.n < 16) { bad = fail(hipErrorInvalidValue); continue; }      // (a slab is padded to a multiple of 16)
             const dim3 grid((unsigned)((pt.n_rec * 16u + 255u) / 256u));
             with_bool(pt.sl->packed, [&](auto packed) {
-                hipLaunchKernelGGL(gather_kernel<decltype(packed)::value>, grid, dim3(256), 0, st, (const uint8_t *)pt.sl->d, pt.n, d_start, d_len, d_off,
-                                   pt.rec_base, pt.n_rec, pt.sl->slot, (uint8_t *)sl.d);
+                hipLaunchKernelGGL(gather_kernel<decltype(packed)::value>, grid, dim3(256), 0, st, (const uint8_t *)pt.sl->d, pt.n, sp.d_start, sp.d_end,
+                                   sp.d_len, d_off, pt.rec_base, pt.n_rec, pt.sl->slot, pt.sl->packed ? pt.sl->L : 0u, (uint8_t *)sl.d);
             });
             bad = fail(hipGetLastError());
         }

@@ -42,10 +42,20 @@ struct RecHits {
 // hits whose k-mer has label j.
 int rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls, const uint8_t *d_slot_label = nullptr,
                 uint32_t n_labels = 1);
+// pass 1 of rec_hits_of alone: parts, tile bases and the record numbering (d_rec_hits stays nullptr); device < 0: any device
+int record_index_of(const ss_reads *R, int device, RecHits *out, std::atomic<uint64_t> *calls);
 // pass 3 of ss_reads_support on one slice of rec_hits: hist[n_bins] and *hits (scratch from rh)
 int rec_hits_histogram(RecHits *rh, const uint32_t *d_rec_hits, uint32_t n_bins, uint64_t *hist, uint64_t *hits);
 // passes 2-4 of ss_reads_select (ss_select.hip) on one slice of rec_hits: the records with at least min_hits there, as a new set
 int select_records(RecHits *rh, const uint32_t *d_rec_hits, uint32_t min_hits, ss_reads **out);
+// The halves of select_records, which ss_reads_resample (ss_resample.hip) shares.  record_spans_of is pass 2 and the scratch of
+// pass 3: start[] / end[] of the records of the ASCII slabs (nullptr when the set has none), len[] and tot[2] = {0, 0}; SS_ERANGE
+// for more records than hipcub's int item count holds.  The caller fills len[rec] = copies * (length + 1), the bytes a record
+// takes in the new slab, and adds the copies and their bytes to tot[0] and tot[1]; a record whose span does not lie in its slab
+// gets 0.  gather_records is the exclusive sum of len[], the new slab and pass 4: every record copied len / (length + 1) times.
+struct RecSpans { unsigned long long *d_start = nullptr, *d_end = nullptr, *d_len = nullptr, *d_tot = nullptr; };
+int record_spans_of(RecHits *rh, RecSpans *sp);
+int gather_records(RecHits *rh, const RecSpans &sp, const char *who, ss_reads **out);
 // row labels (host, db->n_rows of them; only != 0: folded to 1 = `only`, 0 = the rest) -> *d_slot_label [db->n_slots] in `scratch`
 // (ss_label.hip); SS_EINVAL for a label above n_labels
 int slot_labels_for(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t only, PoolScratch &scratch, uint8_t **d_slot_label);

@@ -81,18 +81,43 @@ std::atomic<uint64_t> g_support_calls{0};
 
 }  // namespace
 
-// passes 1 and 2 (ss_support.h): ss_reads_support reduces rec_hits to a histogram, ss_reads_select (ss_select.hip) acts on it
+// passes 1 and 2 (ss_support.h): ss_reads_support reduces rec_hits to a histogram, ss_reads_select (ss_select.hip) acts on it;
+// pass 1 alone is record_index_of, all that ss_reads_resample (ss_resample.hip) needs of a set
 int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomic<uint64_t> *calls, const uint8_t *d_slot_label, uint32_t n_labels)
 {
     if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
     if (R->has_cut_record && db->k != 31) return SS_ERANGE;         // cut records carry a 30-base overlap (as ss_scan_reads)
+    const int rc0 = ss::record_index_of(R, db->device, out, calls);
+    if (rc0) return rc0;
+    const hipStream_t st = ss::l2s::stream();
+    PoolScratch &scratch = out->scratch;
+    const uint64_t rec_total = out->rec_total;
+    uint32_t *d_base = out->d_tile_base, *d_rec = nullptr;
+    // 2. hits per record (the labelled form: a slice per label)
+    SS_HIP(scratch.get((void **)&d_rec, rec_total * 4 * n_labels));
+    SS_HIP(ss::l2s::set(d_rec, 0, std::max<uint64_t>(rec_total * 4 * n_labels, 16)));
+    for (const RecHits::Part &pt : out->parts) {
+        if (pt.n >= (uint64_t)db->k && pt.n_rec) {
+            const ss::SupportArgs a{d_rec, pt.sl->packed ? nullptr : d_base + pt.tile_off, pt.rec_base, rec_total, pt.sl->packed ? pt.sl->slot : 0u};
+            const int rc = d_slot_label ? ss::launch_label_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, d_slot_label, n_labels, st)
+                                        : ss::launch_support_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, st);
+            if (rc) return rc;
+        }
+    }
+    out->d_rec_hits = d_rec;
+    return SS_OK;
+}
+
+// pass 1 (ss_support.h): the set's slabs that hold positions, their records numbered slab after slab
+int ss::record_index_of(const ss_reads *R, int device, RecHits *out, std::atomic<uint64_t> *calls)
+{
     using Part = RecHits::Part;
     std::vector<Part> &parts = out->parts;
     uint64_t tiles_total = 0;
     for (const auto &sl : R->slabs) {
         if (!sl.used || !sl.positions()) continue;
         hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, sl.d) != hipSuccess || at.device != db->device) { (void)hipGetLastError(); return SS_EINVAL; }
+        if (hipPointerGetAttributes(&at, sl.d) != hipSuccess || (device >= 0 && at.device != device)) { (void)hipGetLastError(); return SS_EINVAL; }
         Part pt{&sl, sl.positions(), 0, tiles_total, 0, 0};
         pt.n_tiles = (pt.n + SUP_TILE - 1) / SUP_TILE;
         if (sl.packed) {
@@ -107,7 +132,7 @@ int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomi
     if (calls) (*calls)++;
     const hipStream_t st = ss::l2s::stream();
     PoolScratch &scratch = out->scratch;
-    uint32_t *d_ends = nullptr, *d_base = nullptr, *d_rec = nullptr;
+    uint32_t *d_ends = nullptr, *d_base = nullptr;
     // 1. ASCII slabs: record ends per tile -> the record index at which each tile begins; [n_tiles] of a slab = its records
     if (tiles_total) {
         SS_HIP(scratch.get((void **)&d_ends, tiles_total * 4));
@@ -141,21 +166,9 @@ int ss::rec_hits_of(const ss_db *db, const ss_reads *R, RecHits *out, std::atomi
     }
     uint64_t rec_total = 0;
     for (Part &pt : parts) { pt.rec_base = rec_total; rec_total += pt.n_rec; }
-    // 2. hits per record (the labelled form: a slice per label)
-    SS_HIP(scratch.get((void **)&d_rec, rec_total * 4 * n_labels));
-    SS_HIP(ss::l2s::set(d_rec, 0, std::max<uint64_t>(rec_total * 4 * n_labels, 16)));
-    for (const Part &pt : parts) {
-        if (pt.n >= (uint64_t)db->k && pt.n_rec) {
-            const ss::SupportArgs a{d_rec, pt.sl->packed ? nullptr : d_base + pt.tile_off, pt.rec_base, rec_total, pt.sl->packed ? pt.sl->slot : 0u};
-            const int rc = d_slot_label ? ss::launch_label_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, d_slot_label, n_labels, st)
-                                        : ss::launch_support_minik(db, pt.sl->d, pt.n, pt.sl->packed, a, st);
-            if (rc) return rc;
-        }
-    }
     out->tiles_total = tiles_total;
     out->rec_total = rec_total;
     out->d_tile_base = d_base;
-    out->d_rec_hits = d_rec;
     return SS_OK;
 }
 

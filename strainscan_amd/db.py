@@ -462,6 +462,217 @@ def write_strain_support(out_dir, scope=None):
     return path
 
 
+# --bootstrap B (StrainScan.apply_bootstrap turns it on): how firm are a multi-strain cluster's numbers?  After the cluster has
+# written its StrainVote.report, collect_bootstrap resamples the reads that carry k-mers of its table B times on the device
+# (ReadSet.resample: a Poisson bootstrap over reads, replicate b of seed S), re-counts the table from each resampled set and solves
+# each replicate again with the main solve's strains and alpha held fixed (replicate_coefs).
+# "solve": the main solve's state, left by detect_core per solving thread while the flag is on; "rows": per scope (READ_SUPPORT's)
+# and cluster, the report's rows and the [B, p] matrix of replicate coefficients; "order": the clusters as they were scanned;
+# "skipped": why nothing is written (said once on stderr).  strain_bootstrap.tsv is a pure function of the rows (bootstrap_text).
+BOOTSTRAP = {"b": 0, "seed": 1, "solve": {}, "rows": {}, "order": {}, "skipped": None}
+BOOTSTRAP_FILE = "strain_bootstrap.tsv"
+BOOTSTRAP_QUANTILES = (0.025, 0.975)
+_BOOTSTRAP_LOCK = threading.Lock()
+
+
+def bootstrap_reset(b=0, seed=1):
+    BOOTSTRAP.update(b=int(b or 0), seed=int(seed), solve={}, rows={}, order={}, skipped=None)
+
+
+def bootstrap_note_solve(**state):
+    """detect_core and enet_cv_fit leave the main solve's state here (columns, strains, alpha, the row filter's bounds, the
+    identified clusters), under the solving thread; a no-op unless --bootstrap is on."""
+    if BOOTSTRAP["b"]:
+        if state.pop("begin", False):
+            BOOTSTRAP["solve"][threading.get_ident()] = {}
+        BOOTSTRAP["solve"].setdefault(threading.get_ident(), {}).update(state)
+
+
+def bootstrap_scanned(table):
+    """A cluster table has been scanned: strain_bootstrap.tsv lists the clusters in this order."""
+    if BOOTSTRAP["b"]:
+        order = BOOTSTRAP["order"].setdefault(READ_SUPPORT["scope"], [])
+        if table not in order:
+            order.append(table)
+
+
+def bootstrap_replicates(scope=None):
+    """{cluster: (strain names, np.float64[B, p])}: the replicate coefficients collected under `scope`, a column per selected
+    strain in pre-scan order (tests; strain_bootstrap.tsv is bootstrap_text of these and the reports' rows)."""
+    return {cls: (list(r["strains"]), r["coefs"].copy()) for cls, r in BOOTSTRAP["rows"].get(scope, {}).items()}
+
+
+def bootstrap_index(q, b):
+    """Which of b ascending values stands for quantile q: floor(q * (b - 1) + 0.5)."""
+    return int(np.floor(q * (b - 1) + 0.5))
+
+
+def bootstrap_summary(coefs):
+    """np.float64[B, p] replicate coefficients -> per column (depth_lo, depth_hi, frac_lo, frac_hi, present): the values at
+    bootstrap_index(0.025 / 0.975, B) of the ascending coefficients and of the ascending fractions coef / sum over the
+    replicate's columns (0 where that sum is 0), and the replicates with coef > 0."""
+    coefs = np.asarray(coefs, np.float64)
+    b = coefs.shape[0]
+    tot = coefs.sum(axis=1, keepdims=True)
+    frac = np.divide(coefs, tot, out=np.zeros_like(coefs), where=tot != 0)
+    lo, hi = (bootstrap_index(q, b) for q in BOOTSTRAP_QUANTILES)
+    cs, fs = np.sort(coefs, axis=0), np.sort(frac, axis=0)
+    return [(float(cs[lo, j]), float(cs[hi, j]), float(fs[lo, j]), float(fs[hi, j]), int((coefs[:, j] > 0).sum()))
+            for j in range(coefs.shape[1])]
+
+
+def bootstrap_text(rows):
+    """The text of strain_bootstrap.tsv for rows of (table, strain, depth text, frac text, column, coefs [B, p]): depth and frac
+    are copied from the strain's report row, `column` is the strain's column of the replicate matrix."""
+    out = ["table\tstrain\treplicates\tdepth\tdepth_lo\tdepth_hi\tfrac\tfrac_lo\tfrac_hi\tpresent\n"]
+    summaries = {}
+    for table, strain, depth, frac, col, coefs in rows:
+        if id(coefs) not in summaries:
+            summaries[id(coefs)] = bootstrap_summary(coefs)
+        d_lo, d_hi, f_lo, f_hi, present = summaries[id(coefs)][col]
+        out.append("\t".join([table, strain, str(int(np.asarray(coefs).shape[0])), depth, str(d_lo), str(d_hi), frac, str(f_lo), str(f_hi),
+                              str(present)]) + "\n")
+    return "".join(out)
+
+
+def _bootstrap_skip(why):
+    import sys
+    from . import dist
+    if BOOTSTRAP["skipped"] is None:
+        BOOTSTRAP["skipped"] = why
+        if dist.rank_world()[0] == 0:
+            print("bootstrap: %s and no intervals were computed" % why, file=sys.stderr)
+            sys.stderr.flush()
+
+
+def report_rows(report_path):
+    """[(n, name, frac text, depth text)] of a StrainVote.report: columns 1, 2 (without -e's mark), 4 and 5 of its rows."""
+    out = []
+    with open(report_path) as f:
+        f.readline()
+        for line in f:
+            ele = line.rstrip("\n").split("\t")
+            if len(ele) < 5 or not ele[0].strip():
+                break
+            name = ele[1][:-len(EXTRA_REGION_MARK)] if ele[1].endswith(EXTRA_REGION_MARK) else ele[1]
+            out.append((int(ele[0]), name, ele[3], ele[4]))
+    return out
+
+
+def replicate_coefs(img, om, solve, counts):
+    """One bootstrap replicate of a cluster (--bootstrap, db.collect_bootstrap): the coefficients of the strains the main solve
+    selected, from the k-mer counts of a resampled read set.  Held fixed from the main solve (`solve`, what detect_core and
+    enet_cv_fit left with bootstrap_note_solve): the selected columns in pre-scan order, the alpha lasso_mpm picked, npp25,
+    npp75, npp_out and the identified clusters.  Recomputed: y = remove_1(counts), the device vectors and with them the kept rows.
+    p >= 2: the pattern statistics of all kept rows -> Gram -> one elastic-net fit at that alpha, with the arguments of
+    enet_cv_fit's refit; no kept row: zeros.  p = 1 (the main solve never reached the elastic net): pre_scan's get_avg_depth
+    of the one column, 0.0 where the column has no count."""
+    from . import l2 as L2
+    from .Vote_Strain_L2_Lasso_new_sp import remove_1
+    from .identify_strains_L2_Enet_Pscan_new_sp import MAX_NITER
+    cols = list(solve["columns"])
+    p = len(cols)
+    if img.om_cols is None:
+        img.set_overlap(om)
+    vec = img.prepare(remove_1(counts), solve["new_als"], solve["npp25"], solve["npp75"], solve["npp_out"])
+    try:
+        if p == 1:
+            qd = img.quantile_sums(vec.yu if vec.use_u else vec.y, cols, 25, 75)
+            if qd["n_nz"][0] == 0 or qd["cnt_in"][0] == 0:
+                return np.zeros(1)
+            return np.array([float(qd["sum_in"][0]) / float(qd["cnt_in"][0])])
+        n = vec.n_keep
+        if n == 0:
+            return np.zeros(p)
+        fold = img.fold_words(vec.keep, np.zeros(n, np.uint32), n)
+        try:
+            stats = img.pattern_stats(cols, vec.ykeep, fold, 0)
+        finally:
+            fold.close()
+        Qt, qt, yyt, nt = L2.gram_from_stats(stats[0], p)
+        fit = L2.enet_path_gram(Qt[None], qt[None], [yyt], [nt], [solve["alpha"]], l1_ratio=0.5, max_iter=MAX_NITER, tol=1e-4,
+                                positive=True)
+        return fit["coefs"][0, 0].copy()
+    finally:
+        vec.close()
+
+
+def collect_bootstrap(cls, cls_db_dir, report_path, ksize, paths):
+    """After cluster `cls` ('C<id>') has written report_path: B replicate solves of it.  A no-op unless --bootstrap is on.  Every
+    rank calls this at the same point (it holds collectives): each resamples its own shard of the reads -- the weights depend on
+    a read's bytes alone, so the summed counts are those of one process."""
+    solve = BOOTSTRAP["solve"].pop(threading.get_ident(), None)
+    b = BOOTSTRAP["b"]
+    if not b or BOOTSTRAP["skipped"] is not None or solve is None or not solve.get("columns") or not os.path.exists(report_path):
+        return
+    from . import dist
+    from . import identify_strains_L2_Enet_Pscan_new_sp as enet
+    with _BOOTSTRAP_LOCK:
+        if BOOTSTRAP["skipped"] is not None:
+            return
+        rows = BOOTSTRAP["rows"].setdefault(READ_SUPPORT["scope"], {})
+        if cls in rows:
+            return
+        called = report_rows(report_path)
+        if not called:
+            return
+        if int(ksize) < 17:
+            return _bootstrap_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % int(ksize))
+        rs = resident_reads(paths)
+        if rs is None:
+            return _bootstrap_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
+        kdb = fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)
+        kdb.expect_hits()
+        sub = img = None
+        try:
+            try:
+                sub = rs.select(kdb, 1)          # reads without a hit add nothing to any count: only these are resampled
+            except _lib.SSError as e:
+                if e.code != _lib.SS_ERANGE:
+                    raise
+                return _bootstrap_skip("cannot resample the reads of a sample with a record longer than a block (it was cut)")
+            img, om = enet.open_cluster_image(cls_db_dir + "/all_strains_re.npz", cls_db_dir + "/overlap_matrix.npz")
+            coefs = np.zeros((b, len(solve["columns"])), np.float64)
+            for rep in range(b):
+                rb = sub.resample(BOOTSTRAP["seed"], rep)
+                try:
+                    kdb.reset()
+                    rb.order().scan_into(kdb)    # binned first: 2.2 + 6.2 ms beside 16.6 ms for 20 M reads (profiles/r21_bootstrap.md)
+                    if dist.is_distributed():
+                        dist.allreduce_table(kdb)
+                    _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
+                    counts = kdb.counts_rows()
+                finally:
+                    rb.close()
+                coefs[rep] = replicate_coefs(img, om, solve, counts)
+        finally:
+            if img is not None:
+                img.close()
+            if sub is not None:
+                sub.close()
+            kdb.close()
+        col_of = {str(name): j for j, name in enumerate(solve["strains"])}
+        rows[cls] = dict(strains=[str(s) for s in solve["strains"]], coefs=coefs,
+                         called=[(n, name, depth, frac, col_of[name]) for n, name, frac, depth in called if name in col_of])
+
+
+def write_bootstrap(out_dir, scope=None):
+    """out_dir/strain_bootstrap.tsv from the replicates collected under `scope`, clusters in the order scanned, strains in report
+    order; nothing without the flag, without a solved multi-strain cluster, or after a skip."""
+    rows = BOOTSTRAP["rows"].get(scope)
+    if not BOOTSTRAP["b"] or BOOTSTRAP["skipped"] is not None or not rows:
+        return None
+    order = [t for t in BOOTSTRAP["order"].get(scope, []) if t in rows]
+    order += sorted(t for t in rows if t not in order)
+    lines = [("%s.%d" % (t, n), name, depth, frac, col, rows[t]["coefs"]) for t in order for n, name, depth, frac, col in rows[t]["called"]]
+    if not lines:
+        return None
+    path = os.path.join(out_dir, BOOTSTRAP_FILE)
+    with open(path, "w") as f:
+        f.write(bootstrap_text(lines))
+    return path
+
+
 def resident_reads(paths):
     """The sample's reads as flat base blocks in HBM (parsed and copied over PCIe once), or None
     when they would not fit the budget (then every scan streams the files again).  Under

@@ -40,6 +40,12 @@ def lasso_mpm(alphas, mse_path):
     return alphas[pick], mse_mean[pick], mse_std[pick]
 
 
+def _note_solve(**state):
+    """--bootstrap: what the replicate solves hold fixed goes to db.BOOTSTRAP (a no-op while the flag is off)."""
+    from . import db
+    db.bootstrap_note_solve(**state)
+
+
 def _stat_cov(valid, total):
     """:33-43 with the popcounts already done."""
     valid, total = int(valid), int(total)
@@ -173,6 +179,7 @@ def enet_cv_fit(img, cols, vec, trace=None, split=None):
                            max_iter=MAX_NITER, tol=1e-4, positive=True)
     mark("enet_cv_path")
     alpha, _, _ = lasso_mpm(alphas, cv["mse"])
+    _note_solve(alpha=float(alpha))
     fit = L2.enet_path_gram(Qt[None], qt[None], [yyt], [nt], [alpha], l1_ratio=0.5, max_iter=MAX_NITER, tol=1e-4,
                             positive=True)
     coef = fit["coefs"][0, 0].copy()
@@ -220,6 +227,8 @@ def detect_core(X, om, sid, input_y, ksize, npp25, npp75, npp_out, cls_cov, all_
         t_vec = time.perf_counter()
         out_columns, out_strains, strain_cov, strain_val, final_src, depth = pre_scan(
             img, vec, sid, cutoff, l2, pmode, emode)
+        _note_solve(begin=True, columns=[int(c) for c in out_columns], strains=list(out_strains), new_als=new_als, npp25=npp25,
+                    npp75=npp75, npp_out=npp_out, l2=l2, pmode=pmode, emode=emode)
         if trace is not None:
             trace["timing_ms"].update(prologue_host=(t_pro - t_begin) * 1e3, image=(t_img - t_pro) * 1e3,
                                       vectors=(t_vec - t_img) * 1e3, pre_scan=(time.perf_counter() - t_vec) * 1e3)
@@ -456,6 +465,17 @@ def detect_strains(input_csv, input_y, ids, ksize, npp25, npp75, npp_out, cls_co
     omatrix = <C>/overlap_matrix.npz, input_y = counts ordered by k-mer id with 1s zeroed."""
     from .tree import load_plain_pkl
     sid = load_plain_pkl(ids)
+    img, om = open_cluster_image(input_csv, omatrix)
+    try:
+        return detect_core(None, om, sid, input_y, ksize, npp25, npp75, npp_out, cls_cov, all_cls, l2, msn, pmode,
+                           emode, img=img)
+    finally:
+        img.close()
+
+
+def open_cluster_image(input_csv, omatrix):
+    """-> (img, om): the device image of <C>/all_strains_re.npz and the overlap matrix (None when the image came from the
+    package's cache and carries it already).  The caller closes img."""
     cache = _l2_cache_path(input_csv, omatrix)
     img = om = None
     if cache:
@@ -475,8 +495,4 @@ def detect_strains(input_csv, input_y, ids, ksize, npp25, npp75, npp_out, cls_co
                 _write_l2_cache(cache, img, om)
             except OSError:
                 pass
-    try:
-        return detect_core(None, om, sid, input_y, ksize, npp25, npp75, npp_out, cls_cov, all_cls, l2, msn, pmode,
-                           emode, img=img)
-    finally:
-        img.close()
+    return img, om

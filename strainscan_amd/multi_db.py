@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -151,6 +151,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
             finally:
                 dbm.write_read_support(od, label)
                 dbm.write_strain_support(od, label)     # (--by_strain: OUT/<label>/strain_support.tsv)
+                dbm.write_bootstrap(od, label)          # (--bootstrap: OUT/<label>/strain_bootstrap.tsv)
                 dbm.READ_SUPPORT["scope"] = None
                 dbm.EXTRACT_READS.update(scope=None, dir=None)
             rows.append((label, d, status))
@@ -171,6 +172,7 @@ def main(argv=None):
     StrainScan.apply_read_support(args.read_support)
     StrainScan.apply_extract_reads(args.extract_reads)
     StrainScan.apply_by_strain(args.by_strain)
+    StrainScan.apply_bootstrap(args.bootstrap, args.bootstrap_seed)
     try:
         rows = identify_databases((args.input_fq, args.input_fq2 or ""), dbs, out_dir, ksize=opts["ksize"], ldep=opts["ldep"],
                                   sprob=opts["sprob"], emode=opts["emode"], msn=opts["msn"], pmode=opts["pmode"], rank=rank)
@@ -178,6 +180,7 @@ def main(argv=None):
         StrainScan.apply_read_support(False)
         StrainScan.apply_extract_reads(0)
         StrainScan.apply_by_strain(False)
+        StrainScan.apply_bootstrap(0)
     return 1 if any(st.startswith("error:") for _, _, st in rows) else 0
 
 
