@@ -5,7 +5,7 @@ table (every 31-mer of a 5 Mb genome, both orientations; ss_db_expect_hits) and 
   resample   ReadSet.resample alone (record index, spans, digest + weight, prefix sum, gather) from the packed resident set and
              from the same reads in file order (ASCII); device events around the synchronous call, the median of --reps after a
              warm-up, and the wall time.  A kernel-stats run of this script (scripts/gpu_kstats.sh) says how the call splits.
-  replicate  one replicate as db.collect_bootstrap runs it: resample -> order (ReadSet.order: the resampled records binned in
+  replicate  one replicate as read_reports.collect_bootstrap runs it: resample -> order (ReadSet.order: the resampled records binned in
              place) -> reset -> scan -> sync -> counts to the host -> destroy; and the same without the binning, the resampled set
              scanned as it is (one ASCII slab, the records in the source's order) -- the alternative that was not kept.  Then the
              parts: the scan of a resampled set as it is, the binning, the scan of the binned set, the counts to the host.

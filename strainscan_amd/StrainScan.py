@@ -205,32 +205,32 @@ def apply_min_base_qual(q):
 
 
 def apply_read_support(on):
-    """--read_support (strainscan_amd.set_read_support): the tables scanned from here on leave a row each with db.READ_SUPPORT;
+    """--read_support (strainscan_amd.set_read_support): the tables scanned from here on leave a row each with read_reports.READ_SUPPORT;
     the command writes them to read_support.tsv when it ends.  stdout and the other report files are untouched."""
-    from . import db
-    db.read_support_reset(on)
+    from . import read_reports
+    read_reports.read_support_reset(on)
 
 
 def apply_extract_reads(n, out_dir=None):
-    """-x N (strainscan_amd.set_extract_reads): the tables scanned from here on leave their reads in out_dir/extracted/ (db.
-    collect_extract_reads).  stdout and the report files are untouched; 0 turns it off."""
-    from . import db
-    db.extract_reads_reset(n, out_dir)
+    """-x N (strainscan_amd.set_extract_reads): the tables scanned from here on leave their reads in out_dir/extracted/
+    (read_reports.collect_extract_reads).  stdout and the report files are untouched; 0 turns it off."""
+    from . import read_reports
+    read_reports.extract_reads_reset(n, out_dir)
 
 
 def apply_by_strain(on):
     """--by_strain (strainscan_amd.set_by_strain): the multi-strain clusters solved from here on attribute their reads to the called
-    strains (db.collect_by_strain).  stdout, the reports, read_support.tsv and extracted/C<id>_* are untouched."""
-    from . import db
-    db.by_strain_reset(on)
+    strains (read_reports.collect_by_strain).  stdout, the reports, read_support.tsv and extracted/C<id>_* are untouched."""
+    from . import read_reports
+    read_reports.by_strain_reset(on)
 
 
 def apply_bootstrap(b, seed=1):
     """--bootstrap B --bootstrap_seed S (strainscan_amd.set_bootstrap): the multi-strain clusters solved from here on are solved
-    B more times on resampled reads (db.collect_bootstrap); the command writes strain_bootstrap.tsv when it ends.  stdout and
+    B more times on resampled reads (read_reports.collect_bootstrap); the command writes strain_bootstrap.tsv when it ends.  stdout and
     the other files are untouched; 0 turns it off."""
-    from . import db
-    db.bootstrap_reset(b, seed)
+    from . import read_reports
+    read_reports.bootstrap_reset(b, seed)
 
 
 def settings(args):
@@ -331,14 +331,9 @@ def main(argv=None):
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:
-        from . import db
-        db.write_read_support(out_dir)      # (in a finally: the reference's own early exit()s come through here as SystemExit)
-        db.write_strain_support(out_dir)
-        db.write_bootstrap(out_dir)
-        db.read_support_reset()
-        db.extract_reads_reset()
-        db.by_strain_reset()
-        db.bootstrap_reset()
+        from . import read_reports
+        read_reports.write_all(out_dir)     # (in a finally: the reference's own early exit()s come through here as SystemExit)
+        read_reports.reset_all()
 
 
 def cli(main_fn=None):

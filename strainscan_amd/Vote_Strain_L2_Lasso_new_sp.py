@@ -120,15 +120,14 @@ def cluster_counts(input_fq, fq2, cls_db_dir, ksize):
     """The `jellyfish count -m ksize --if all_kmer.fasta` + dump + load_kmer_count + ordering by
     k-mer id of :354-389, as one device scan.  Row r of all_kmer.fasta is k-mer id r+1
     (Build_kmer_sets_unique_region_lasso_test_allinone_sp.py:397-399,409-410)."""
-    from .db import bootstrap_scanned, collect_extract_reads, collect_read_support, fasta_index, scan_into
+    from .db import fasta_index, scan_into
+    from .read_reports import table_scanned
     db = fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)
     db.expect_hits()                         # every k-mer of the cluster's strains, and the sample holds the cluster
     try:
         scan_into(db, [input_fq, fq2])       # resident reads: no second parse, no second PCIe trip
         _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
-        collect_read_support(os.path.basename(os.path.normpath(cls_db_dir)), db, [input_fq, fq2])      # (--read_support)
-        collect_extract_reads(os.path.basename(os.path.normpath(cls_db_dir)), db, [input_fq, fq2])     # (-x)
-        bootstrap_scanned(os.path.basename(os.path.normpath(cls_db_dir)))                              # (--bootstrap)
+        table_scanned(os.path.basename(os.path.normpath(cls_db_dir)), db, [input_fq, fq2])      # (--read_support, -x, --bootstrap)
         return db.counts_rows()
     finally:
         db.close()
@@ -138,7 +137,8 @@ def cluster_counts_many(input_fq, fq2, cls_db_dirs, ksize, group=16):
     """cluster_counts for several clusters with ONE pass over the resident reads per `group` tables (the reference's loop
     :295-296 runs jellyfish over the whole FASTQ once per cluster, :354-372): ss_scan_reads_multi.  -> list of count arrays,
     in the order of cls_db_dirs.  Without a resident read set (too large for the device) the clusters are scanned one by one."""
-    from .db import bootstrap_scanned, collect_extract_reads, collect_read_support, fasta_index, resident_reads
+    from .db import fasta_index, resident_reads
+    from .read_reports import table_scanned
     from . import dist
     rs = resident_reads([input_fq, fq2]) if len(cls_db_dirs) > 1 else None
     if rs is None:
@@ -156,10 +156,8 @@ def cluster_counts_many(input_fq, fq2, cls_db_dirs, ksize, group=16):
                 for db in dbs:                       # same order on every rank
                     dist.allreduce_table(db)
             _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
-            for d, db in zip(cls_db_dirs[g0:g0 + group], dbs):      # (--read_support; same order on every rank)
-                collect_read_support(os.path.basename(os.path.normpath(d)), db, [input_fq, fq2])
-                collect_extract_reads(os.path.basename(os.path.normpath(d)), db, [input_fq, fq2])      # (-x)
-                bootstrap_scanned(os.path.basename(os.path.normpath(d)))                               # (--bootstrap)
+            for d, db in zip(cls_db_dirs[g0:g0 + group], dbs):      # (--read_support, -x, --bootstrap; same order on every rank)
+                table_scanned(os.path.basename(os.path.normpath(d)), db, [input_fq, fq2])
             out.extend(db.counts_rows() for db in dbs)
         finally:
             for db in dbs:
@@ -201,9 +199,8 @@ def vote_strain_L2(item, counts=None):
                 o.write(str(c) + "\t" + name + " (With_ExtraRegion_covered)" + body + "\t\n")
             else:
                 o.write(str(c) + "\t" + name + body + "\t\n")
-    from .db import collect_bootstrap, collect_by_strain
-    collect_by_strain(cls, db_dir, out_dir + "/StrainVote.report", ksize, [input_fq, fq2])      # (--by_strain)
-    collect_bootstrap(cls, db_dir, out_dir + "/StrainVote.report", ksize, [input_fq, fq2])      # (--bootstrap)
+    from .read_reports import cluster_reported
+    cluster_reported(cls, db_dir, out_dir + "/StrainVote.report", ksize, [input_fq, fq2])      # (--by_strain, --bootstrap)
 
 
 def vote_strain_L2_batch(input_fq, fq2, db_dir, out_dir, ksize, res, l2, msn, pmode, emode):

@@ -13,10 +13,10 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.StrainScan.main                            (StrainScan.py:113, the `strainscan` CLI)
 
     strainscan_amd.set_min_base_qual / get_min_base_qual      (the base-quality mask of `strainscan -q`; process-wide, off by default)
-    strainscan_amd.set_read_support                           (`strainscan --read_support`: rows of reads per table, db.READ_SUPPORT)
-    strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, db.EXTRACT_READS)
-    strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, db.BY_STRAIN)
-    strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, db.BOOTSTRAP)
+    strainscan_amd.set_read_support                           (`strainscan --read_support`: rows of reads per table, read_reports.READ_SUPPORT)
+    strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, read_reports.EXTRACT_READS)
+    strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, read_reports.BY_STRAIN)
+    strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, read_reports.BOOTSTRAP)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -34,11 +34,11 @@ def set_min_base_qual(q):
 
 def set_read_support(on):
     """`strainscan --read_support` for callers of the functions above: from here on the tree scan of identify_cluster and the
-    cluster scans of vote_strain_L2_batch each leave a row in strainscan_amd.db.READ_SUPPORT["rows"][None] -- (table, distinct
-    k-mers, reads, hits, 65-bin histogram of hits per read) -- and db.write_read_support(out_dir) writes them as
+    cluster scans of vote_strain_L2_batch each leave a row in strainscan_amd.read_reports.READ_SUPPORT["rows"][None] -- (table, distinct
+    k-mers, reads, hits, 65-bin histogram of hits per read) -- and read_reports.write_read_support(out_dir) writes them as
     read_support.tsv.  set_read_support(False) turns it off and drops the rows.  Off by default; nothing runs while it is off."""
-    from . import db
-    db.read_support_reset(bool(on))
+    from . import read_reports
+    read_reports.read_support_reset(bool(on))
 
 
 def set_extract_reads(n, out_dir=None):
@@ -48,33 +48,34 @@ def set_extract_reads(n, out_dir=None):
     directory.  n is an integer of at least 1; 0 (or None) turns it off.  Off by default; nothing runs while it is off."""
     if n and (isinstance(n, bool) or not isinstance(n, int) or n < 1):
         raise ValueError("extract_reads must be an integer >= 1 (or 0 for off), not %r" % (n,))
-    from . import db
-    db.extract_reads_reset(n or 0, out_dir)
+    from . import read_reports
+    read_reports.extract_reads_reset(n or 0, out_dir)
 
 
 def set_by_strain(on):
     """`strainscan --by_strain` for callers of the functions above: from here on vote_strain_L2_batch, after a multi-strain
     cluster has written its StrainVote.report, attributes reads to the called strains -- with set_read_support on, rows for
-    db.write_strain_support(out_dir) (strain_support.tsv); with set_extract_reads on, extracted/C<id>.<n>_1.<ext>.  A k-mer
+    read_reports.write_strain_support(out_dir) (strain_support.tsv); with set_extract_reads on, extracted/C<id>.<n>_1.<ext>.  A k-mer
     counts for a called strain when no other called strain of the cluster has it.  Off by default; nothing runs while it is
     off, or while both of the other two are off."""
-    from . import db
-    db.by_strain_reset(bool(on))
+    from . import read_reports
+    read_reports.by_strain_reset(bool(on))
 
 
 def set_bootstrap(b, seed=1):
     """`strainscan --bootstrap B --bootstrap_seed S` for callers of the functions above: from here on vote_strain_L2_batch, after
     a multi-strain cluster has written its StrainVote.report, solves the cluster `b` more times, each on the reads resampled with
     replacement on the device (ReadSet.resample(seed, replicate)), with the called strains and the penalty of the main solve held
-    fixed.  db.bootstrap_replicates() returns the replicate coefficients, db.write_bootstrap(out_dir) writes strain_bootstrap.tsv.
+    fixed.  read_reports.bootstrap_replicates() returns the replicate coefficients, read_reports.write_bootstrap(out_dir) writes
+    strain_bootstrap.tsv.
     b is an integer in 2..1000 (0 or None turns it off), seed an integer in 0..2^63-1.  Off by default; nothing runs while it is
     off."""
     if b and (isinstance(b, bool) or not isinstance(b, int) or not 2 <= b <= 1000):
         raise ValueError("bootstrap must be an integer in 2..1000 (or 0 for off), not %r" % (b,))
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= (1 << 63) - 1:
         raise ValueError("bootstrap seed must be an integer in 0..2^63-1, not %r" % (seed,))
-    from . import db
-    db.bootstrap_reset(b or 0, seed)
+    from . import read_reports
+    read_reports.bootstrap_reset(b or 0, seed)
 
 
 def get_min_base_qual():

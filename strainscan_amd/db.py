@@ -11,7 +11,9 @@ Kmer_Sets_L2/Kmer_Sets/C<id>/ is handled by strainscan_amd/Vote_Strain_L2_Lasso_
 A TreeImage owns the device k-mer table of kmer.fa and the node row lists; scans accumulate in
 it.  Images are cached per (directory, key mode) for the life of the process so that the cutoff
 ladder of StrainScan.py:196-216 (which calls identify_cluster up to twice) parses and uploads a
-database once.
+database once.  The sample's reads live here as well: one resident set at a time (resident_reads,
+with -q's line about what the load masked), the scans of a table over them, and the image caches.
+The opt-in reports about the reads (--read_support, -x, --by_strain, --bootstrap) are read_reports.py.
 """
 import os
 import threading
@@ -93,584 +95,6 @@ def report_mask(masked=None, no_qual=None, bases=None):
         line = "rank %d of %d (its share): " % (rank, world) + line
     print(line, file=sys.stderr)
     sys.stderr.flush()
-
-
-# --read_support (StrainScan.apply_read_support turns it on): how many reads carry k-mers of each table the run scans.  Rows are
-# collected while the tables are open -- the tree's after the tree scan (TreeImage), a cluster's in cluster_counts /
-# cluster_counts_many -- under the scope of the database at work (strainscan-multi: its label), and written by the command when
-# it ends.  "skipped": why nothing is written (said once on stderr).
-READ_SUPPORT = {"on": False, "scope": None, "rows": {}, "skipped": None}
-READ_SUPPORT_FILE = "read_support.tsv"
-READ_SUPPORT_BINS = 65
-READ_SUPPORT_GE = (1, 2, 4, 8, 16, 32, 64)
-_READ_SUPPORT_LOCK = threading.Lock()
-
-
-def read_support_reset(on=False):
-    READ_SUPPORT.update(on=bool(on), scope=None, rows={}, skipped=None)
-
-
-def read_support_ge(hist):
-    """A 65-bin histogram (hist[b]: records with exactly b hits, hist[64]: 64 and more) -> records with >= 1, 2, 4, ... 64 hits."""
-    h = [int(v) for v in hist]
-    assert len(h) == READ_SUPPORT_BINS
-    return [sum(h[t:]) for t in READ_SUPPORT_GE]
-
-
-def read_support_text(rows):
-    """The text of read_support.tsv for rows of (table, kmers, reads, hits, hist)."""
-    out = ["table\tkmers\treads\thits\t" + "\t".join("ge%d" % t for t in READ_SUPPORT_GE) + "\n"]
-    for table, kmers, reads, hits, hist in rows:
-        out.append("\t".join([table] + [str(int(v)) for v in [kmers, reads, hits] + read_support_ge(hist)]) + "\n")
-    return "".join(out)
-
-
-def _read_support_skip(why):
-    import sys
-    if READ_SUPPORT["skipped"] is None:
-        READ_SUPPORT["skipped"] = why
-        print("read_support: %s and was not computed" % why, file=sys.stderr)
-        sys.stderr.flush()
-
-
-def collect_read_support(table, kdb, paths):
-    """One row of read_support.tsv: the resident reads of `paths` against `kdb` (ReadSet.support), summed over the ranks.  A no-op
-    unless --read_support is on; a table that already has its row under the current scope keeps it.  Every rank calls this at the
-    same point (it holds a collective)."""
-    if not READ_SUPPORT["on"] or READ_SUPPORT["skipped"] is not None:
-        return
-    with _READ_SUPPORT_LOCK:
-        rows = READ_SUPPORT["rows"].setdefault(READ_SUPPORT["scope"], {})
-        if table in rows:
-            return
-        if kdb.k < 17:
-            return _read_support_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % kdb.k)
-        rs = resident_reads(paths)
-        if rs is None:
-            return _read_support_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
-        hist, hits = rs.support(kdb, READ_SUPPORT_BINS)
-        v = np.concatenate([hist.astype(np.int64), np.array([hits, rs.info()["n_records"]], np.int64)])
-        from . import dist
-        if dist.is_distributed():
-            v = dist.allreduce_int64(v)
-        rows[table] = (table, kdb.info()["n_distinct"], int(v[-1]), int(v[-2]), [int(x) for x in v[:-2]])
-
-
-def write_read_support(out_dir, scope=None):
-    """out_dir/read_support.tsv from the rows collected under `scope`; nothing without the flag, without rows, or after a skip."""
-    rows = READ_SUPPORT["rows"].get(scope)
-    if not READ_SUPPORT["on"] or READ_SUPPORT["skipped"] is not None or not rows:
-        return None
-    path = os.path.join(out_dir, READ_SUPPORT_FILE)
-    with open(path, "w") as f:
-        f.write(read_support_text(rows.values()))
-    return path
-
-
-# -x N / --extract_reads N (StrainScan.apply_extract_reads turns it on): the reads that carry at least N k-mers of a table, written
-# beside the reports as `dir`/extracted/<table>_1.<ext> (and _2 with a second mate), at the points where --read_support collects
-# its rows and while the table is open.  The device selects the records (ReadSet.select); they are found in the input files again
-# by the digest of their sequence, not by position -- a resident set keeps no map back to file order.  "done": the tables written
-# under each scope (strainscan-multi: a database's label, with `dir` = its report directory); "skipped": why nothing is written.
-# "files": what this run has written so far (a skip takes them away again: after a skip the run leaves no extracted/ of its own).
-# A BAM sample (every input a BAM) takes another way: ss_bam_extract per input file and table, from the file and the open table alone --
-# extracted/<table>_<i>.bam holds the input's header and the kept records of the selected templates (_write_selected_bam).
-EXTRACT_READS = {"n": 0, "scope": None, "dir": None, "done": {}, "skipped": None, "files": []}
-EXTRACT_READS_DIR = "extracted"
-_EXTRACT_READS_LOCK = threading.Lock()
-
-
-def extract_reads_reset(n=0, out_dir=None):
-    EXTRACT_READS.update(n=int(n or 0), scope=None, dir=out_dir, done={}, skipped=None, files=[])
-
-
-def _extract_reads_skip(why):
-    import sys
-    from . import dist
-    if EXTRACT_READS["skipped"] is None:
-        EXTRACT_READS["skipped"] = why
-        for f in EXTRACT_READS["files"]:
-            try:
-                os.remove(f)
-                os.rmdir(os.path.dirname(f))      # (once it is empty)
-            except OSError:
-                pass
-        EXTRACT_READS["files"] = []
-        if dist.rank_world()[0] == 0:
-            print("extract_reads: %s and nothing was extracted" % why, file=sys.stderr)
-            sys.stderr.flush()
-
-
-def fastx_record_type(path):
-    """'fasta' or 'fastq': the record type of a FASTA/FASTQ file, plain or gzip, by its first record's marker."""
-    import gzip
-    with open(path, "rb") as f:
-        head = f.read(2)
-    with (gzip.open(path, "rb") if head == b"\x1f\x8b" else open(path, "rb")) as f:
-        for line in f:
-            if line.strip():
-                return "fasta" if line.startswith(b">") else "fastq"
-    return "fastq"
-
-
-def collect_extract_reads(table, kdb, paths):
-    """extracted/<table>_1.<ext> (and _2): every read of `paths` with at least N k-mer hits against `kdb`, a pair when either
-    mate has them.  A no-op unless -x is on; a table that was written under the current scope is not written again."""
-    n = EXTRACT_READS["n"]
-    if not n or EXTRACT_READS["skipped"] is not None:
-        return
-    from . import dist
-    with _EXTRACT_READS_LOCK:
-        done = EXTRACT_READS["done"].setdefault(EXTRACT_READS["scope"], set())
-        if table in done:
-            return
-        if dist.is_distributed():
-            return _extract_reads_skip("runs on one rank only (this run has several)")
-        if kdb.k < 17:
-            return _extract_reads_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % kdb.k)
-        ps = [p for p in paths if p]
-        bam = _extract_inputs_bam(ps)
-        if bam is None:
-            return
-        if bam:
-            return _write_selected_bam(table, kdb, None, 0, 0, ps, n, done)
-        rs = resident_reads(paths)
-        if rs is None:
-            return _extract_reads_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
-        _write_selected(table, lambda: rs.select(kdb, n), ps, n, done)
-
-
-def _extract_inputs_bam(ps):
-    """True: every input is a BAM (-x writes BAM subsets, from the files and the open table alone); False: none is; None: a mix,
-    refused (_EXTRACT_READS_LOCK held)."""
-    bam = [_lib.input_kind(p) == "bam" for p in ps]
-    if any(bam) and not all(bam):
-        _extract_reads_skip("takes BAM inputs or FASTA/FASTQ inputs, not both (this run mixes them)")
-        return None
-    return bool(bam) and all(bam)
-
-
-def _write_selected_bam(table, kdb, labels, n_labels, label, ps, n, done):
-    """extracted/<table>_<i>.bam for each BAM input i: its header and the kept records of the templates with a record of at least
-    n hits against kdb (of `label` when labels are given), selected and copied on the device (_lib.bam_extract;
-    _EXTRACT_READS_LOCK held)."""
-    import sys
-    out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
-    os.makedirs(out_dir, exist_ok=True)
-    for i, p in enumerate(ps):
-        out = os.path.join(out_dir, "%s_%d.bam" % (table, i + 1))
-        c = _lib.bam_extract(p, kdb, n, out, labels, n_labels, label)
-        EXTRACT_READS["files"].append(out)
-        print("extract_reads: %s\tN=%d\tfile %d\tkept %d\tselected on the device %d\twritten %d" %
-              (table, n, i + 1, c["kept"], c["selected"], c["written"]), file=sys.stderr)
-    done.add(table)
-    sys.stderr.flush()
-
-
-def _write_selected(table, select, ps, n, done):
-    """select() -> the ReadSet of the selected records; read back, digested, found in the files `ps` again and written as
-    extracted/<table>_<mate>.<ext> (_EXTRACT_READS_LOCK held)."""
-    import sys
-    try:
-        sub = select()
-    except _lib.SSError as e:
-        if e.code != _lib.SS_ERANGE:
-            raise
-        return _extract_reads_skip("cannot name the reads of a sample with a record longer than a block (it was cut)")
-    try:
-        selected = sub.info()["n_records"]
-        flat = sub.read_back()
-    finally:
-        sub.close()
-    keys = _lib.flat_record_keys(flat)
-    del flat
-    out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
-    os.makedirs(out_dir, exist_ok=True)
-    outs = [os.path.join(out_dir, "%s_%d.%s" % (table, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
-    c = _lib.extract_write(ps, keys, outs)
-    done.add(table)
-    EXTRACT_READS["files"].extend(outs)
-    print("extract_reads: %s\tN=%d\tselected on the device %d\twritten %d" % (table, n, selected, c["written"]), file=sys.stderr)
-    sys.stderr.flush()
-
-
-# --by_strain (StrainScan.apply_by_strain turns it on; it needs --read_support and/or -x): a cluster table holds the k-mers of ALL
-# strains of its cluster, so its row of read_support.tsv and its extracted/C<id>_* are the cluster's reads.  After a cluster's
-# StrainVote.report has been written, collect_by_strain labels the table's rows by the called strain that alone has them
-# (strain_row_labels) and asks the device the same two questions per label (ReadSet.support_labeled / select_labeled): rows of
-# strain_support.tsv, and extracted/C<id>.<n>_1.<ext>.  Rows are kept per scope and cluster (READ_SUPPORT's scope: strainscan-multi
-# sets one per database) and written in the order the clusters were scanned.
-BY_STRAIN = {"on": False, "rows": {}}
-STRAIN_SUPPORT_FILE = "strain_support.tsv"
-_BY_STRAIN_LOCK = threading.Lock()
-EXTRA_REGION_MARK = " (With_ExtraRegion_covered)"      # what -e 1 appends to a strain's name in StrainVote.report
-
-
-def by_strain_reset(on=False):
-    BY_STRAIN.update(on=bool(on), rows={})
-
-
-def strain_support_text(rows):
-    """The text of strain_support.tsv for rows of (table, strain, kmers, reads, hits, hist)."""
-    out = ["table\tstrain\tkmers\treads\thits\t" + "\t".join("ge%d" % t for t in READ_SUPPORT_GE) + "\n"]
-    for table, strain, kmers, reads, hits, hist in rows:
-        out.append("\t".join([table, strain] + [str(int(v)) for v in [kmers, reads, hits] + read_support_ge(hist)]) + "\n")
-    return "".join(out)
-
-
-def called_strains(report_path):
-    """[(n, name)] of a StrainVote.report: its rows in order, n = column 1, name = column 2 without -e's mark."""
-    out = []
-    with open(report_path) as f:
-        f.readline()
-        for line in f:
-            ele = line.rstrip("\n").split("\t")
-            if len(ele) < 2 or not ele[0].strip():
-                break
-            name = ele[1][:-len(EXTRA_REGION_MARK)] if ele[1].endswith(EXTRA_REGION_MARK) else ele[1]
-            out.append((int(ele[0]), name))
-    return out
-
-
-def strain_row_labels(indptr, indices, data, n_rows, called_cols):
-    """np.uint8[n_rows] from a cluster's CSR matrix (row = k-mer, column = strain) and the called columns c_1 .. c_L: row r has
-    label j when it is non-zero in column c_j and in no other called column; every other row -- shared between called strains, or
-    in none of them -- has label 0.  Uncalled columns are not looked at."""
-    indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices)
-    n_mat = indptr.size - 1
-    n_cols = int(indices.max()) + 1 if indices.size else 0
-    col_label = np.zeros(max(n_cols, max(list(called_cols) + [0]) + 1), np.uint8)
-    for j, c in enumerate(called_cols, 1):
-        col_label[c] = j
-    lab = col_label[indices]                                         # the called columns only ...
-    if data is not None and not np.asarray(data).all():
-        lab = np.where(np.asarray(data) != 0, lab, 0).astype(np.uint8)
-    at = np.flatnonzero(lab)                                         # (a few of a cluster's many columns: short from here on)
-    rows = np.searchsorted(indptr, at, side="right") - 1
-    called = np.bincount(rows, minlength=n_mat)                      # ... a row sum over them ...
-    which = np.bincount(rows, weights=lab[at], minlength=n_mat).astype(np.int64)      # ... and, where it is 1, the arg-max
-    out = np.zeros(n_rows, np.uint8)
-    m = min(n_rows, n_mat)
-    out[:m] = np.where(called == 1, which, 0)[:m]
-    return out
-
-
-def cluster_csr_arrays(path):
-    """(indptr, indices, data) of a cluster's all_strains_re.npz.  Members that the archive stores without compression are
-    mapped, not read: np.load copies and checksums them (~7 ms per million non-zeros), and the solver has read and checked this
-    same file in this run already.  Anything else goes the solver's way (_load_npz_csr)."""
-    import zipfile
-    from .identify_strains_L2_Enet_Pscan_new_sp import _load_npz_csr, _npy_header, _npz_directory
-    try:
-        d = _npz_directory(path)
-        out = []
-        with open(path, "rb") as f:
-            for name in ("indptr", "indices", "data"):
-                off, _, _, usize, method = d[name + ".npy"]
-                if method != zipfile.ZIP_STORED:
-                    raise ValueError(name)
-                f.seek(off)
-                dtype, shape, _, hlen = _npy_header(f.read(min(usize, 4096)))
-                if len(shape) != 1 or dtype.hasobject or hlen + dtype.itemsize * shape[0] != usize:
-                    raise ValueError(name)
-                out.append(np.memmap(path, dtype=dtype, mode="r", offset=off + hlen, shape=shape) if shape[0] else np.zeros(0, dtype))
-        with np.load(path, allow_pickle=False) as z:
-            fmt = z["format"].item()
-        if (fmt.decode() if isinstance(fmt, bytes) else fmt) != "csr" or out[0].size < 1 or out[1].size != out[2].size:
-            raise ValueError("format")
-        return tuple(out)
-    except (OSError, KeyError, ValueError, zipfile.BadZipFile):
-        m = _load_npz_csr(path)
-        return m.indptr, m.indices, m.data
-
-
-def collect_by_strain(cls, cls_db_dir, report_path, ksize, paths):
-    """After cluster `cls` ('C<id>') has written report_path: its called strains' rows of strain_support.tsv (--read_support)
-    and their extracted/<cls>.<n>_* files (-x).  A no-op unless --by_strain is on.  Every rank calls this at the same point (it
-    holds collectives)."""
-    if not BY_STRAIN["on"] or not os.path.exists(report_path):
-        return
-    support = READ_SUPPORT["on"] and READ_SUPPORT["skipped"] is None
-    extract = bool(EXTRACT_READS["n"]) and EXTRACT_READS["skipped"] is None
-    if not (support or extract):
-        return
-    from . import dist
-    from .tree import load_plain_pkl
-    with _BY_STRAIN_LOCK:
-        scope = READ_SUPPORT["scope"]
-        rows = BY_STRAIN["rows"].setdefault(scope, {})
-        if cls in rows:
-            return
-        called = called_strains(report_path)
-        if not called:
-            return
-        sid = load_plain_pkl(os.path.join(cls_db_dir, "id2strain_re.pkl"))
-        col_of = {name: c for c, name in (sid.items() if isinstance(sid, dict) else enumerate(sid))}
-        indptr, indices, data = cluster_csr_arrays(os.path.join(cls_db_dir, "all_strains_re.npz"))
-        ps = [p for p in paths if p]
-        bam = extract and bool(ps) and all(_lib.input_kind(p) == "bam" for p in ps)      # (-x on a BAM needs no resident set)
-        rs = resident_reads(paths)
-        if rs is None:                                               # (said by --read_support / -x already)
-            support = False
-            if not bam:
-                return
-        kdb = fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)
-        try:
-            if kdb.k < 17:
-                return
-            labels = strain_row_labels(indptr, indices, data, kdb.n_rows, [col_of[name] for _, name in called])
-            n_reads = rs.info()["n_records"] if support else 0
-            out = []
-            for j0 in range(0, len(called), _lib.LABELS_MAX):        # (more called strains than a call takes: several calls)
-                part = called[j0:j0 + _lib.LABELS_MAX]
-                lab = np.where((labels > j0) & (labels <= j0 + len(part)), labels - j0, 0).astype(np.uint8)
-                if support:
-                    hist, hits, kmers = rs.support_labeled(kdb, lab, len(part), READ_SUPPORT_BINS)
-                    v = np.concatenate([hist.astype(np.int64).ravel(), hits.astype(np.int64), [n_reads]])
-                    if dist.is_distributed():
-                        v = dist.allreduce_int64(v)
-                    hist = v[:hist.size].reshape(hist.shape)
-                    for i, (n, name) in enumerate(part):
-                        out.append(("%s.%d" % (cls, n), name, int(kmers[i]), int(v[-1]), int(v[hist.size + i]), [int(x) for x in hist[i]]))
-                if extract:
-                    with _EXTRACT_READS_LOCK:
-                        done = EXTRACT_READS["done"].setdefault(EXTRACT_READS["scope"], set())
-                        for i, (n, name) in enumerate(part):
-                            if EXTRACT_READS["skipped"] is not None or "%s.%d" % (cls, n) in done:
-                                continue
-                            if bam:
-                                _write_selected_bam("%s.%d" % (cls, n), kdb, lab, len(part), i + 1, ps, EXTRACT_READS["n"], done)
-                            else:
-                                _write_selected("%s.%d" % (cls, n), lambda i=i: rs.select_labeled(kdb, lab, len(part), i + 1, EXTRACT_READS["n"]),
-                                                    ps, EXTRACT_READS["n"], done)
-            rows[cls] = out
-        finally:
-            kdb.close()
-
-
-def write_strain_support(out_dir, scope=None):
-    """out_dir/strain_support.tsv from the rows collected under `scope`, clusters in the order of read_support.tsv's rows;
-    nothing without --by_strain and --read_support, without rows, or after a skip."""
-    rows = BY_STRAIN["rows"].get(scope)
-    if not BY_STRAIN["on"] or not READ_SUPPORT["on"] or READ_SUPPORT["skipped"] is not None or not rows or not any(rows.values()):
-        return None
-    order = [t for t in READ_SUPPORT["rows"].get(scope, {}) if t in rows]
-    order += sorted(t for t in rows if t not in order)
-    path = os.path.join(out_dir, STRAIN_SUPPORT_FILE)
-    with open(path, "w") as f:
-        f.write(strain_support_text([r for t in order for r in sorted(rows[t], key=lambda r: int(r[0].rsplit(".", 1)[1]))]))
-    return path
-
-
-# --bootstrap B (StrainScan.apply_bootstrap turns it on): how firm are a multi-strain cluster's numbers?  After the cluster has
-# written its StrainVote.report, collect_bootstrap resamples the reads that carry k-mers of its table B times on the device
-# (ReadSet.resample: a Poisson bootstrap over reads, replicate b of seed S), re-counts the table from each resampled set and solves
-# each replicate again with the main solve's strains and alpha held fixed (replicate_coefs).
-# "solve": the main solve's state, left by detect_core per solving thread while the flag is on; "rows": per scope (READ_SUPPORT's)
-# and cluster, the report's rows and the [B, p] matrix of replicate coefficients; "order": the clusters as they were scanned;
-# "skipped": why nothing is written (said once on stderr).  strain_bootstrap.tsv is a pure function of the rows (bootstrap_text).
-BOOTSTRAP = {"b": 0, "seed": 1, "solve": {}, "rows": {}, "order": {}, "skipped": None}
-BOOTSTRAP_FILE = "strain_bootstrap.tsv"
-BOOTSTRAP_QUANTILES = (0.025, 0.975)
-_BOOTSTRAP_LOCK = threading.Lock()
-
-
-def bootstrap_reset(b=0, seed=1):
-    BOOTSTRAP.update(b=int(b or 0), seed=int(seed), solve={}, rows={}, order={}, skipped=None)
-
-
-def bootstrap_note_solve(**state):
-    """detect_core and enet_cv_fit leave the main solve's state here (columns, strains, alpha, the row filter's bounds, the
-    identified clusters), under the solving thread; a no-op unless --bootstrap is on."""
-    if BOOTSTRAP["b"]:
-        if state.pop("begin", False):
-            BOOTSTRAP["solve"][threading.get_ident()] = {}
-        BOOTSTRAP["solve"].setdefault(threading.get_ident(), {}).update(state)
-
-
-def bootstrap_scanned(table):
-    """A cluster table has been scanned: strain_bootstrap.tsv lists the clusters in this order."""
-    if BOOTSTRAP["b"]:
-        order = BOOTSTRAP["order"].setdefault(READ_SUPPORT["scope"], [])
-        if table not in order:
-            order.append(table)
-
-
-def bootstrap_replicates(scope=None):
-    """{cluster: (strain names, np.float64[B, p])}: the replicate coefficients collected under `scope`, a column per selected
-    strain in pre-scan order (tests; strain_bootstrap.tsv is bootstrap_text of these and the reports' rows)."""
-    return {cls: (list(r["strains"]), r["coefs"].copy()) for cls, r in BOOTSTRAP["rows"].get(scope, {}).items()}
-
-
-def bootstrap_index(q, b):
-    """Which of b ascending values stands for quantile q: floor(q * (b - 1) + 0.5)."""
-    return int(np.floor(q * (b - 1) + 0.5))
-
-
-def bootstrap_summary(coefs):
-    """np.float64[B, p] replicate coefficients -> per column (depth_lo, depth_hi, frac_lo, frac_hi, present): the values at
-    bootstrap_index(0.025 / 0.975, B) of the ascending coefficients and of the ascending fractions coef / sum over the
-    replicate's columns (0 where that sum is 0), and the replicates with coef > 0."""
-    coefs = np.asarray(coefs, np.float64)
-    b = coefs.shape[0]
-    tot = coefs.sum(axis=1, keepdims=True)
-    frac = np.divide(coefs, tot, out=np.zeros_like(coefs), where=tot != 0)
-    lo, hi = (bootstrap_index(q, b) for q in BOOTSTRAP_QUANTILES)
-    cs, fs = np.sort(coefs, axis=0), np.sort(frac, axis=0)
-    return [(float(cs[lo, j]), float(cs[hi, j]), float(fs[lo, j]), float(fs[hi, j]), int((coefs[:, j] > 0).sum()))
-            for j in range(coefs.shape[1])]
-
-
-def bootstrap_text(rows):
-    """The text of strain_bootstrap.tsv for rows of (table, strain, depth text, frac text, column, coefs [B, p]): depth and frac
-    are copied from the strain's report row, `column` is the strain's column of the replicate matrix."""
-    out = ["table\tstrain\treplicates\tdepth\tdepth_lo\tdepth_hi\tfrac\tfrac_lo\tfrac_hi\tpresent\n"]
-    summaries = {}
-    for table, strain, depth, frac, col, coefs in rows:
-        if id(coefs) not in summaries:
-            summaries[id(coefs)] = bootstrap_summary(coefs)
-        d_lo, d_hi, f_lo, f_hi, present = summaries[id(coefs)][col]
-        out.append("\t".join([table, strain, str(int(np.asarray(coefs).shape[0])), depth, str(d_lo), str(d_hi), frac, str(f_lo), str(f_hi),
-                              str(present)]) + "\n")
-    return "".join(out)
-
-
-def _bootstrap_skip(why):
-    import sys
-    from . import dist
-    if BOOTSTRAP["skipped"] is None:
-        BOOTSTRAP["skipped"] = why
-        if dist.rank_world()[0] == 0:
-            print("bootstrap: %s and no intervals were computed" % why, file=sys.stderr)
-            sys.stderr.flush()
-
-
-def report_rows(report_path):
-    """[(n, name, frac text, depth text)] of a StrainVote.report: columns 1, 2 (without -e's mark), 4 and 5 of its rows."""
-    out = []
-    with open(report_path) as f:
-        f.readline()
-        for line in f:
-            ele = line.rstrip("\n").split("\t")
-            if len(ele) < 5 or not ele[0].strip():
-                break
-            name = ele[1][:-len(EXTRA_REGION_MARK)] if ele[1].endswith(EXTRA_REGION_MARK) else ele[1]
-            out.append((int(ele[0]), name, ele[3], ele[4]))
-    return out
-
-
-def replicate_coefs(img, om, solve, counts):
-    """One bootstrap replicate of a cluster (--bootstrap, db.collect_bootstrap): the coefficients of the strains the main solve
-    selected, from the k-mer counts of a resampled read set.  Held fixed from the main solve (`solve`, what detect_core and
-    enet_cv_fit left with bootstrap_note_solve): the selected columns in pre-scan order, the alpha lasso_mpm picked, npp25,
-    npp75, npp_out and the identified clusters.  Recomputed: y = remove_1(counts), the device vectors and with them the kept rows.
-    p >= 2: the pattern statistics of all kept rows -> Gram -> one elastic-net fit at that alpha, with the arguments of
-    enet_cv_fit's refit; no kept row: zeros.  p = 1 (the main solve never reached the elastic net): pre_scan's get_avg_depth
-    of the one column, 0.0 where the column has no count."""
-    from . import l2 as L2
-    from .Vote_Strain_L2_Lasso_new_sp import remove_1
-    from .identify_strains_L2_Enet_Pscan_new_sp import MAX_NITER
-    cols = list(solve["columns"])
-    p = len(cols)
-    if img.om_cols is None:
-        img.set_overlap(om)
-    vec = img.prepare(remove_1(counts), solve["new_als"], solve["npp25"], solve["npp75"], solve["npp_out"])
-    try:
-        if p == 1:
-            qd = img.quantile_sums(vec.yu if vec.use_u else vec.y, cols, 25, 75)
-            if qd["n_nz"][0] == 0 or qd["cnt_in"][0] == 0:
-                return np.zeros(1)
-            return np.array([float(qd["sum_in"][0]) / float(qd["cnt_in"][0])])
-        n = vec.n_keep
-        if n == 0:
-            return np.zeros(p)
-        fold = img.fold_words(vec.keep, np.zeros(n, np.uint32), n)
-        try:
-            stats = img.pattern_stats(cols, vec.ykeep, fold, 0)
-        finally:
-            fold.close()
-        Qt, qt, yyt, nt = L2.gram_from_stats(stats[0], p)
-        fit = L2.enet_path_gram(Qt[None], qt[None], [yyt], [nt], [solve["alpha"]], l1_ratio=0.5, max_iter=MAX_NITER, tol=1e-4,
-                                positive=True)
-        return fit["coefs"][0, 0].copy()
-    finally:
-        vec.close()
-
-
-def collect_bootstrap(cls, cls_db_dir, report_path, ksize, paths):
-    """After cluster `cls` ('C<id>') has written report_path: B replicate solves of it.  A no-op unless --bootstrap is on.  Every
-    rank calls this at the same point (it holds collectives): each resamples its own shard of the reads -- the weights depend on
-    a read's bytes alone, so the summed counts are those of one process."""
-    solve = BOOTSTRAP["solve"].pop(threading.get_ident(), None)
-    b = BOOTSTRAP["b"]
-    if not b or BOOTSTRAP["skipped"] is not None or solve is None or not solve.get("columns") or not os.path.exists(report_path):
-        return
-    from . import dist
-    from . import identify_strains_L2_Enet_Pscan_new_sp as enet
-    with _BOOTSTRAP_LOCK:
-        if BOOTSTRAP["skipped"] is not None:
-            return
-        rows = BOOTSTRAP["rows"].setdefault(READ_SUPPORT["scope"], {})
-        if cls in rows:
-            return
-        called = report_rows(report_path)
-        if not called:
-            return
-        if int(ksize) < 17:
-            return _bootstrap_skip("needs page-index tables (17 <= k <= 31), this run's k is %d," % int(ksize))
-        rs = resident_reads(paths)
-        if rs is None:
-            return _bootstrap_skip("needs the sample resident on the device (SS_READS_RESIDENT_GB)")
-        kdb = fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)
-        kdb.expect_hits()
-        sub = img = None
-        try:
-            try:
-                sub = rs.select(kdb, 1)          # reads without a hit add nothing to any count: only these are resampled
-            except _lib.SSError as e:
-                if e.code != _lib.SS_ERANGE:
-                    raise
-                return _bootstrap_skip("cannot resample the reads of a sample with a record longer than a block (it was cut)")
-            img, om = enet.open_cluster_image(cls_db_dir + "/all_strains_re.npz", cls_db_dir + "/overlap_matrix.npz")
-            coefs = np.zeros((b, len(solve["columns"])), np.float64)
-            for rep in range(b):
-                rb = sub.resample(BOOTSTRAP["seed"], rep)
-                try:
-                    kdb.reset()
-                    rb.order().scan_into(kdb)    # binned first: 2.2 + 6.2 ms beside 16.6 ms for 20 M reads (profiles/r21_bootstrap.md)
-                    if dist.is_distributed():
-                        dist.allreduce_table(kdb)
-                    _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
-                    counts = kdb.counts_rows()
-                finally:
-                    rb.close()
-                coefs[rep] = replicate_coefs(img, om, solve, counts)
-        finally:
-            if img is not None:
-                img.close()
-            if sub is not None:
-                sub.close()
-            kdb.close()
-        col_of = {str(name): j for j, name in enumerate(solve["strains"])}
-        rows[cls] = dict(strains=[str(s) for s in solve["strains"]], coefs=coefs,
-                         called=[(n, name, depth, frac, col_of[name]) for n, name, frac, depth in called if name in col_of])
-
-
-def write_bootstrap(out_dir, scope=None):
-    """out_dir/strain_bootstrap.tsv from the replicates collected under `scope`, clusters in the order scanned, strains in report
-    order; nothing without the flag, without a solved multi-strain cluster, or after a skip."""
-    rows = BOOTSTRAP["rows"].get(scope)
-    if not BOOTSTRAP["b"] or BOOTSTRAP["skipped"] is not None or not rows:
-        return None
-    order = [t for t in BOOTSTRAP["order"].get(scope, []) if t in rows]
-    order += sorted(t for t in rows if t not in order)
-    lines = [("%s.%d" % (t, n), name, depth, frac, col, rows[t]["coefs"]) for t in order for n, name, depth, frac, col in rows[t]["called"]]
-    if not lines:
-        return None
-    path = os.path.join(out_dir, BOOTSTRAP_FILE)
-    with open(path, "w") as f:
-        f.write(bootstrap_text(lines))
-    return path
 
 
 def resident_reads(paths):

@@ -41,9 +41,9 @@ def lasso_mpm(alphas, mse_path):
 
 
 def _note_solve(**state):
-    """--bootstrap: what the replicate solves hold fixed goes to db.BOOTSTRAP (a no-op while the flag is off)."""
-    from . import db
-    db.bootstrap_note_solve(**state)
+    """--bootstrap: what the replicate solves hold fixed goes to read_reports.BOOTSTRAP (a no-op while the flag is off)."""
+    from . import read_reports
+    read_reports.bootstrap_note_solve(**state)
 
 
 def _stat_cov(valid, total):

@@ -112,7 +112,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
     """in_fq = (fq1, fq2 or ''); db_dirs: [dir or (label, dir)] -> [(label, dir, status)] in that order, also written to
     out_dir/databases.tsv (rank 0).  Database i's reports go to out_dir/<label>.  before_each(i) is called just before
     database i's work (tests seed numpy's RNG there: the walk's Poisson draw is unseeded, as in the reference)."""
-    from . import db as dbm
+    from . import db as dbm, read_reports
     fq1, fq2 = in_fq[0], in_fq[1] or ""
     dbs = [(d if isinstance(d, tuple) else parse_database(d)) for d in db_dirs]
     paths = [p for p in (fq1, fq2) if p]
@@ -129,12 +129,11 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
             if before_each is not None:
                 before_each(i)
             stage = "layer1"
-            dbm.READ_SUPPORT["scope"] = label       # (--read_support: this database's rows, OUT/<label>/read_support.tsv)
-            dbm.EXTRACT_READS.update(scope=label, dir=od)      # (-x: OUT/<label>/extracted/)
             try:
-                cls_dict, l2 = StrainScan.identify_layer1(fq1, fq2, d, od, ldep, sprob)
-                stage = "layer2"
-                Vote_Strain_L2_Lasso_new_sp.vote_strain_L2_batch(fq1, fq2, d, od, ksize, dict(cls_dict), l2, msn, pmode, emode)
+                with read_reports.database_scope(label, od):      # (this database's rows; -x: OUT/<label>/extracted/)
+                    cls_dict, l2 = StrainScan.identify_layer1(fq1, fq2, d, od, ldep, sprob)
+                    stage = "layer2"
+                    Vote_Strain_L2_Lasso_new_sp.vote_strain_L2_batch(fq1, fq2, d, od, ksize, dict(cls_dict), l2, msn, pmode, emode)
                 status = "reports"
             except SystemExit as e:
                 if e.code in (None, 0):
@@ -149,11 +148,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
                 sys.stderr.flush()
                 status = "error:" + type(e).__name__
             finally:
-                dbm.write_read_support(od, label)
-                dbm.write_strain_support(od, label)     # (--by_strain: OUT/<label>/strain_support.tsv)
-                dbm.write_bootstrap(od, label)          # (--bootstrap: OUT/<label>/strain_bootstrap.tsv)
-                dbm.READ_SUPPORT["scope"] = None
-                dbm.EXTRACT_READS.update(scope=None, dir=None)
+                read_reports.write_all(od, label)       # (OUT/<label>/read_support.tsv, strain_support.tsv, strain_bootstrap.tsv)
             rows.append((label, d, status))
     if rank == 0:
         write_table(os.path.join(out_dir, TSV), rows)
@@ -166,7 +161,7 @@ def main(argv=None):
     StrainScan.apply_min_base_qual(args.min_base_qual)
     out_dir = StrainScan.output_dir(args.out_dir, os.getcwd())
     os.makedirs(out_dir, exist_ok=True)
-    from . import dist
+    from . import dist, read_reports
     rank, _ = dist.init_from_env()
     out_dir = StrainScan.rank_output_dir(out_dir, rank)
     StrainScan.apply_read_support(args.read_support)
@@ -177,10 +172,7 @@ def main(argv=None):
         rows = identify_databases((args.input_fq, args.input_fq2 or ""), dbs, out_dir, ksize=opts["ksize"], ldep=opts["ldep"],
                                   sprob=opts["sprob"], emode=opts["emode"], msn=opts["msn"], pmode=opts["pmode"], rank=rank)
     finally:
-        StrainScan.apply_read_support(False)
-        StrainScan.apply_extract_reads(0)
-        StrainScan.apply_by_strain(False)
-        StrainScan.apply_bootstrap(0)
+        read_reports.reset_all()
     return 1 if any(st.startswith("error:") for _, _, st in rows) else 0
 
 

@@ -1,7 +1,7 @@
 """`strainscan --bootstrap 8 --bootstrap_seed 3` on the mid-size database and its M_mix pair (two strains of C7, three of C19, one
 of C23, a singleton).
 
-The replicate coefficients (db.bootstrap_replicates) equal a model that never touches the device: the reads resampled in Python
+The replicate coefficients (read_reports.bootstrap_replicates) equal a model that never touches the device: the reads resampled in Python
 with the weight model (tests/boot_model.py), counted by the CPU oracle, and solved by the oracle's pre-scan / elastic net with the
 main solve's columns and alpha held fixed -- to the project's abundance tolerance, 1e-5 relative (|got - want| <= 1e-5 * max(1,
 |want|), as the reports' depths are compared elsewhere).  strain_bootstrap.tsv is the writer applied to them; every other output is
@@ -44,8 +44,8 @@ class _Spy:
 
     def __init__(self):
         from strainscan_amd import Vote_Strain_L2_Lasso_new_sp as vote
-        from strainscan_amd import db as ssdb
-        self.vote, self.ssdb = vote, ssdb
+        from strainscan_amd import read_reports
+        self.vote, self.ssdb = vote, read_reports
         self.args, self.replicates = {}, {}
 
     def __enter__(self):
@@ -140,7 +140,7 @@ def _model(L, db_dir, spy, pair):
 
 
 def test_replicates_are_the_models_and_the_file_is_the_writer(L, runs, mid_dbs, pair):
-    from strainscan_amd import db as ssdb
+    from strainscan_amd import read_reports
     err, _, errs, od, calls = runs["flag"]
     assert _ok(err), err
     assert "bootstrap:" not in errs
@@ -173,7 +173,7 @@ def test_replicates_are_the_models_and_the_file_is_the_writer(L, runs, mid_dbs, 
             f = ln.split("\t")
             if len(f) > 5:
                 rows.append(("%s.%s" % (cls, f[0]), f[1], f[4], f[3], names.index(f[1]), coefs))
-    assert text == ssdb.bootstrap_text(rows)
+    assert text == read_reports.bootstrap_text(rows)
     for ln in lines[1:-1]:
         f = ln.split("\t")
         assert f[2] == str(B) and float(f[4]) <= float(f[5]) and float(f[7]) <= float(f[8]) and 0 <= int(f[9]) <= B

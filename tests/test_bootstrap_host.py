@@ -83,14 +83,14 @@ def test_model_mix_is_written_out(L):
 
 
 def test_index_rule():
-    from strainscan_amd import db
-    assert [(db.bootstrap_index(0.025, b), db.bootstrap_index(0.975, b)) for b in (2, 8, 41, 100, 1000)] == \
+    from strainscan_amd import read_reports
+    assert [(read_reports.bootstrap_index(0.025, b), read_reports.bootstrap_index(0.975, b)) for b in (2, 8, 41, 100, 1000)] == \
         [(0, 1), (0, 7), (1, 39), (2, 97), (25, 974)]
 
 
 @pytest.mark.parametrize("b", [2, 8, 41])
 def test_writer_on_hand_made_matrices(b):
-    from strainscan_amd import db
+    from strainscan_amd import read_reports
     rs = np.random.RandomState(b)
     coefs = np.zeros((b, 3))
     coefs[:, 0] = rs.permutation(np.arange(b)) + 1.0                 # 1 .. b in some order
@@ -99,7 +99,7 @@ def test_writer_on_hand_made_matrices(b):
     lo, hi = {2: (0, 1), 8: (0, 7), 41: (1, 39)}[b]
     frac = coefs / coefs.sum(axis=1, keepdims=True)
     rows = [("C7.1", "strain A", "3.25", "0.75", 0, coefs), ("C7.2", "strain B", "1.0", "0.25", 1, coefs), ("C7.3", "strain C", "0.0", "0.0", 2, coefs)]
-    text = db.bootstrap_text(rows)
+    text = read_reports.bootstrap_text(rows)
     lines = text.split("\n")
     assert text.startswith(HEADER) and lines[-1] == "" and len(lines) == 5
     for j, (table, strain, depth, fr, _, _) in enumerate(rows):
@@ -114,11 +114,11 @@ def test_writer_on_hand_made_matrices(b):
 
 def test_writer_all_zero_replicate():
     """a replicate whose coefficients are all 0 has fraction 0 for every strain (not 0 / 0), and nobody is present in it"""
-    from strainscan_amd import db
+    from strainscan_amd import read_reports
     coefs = np.array([[2.0, 2.0], [0.0, 0.0], [1.0, 3.0], [3.0, 1.0]])
-    s = db.bootstrap_summary(coefs)
+    s = read_reports.bootstrap_summary(coefs)
     assert s == [(0.0, 3.0, 0.0, 0.75, 3), (0.0, 3.0, 0.0, 0.75, 3)]
-    text = db.bootstrap_text([("C1.1", "a", "2.0", "0.5", 0, coefs), ("C1.2", "b", "2.0", "0.5", 1, coefs)])
+    text = read_reports.bootstrap_text([("C1.1", "a", "2.0", "0.5", 0, coefs), ("C1.2", "b", "2.0", "0.5", 1, coefs)])
     assert text == HEADER + "C1.1\ta\t4\t2.0\t0.0\t3.0\t0.5\t0.0\t0.75\t3\n" + "C1.2\tb\t4\t2.0\t0.0\t3.0\t0.5\t0.0\t0.75\t3\n"
     assert "nan" not in text
 
@@ -168,34 +168,34 @@ def test_commands_refuse_a_bad_value_before_any_input_is_opened(tmp_path):
 
 def test_set_bootstrap_and_the_idle_collector(tmp_path):
     import strainscan_amd
-    from strainscan_amd import db
-    assert db.BOOTSTRAP["b"] == 0 and db.BOOTSTRAP["seed"] == 1             # off by default
+    from strainscan_amd import read_reports
+    assert read_reports.BOOTSTRAP["b"] == 0 and read_reports.BOOTSTRAP["seed"] == 1             # off by default
     report = tmp_path / "StrainVote.report"
     report.write_text("header\n1\ts\tC1\t1.0\t2.0\n")
-    db.bootstrap_note_solve(begin=True, columns=[0], strains=["s"])          # off: nothing is kept, nothing is looked at
-    db.bootstrap_scanned("C1")
-    db.collect_bootstrap("C1", str(tmp_path / "no_such_cluster"), str(report), 31, [str(tmp_path / "no_such.fq")])
-    assert db.BOOTSTRAP["solve"] == {} and db.BOOTSTRAP["rows"] == {} and db.BOOTSTRAP["order"] == {}
-    assert db.write_bootstrap(str(tmp_path)) is None and db.bootstrap_replicates() == {}
+    read_reports.bootstrap_note_solve(begin=True, columns=[0], strains=["s"])          # off: nothing is kept, nothing is looked at
+    read_reports.bootstrap_scanned("C1")
+    read_reports.collect_bootstrap("C1", str(tmp_path / "no_such_cluster"), str(report), 31, [str(tmp_path / "no_such.fq")])
+    assert read_reports.BOOTSTRAP["solve"] == {} and read_reports.BOOTSTRAP["rows"] == {} and read_reports.BOOTSTRAP["order"] == {}
+    assert read_reports.write_bootstrap(str(tmp_path)) is None and read_reports.bootstrap_replicates() == {}
     try:
         strainscan_amd.set_bootstrap(8, 3)
-        assert db.BOOTSTRAP["b"] == 8 and db.BOOTSTRAP["seed"] == 3 and db.BOOTSTRAP["skipped"] is None
+        assert read_reports.BOOTSTRAP["b"] == 8 and read_reports.BOOTSTRAP["seed"] == 3 and read_reports.BOOTSTRAP["skipped"] is None
         for bad in (1, 1001, -2, 2.5, "8", True):
             with pytest.raises(ValueError):
                 strainscan_amd.set_bootstrap(bad)
         for bad in (-1, 1 << 63, 1.5, "1", True):
             with pytest.raises(ValueError):
                 strainscan_amd.set_bootstrap(8, bad)
-        assert db.BOOTSTRAP["b"] == 8 and db.BOOTSTRAP["seed"] == 3
-        assert db.write_bootstrap(str(tmp_path)) is None                    # on, but no multi-strain cluster was solved: no file
+        assert read_reports.BOOTSTRAP["b"] == 8 and read_reports.BOOTSTRAP["seed"] == 3
+        assert read_reports.write_bootstrap(str(tmp_path)) is None                    # on, but no multi-strain cluster was solved: no file
     finally:
         strainscan_amd.set_bootstrap(0)
-    assert db.BOOTSTRAP["b"] == 0 and db.BOOTSTRAP["seed"] == 1
+    assert read_reports.BOOTSTRAP["b"] == 0 and read_reports.BOOTSTRAP["seed"] == 1
     assert sorted(os.listdir(tmp_path)) == ["StrainVote.report"]
 
 
 def test_report_rows(tmp_path):
-    from strainscan_amd import db
+    from strainscan_amd import read_reports
     p = tmp_path / "StrainVote.report"
     p.write_text("h\n1\tA (With_ExtraRegion_covered)\tC7\t0.75\t3.25\t9.0\t0.9\t5/6\t5\t0.9\t\n2\tB\tC7\t0.25\t1.0\t3.0\t0.8\t4/5\t4\t0.8\t*\n")
-    assert db.report_rows(str(p)) == [(1, "A", "0.75", "3.25"), (2, "B", "0.25", "1.0")]
+    assert read_reports.report_rows(str(p)) == [(1, "A", "0.75", "3.25"), (2, "B", "0.25", "1.0")]

@@ -72,7 +72,7 @@ def _model(db_dir, out_dir, pair):
     if out_dir in _MODEL:
         return _MODEL[out_dir]
     import scipy.sparse as sp
-    from strainscan_amd import db as ssdb
+    from strainscan_amd import read_reports
     rs_rows = [ln.split("\t")[0] for ln in open(os.path.join(out_dir, "read_support.tsv")).read().split("\n")[1:] if ln]
     texts = [b"".join(s + b"\n" for _, s in pair["recs"][m]) for m in range(2)]
     n_reads = 2 * len(pair["recs"][0])
@@ -101,7 +101,7 @@ def _model(db_dir, out_dir, pair):
             rows.append(("%s.%d" % (cls, n), name, int((ul == j).sum()), n_reads, int(both.sum()), rs_model.histogram(both, 65)))
             keep = np.nonzero((per[0][j] >= N) | (per[1][j] >= N))[0]
             files["%s.%d" % (cls, n)] = [b"".join(pair["recs"][m][i][0] for i in keep) for m in range(2)]
-    _MODEL[out_dir] = (ssdb.strain_support_text(rows), files, called_of)
+    _MODEL[out_dir] = (read_reports.strain_support_text(rows), files, called_of)
     return _MODEL[out_dir]
 
 

@@ -337,30 +337,30 @@ def test_commands_refuse_a_bad_value_before_any_input_is_opened(tmp_path):
 
 def test_set_extract_reads_and_the_idle_collector(tmp_path):
     import strainscan_amd
-    from strainscan_amd import db
-    assert db.EXTRACT_READS["n"] == 0                                       # off by default
-    db.collect_extract_reads("tree", None, [str(tmp_path / "no_such.fq")])  # off: nothing is looked at
+    from strainscan_amd import read_reports
+    assert read_reports.EXTRACT_READS["n"] == 0                                       # off by default
+    read_reports.collect_extract_reads("tree", None, [str(tmp_path / "no_such.fq")])  # off: nothing is looked at
     try:
         strainscan_amd.set_extract_reads(16, str(tmp_path))
-        assert db.EXTRACT_READS["n"] == 16 and db.EXTRACT_READS["dir"] == str(tmp_path) and db.EXTRACT_READS["skipped"] is None
+        assert read_reports.EXTRACT_READS["n"] == 16 and read_reports.EXTRACT_READS["dir"] == str(tmp_path) and read_reports.EXTRACT_READS["skipped"] is None
         for bad in (-1, 1.5, "3", True):
             with pytest.raises(ValueError):
                 strainscan_amd.set_extract_reads(bad)
-        assert db.EXTRACT_READS["n"] == 16
+        assert read_reports.EXTRACT_READS["n"] == 16
     finally:
         strainscan_amd.set_extract_reads(0)
-    assert db.EXTRACT_READS["n"] == 0 and db.EXTRACT_READS["dir"] is None
-    db.collect_extract_reads("tree", None, [str(tmp_path / "no_such.fq")])
+    assert read_reports.EXTRACT_READS["n"] == 0 and read_reports.EXTRACT_READS["dir"] is None
+    read_reports.collect_extract_reads("tree", None, [str(tmp_path / "no_such.fq")])
     assert os.listdir(tmp_path) == []
 
 
 def test_record_type(tmp_path):
-    from strainscan_amd import db
+    from strainscan_amd import read_reports
     (tmp_path / "a").write_bytes(b"\n>s\nACGT\n")
     (tmp_path / "b").write_bytes(b"@r\nACGT\n+\nIIII\n")
     (tmp_path / "c.gz").write_bytes(gzip.compress(b">s\nACGT\n"))
     (tmp_path / "d.gz").write_bytes(gzip.compress(b"@r\nACGT\n+\nIIII\n"))
-    assert [db.fastx_record_type(str(tmp_path / n)) for n in ("a", "b", "c.gz", "d.gz")] == ["fasta", "fastq", "fasta", "fastq"]
+    assert [read_reports.fastx_record_type(str(tmp_path / n)) for n in ("a", "b", "c.gz", "d.gz")] == ["fasta", "fastq", "fasta", "fastq"]
 
 
 # ---------------------------------------------------------------------------------------------- the walker under sanitizers

@@ -1,4 +1,4 @@
-"""`--by_strain` on the host: the row labels of tests/label_model.py on hand-written matrices, db.strain_row_labels (the CSR form the
+"""`--by_strain` on the host: the row labels of tests/label_model.py on hand-written matrices, read_reports.strain_row_labels (the CSR form the
 command uses) against them, the slot rule for a k-mer listed twice, the labelled model against rs_model on each label's sub-table,
 the text of strain_support.tsv, and the flag parser."""
 import numpy as np
@@ -9,9 +9,9 @@ from tests import label_model, rs_model
 
 def _csr_labels(dense, called, n_rows=None):
     import scipy.sparse as sp
-    from strainscan_amd import db as ssdb
+    from strainscan_amd import read_reports
     m = sp.csr_matrix(np.asarray(dense, np.int8))
-    return ssdb.strain_row_labels(m.indptr, m.indices, m.data, m.shape[0] if n_rows is None else n_rows, called)
+    return read_reports.strain_row_labels(m.indptr, m.indices, m.data, m.shape[0] if n_rows is None else n_rows, called)
 
 
 #            s0 s1 s2 s3
@@ -53,7 +53,7 @@ def test_row_labels_random_matrix_csr_equals_dense():
 def test_cluster_csr_arrays_stored_and_deflated(tmp_path):
     """a .npz whose members are stored is mapped, one that is deflated is read the solver's way: the same arrays, the same labels"""
     import scipy.sparse as sp
-    from strainscan_amd import db as ssdb
+    from strainscan_amd import read_reports
     rs = np.random.RandomState(9)
     dense = (rs.random_sample((300, 7)) < 0.4).astype(np.int8)
     dense[5] = 0                                         # an empty row
@@ -63,10 +63,10 @@ def test_cluster_csr_arrays_stored_and_deflated(tmp_path):
     sp.save_npz(deflated, m, compressed=True)
     want = label_model.row_labels(dense, [6, 1, 3])
     for path, mapped in ((stored, True), (deflated, False)):
-        indptr, indices, data = ssdb.cluster_csr_arrays(path)
+        indptr, indices, data = read_reports.cluster_csr_arrays(path)
         assert isinstance(indices, np.memmap) == mapped
         assert (np.asarray(indptr) == m.indptr).all() and (np.asarray(indices) == m.indices).all() and (np.asarray(data) == m.data).all()
-        assert ssdb.strain_row_labels(indptr, indices, data, 300, [6, 1, 3]).tolist() == want.tolist()
+        assert read_reports.strain_row_labels(indptr, indices, data, 300, [6, 1, 3]).tolist() == want.tolist()
 
 
 def test_slot_rule_for_a_kmer_listed_twice():
@@ -103,22 +103,22 @@ def test_labeled_model_is_rs_model_on_each_sub_table():
 
 
 def test_strain_support_text():
-    from strainscan_amd import db as ssdb
+    from strainscan_amd import read_reports
     hist = [0] * 65
     hist[0], hist[1], hist[3], hist[20], hist[64] = 90, 4, 3, 2, 1
-    text = ssdb.strain_support_text([("C12.1", "GCF_000123", 4321, 100, 999, hist), ("C12.2", "GCF_000456", 0, 100, 0, [100] + [0] * 64)])
+    text = read_reports.strain_support_text([("C12.1", "GCF_000123", 4321, 100, 999, hist), ("C12.2", "GCF_000456", 0, 100, 0, [100] + [0] * 64)])
     assert text == ("table\tstrain\tkmers\treads\thits\tge1\tge2\tge4\tge8\tge16\tge32\tge64\n"
                     "C12.1\tGCF_000123\t4321\t100\t999\t10\t6\t3\t3\t3\t1\t1\n"
                     "C12.2\tGCF_000456\t0\t100\t0\t0\t0\t0\t0\t0\t0\t0\n")
 
 
 def test_called_strains_of_a_report(tmp_path):
-    from strainscan_amd import db as ssdb
+    from strainscan_amd import read_reports
     from strainscan_amd.Vote_Strain_L2_Lasso_new_sp import STRAINVOTE_HEADER
     p = tmp_path / "StrainVote.report"
     p.write_text(STRAINVOTE_HEADER + "1\tGCF_A\tC7\t0.7\t8.0\t9.3\t0.99\t1/2\t1\t0.9\t*\n"
                  "2\tGCF_B (With_ExtraRegion_covered)\tC7\t0.3\t3.1\t3.6\t0.9\t1/2\t1\t0.7\t\n")
-    assert ssdb.called_strains(str(p)) == [(1, "GCF_A"), (2, "GCF_B")]
+    assert read_reports.called_strains(str(p)) == [(1, "GCF_A"), (2, "GCF_B")]
 
 
 @pytest.mark.parametrize("mod", ["StrainScan", "multi_db"])
