@@ -269,7 +269,8 @@ int ss_ingest_warm_up(void);
  * counts, and the ranks of one node (one process per GPU under torchrun) share it; SS_INGEST_THREADS overrides. */
 int ss_ingest_threads(int *n);
 /* A resident read set from a flat base block that is already on the device (copied; order != 0: its records are put
- * in locality order, see below). */
+ * in locality order, see below).  Its records are not counted here: the first ss_reads_info that asks for n_records counts
+ * them on the device (one pass over an ASCII slab; a packed slab knows). */
 int ss_reads_from_flat_dev(const void *flat_dev, uint64_t n, int order, ss_reads **out);
 /* The records of a set that is in file order (ss_reads_from_flat_dev with order = 0, what ss_reads_select and ss_reads_resample
  * return) put in locality order in place, whatever SS_READS_ORDER says: every slab that is not binned yet is replaced by its binned

@@ -138,6 +138,7 @@ struct ss_reads {
     std::vector<Slab> slabs;
     std::mutex mu;
     uint64_t n_records = 0, n_bases = 0, device_bytes = 0, n_blocks = 0;
+    bool records_counted = true;      // false: made from a flat block (ss_reads_from_flat_dev); ss_reads_info counts the records when asked
     bool has_cut_record = false;      // a record longer than a block was cut with a 30-base overlap (k = 31 only)
     uint64_t first_slab = 0;          // size of the first slab (estimate from the file sizes)
     uint64_t serial = next_serial();  // names this set: a table remembers which set it was last probed with

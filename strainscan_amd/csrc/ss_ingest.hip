@@ -771,6 +771,48 @@ struct LoadSink : ss::InputSink {
         return SS_OK;
     }
 };
+
+// record starts of a flat block (a byte other than '\n' at the block's first byte or behind a '\n'): 16 bytes per thread
+__global__ __launch_bounds__(256) void count_records_kernel(const char *__restrict__ b, uint64_t n, unsigned long long *__restrict__ out)
+{
+    const uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u;
+    uint32_t c = 0;
+    if (i0 < n) {
+        char prev = i0 ? b[i0 - 1] : '\n';
+        for (uint64_t i = i0; i < i0 + 16 && i < n; i++) {
+            const char ch = b[i];
+            c += (uint32_t)(ch != '\n' && prev == '\n');
+            prev = ch;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_down((int)c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
+}
+
+// the records of a set whose maker did not count them (ss_reads_from_flat_dev): a packed slab holds n_pos / slot, an ASCII one
+// is counted on the device
+int count_records(const ss_reads *R, uint64_t *n_records)
+{
+    uint64_t total = 0;
+    unsigned long long *d_n = nullptr;
+    for (const auto &sl : R->slabs) {
+        if (sl.packed) { total += sl.slot ? sl.n_pos / sl.slot : 0; continue; }
+        if (!sl.used) continue;
+        if (!d_n) SS_HIP(hipMalloc((void **)&d_n, 8));
+        unsigned long long c = 0;
+        hipError_t e = hipMemsetAsync(d_n, 0, 8, 0);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(count_records_kernel, dim3((unsigned)((sl.used + 4095) / 4096)), dim3(256), 0, 0, sl.d, sl.used, d_n);
+            e = hipMemcpy(&c, d_n, 8, hipMemcpyDeviceToHost);
+        }
+        if (e != hipSuccess) { hipFree(d_n); SS_HIP(e); }
+        total += c;
+    }
+    if (d_n) hipFree(d_n);
+    *n_records = total;
+    return SS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -846,6 +888,7 @@ int ss_reads_from_flat_dev(const void *flat_dev, uint64_t n, int order, ss_reads
     if (!R) return SS_ENOMEM;
     R->first_slab = n + 64;
     R->n_bases = n;
+    R->records_counted = false;                                     // (counted when ss_reads_info is asked: not on the binning's time)
     if (n && order && n >= 64) {
         // binned straight out of the caller's block (ss_reorder.hip): no intermediate copy
         ss_reads::Slab sl;
@@ -966,6 +1009,15 @@ int ss_reads_destroy(ss_reads *R)
 int ss_reads_info(const ss_reads *R, uint64_t *n_records, uint64_t *n_bases, uint64_t *n_blocks, uint64_t *device_bytes)
 {
     if (!R) return SS_EINVAL;
+    if (n_records && !R->records_counted) {                         // a set from a flat block: its records are counted now, once
+        ss_reads *W = const_cast<ss_reads *>(R);
+        std::lock_guard<std::mutex> g(W->mu);
+        if (!W->records_counted) {
+            const int rc = count_records(W, &W->n_records);
+            if (rc != SS_OK) return rc;
+            W->records_counted = true;
+        }
+    }
     if (n_records) *n_records = R->n_records;
     if (n_bases) *n_bases = R->n_bases;
     if (n_blocks) *n_blocks = R->n_blocks;

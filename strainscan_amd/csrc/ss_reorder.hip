@@ -18,7 +18,7 @@
 //   bin  = top 12 to 22 bits (order_bits) of h = mix30(minimizer of the record's first 31 bases) -- the hash that addresses the
 //          index pages (ss_mini.hip), so a bin's FIRST lookups also walk the page table in ascending order;
 //          records without a first k-mer (shorter, or a non-ACGT base in it) go to one extra bin at the end
-//   pass 1  count_kernel: find the record starts of a 4 KB tile (16 bytes per lane, SWAR newline masks), the end of each
+//   pass 1  count_kernel: find the record starts of a 16 KB tile (64 bytes per lane, SWAR newline masks), the end of each
 //           record (suffix minimum over the tile + a 512-byte halo), its bin; atomicAdd of the record's slot size to the
 //           bin's byte count.  A slot = record + '\n', padded with '\n' to 8 bytes (152 bytes for a 150-base read: nothing
 //           added) so that every piece of the copy is an aligned store
@@ -156,7 +156,7 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane)
     return v;
 }
 
-// ---- what a workgroup knows about its 4 KB tile -------------------------------------------------------------------
+// ---- what a workgroup knows about its 16 KB tile ------------------------------------------------------------------
 // Per-tile record table, written by the first pass and read by the second (so the second neither looks for newlines
 // nor keys anything): entry = start in the tile (14 bits) | length (26 bits) | bin (24 bits); a tile with more than
 // TCAP record starts (reads shorter than ~125 bases), or a record of 64 MB, says T_OVERFLOW and is discovered again.

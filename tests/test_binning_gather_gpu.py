@@ -9,6 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.binmodel import bin_of as _bin, one_length_candidate as _one_length_candidate, order_bits as _order_bits
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,36 +19,6 @@ def L():
     from strainscan_amd import _lib
     _lib.require_gpu()
     return _lib
-
-
-def _bin(rec, bits, k=31, m=15):
-    """Bin of a record (ss_reorder.hip record_bin): top `bits` bits of mix30 of the minimizer of its first 31 bases."""
-    code = {65: 0, 67: 1, 84: 2, 71: 3}
-    if len(rec) < k:
-        return 1 << bits
-    cs = [code.get(c & 0xDF, -1) for c in rec[:k]]
-    if min(cs) < 0:
-        return 1 << bits
-    km = sum(c << (2 * j) for j, c in enumerate(cs))
-    best, bx = None, 0
-    for i in range(k - m + 1):
-        x = (km >> (2 * i)) & 0x3FFFFFFF
-        h = (((x & 0xFFFFFF) * (0x4F1BB << 5) + 0x7F4A7C00) & 0xFFFFFFFF) & ~31
-        if best is None or h < best:
-            best, bx = h, x
-    M30 = 0x3FFFFFFF
-    h = (bx * 0x9E3779B1) & M30
-    h ^= h >> 15
-    h = (h * 0x2C1B3C6D) & M30
-    h ^= h >> 14
-    return h >> (30 - bits)
-
-
-def _order_bits(n_bytes):
-    bits = 12
-    while bits < 22 and (n_bytes // 152) >> (bits + 2):
-        bits += 1
-    return bits
 
 
 def _order_counters(L):
@@ -78,16 +50,6 @@ def _records(seed, length, n_rec, g, lower_first=False, mid=None):
 def _kdb(L, g):
     kfa = b"".join(b">1\n" + g[i:i + 31].tobytes() + b"\n" for i in range(0, len(g) - 31, 7))
     return L.KmerDB.from_text(kfa, 31, True)
-
-
-def _one_length_candidate(block):
-    """(L, n_rec) when order_flat_dev takes the block for the one-length paths, else None: the first newline says L, within
-    FIX_MIN_L..FIX_MAX_L, at least 64 bytes (`qualifies` of test_binning_of_records_of_one_length), fewer than 64 bytes behind
-    the last whole record."""
-    n, length = len(block), block[:1025].find(b"\n")
-    if n < 64 or not 32 <= length <= 1023 or n % (length + 1) >= 64:
-        return None
-    return length, n // (length + 1)
 
 
 def _ragged_block(seed, n_rec, g):

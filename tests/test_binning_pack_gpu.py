@@ -10,6 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.binmodel import order_bits as _order_bits, slot_of as _slot
+
 pytestmark = pytest.mark.gpu
 
 BIG_KEEP_MIN = 256 << 20          # ss_common.h
@@ -33,17 +35,6 @@ def db(L, genome):
     d = L.KmerDB.from_text(kfa, 31, True)
     yield d
     d.close()
-
-
-def _slot(length):
-    return (length + 1 + 7) & ~7
-
-
-def _order_bits(n_bytes):
-    bits = 12
-    while bits < 22 and (n_bytes // 152) >> (bits + 2):
-        bits += 1
-    return bits
 
 
 _CODE = np.full(256, 255, np.uint8)

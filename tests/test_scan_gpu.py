@@ -1195,32 +1195,15 @@ def _locality_bin(rec, bits=12, k=31, m=15):
     """Bin of ss_reorder.hip restated: the top `bits` bits of mix30 (the index's page hash, ss_scan_dev.h) of the 30-bit
     minimizer (ordering key of the index: ((x & 0xFFFFFF) * C1 + C0) with the low five bits cleared, leftmost on ties)
     of the record's first 31 bases; 1 << bits when there is none."""
-    code = {65: 0, 67: 1, 84: 2, 71: 3}
-    if len(rec) < k:
-        return 1 << bits
-    cs = [code.get(c & 0xDF, -1) for c in rec[:k]]
-    if min(cs) < 0:
-        return 1 << bits
-    km = sum(c << (2 * j) for j, c in enumerate(cs))
-    best, bx = None, 0
-    for i in range(k - m + 1):
-        x = (km >> (2 * i)) & 0x3FFFFFFF
-        h = (((x & 0xFFFFFF) * (0x4F1BB << 5) + 0x7F4A7C00) & 0xFFFFFFFF) & ~31
-        if best is None or h < best:
-            best, bx = h, x
-    M30 = 0x3FFFFFFF
-    h = (bx * 0x9E3779B1) & M30
-    h ^= h >> 15
-    h = (h * 0x2C1B3C6D) & M30
-    h ^= h >> 14
-    return h >> (30 - bits)
+    from tests.binmodel import bin_of
+    return bin_of(rec, bits, k, m)
 
 
 def test_locality_ordered_read_set(L):
     """ss_reorder.hip: a resident read set keeps its records binned by the minimizer of their first k-mer (4096 bins in
     ascending order + one for the records without a first k-mer).  Counting must not notice: every record survives
     exactly once, whole, '\\n'-terminated -- ragged lengths, records shorter than a k-mer, N inside the first 31 bases,
-    lower case, runs of empty lines (the 16-byte padding of the blocks), records straddling the 4096-byte tiles and
+    lower case, runs of empty lines (the 16-byte padding of the blocks), records straddling the 16384-byte tiles and
     their 512-byte halo (a 4500-base record), a block without a final newline, a block whose length is not a
     multiple of 16."""
     import ctypes as C
