@@ -361,6 +361,30 @@ int ss_reads_labeled_calls(uint64_t *n);   /* calls of either so far in this pro
  * Synchronous.  SS_EINVAL: a NULL argument.  SS_ERANGE: a set with a cut record; more records than hipcub's int item count holds. */
 int ss_reads_resample(const ss_reads *r, uint64_t seed, uint32_t replicate, ss_reads **out);
 int ss_reads_resample_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* Every record of a resident set assigned to a node of a tree over the table's k-mers (`--classify_reads`); a record and a hit are
+ * those of ss_reads_support.  row_node[i], i < the table's rows (host memory): 0 = the row counts for nobody, v in 1..n_nodes = it
+ * is a k-mer of node v.  Rows that share a slot (the same k-mer listed twice) keep their common node; where they disagree the
+ * k-mer counts for nobody.  parent[v], v in 1..n_nodes (parent[0] is not read): v's parent, 0 = none; the array must describe a
+ * forest (parent[v] < v is not required), which is checked on the host before anything is launched.
+ *   h[v]     = the record's hits whose k-mer has node v
+ *   score(v) = the sum of h[u] over the path from v's root to v, v included, for every v with h[v] > 0
+ *   class    = the node with the largest score; several nodes with that score (never on one path): their lowest common ancestor,
+ *              which may have no hits itself, and 0 when they stand in different trees; 0 (unclassified) when the largest score
+ *              is below min_score or no hit has a node
+ * direct[c], c in 0..n_nodes: records of class c; sum(direct) = the set's non-empty records.  node_hits[v]: the sum of h[v] over
+ * all records, node_hits[0] the hits of k-mers without a node.  kmers[v]: the distinct k-mers (slots) of node v, kmers[0] = 0.  All
+ * three hold n_nodes + 1 entries.  rec_class (host memory, NULL to skip): the class of every record, in the record order of
+ * ss_reads_read_back (the records numbered slab after slab).  Nothing depends on the order of the records: file order, binned
+ * ASCII and packed slabs give the same direct and node_hits, and the results of a set's shards add up to the whole set's.
+ * Synchronous.  Reads the table's index, never its counters.  SS_ERANGE: as ss_reads_select states it.  SS_EINVAL: a NULL argument
+ * other than rec_class, min_score == 0, n_nodes outside 1..SS_CLASS_NODES_MAX, a row node above n_nodes, a parent above n_nodes or
+ * a cycle, a table and a set on different devices. */
+#define SS_CLASS_NODES_MAX 65535
+int ss_reads_classify(const ss_db *db, const ss_reads *r, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent,
+                      uint32_t min_score, uint64_t *direct, uint64_t *node_hits, uint64_t *kmers, uint32_t *rec_class);
+int ss_reads_classify_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* the records whose class came from a tie (score >= min_score) in the calling thread's last ss_reads_classify */
+int ss_reads_classify_ties(uint64_t *n);
 
 /* --------------------------------------------------------------------------------------------
  * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input

@@ -142,6 +142,14 @@ def add_arguments(ap, multi=False):
                          "sample resident on the device and k >= 17 (default: off)")
     ap.add_argument("--bootstrap_seed", dest="bootstrap_seed", type=bootstrap_seed_arg, default=1, metavar="S",
                     help="The seed of --bootstrap's replicates: the same S gives the same file.  An integer in 0..2^63-1 (default: 1)")
+    ap.add_argument("--classify_reads", dest="classify_reads", type=classify_reads_arg, default=0, metavar="M",
+                    help="Also write read_classes.tsv: every read assigned to a node of the cluster search tree.  A read's hits "
+                         "against the tree's k-mers point at the nodes that list them; the read goes to the node whose path from the "
+                         "root collects the most hits, to the lowest common ancestor where several nodes tie, and to nobody "
+                         "(`unclassified`) below M hits on the best path.  One row per node: its k-mers, their hits, the reads "
+                         "assigned to it (reads_direct) and to it or anything below it (reads_clade).  An integer >= 1 (1 or 2 "
+                         "for the sampled node sets of a tree); needs the sample resident on the device and a database with "
+                         "more than one cluster (default: off)")
 
 
 def refuse_by_strain_alone(ap, args):
@@ -171,6 +179,17 @@ def extract_reads_arg(text):
     if n < 1 or n > 0xFFFFFFFF:
         raise argparse.ArgumentTypeError("%d is outside 1..%d" % (n, 0xFFFFFFFF))
     return n
+
+
+def classify_reads_arg(text):
+    """--classify_reads' value: an integer of at least 1, or the parser's error (exit status 2, before any input is opened)."""
+    try:
+        m = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not an integer >= 1" % text)
+    if m < 1 or m > 0xFFFFFFFF:
+        raise argparse.ArgumentTypeError("%d is outside 1..%d" % (m, 0xFFFFFFFF))
+    return m
 
 
 def bootstrap_arg(text):
@@ -231,6 +250,14 @@ def apply_bootstrap(b, seed=1):
     the other files are untouched; 0 turns it off."""
     from . import read_reports
     read_reports.bootstrap_reset(b, seed)
+
+
+def apply_classify_reads(m):
+    """--classify_reads M (strainscan_amd.set_classify_reads): the tree scans from here on assign every read to a node of the tree
+    (read_reports.collect_read_classes); the command writes read_classes.tsv when it ends.  stdout and the other files are
+    untouched; 0 turns it off."""
+    from . import read_reports
+    read_reports.classify_reads_reset(m)
 
 
 def settings(args):
@@ -328,6 +355,7 @@ def main(argv=None):
     apply_extract_reads(args.extract_reads, out_dir)
     apply_by_strain(args.by_strain)
     apply_bootstrap(args.bootstrap, args.bootstrap_seed)
+    apply_classify_reads(args.classify_reads)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:

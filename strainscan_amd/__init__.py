@@ -17,6 +17,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, read_reports.EXTRACT_READS)
     strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, read_reports.BY_STRAIN)
     strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, read_reports.BOOTSTRAP)
+    strainscan_amd.set_classify_reads                         (`strainscan --classify_reads M`: reads per node of the cluster tree, read_reports.CLASSIFY_READS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -76,6 +77,18 @@ def set_bootstrap(b, seed=1):
         raise ValueError("bootstrap seed must be an integer in 0..2^63-1, not %r" % (seed,))
     from . import read_reports
     read_reports.bootstrap_reset(b or 0, seed)
+
+
+def set_classify_reads(m):
+    """`strainscan --classify_reads M` for callers of the functions above: from here on identify_cluster, behind its scan of the
+    tree's table, assigns every read of the sample to a node of the cluster search tree (ReadSet.classify: the node whose path from
+    the root collects the most of the read's k-mer hits, the lowest common ancestor on a tie, nobody below m hits) and keeps the
+    numbers with read_reports.CLASSIFY_READS; read_reports.write_read_classes(out_dir) writes read_classes.tsv.
+    m is an integer >= 1 (0 or None turns it off).  Off by default; nothing runs while it is off."""
+    if m and (isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 0xFFFFFFFF):
+        raise ValueError("classify_reads must be an integer >= 1 (or 0 for off), not %r" % (m,))
+    from . import read_reports
+    read_reports.classify_reads_reset(m or 0)
 
 
 def get_min_base_qual():

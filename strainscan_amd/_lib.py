@@ -115,6 +115,9 @@ SIGNATURES = {
     "ss_reads_labeled_calls": (i32, [P(u64)]),
     "ss_reads_resample": (i32, [vp, u64, u32, P(vp)]),
     "ss_reads_resample_calls": (i32, [P(u64)]),
+    "ss_reads_classify": (i32, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp]),
+    "ss_reads_classify_calls": (i32, [P(u64)]),
+    "ss_reads_classify_ties": (i32, [P(u64)]),
     "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
@@ -531,6 +534,30 @@ class ReadSet:
         sub._h = h
         return sub
 
+    def classify(self, kdb, row_node, parent, min_score, want_classes=False):
+        """Every record assigned to a node of a tree over the table's k-mers (ss_reads_classify; tests/class_model.py restates it).
+        row_node[i] in 0..n for row i of the table (0 = counts for nobody), parent[v] for v in 1..n (entry 0 is not read; 0 = no
+        parent), n = len(parent) - 1.  -> dict(direct=, node_hits=, kmers= np.uint64[n + 1], ties= records whose class came from a
+        tie, classes= np.uint32 per record in read_back() order, or None).  Rows that share a k-mer under different nodes count
+        for nobody.  The table's counters are left alone."""
+        rn = np.ascontiguousarray(row_node, np.uint32)
+        if rn.ndim != 1 or rn.size != kdb.n_rows:
+            raise ValueError("one node per row of the table (%d), not %r" % (kdb.n_rows, rn.shape))
+        par = np.ascontiguousarray(parent, np.uint32)
+        if par.ndim != 1 or par.size < 1:
+            raise ValueError("parent holds an entry per node and entry 0")
+        n = par.size - 1
+        direct, node_hits, kmers = (np.zeros(n + 1, np.uint64) for _ in range(3))
+        # (the records as ss_reads_support counts them: ss_reads_info's count includes reads without a base)
+        classes = np.zeros(max(1, int(self.support(kdb, 2)[0].sum())), np.uint32) if want_classes else None
+        check(lib().ss_reads_classify(kdb.handle, self._h, ptr(rn if rn.size else np.zeros(1, np.uint32)), n, ptr(par), int(min_score),
+                                      ptr(direct), ptr(node_hits), ptr(kmers), ptr(classes) if want_classes else None), "ss_reads_classify")
+        ties = C.c_uint64()
+        check(lib().ss_reads_classify_ties(C.byref(ties)), "ss_reads_classify_ties")
+        if want_classes:
+            classes = classes[:int(direct.sum())]
+        return dict(direct=direct, node_hits=node_hits, kmers=kmers, ties=int(ties.value), classes=classes)
+
     def order(self):
         """Put the records of a set in file order (from_flat_dev(order=False), select(), resample()) in locality order, in place
         (ss_reads_order): the records and every count stay, a scan of a cluster table gets faster.  -> self"""
@@ -576,6 +603,16 @@ def resample_calls():
     """Calls of ss_reads_resample so far in this process."""
     n = C.c_uint64()
     check(lib().ss_reads_resample_calls(C.byref(n)), "ss_reads_resample_calls")
+    return n.value
+
+
+CLASS_NODES_MAX = 65535     # SS_CLASS_NODES_MAX (strainscan_hip.h)
+
+
+def classify_calls():
+    """Calls of ss_reads_classify so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_classify_calls(C.byref(n)), "ss_reads_classify_calls")
     return n.value
 
 

@@ -324,6 +324,11 @@ int launch_support_minik(const ss_db *db, const void *bases_dev, uint64_t n, boo
 // 1..n_labels; a found k-mer of label j adds 1 to a.rec_hits[(j - 1) * a.rec_limit + record]; label 0 counts nowhere.
 int launch_label_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const SupportArgs &a, const uint8_t *slot_label,
                        uint32_t n_labels, hipStream_t stream);
+// ss_reads_classify (ss_classify.hip): the same with the class sink.  slot_node[n_slots] (indexed like d_counts) is 0 or
+// 1..n_nodes; pos_node[p] = the node of the k-mer found at position p of the slab (0: no hit, or a hit without a node), written for
+// every position of every tile: room for ((n + 1023) / 1024) * 1024 fields, 16-byte aligned.  *hits0 += the hits without a node.
+int launch_class_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, uint16_t *pos_node, const uint16_t *slot_node,
+                       unsigned long long *hits0, hipStream_t stream);
 // the scan of one table through the same kernel (ss_minik.hip): launch_scan_mini sends it the tables it does not take itself
 int launch_scan_minik(ss_db *db, const uint8_t *bases_dev, uint64_t n, hipStream_t stream, bool packed);
 // the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster

@@ -61,6 +61,25 @@ struct LabelSink {
     __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *bits, uint32_t p) const { mark(slot_label[cbase + page_slot], bits, p); }
 };
 static_assert(SS_LABELS_MAX <= 15, "a position's label is a 4-bit field");
+// ClassSink (ss_reads_classify, ss_classify.hip): the NODE of its slot (slot_node[], indexed like the counters; 0 = none) in a
+// 16-bit field per position, a plain LDS store; a hit whose slot has no node sets the bit of its position in a bitmap behind the
+// fields.  Its tail knows no records: a lane writes the sixteen fields of the positions it decoded to pos_node[] of the slab (two
+// 16-byte stores, every position of every tile written, so the array needs no clearing) and the bitmap's bits go to *hits0.
+struct ClassSink {
+    static constexpr int PER_POS = 16;
+    uint16_t *__restrict__ pos_node;            // [n_tiles * KPOS] node of the hit at each position of the slab, 0 = none
+    const uint16_t *__restrict__ slot_node;     // [n_slots] 0 or 1..n_nodes
+    unsigned long long *__restrict__ hits0;     // += hits whose slot has node 0
+    uint32_t cbase;
+    __device__ __forceinline__ void mark(uint32_t v, uint32_t *bits, uint32_t p) const
+    {
+        if (v) reinterpret_cast<uint16_t *>(bits)[p] = (uint16_t)v;
+        else atomicOr(&bits[KPOS / 2 + (p >> 5)], 1u << (p & 31u));
+    }
+    __device__ __forceinline__ void bucket(uint32_t slot, uint32_t *bits, uint32_t p) const { mark(slot_node[slot], bits, p); }
+    __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *bits, uint32_t p) const { mark(slot_node[cbase + page_slot], bits, p); }
+};
+static_assert(SS_CLASS_NODES_MAX <= 0xFFFF, "a position's node is a 16-bit field");
 // the tile's LDS: the sinks with a tail add the positions' bits and the '\n' flags of the tile's bytes (nl[0]: bit 15 = the byte before the tile)
 // (LEAN: no '\n' flags -- the label sink over a packed slab, which has no '\n': the 132 bytes are what keeps the 21st one-wave
 // workgroup on a CU)
@@ -73,6 +92,11 @@ template <int PER_POS, bool LEAN> struct KSharedT : KShared {
 template <> struct KSharedT<4, true> : KShared {
     static constexpr int HIT_WORDS = KPOS * 4 / 32;
     uint32_t hit[HIT_WORDS];
+    __device__ __forceinline__ uint32_t *bits() { return hit; }
+};
+template <bool LEAN> struct KSharedT<16, LEAN> : KShared {      // the class sink: 16-bit fields, then a bit per position; no '\n' flags
+    static constexpr int HIT_WORDS = KPOS / 2 + KPOS / 32;
+    alignas(16) uint32_t hit[HIT_WORDS];
     __device__ __forceinline__ uint32_t *bits() { return hit; }
 };
 template <bool LEAN> struct KSharedT<0, LEAN> : KShared { __device__ __forceinline__ uint32_t *bits() { return nullptr; } };
@@ -165,7 +189,7 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
             S.inv[t] = (uint16_t)inv;
             if constexpr (SINK::PER_POS != 0) {
                 for (int i = t; i < S.HIT_WORDS; i += KT) S.hit[i] = 0u;
-                if constexpr (IN != IN_PACKED) {
+                if constexpr (IN != IN_PACKED && SINK::PER_POS != 16) {
                     S.nl[t + 1] = (uint16_t)newline_mask16(w);
                     if (t == 0) S.nl[0] = (b0 == 0 || bases[b0 - 1] == 0x0Au) ? 0x8000u : 0u;      // (a slab begins behind a boundary)
                 }
@@ -296,7 +320,17 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
         // index steps up (ASCII: a record end, a '\n' behind a byte that is none -- no k-mer starts there; packed: the first
         // position of a slot), r is the record of its first position: the tile's base + the boundaries of the lanes before (a wave
         // prefix sum), or position / slot.  One atomic per (lane, record) with hits: neighbouring lanes, neighbouring words.
-        if constexpr (SINK::PER_POS != 0) {
+        if constexpr (SINK::PER_POS == 16) {
+            // ---- classes: the lane's sixteen node fields to the slab's pos_node (32 bytes, the wave's 2 KB in one piece); the hits
+            // without a node are counted, one vector atomic per tile that has any
+            uint4 *__restrict__ dst = reinterpret_cast<uint4 *>(sink.pos_node + b0 + 16u * (uint32_t)t);
+            dst[0] = reinterpret_cast<const uint4 *>(S.hit)[2 * t];
+            dst[1] = reinterpret_cast<const uint4 *>(S.hit)[2 * t + 1];
+            uint32_t c = t < KPOS / 32 ? (uint32_t)__popc(S.hit[KPOS / 2 + t]) : 0u;
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+            if (t == 0 && c) atomicAdd(sink.hits0, (unsigned long long)c);
+        } else if constexpr (SINK::PER_POS != 0) {
             const ss::SupportArgs &A = sink.a;
             uint32_t bnd = 0;
             uint64_t r = A.rec_base;
@@ -374,6 +408,15 @@ int launch_label_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool 
     if (!n || db->layout != 1 || (packed ? a.slot == 0 : a.tile_base == nullptr)) return SS_EINVAL;
     if (!slot_label || n_labels < 1 || n_labels > SS_LABELS_MAX) return SS_EINVAL;
     return launch_minik(db, (const uint8_t *)bases_dev, n, packed, LabelSink{a, slot_label, (uint32_t)db->n_mslots, n_labels}, stream);
+}
+
+// ... and for ss_reads_classify (ss_classify.hip): a found k-mer leaves the node of its slot at its position in pos_node, which
+// holds a whole number of tiles: ((n + 1023) / 1024) * 1024 fields
+int launch_class_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, uint16_t *pos_node, const uint16_t *slot_node,
+                       unsigned long long *hits0, hipStream_t stream)
+{
+    if (!n || db->layout != 1 || !pos_node || !slot_node || !hits0 || (((uintptr_t)pos_node) & 15)) return SS_EINVAL;
+    return launch_minik(db, (const uint8_t *)bases_dev, n, packed, ClassSink{pos_node, slot_node, hits0, (uint32_t)db->n_mslots}, stream);
 }
 
 }  // namespace ss

@@ -78,8 +78,8 @@ def _identify(fq_path, db_dir, cutoff, params, upper_keys):
             pre.join()
     if not img.is_external:
         img.scan(_paths(fq_path))
-        from .read_reports import table_scanned
-        table_scanned("tree", img.kdb, _paths(fq_path))      # (--read_support, -x; once per database)
+    from .read_reports import tree_scanned
+    tree_scanned(img, _paths(fq_path))      # (--read_support, -x, --classify_reads; once per database)
     walk = cst.Walk(cst.ImageProvider(img), db_dir, cutoff, params, out=_trace)
     res = walk.run()
     _trace("- The total running time of tree search is ", str(time.time() - start), " s\n")

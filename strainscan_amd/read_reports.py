@@ -1,8 +1,9 @@
-"""The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain and --bootstrap.
+"""The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap and
+--classify_reads.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
-them through table_scanned and cluster_reported, the commands end with write_all and reset_all.  The scope is the database at
+them through tree_scanned, table_scanned and cluster_reported, the commands end with write_all and reset_all.  The scope is the database at
 work: SCOPE["label"], None but inside strainscan-multi's database_scope.
 """
 import contextlib
@@ -33,6 +34,14 @@ def database_scope(label, out_dir):
         SCOPE["label"], EXTRACT_READS["dir"] = before
 
 
+def tree_scanned(img, paths):
+    """The tree image `img` (db.TreeImage) holds the scan of `paths`, or counts made elsewhere (img.is_external): the tree's
+    table_scanned, then --classify_reads, which needs the node lists and the tree as well as the table."""
+    if not img.is_external:
+        table_scanned("tree", img.kdb, paths)
+    collect_read_classes(img, paths)
+
+
 def table_scanned(table, kdb, paths):
     """`kdb` is open and holds the scan of `paths`: --read_support's row, -x's files and --bootstrap's order of the clusters.
     ("tree" enters that order too; write_bootstrap keeps only tables with rows, and the tree never has any.)"""
@@ -51,6 +60,7 @@ def write_all(out_dir, scope=None):
     write_read_support(out_dir, scope)
     write_strain_support(out_dir, scope)
     write_bootstrap(out_dir, scope)
+    write_read_classes(out_dir, scope)
 
 
 def reset_all():
@@ -58,6 +68,7 @@ def reset_all():
     extract_reads_reset()
     by_strain_reset()
     bootstrap_reset()
+    classify_reads_reset()
 
 
 def _skip(state, name, closing, rank0_only, why):
@@ -572,3 +583,112 @@ def write_bootstrap(out_dir, scope=None):
              for t in _in_order(BOOTSTRAP["order"].get(scope, []), rows) for n, name, depth, frac, col in rows[t]["called"]]
     return _write(out_dir, BOOTSTRAP_FILE, bootstrap_text(lines)) if lines else None
 
+
+
+# --classify_reads M (StrainScan.apply_classify_reads turns it on): every read assigned to a node of the cluster search tree.
+# kmers/<id> lists each k-mer of the tree's table under one node, so a read's hits against that table point at nodes; the read goes
+# to the node whose root path collects the most hits, ties to the tied nodes' lowest common ancestor, fewer than M hits on the best
+# path to nobody (ReadSet.classify; tests/class_model.py restates it).  Collected once per scope behind the tree scan, summed over
+# the ranks, written as read_classes.tsv: a row per node, reads_direct the reads of that class, reads_clade those of the node and
+# everything below it.
+CLASSIFY_READS = {"m": 0, "rows": {}, "skipped": None}
+READ_CLASSES_FILE = "read_classes.tsv"
+_CLASSIFY_READS_LOCK = threading.Lock()
+_classify_reads_skip = functools.partial(_skip, CLASSIFY_READS, "classify_reads", "and no read was classified", True)
+
+
+def classify_reads_reset(m=0):
+    CLASSIFY_READS.update(m=int(m or 0), rows={}, skipped=None)
+
+
+def tree_row_nodes(node_ids, node_rows, n_rows):
+    """np.uint32[n_rows]: the node (1-based position in node_ids) that lists each row of the tree's table, 0 for a row that no
+    node lists or that two different nodes list."""
+    rows = [np.asarray(node_rows.get(nid, ()), np.int64).ravel() for nid in node_ids]
+    node = np.concatenate([np.full(r.size, v, np.int64) for v, r in enumerate(rows, 1)] or [np.zeros(0, np.int64)])
+    row = np.concatenate(rows or [np.zeros(0, np.int64)])
+    keep = (row >= 0) & (row < n_rows)
+    row, node = row[keep], node[keep]
+    lo = np.full(n_rows, np.iinfo(np.int64).max, np.int64)
+    hi = np.zeros(n_rows, np.int64)
+    np.minimum.at(lo, row, node)
+    np.maximum.at(hi, row, node)
+    return np.where(lo == hi, hi, 0).astype(np.uint32)
+
+
+def read_classes_text(node_ids, parent_of, leaves, direct, node_hits, kmers):
+    """The text of read_classes.tsv.  node_ids: ascending, node v of the arrays (1-based) is node_ids[v - 1]; parent_of: {id: parent
+    id, None for a root}; leaves: the ids that are clusters; direct / node_hits / kmers: [n + 1], entry 0 the unclassified reads,
+    the hits of k-mers without a node, and 0."""
+    n = len(node_ids)
+    num = {nid: v for v, nid in enumerate(node_ids, 1)}
+    clade = [int(x) for x in direct]
+    for v, nid in enumerate(node_ids, 1):
+        p, seen = parent_of.get(nid), 0
+        while p is not None and seen <= n:
+            clade[num[p]] += int(direct[v])
+            p, seen = parent_of.get(p), seen + 1
+    out = ["node\tparent\tcluster\tkmers\thits\treads_direct\treads_clade\n",
+           "unclassified\t-\t-\t0\t%d\t%d\t%d\n" % (int(node_hits[0]), int(direct[0]), int(direct[0]))]
+    for v, nid in enumerate(node_ids, 1):
+        p = parent_of.get(nid)
+        out.append("%s\t%s\t%s\t%d\t%d\t%d\t%d\n" % (nid, "-" if p is None else p, "C%s" % nid if nid in leaves else "-", int(kmers[v]),
+                                                     int(node_hits[v]), int(direct[v]), clade[v]))
+    return "".join(out)
+
+
+def collect_read_classes(img, paths):
+    """read_classes.tsv's numbers: the resident reads of `paths` against the tree's table (ReadSet.classify), summed over the
+    ranks.  A no-op unless --classify_reads is on; a scope that has its numbers keeps them.  Every rank calls this at the same
+    point (it holds a collective)."""
+    m = CLASSIFY_READS["m"]
+    if not m or CLASSIFY_READS["skipped"] is not None:
+        return
+    from .tree import read_tree_structure
+    with _CLASSIFY_READS_LOCK:
+        if SCOPE["label"] in CLASSIFY_READS["rows"]:
+            return
+        if img.is_external:
+            return _classify_reads_skip("needs the tree's table scanned by this process (its counts came from elsewhere)")
+        kdb = img.kdb
+        if kdb.k < 17:
+            return _classify_reads_skip(NEEDS_PAGE_INDEX % kdb.k)
+        tree, _ = read_tree_structure(img.db_dir)
+        if len(tree) < 2:
+            return _classify_reads_skip("needs a cluster search tree (this database has a single cluster)")
+        node_ids = sorted(set(img.node_ids) | {nd.identifier for nd in tree.all_nodes()})
+        if len(node_ids) > _lib.CLASS_NODES_MAX:
+            return _classify_reads_skip("takes trees of up to %d nodes (this one has %d)" % (_lib.CLASS_NODES_MAX, len(node_ids)))
+        rs = db.resident_reads(paths)
+        if rs is None:
+            return _classify_reads_skip(NEEDS_RESIDENT)
+        num = {nid: v for v, nid in enumerate(node_ids, 1)}
+        parent_of = {nid: (tree.parent(nid).identifier if tree.get_node(nid) is not None and tree.parent(nid) is not None else None)
+                     for nid in node_ids}
+        parent = np.zeros(len(node_ids) + 1, np.uint32)
+        for nid, p in parent_of.items():
+            parent[num[nid]] = num[p] if p is not None else 0
+        row_node = tree_row_nodes(node_ids, img.node_rows, kdb.n_rows)
+        res = _select_or_skip(lambda: rs.classify(kdb, row_node, parent, m), _classify_reads_skip, "classify")
+        if res is None:
+            return
+        v = np.concatenate([res["direct"].astype(np.int64), res["node_hits"].astype(np.int64), [res["ties"]]])
+        if dist.is_distributed():
+            v = dist.allreduce_int64(v)
+        n1 = len(node_ids) + 1
+        direct, node_hits = v[:n1], v[n1:2 * n1]
+        CLASSIFY_READS["rows"][SCOPE["label"]] = dict(node_ids=node_ids, parent_of=parent_of, leaves={nd.identifier for nd in tree.leaves()},
+                                                      direct=direct, node_hits=node_hits, kmers=res["kmers"], ties=int(v[-1]), m=m)
+        if dist.rank_world()[0] == 0:
+            records = int(direct.sum())
+            print("classify_reads: M=%d\trecords %d\tclassified %d\tfrom a tie %d" % (m, records, records - int(direct[0]), int(v[-1])),
+                  file=sys.stderr)
+            sys.stderr.flush()
+
+
+def write_read_classes(out_dir, scope=None):
+    """out_dir/read_classes.tsv from the numbers collected under `scope`; nothing without the flag, without numbers, or after a skip."""
+    r = CLASSIFY_READS["rows"].get(scope)
+    if not CLASSIFY_READS["m"] or CLASSIFY_READS["skipped"] is not None or not r:
+        return None
+    return _write(out_dir, READ_CLASSES_FILE, read_classes_text(r["node_ids"], r["parent_of"], r["leaves"], r["direct"], r["node_hits"], r["kmers"]))
