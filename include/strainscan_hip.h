@@ -385,6 +385,26 @@ int ss_reads_classify(const ss_db *db, const ss_reads *r, const uint32_t *row_no
 int ss_reads_classify_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
 /* the records whose class came from a tie (score >= min_score) in the calling thread's last ss_reads_classify */
 int ss_reads_classify_ties(uint64_t *n);
+/* The records of chosen classes as NEW resident sets (`--extract_class`): one classification of the set, exactly that of
+ * ss_reads_classify for the same row_node, n_nodes, parent and min_score, and one set per entry of clades[] (host memory):
+ *   clades[i] == 0:              out[i] holds the non-empty records of class 0 (unclassified)
+ *   clades[i] == v, 1..n_nodes:  out[i] holds the records whose class is v or a descendant of v -- the reads that the sum of
+ *                                direct[] over v's subtree counts; a record of class 0 is in no such clade
+ * The same clade may be listed twice: each entry gets its own set.  An empty record is never selected.  Every out[i] has the layout
+ * of ss_reads_select's *out: one ASCII, unbinned slab, each record's bytes and '\n', the block padded with '\n', letters from a
+ * packed slab as ss_reads_read_back writes them, n_records and n_bases of ss_reads_info exact, the order unspecified; nothing
+ * selected: a valid set of 0 records.  ss_reads_read_back, ss_scan_reads, ss_reads_support and ss_reads_order work on each set, and
+ * the caller destroys each.  direct, node_hits and kmers, each NULL or [n_nodes + 1], are what ss_reads_classify returns, and
+ * ss_reads_classify_ties reports this call's ties too.  The classes stay on the device, and the set is classified once however
+ * many clades are listed.  Synchronous.  Reads the table's index, never its counters.  SS_ERANGE: as ss_reads_select states it.
+ * SS_EINVAL: as ss_reads_classify states it (but direct, node_hits and kmers may be NULL), and clades or out NULL, n_clades
+ * outside 1..SS_SELECT_CLADES_MAX, a clade above n_nodes.  On any error every set made so far is destroyed and every out[i] is
+ * NULL. */
+#define SS_SELECT_CLADES_MAX 64
+int ss_reads_select_class(const ss_db *db, const ss_reads *r, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent,
+                          uint32_t min_score, const uint32_t *clades, uint32_t n_clades, ss_reads **out /* [n_clades] */,
+                          uint64_t *direct, uint64_t *node_hits, uint64_t *kmers /* each NULL, or [n_nodes + 1] */);
+int ss_reads_select_class_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
 
 /* --------------------------------------------------------------------------------------------
  * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input

@@ -150,6 +150,21 @@ def add_arguments(ap, multi=False):
                          "assigned to it (reads_direct) and to it or anything below it (reads_clade).  An integer >= 1 (1 or 2 "
                          "for the sampled node sets of a tree); needs the sample resident on the device and a database with "
                          "more than one cluster (default: off)")
+    ap.add_argument("--extract_class", dest="extract_class", type=extract_class_arg, default=None, metavar="LIST",
+                    help="With --classify_reads M: also write the reads of chosen classes of read_classes.tsv to "
+                         "OUT/extracted/class_<item>_1.<ext> (and _2 with -j).  LIST is comma-separated, at most 64 items, each one "
+                         "of `unclassified`, `C<id>` (a cluster, under the name read_classes.tsv gives it), `<id>` (any node of "
+                         "read_classes.tsv: the reads of the node and of everything below it, its reads_clade) and `called` (the "
+                         "clusters the tree walk identifies, each as class_C<id>_*).  Written with -x's rules: the original text in "
+                         "file order, selected by content, a pair when either mate is in the class -- so a pair under "
+                         "`unclassified` has at least one unclassified mate.  Needs FASTA/FASTQ input and one rank (default: off)")
+
+
+def refuse_extract_class_alone(ap, args):
+    """--extract_class without --classify_reads has no classes to take reads from: the parser's error (exit status 2, before any
+    input is opened)."""
+    if args.extract_class and not args.classify_reads:
+        ap.error("--extract_class needs --classify_reads M")
 
 
 def refuse_by_strain_alone(ap, args):
@@ -190,6 +205,16 @@ def classify_reads_arg(text):
     if m < 1 or m > 0xFFFFFFFF:
         raise argparse.ArgumentTypeError("%d is outside 1..%d" % (m, 0xFFFFFFFF))
     return m
+
+
+def extract_class_arg(text):
+    """--extract_class' value: the items of the list (read_reports.parse_class_list), or the parser's error (exit status 2, before
+    any input is opened)."""
+    from . import read_reports
+    try:
+        return read_reports.parse_class_list(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def bootstrap_arg(text):
@@ -260,6 +285,14 @@ def apply_classify_reads(m):
     read_reports.classify_reads_reset(m)
 
 
+def apply_extract_class(items):
+    """--extract_class LIST (strainscan_amd.set_extract_class): the tree scans from here on, which classify the reads, also write
+    the reads of the listed classes beside -x's files (read_reports.collect_read_classes, collect_called_classes).  stdout and the
+    other files are untouched; nothing turns it off."""
+    from . import read_reports
+    read_reports.extract_class_reset(items)
+
+
 def settings(args):
     """The parsed flags as StrainScan.py:150-160 reads them: dict(ksize, ldep, sprob, pmode, emode, msn)."""
     return dict(ksize=args.ksize if args.ksize else 31, ldep=int(args.ldep) if args.ldep else 0,
@@ -312,6 +345,9 @@ def identify_layer1(fq_dir, fq2, db_dir, out_dir, ldep, sprob):
     cls_dict, l2 = identify_with_ladder(in_fq, tdb, ldep, mdb)
     _clock("clusters identified")
     print(cls_dict)
+    from . import read_reports
+    read_reports.collect_called_classes(list(cls_dict), tdb, (identify_low_mem if mdb else identify)._UPPER_KEYS,
+                                        [p for p in in_fq if p])      # (--extract_class called)
     if len(cls_dict) == 0:
         print("Warning: No clusters can be detected!")
         raise SystemExit
@@ -337,6 +373,7 @@ def main(argv=None):
     add_arguments(ap)
     args = ap.parse_args(argv)
     refuse_by_strain_alone(ap, args)
+    refuse_extract_class_alone(ap, args)
 
     fq_dir = args.input_fq
     fq2 = args.input_fq2 or ""
@@ -356,6 +393,7 @@ def main(argv=None):
     apply_by_strain(args.by_strain)
     apply_bootstrap(args.bootstrap, args.bootstrap_seed)
     apply_classify_reads(args.classify_reads)
+    apply_extract_class(args.extract_class)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:

@@ -18,6 +18,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, read_reports.BY_STRAIN)
     strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, read_reports.BOOTSTRAP)
     strainscan_amd.set_classify_reads                         (`strainscan --classify_reads M`: reads per node of the cluster tree, read_reports.CLASSIFY_READS)
+    strainscan_amd.set_extract_class                          (`strainscan --extract_class LIST`: the reads of chosen classes, read_reports.EXTRACT_CLASS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -89,6 +90,20 @@ def set_classify_reads(m):
         raise ValueError("classify_reads must be an integer >= 1 (or 0 for off), not %r" % (m,))
     from . import read_reports
     read_reports.classify_reads_reset(m or 0)
+
+
+def set_extract_class(names, out_dir=None):
+    """`strainscan --extract_class LIST` for callers of the functions above, with set_classify_reads on: from here on
+    identify_cluster, where it classifies the reads, also writes the reads of the listed classes to
+    out_dir/extracted/class_<item>_1.<ext> (and _2 for a pair, written when either mate is in the class); out_dir defaults to the
+    directory of set_extract_reads, then to the current one.  names: a list (or the command's comma-separated text) of
+    `unclassified`, `C<id>`, `<id>` and `called`; `called` is written by StrainScan.identify_layer1, which knows the called
+    clusters.  None or an empty list turns it off.  Off by default; nothing runs while it is off."""
+    from . import read_reports
+    items = read_reports.parse_class_list(names if isinstance(names, str) else ",".join(str(n) for n in names)) if names else []
+    read_reports.extract_class_reset(items)
+    if out_dir is not None:
+        read_reports.EXTRACT_READS["dir"] = out_dir
 
 
 def get_min_base_qual():

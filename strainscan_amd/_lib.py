@@ -118,6 +118,8 @@ SIGNATURES = {
     "ss_reads_classify": (i32, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp]),
     "ss_reads_classify_calls": (i32, [P(u64)]),
     "ss_reads_classify_ties": (i32, [P(u64)]),
+    "ss_reads_select_class": (i32, [vp, vp, vp, u32, vp, u32, vp, u32, P(vp), vp, vp, vp]),
+    "ss_reads_select_class_calls": (i32, [P(u64)]),
     "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
@@ -558,6 +560,38 @@ class ReadSet:
             classes = classes[:int(direct.sum())]
         return dict(direct=direct, node_hits=node_hits, kmers=kmers, ties=int(ties.value), classes=classes)
 
+    def select_class(self, kdb, row_node, parent, min_score, clades, want_counts=False):
+        """A list of new ReadSets, one per entry of `clades`: the records that classify() with the same arguments puts in that
+        clade (ss_reads_select_class; tests/select_class_model.py restates it).  Clade 0: the unclassified records; clade v in
+        1..n: the records of class v or of a node below v.  The set is classified once, the classes stay on the device.  Each set
+        is one ASCII, unbinned block in an unspecified order; the caller closes each.  want_counts: -> (sets, dict(direct=,
+        node_hits=, kmers=, ties=)), classify()'s numbers from the same call.  The table's counters are left alone."""
+        rn = np.ascontiguousarray(row_node, np.uint32)
+        if rn.ndim != 1 or rn.size != kdb.n_rows:
+            raise ValueError("one node per row of the table (%d), not %r" % (kdb.n_rows, rn.shape))
+        par = np.ascontiguousarray(parent, np.uint32)
+        if par.ndim != 1 or par.size < 1:
+            raise ValueError("parent holds an entry per node and entry 0")
+        n = par.size - 1
+        cl = np.ascontiguousarray(clades, np.uint32)
+        if cl.ndim != 1:
+            raise ValueError("clades is a list of nodes")
+        direct, node_hits, kmers = (np.zeros(n + 1, np.uint64) if want_counts else None for _ in range(3))
+        hs = (C.c_void_p * max(int(cl.size), 1))()
+        check(lib().ss_reads_select_class(kdb.handle, self._h, ptr(rn if rn.size else np.zeros(1, np.uint32)), n, ptr(par), int(min_score),
+                                          ptr(cl if cl.size else np.zeros(1, np.uint32)), int(cl.size), hs,
+                                          *(ptr(a) if want_counts else None for a in (direct, node_hits, kmers))), "ss_reads_select_class")
+        sets = []
+        for h in hs[:cl.size]:
+            sub = ReadSet.__new__(ReadSet)
+            sub._h = C.c_void_p(h)
+            sets.append(sub)
+        if not want_counts:
+            return sets
+        ties = C.c_uint64()
+        check(lib().ss_reads_classify_ties(C.byref(ties)), "ss_reads_classify_ties")
+        return sets, dict(direct=direct, node_hits=node_hits, kmers=kmers, ties=int(ties.value))
+
     def order(self):
         """Put the records of a set in file order (from_flat_dev(order=False), select(), resample()) in locality order, in place
         (ss_reads_order): the records and every count stay, a scan of a cluster table gets faster.  -> self"""
@@ -613,6 +647,16 @@ def classify_calls():
     """Calls of ss_reads_classify so far in this process."""
     n = C.c_uint64()
     check(lib().ss_reads_classify_calls(C.byref(n)), "ss_reads_classify_calls")
+    return n.value
+
+
+CLASS_CLADES_MAX = 64       # SS_SELECT_CLADES_MAX (strainscan_hip.h): clades per call of select_class
+
+
+def select_class_calls():
+    """Calls of ss_reads_select_class so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_select_class_calls(C.byref(n)), "ss_reads_select_class_calls")
     return n.value
 
 

@@ -22,6 +22,14 @@
 //      a dense h[n_nodes + 1] of the workgroup in global memory, every hit position then sums h[] along its node's root path,
 //      the workgroup reduces (score, node) with the same tie fold, and h[] is cleared by the positions that filled it.
 //   direct[] and node_hits[] are added up in LDS per workgroup where n_nodes + 1 <= CLS_LDS, with 64-bit global atomics otherwise.
+// All of this is classify_records, which leaves its results -- the classes of the records among them -- on the device, in the
+// scratch of the call.  ss_reads_classify copies them back.
+//
+// ss_reads_select_class (`--extract_class`) runs classify_records once and then, per listed clade:
+//   5. select_class_len_kernel: one thread per record, out_len[rec] = the record's class lies in the clade ? length + 1 : 0 -- the
+//      shape of select_len_kernel (ss_select.hip) with the Euler interval of the clade's node in the place of the hit threshold;
+//      clade 0 is class 0.  gather_records (ss_select.hip) then makes the new set from out_len[], which is reset for the next clade.
+// The classes never leave the device, and a second clade costs a length pass, a prefix sum and a gather.
 #include "ss_scan_dev.h"
 #include "ss_support.h"
 
@@ -254,7 +262,48 @@ __global__ __launch_bounds__(256) void classify_long_kernel(const ClassArgs A, c
     }
 }
 
-std::atomic<uint64_t> g_classify_calls{0};
+// records [rec0, rec0 + n_rec) of one slab: out_len = the bytes a record takes in the new slab (its length + '\n'; 0 when its
+// class is not in the clade), tot[0] += selected records, tot[1] += their bytes.  The clade of node c > 0 is the classes whose tin
+// lies in [lo, hi) = [tin[c], tout[c]); unclassified == true is the clade 0: class 0 alone.  fixed_len != 0: a packed slab, every record
+// that long.  A span that does not lie inside the slab's n positions selects nothing, as in select_len_kernel: classify_kernel gave
+// such a record no class, and the gather must not read outside the slab.
+__global__ __launch_bounds__(256) void select_class_len_kernel(const uint32_t *__restrict__ rec_class, const uint32_t *__restrict__ tin,
+                                                               const unsigned long long *__restrict__ start, const unsigned long long *__restrict__ end,
+                                                               uint64_t rec0, uint64_t n_rec, uint64_t n, uint32_t slot, uint32_t fixed_len,
+                                                               uint32_t n_nodes, bool unclassified, uint32_t lo, uint32_t hi, unsigned long long *__restrict__ out_len,
+                                                               unsigned long long *__restrict__ tot)
+{
+    unsigned long long cnt = 0, bytes = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
+        const uint64_t r = rec0 + i;
+        const uint32_t c = rec_class[r];
+        unsigned long long len = 0;
+        bool in = unclassified ? c == 0u : false;
+        if (!unclassified && c != 0u && c <= n_nodes) {
+            const uint32_t t = tin[c];
+            in = lo <= t && t < hi;
+        }
+        if (in) {
+            bool ok = true;
+            if (fixed_len) {
+                ok = i * (unsigned long long)slot + fixed_len <= n;      // (span_of's test)
+                len = fixed_len;
+            } else {
+                const unsigned long long s = start[r], e = end[r];
+                ok = s < e && e <= n;
+                len = e - s;
+            }
+            if (ok) { len += 1ull; cnt++; bytes += len; }
+            else len = 0;
+        }
+        out_len[r] = len;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); bytes += __shfl_xor(bytes, d, 64); }
+    if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
+}
+
+std::atomic<uint64_t> g_classify_calls{0}, g_select_class_calls{0};
 thread_local uint64_t t_last_ties = 0;
 
 // parent[1..n_nodes] (0 = a root) -> par / depth / tin / tout [n_nodes + 1]; false: a parent above n_nodes, or a cycle
@@ -298,29 +347,22 @@ bool walk_forest(const uint32_t *parent, uint32_t n_nodes, std::vector<uint32_t>
     return seen == n_nodes;
 }
 
-}  // namespace
+// What classify_records leaves behind: everything on the device lives in rh.scratch and is enqueued on ss::l2s::stream() when
+// the call returns.
+struct Classified {
+    ss::RecHits rh;
+    ss::RecSpans sp;
+    Forest F{nullptr, nullptr, nullptr, nullptr};
+    unsigned long long *d_out = nullptr;      // direct[n1], node_hits[n1], kmers[n1], tot[2]
+    uint32_t *d_class = nullptr;              // [rh.rec_total] the class of every record (keep_class; nullptr for a set without records)
+    std::vector<uint32_t> tin, tout;          // the host's copy of the Euler intervals
+};
 
-extern "C" {
-
-int ss_reads_classify_calls(uint64_t *n)
+// The whole of ss_reads_classify but the copy back (the passes 0-4 above).  *calls is counted once the arguments have passed.
+int classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
+                     bool keep_class, std::atomic<uint64_t> *calls, Classified *C)
 {
-    if (!n) return SS_EINVAL;
-    *n = g_classify_calls.load();
-    return SS_OK;
-}
-
-int ss_reads_classify_ties(uint64_t *n)
-{
-    if (!n) return SS_EINVAL;
-    *n = t_last_ties;
-    return SS_OK;
-}
-
-int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
-                      uint64_t *direct, uint64_t *node_hits, uint64_t *kmers, uint32_t *rec_class)
-{
-    if (!db || !R || !row_node || !parent || !direct || !node_hits || !kmers || min_score == 0 || n_nodes < 1 || n_nodes > SS_CLASS_NODES_MAX)
-        return SS_EINVAL;
+    if (!db || !R || !row_node || !parent || min_score == 0 || n_nodes < 1 || n_nodes > SS_CLASS_NODES_MAX) return SS_EINVAL;
     if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
     if (R->has_cut_record) return SS_ERANGE;                        // at any k: a cut piece is not a read
     const uint64_t n_rows = db->n_rows, n_slots = db->n_slots;
@@ -329,12 +371,13 @@ int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_no
     uint32_t top = 0;
     for (uint64_t i = 0; i < n_rows; i++) { top = std::max(top, row_node[i]); rows16[i] = (uint16_t)row_node[i]; }
     if (top > n_nodes) return SS_EINVAL;
-    std::vector<uint32_t> par, depth, tin, tout;
+    std::vector<uint32_t> par, depth;
+    std::vector<uint32_t> &tin = C->tin, &tout = C->tout;
     if (!walk_forest(parent, n_nodes, par, depth, tin, tout)) return SS_EINVAL;
 
-    ss::RecHits rh;
-    ss::RecSpans sp;
-    int rc = ss::record_index_of(R, db->device, &rh, &g_classify_calls);
+    ss::RecHits &rh = C->rh;
+    ss::RecSpans &sp = C->sp;
+    int rc = ss::record_index_of(R, db->device, &rh, calls);
     if (rc) return rc;
     rc = ss::record_spans_of(&rh, &sp);
     if (rc) return rc;
@@ -344,7 +387,7 @@ int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_no
 
     // the forest, the results
     uint32_t *d_forest = nullptr;
-    unsigned long long *d_out = nullptr;      // direct[n1], node_hits[n1], kmers[n1], tot[2]
+    unsigned long long *&d_out = C->d_out;
     SS_HIP(scratch.get((void **)&d_forest, 4 * n1 * 4));
     SS_HIP(scratch.get((void **)&d_out, (3 * n1 + 2) * 8));
     {
@@ -357,6 +400,7 @@ int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_no
     }
     SS_HIP(ss::l2s::set(d_out, 0, (3 * n1 + 2) * 8));
     const Forest F{d_forest, d_forest + n1, d_forest + 2 * n1, d_forest + 3 * n1};
+    C->F = F;
     unsigned long long *d_direct = d_out, *d_hits = d_out + n1, *d_kmers = d_out + 2 * n1, *d_tot = d_out + 3 * n1;
 
     // 1. nodes per slot
@@ -384,14 +428,15 @@ int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_no
     for (const auto &pt : rh.parts)
         if (pt.n_rec) { max_fields = std::max(max_fields, pt.n_tiles * (uint64_t)ss::SUP_TILE); max_rec = std::max(max_rec, pt.n_rec); }
     uint16_t *d_pos = nullptr;
-    uint32_t *d_class = nullptr, *d_list = nullptr, *d_h = nullptr;
+    uint32_t *&d_class = C->d_class;
+    uint32_t *d_list = nullptr, *d_h = nullptr;
     if (max_fields) {
         SS_HIP(scratch.get((void **)&d_pos, max_fields * 2));
         SS_HIP(scratch.get((void **)&d_list, max_rec * 4));
         SS_HIP(scratch.get((void **)&d_h, (uint64_t)CLS_LONG_WGS * n1 * 4));
         SS_HIP(ss::l2s::set(d_h, 0, (uint64_t)CLS_LONG_WGS * n1 * 4));
     }
-    if (rec_class && rec_total) {
+    if (keep_class && rec_total) {
         SS_HIP(scratch.get((void **)&d_class, rec_total * 4));
         SS_HIP(ss::l2s::set(d_class, 0, rec_total * 4));
     }
@@ -412,13 +457,102 @@ int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_no
         hipLaunchKernelGGL(classify_long_kernel, dim3(CLS_LONG_WGS), dim3(256), 0, st, A, F, d_h);
         SS_HIP(hipGetLastError());
     }
-    std::vector<unsigned long long> out(3 * n1 + 2);
-    SS_HIP(ss::l2s::copy(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t v = 0; v < n1; v++) { direct[v] = out[v]; node_hits[v] = out[n1 + v]; kmers[v] = out[2 * n1 + v]; }
-    kmers[0] = 0;
-    t_last_ties = out[3 * n1];
-    if (d_class) SS_HIP(ss::l2s::copy(rec_class, d_class, rec_total * 4, hipMemcpyDeviceToHost));
     return SS_OK;
+}
+
+// direct / node_hits / kmers [n1] (each nullptr to skip) and the calling thread's ties from what classify_records left; synchronous
+int classify_results(const Classified &C, size_t n1, uint64_t *direct, uint64_t *node_hits, uint64_t *kmers)
+{
+    std::vector<unsigned long long> out(3 * n1 + 2);
+    SS_HIP(ss::l2s::copy(out.data(), C.d_out, out.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < n1; v++) {
+        if (direct) direct[v] = out[v];
+        if (node_hits) node_hits[v] = out[n1 + v];
+        if (kmers) kmers[v] = v ? out[2 * n1 + v] : 0;
+    }
+    t_last_ties = out[3 * n1];
+    return SS_OK;
+}
+
+// the sets of ss_reads_select_class, one per clade, from the classes on the device; out[i] is set as it is made
+int select_clades(Classified &C, uint32_t n_nodes, const uint32_t *clades, uint32_t n_clades, ss_reads **out)
+{
+    const hipStream_t st = ss::l2s::stream();
+    for (uint32_t i = 0; i < n_clades; i++) {
+        const uint32_t c = clades[i];
+        if (i && C.sp.d_tot) SS_HIP(ss::l2s::set(C.sp.d_tot, 0, 16));      // (d_len is written whole by every pass)
+        for (const auto &pt : C.rh.parts) {
+            if (!pt.n_rec) continue;
+            const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 4096);
+            hipLaunchKernelGGL(select_class_len_kernel, dim3(blocks), dim3(256), 0, st, C.d_class, C.F.tin, C.sp.d_start, C.sp.d_end, pt.rec_base,
+                               pt.n_rec, pt.n, pt.sl->packed ? pt.sl->slot : 0u, pt.sl->packed ? pt.sl->L : 0u, n_nodes, c == 0u, c ? C.tin[c] : 0u,
+                               c ? C.tout[c] : 0u, C.sp.d_len, C.sp.d_tot);
+            SS_HIP(hipGetLastError());
+        }
+        const int rc = ss::gather_records(&C.rh, C.sp, "ss_reads_select_class", &out[i]);
+        if (rc) return rc;
+    }
+    return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ss_reads_classify_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_classify_calls.load();
+    return SS_OK;
+}
+
+int ss_reads_select_class_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_select_class_calls.load();
+    return SS_OK;
+}
+
+int ss_reads_classify_ties(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = t_last_ties;
+    return SS_OK;
+}
+
+int ss_reads_classify(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
+                      uint64_t *direct, uint64_t *node_hits, uint64_t *kmers, uint32_t *rec_class)
+{
+    if (!direct || !node_hits || !kmers) return SS_EINVAL;
+    Classified C;
+    int rc = classify_records(db, R, row_node, n_nodes, parent, min_score, rec_class != nullptr, &g_classify_calls, &C);
+    if (rc) return rc;
+    rc = classify_results(C, (size_t)n_nodes + 1, direct, node_hits, kmers);
+    if (rc) return rc;
+    if (C.d_class) SS_HIP(ss::l2s::copy(rec_class, C.d_class, C.rh.rec_total * 4, hipMemcpyDeviceToHost));
+    return SS_OK;
+}
+
+int ss_reads_select_class(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
+                          const uint32_t *clades, uint32_t n_clades, ss_reads **out, uint64_t *direct, uint64_t *node_hits, uint64_t *kmers)
+{
+    if (!out) return SS_EINVAL;
+    if (n_clades >= 1 && n_clades <= SS_SELECT_CLADES_MAX)
+        for (uint32_t i = 0; i < n_clades; i++) out[i] = nullptr;
+    if (!clades || n_clades < 1 || n_clades > SS_SELECT_CLADES_MAX) return SS_EINVAL;
+    for (uint32_t i = 0; i < n_clades; i++)
+        if (clades[i] > n_nodes) return SS_EINVAL;
+    int rc;
+    {
+        Classified C;
+        rc = classify_records(db, R, row_node, n_nodes, parent, min_score, true, &g_select_class_calls, &C);
+        if (!rc) rc = classify_results(C, (size_t)n_nodes + 1, direct, node_hits, kmers);
+        if (!rc) rc = select_clades(C, n_nodes, clades, n_clades, out);
+    }
+    if (rc)
+        for (uint32_t i = 0; i < n_clades; i++)
+            if (out[i]) { ss_reads_destroy(out[i]); out[i] = nullptr; }
+    return rc;
 }
 
 }  // extern "C"

@@ -240,23 +240,24 @@ int ss::record_spans_of(RecHits *rhp, RecSpans *sp)
     return SS_OK;
 }
 
-int ss::gather_records(RecHits *rhp, const RecSpans &sp, const char *who, ss_reads **out)
+int ss::gather_records(RecHits *rhp, RecSpans &sp, const char *who, ss_reads **out)
 {
     RecHits &rh = *rhp;
     const hipStream_t st = ss::l2s::stream();
     const uint64_t rec_total = rh.rec_total;
-    unsigned long long *d_off = nullptr;
     unsigned long long tot[2] = {0, 0};
     if (rec_total) {
         // the exclusive sum of the bytes per record: where each record's copies begin in the new slab
-        SS_HIP(rh.scratch.get((void **)&d_off, rec_total * 8));
-        size_t tmp_bytes = 0;
-        SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, sp.d_len, d_off, (int)rec_total, st));
-        void *d_tmp = nullptr;
-        SS_HIP(rh.scratch.get(&d_tmp, tmp_bytes));
-        SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, sp.d_len, d_off, (int)rec_total, st));
+        if (!sp.d_off) {
+            SS_HIP(rh.scratch.get((void **)&sp.d_off, rec_total * 8));
+            SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sp.tmp_bytes, sp.d_len, sp.d_off, (int)rec_total, st));
+            SS_HIP(rh.scratch.get(&sp.d_tmp, sp.tmp_bytes));
+        }
+        size_t tmp_bytes = sp.tmp_bytes;
+        SS_HIP(hipcub::DeviceScan::ExclusiveSum(sp.d_tmp, tmp_bytes, sp.d_len, sp.d_off, (int)rec_total, st));
         SS_HIP(ss::l2s::copy(tot, sp.d_tot, 16, hipMemcpyDeviceToHost));
     }
+    unsigned long long *const d_off = sp.d_off;
     ss_reads *S = new (std::nothrow) ss_reads();
     if (!S) return SS_ENOMEM;
     S->n_records = tot[0];

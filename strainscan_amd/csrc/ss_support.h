@@ -53,9 +53,16 @@ int select_records(RecHits *rh, const uint32_t *d_rec_hits, uint32_t min_hits, s
 // for more records than hipcub's int item count holds.  The caller fills len[rec] = copies * (length + 1), the bytes a record
 // takes in the new slab, and adds the copies and their bytes to tot[0] and tot[1]; a record whose span does not lie in its slab
 // gets 0.  gather_records is the exclusive sum of len[], the new slab and pass 4: every record copied len / (length + 1) times.
-struct RecSpans { unsigned long long *d_start = nullptr, *d_end = nullptr, *d_len = nullptr, *d_tot = nullptr; };
+// It may be called again on the same spans after len[] and tot[] have been filled anew (ss_reads_select_class, a set per clade):
+// the offsets and hipcub's scratch (d_off, d_tmp) are allocated by the first call and kept.
+struct RecSpans {
+    unsigned long long *d_start = nullptr, *d_end = nullptr, *d_len = nullptr, *d_tot = nullptr;
+    unsigned long long *d_off = nullptr;
+    void *d_tmp = nullptr;
+    size_t tmp_bytes = 0;
+};
 int record_spans_of(RecHits *rh, RecSpans *sp);
-int gather_records(RecHits *rh, const RecSpans &sp, const char *who, ss_reads **out);
+int gather_records(RecHits *rh, RecSpans &sp, const char *who, ss_reads **out);
 // row labels (host, db->n_rows of them; only != 0: folded to 1 = `only`, 0 = the rest) -> *d_slot_label [db->n_slots] in `scratch`
 // (ss_label.hip); SS_EINVAL for a label above n_labels
 int slot_labels_for(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t only, PoolScratch &scratch, uint8_t **d_slot_label);

@@ -1,5 +1,5 @@
-"""The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap and
---classify_reads.
+"""The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
+--classify_reads and --extract_class.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -69,6 +69,7 @@ def reset_all():
     by_strain_reset()
     bootstrap_reset()
     classify_reads_reset()
+    extract_class_reset()
 
 
 def _skip(state, name, closing, rank0_only, why):
@@ -640,7 +641,14 @@ def read_classes_text(node_ids, parent_of, leaves, direct, node_hits, kmers):
 def collect_read_classes(img, paths):
     """read_classes.tsv's numbers: the resident reads of `paths` against the tree's table (ReadSet.classify), summed over the
     ranks.  A no-op unless --classify_reads is on; a scope that has its numbers keeps them.  Every rank calls this at the same
-    point (it holds a collective)."""
+    point (it holds a collective).  With --extract_class the same device call (ReadSet.select_class) also gives the sets of the
+    listed classes, which are written here; a classification that was skipped takes --extract_class with it."""
+    _collect_read_classes(img, paths)
+    if EXTRACT_CLASS["items"] and CLASSIFY_READS["skipped"] is not None:
+        _extract_class_skip("--classify_reads was skipped (%s)" % CLASSIFY_READS["skipped"])
+
+
+def _collect_read_classes(img, paths):
     m = CLASSIFY_READS["m"]
     if not m or CLASSIFY_READS["skipped"] is not None:
         return
@@ -669,15 +677,22 @@ def collect_read_classes(img, paths):
         for nid, p in parent_of.items():
             parent[num[nid]] = num[p] if p is not None else 0
         row_node = tree_row_nodes(node_ids, img.node_rows, kdb.n_rows)
-        res = _select_or_skip(lambda: rs.classify(kdb, row_node, parent, m), _classify_reads_skip, "classify")
+        leaves = {nd.identifier for nd in tree.leaves()}
+        wanted = _extract_class_wanted(paths, num, leaves)      # (None: --extract_class is off, or cannot run here)
+        if not wanted:                                          # (nothing to select, or only `called`, which comes after the walk)
+            res = _select_or_skip(lambda: rs.classify(kdb, row_node, parent, m), _classify_reads_skip, "classify")
+        else:
+            res = _select_or_skip(lambda: _select_classes(rs, kdb, row_node, parent, m, wanted, paths, True), _classify_reads_skip, "classify")
         if res is None:
             return
+        if wanted is not None:
+            EXTRACT_CLASS["tree"][SCOPE["label"]] = dict(row_node=row_node, parent=parent, num=num, leaves=leaves, m=m)
         v = np.concatenate([res["direct"].astype(np.int64), res["node_hits"].astype(np.int64), [res["ties"]]])
         if dist.is_distributed():
             v = dist.allreduce_int64(v)
         n1 = len(node_ids) + 1
         direct, node_hits = v[:n1], v[n1:2 * n1]
-        CLASSIFY_READS["rows"][SCOPE["label"]] = dict(node_ids=node_ids, parent_of=parent_of, leaves={nd.identifier for nd in tree.leaves()},
+        CLASSIFY_READS["rows"][SCOPE["label"]] = dict(node_ids=node_ids, parent_of=parent_of, leaves=leaves,
                                                       direct=direct, node_hits=node_hits, kmers=res["kmers"], ties=int(v[-1]), m=m)
         if dist.rank_world()[0] == 0:
             records = int(direct.sum())
@@ -692,3 +707,150 @@ def write_read_classes(out_dir, scope=None):
     if not CLASSIFY_READS["m"] or CLASSIFY_READS["skipped"] is not None or not r:
         return None
     return _write(out_dir, READ_CLASSES_FILE, read_classes_text(r["node_ids"], r["parent_of"], r["leaves"], r["direct"], r["node_hits"], r["kmers"]))
+
+
+# --extract_class LIST (StrainScan.apply_extract_class turns it on; it needs --classify_reads M): the reads of chosen classes of
+# read_classes.tsv, written as `dir`/extracted/class_<item>_1.<ext> (and _2 with a second mate) through -x's writer with -x's rules
+# -- by content, original text, file order, a pair when either mate is in the class.  An item is `unclassified`, `C<id>` (a leaf
+# under its cluster name), `<id>` (any node: its whole clade) or `called` (the clusters the tree walk identifies, each as C<id>).
+# The device classifies the sample once and selects every listed clade from the classes it keeps (ReadSet.select_class): the
+# call that gives read_classes.tsv its numbers also gives the sets of the listed items (collect_read_classes); `called` is known
+# only after the walk and takes a second call (collect_called_classes).  "tree": per scope, what that second call needs; "done":
+# the items written under each scope; "files": what this run has written so far (a skip takes them away again).  The output
+# directory is EXTRACT_READS["dir"], which database_scope moves per database.
+EXTRACT_CLASS = {"items": [], "tree": {}, "done": {}, "skipped": None, "files": []}
+EXTRACT_CLASS_UNCLASSIFIED = "unclassified"
+EXTRACT_CLASS_CALLED = "called"
+_EXTRACT_CLASS_LOCK = threading.Lock()
+
+
+def extract_class_reset(items=None):
+    EXTRACT_CLASS.update(items=list(items or []), tree={}, done={}, skipped=None, files=[])
+
+
+def parse_class_list(text):
+    """--extract_class' value -> its items in order; ValueError for an empty item, an item that is none of `unclassified`,
+    `called`, `C<id>` and `<id>` (id: decimal digits without a leading zero), an item listed twice, or more items than one device
+    call takes (_lib.CLASS_CLADES_MAX)."""
+    import re
+    items = str(text).split(",")
+    for it in items:
+        if not it:
+            raise ValueError("an empty item in %r" % (text,))
+        if it not in (EXTRACT_CLASS_UNCLASSIFIED, EXTRACT_CLASS_CALLED) and not re.fullmatch(r"C?(0|[1-9][0-9]*)", it):
+            raise ValueError("%r is none of unclassified, called, C<id>, <id>" % (it,))
+        if items.count(it) > 1:
+            raise ValueError("%r is listed twice" % (it,))
+    if len(items) > _lib.CLASS_CLADES_MAX:
+        raise ValueError("%d items, at most %d are taken" % (len(items), _lib.CLASS_CLADES_MAX))
+    return items
+
+
+def _extract_class_skip(why):
+    for f in EXTRACT_CLASS["files"]:
+        with contextlib.suppress(OSError):
+            os.remove(f)
+            os.rmdir(os.path.dirname(f))      # (once it is empty)
+    EXTRACT_CLASS["files"] = []
+    _skip(EXTRACT_CLASS, "extract_class", "and nothing was extracted", True, why)
+
+
+def _class_clade(item, num, leaves):
+    """The clade (0 = unclassified, v = node v's) that `item` names in a tree with the nodes num = {id: v} and the leaf ids
+    `leaves`; None when it names none."""
+    if item == EXTRACT_CLASS_UNCLASSIFIED:
+        return 0
+    nid = int(item[1:] if item.startswith("C") else item)
+    if nid not in num or (item.startswith("C") and nid not in leaves):
+        return None
+    return num[nid]
+
+
+def _extract_class_wanted(paths, num, leaves):
+    """[(item, clade)] for the listed items that name a class of this tree (`called` apart), each other one said on stderr; None
+    when --extract_class is off, was skipped, or cannot run on this sample (said once)."""
+    if not EXTRACT_CLASS["items"] or EXTRACT_CLASS["skipped"] is not None:
+        return None
+    if dist.is_distributed():
+        return _extract_class_skip("runs on one rank only (this run has several)")
+    if any(_lib.input_kind(p) == "bam" for p in paths if p):
+        return _extract_class_skip("takes FASTA/FASTQ inputs (BAM subsets per class are not built)")
+    done = EXTRACT_CLASS["done"].setdefault(SCOPE["label"], set())
+    wanted = []
+    for item in EXTRACT_CLASS["items"]:
+        if item == EXTRACT_CLASS_CALLED or item in done:
+            continue
+        clade = _class_clade(item, num, leaves)
+        if clade is None:
+            print("extract_class: %s names no %s of this database's tree and was not written" %
+                  (item, "cluster" if item.startswith("C") else "node"), file=sys.stderr)
+            sys.stderr.flush()
+        else:
+            wanted.append((item, clade))
+    return wanted
+
+
+def _select_classes(rs, kdb, row_node, parent, m, wanted, paths, want_counts=False):
+    """One ReadSet.select_class for the clades of `wanted` = [(item, clade)], each set written as extracted/class_<item>_*;
+    -> classify()'s numbers of the same call with want_counts."""
+    res = rs.select_class(kdb, row_node, parent, m, [c for _, c in wanted], want_counts)
+    sets, counts = res if want_counts else (res, None)
+    try:
+        with _EXTRACT_CLASS_LOCK:
+            done = EXTRACT_CLASS["done"].setdefault(SCOPE["label"], set())
+            for (item, _), sub in zip(wanted, sets):
+                _write_class(item, sub, [p for p in paths if p], m)
+                done.add(item)
+    finally:
+        for sub in sets:
+            sub.close()
+    return counts
+
+
+def _write_class(item, sub, ps, m):
+    """The set `sub` read back, digested, found in the files `ps` again and written as extracted/class_<item>_<mate>.<ext>
+    (-x's writer: _write_selected)."""
+    selected = sub.info()["n_records"]
+    flat = sub.read_back()
+    sub.close()
+    keys = _lib.flat_record_keys(flat)
+    del flat
+    out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
+    os.makedirs(out_dir, exist_ok=True)
+    outs = [os.path.join(out_dir, "class_%s_%d.%s" % (item, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
+    c = _lib.extract_write(ps, keys, outs)
+    EXTRACT_CLASS["files"].extend(outs)
+    print("extract_class: %s\tM=%d\tselected on the device %d\twritten %d" % (item, m, selected, c["written"]), file=sys.stderr)
+    sys.stderr.flush()
+
+
+def collect_called_classes(cluster_ids, tree_db_dir, upper_keys, paths):
+    """--extract_class called, once the tree walk has identified the clusters `cluster_ids`: extracted/class_C<id>_* for each
+    that is not written yet under the current scope, from a second ReadSet.select_class against the cached tree image.  A no-op
+    unless `called` is listed and the scope's reads were classified."""
+    if EXTRACT_CLASS_CALLED not in EXTRACT_CLASS["items"] or EXTRACT_CLASS["skipped"] is not None:
+        return
+    t = EXTRACT_CLASS["tree"].get(SCOPE["label"])
+    if t is None:
+        return
+    done = EXTRACT_CLASS["done"].setdefault(SCOPE["label"], set())
+    wanted = []
+    for cid in sorted(cluster_ids):
+        item = "C%s" % cid
+        clade = _class_clade(item, t["num"], t["leaves"])
+        if clade is not None and item not in done:
+            wanted.append((item, clade))
+    if not cluster_ids:
+        print("extract_class: called: no cluster was called and none was written", file=sys.stderr)
+        sys.stderr.flush()
+    if not wanted:
+        return
+    rs = db.resident_reads(paths)
+    if rs is None:
+        return _extract_class_skip(NEEDS_RESIDENT)
+    kdb = db.tree_image(tree_db_dir, upper_keys).kdb
+    for i in range(0, len(wanted), _lib.CLASS_CLADES_MAX):      # (more called clusters than a call takes: several calls)
+        part = wanted[i:i + _lib.CLASS_CLADES_MAX]
+        if _select_or_skip(lambda: _select_classes(rs, kdb, t["row_node"], t["parent"], t["m"], part, paths) or True,
+                           _extract_class_skip, "extract") is None:
+            return
