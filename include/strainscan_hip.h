@@ -405,6 +405,29 @@ int ss_reads_select_class(const ss_db *db, const ss_reads *r, const uint32_t *ro
                           uint32_t min_score, const uint32_t *clades, uint32_t n_clades, ss_reads **out /* [n_clades] */,
                           uint64_t *direct, uint64_t *node_hits, uint64_t *kmers /* each NULL, or [n_nodes + 1] */);
 int ss_reads_select_class_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* Read PAIRS as the records of a resident set (`--pairs`, ss_pairs.hip).  A resident set keeps no pair map, and every call above
+ * decides per record from the record's bytes alone: on a set whose records are the pairs they all work on fragments, unchanged.
+ * The join rule: record i of the result is  line1[i] + 'N' + line2[i] + '\n'.  'N' ends a k-mer window, so no k-mer spans the
+ * joint and the fragment's hits against any table are the two mates' hits added up.
+ * ss_reads_join_pairs_dev: flat1_dev / flat2_dev are flat base blocks on the device as ss_fastx_to_flat writes them, exact
+ *   length, every record followed by one '\n'.  A LINE is the bytes between two consecutive '\n' (from the block's start for
+ *   the first) and may be empty -- a record without bases, which ss_fastx_to_flat emits and counts -- so lines are numbered over
+ *   EVERY '\n': an empty record in one file does not shift the pairing.  The 'N' is written even where a mate is empty (two empty
+ *   mates: the record "N"), so n_records = the lines of either block, and the bytes of the lines are copied as they are (lower
+ *   case, IUPAC codes, '\r').  Joined record i begins at byte start1[i] + start2[i] and the result holds exactly n1 + n2 bytes:
+ *   the 'N' takes the place of mate 1's '\n', no prefix sum is needed.
+ *   order == 0: one ASCII, unbinned slab in the layout of ss_reads_select's *out, padded with '\n', in LINE ORDER;
+ *   n_records and n_bases of ss_reads_info exact.  order != 0: the same set after ss_reads_order (order unspecified, packed
+ *   where the records allow it: 150 + 1 + 150 bases of A C G T N do).  Two empty blocks: a valid set of 0 records.
+ *   Synchronous; has no cut record.  SS_EIO: the blocks hold different numbers of lines.  SS_EINVAL: a NULL argument, a non-empty
+ *   block whose last byte is not '\n'.  SS_ERANGE: more than 2^32 - 1 lines.  On any error *out is NULL.
+ * ss_reads_load_pairs: each file as ONE flat block in file order on the device (a thread per file; FASTA and FASTQ, plain or
+ *   gzip, four-line and wrapped, CRLF; the base-quality mask with the grammar of ss_fastx_to_flat), then the join.
+ *   ss_reads_load is not involved.  SS_EINVAL: a BAM or CRAM input, a NULL or empty path.  SS_EIO: an unreadable file, unequal
+ *   record counts. */
+int ss_reads_join_pairs_dev(const void *flat1_dev, uint64_t n1, const void *flat2_dev, uint64_t n2, int order, ss_reads **out);
+int ss_reads_join_pairs_calls(uint64_t *n);    /* joins so far in this process (diagnostics; "flag off = not run") */
+int ss_reads_load_pairs(const char *path1, const char *path2, int order, ss_reads **out);
 
 /* --------------------------------------------------------------------------------------------
  * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input
@@ -424,10 +447,17 @@ int ss_reads_select_class_calls(uint64_t *n);  /* calls so far in this process (
  *   counters[0] records read, all inputs together, [1] records written, all outputs together, [2] pairs written because of
  *   mate 1 only, [3] because of mate 2 only.  SS_EIO: an unreadable input, unequal record counts; SS_EINVAL: a BAM or CRAM input, a bad
  *   argument.  On any error no output file is left behind (the text goes to <name>.tmp, renamed at the end).
+ * ss_extract_write_pairs: the same walk over exactly two inputs (n_in == 2, two outputs) for a selection made on a set of
+ *   joined pairs (ss_reads_join_pairs_dev): pair i is named by the digest of  flat1[i] + 'N' + flat2[i]  -- what
+ *   ss_flat_record_keys gives for the joined set's records -- and BOTH records of the pair are written, original text byte for
+ *   byte, when that digest is among `keys`.  An empty mate is not special: the fragment is never empty.  counters[0] records
+ *   read, [1] records written, [2] pairs written, [3] 0.  Errors and clean-up as ss_extract_write's.
  * ------------------------------------------------------------------------------------------ */
 int ss_flat_record_keys(const char *flat, uint64_t len, uint64_t *keys, uint64_t cap, uint64_t *n_records);
 int ss_extract_write(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys,
                      const char *const *out_paths, uint64_t counters[4]);
+int ss_extract_write_pairs(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys,
+                           const char *const *out_paths, uint64_t counters[4]);
 
 /* --------------------------------------------------------------------------------------------
  * Host FASTA/FASTQ -> flat base block (what jellyfish's sequence parser feeds its counter).

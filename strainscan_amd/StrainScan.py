@@ -137,8 +137,9 @@ def add_arguments(ap, multi=False):
                          "points of its depth and of its share of the cluster over B replicates, and in how many of them it is "
                          "present.  A replicate resamples the reads with replacement on the device (a Poisson bootstrap over reads), "
                          "re-counts the cluster's k-mers and solves again with the called strains and the penalty held fixed: the "
-                         "intervals are conditional on both and on the cluster's abundance, mates are resampled independently and "
-                         "identical reads together -- a lower bound on the real uncertainty.  An integer in 2..1000; needs the "
+                         "intervals are conditional on both and on the cluster's abundance, mates are resampled independently (as "
+                         "one fragment with --pairs) and identical reads together -- a lower bound on the real uncertainty.  An "
+                         "integer in 2..1000; needs the "
                          "sample resident on the device and k >= 17 (default: off)")
     ap.add_argument("--bootstrap_seed", dest="bootstrap_seed", type=bootstrap_seed_arg, default=1, metavar="S",
                     help="The seed of --bootstrap's replicates: the same S gives the same file.  An integer in 0..2^63-1 (default: 1)")
@@ -158,6 +159,24 @@ def add_arguments(ap, multi=False):
                          "clusters the tree walk identifies, each as class_C<id>_*).  Written with -x's rules: the original text in "
                          "file order, selected by content, a pair when either mate is in the class -- so a pair under "
                          "`unclassified` has at least one unclassified mate.  Needs FASTA/FASTQ input and one rank (default: off)")
+    ap.add_argument("--pairs", dest="pairs", action="store_true",
+                    help="With -j and at least one of --read_support, -x N, --bootstrap B, --classify_reads M: those reports (and "
+                         "--by_strain, --extract_class) treat a read PAIR as one fragment -- record i of -i, an N, record i of -j, "
+                         "joined on the device into a second resident set.  No k-mer spans the joint, so every kmers and hits "
+                         "column stays what it is without the flag; `reads` counts pairs, a fragment's hits are both mates' added "
+                         "up, a pair is classified, extracted and resampled as a whole.  The files, headers and columns are "
+                         "unchanged; stdout and the identification reports do not depend on the flag.  Needs FASTA/FASTQ input, "
+                         "one rank and room for a second copy of the bases on the device; where the pairs cannot be joined, one "
+                         "line says why and no per-read report is written (default: off)")
+
+
+def refuse_pairs_alone(ap, args):
+    """--pairs without -j has no pairs, and without a per-read report nothing to apply them to: the parser's error (exit status
+    2, before any input is opened)."""
+    if args.pairs and not args.input_fq2:
+        ap.error("--pairs needs -j (the second file of the pairs)")
+    if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads):
+        ap.error("--pairs needs at least one of --read_support, -x N, --bootstrap B, --classify_reads M")
 
 
 def refuse_extract_class_alone(ap, args):
@@ -293,6 +312,14 @@ def apply_extract_class(items):
     read_reports.extract_class_reset(items)
 
 
+def apply_pairs(on):
+    """--pairs (strainscan_amd.set_pairs): the per-read reports collected from here on work on the set of joined pairs
+    (db.resident_pairs) in the place of the resident reads; the scans do not.  stdout and the identification reports are
+    untouched."""
+    from . import read_reports
+    read_reports.pairs_reset(on)
+
+
 def settings(args):
     """The parsed flags as StrainScan.py:150-160 reads them: dict(ksize, ldep, sprob, pmode, emode, msn)."""
     return dict(ksize=args.ksize if args.ksize else 31, ldep=int(args.ldep) if args.ldep else 0,
@@ -374,6 +401,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     refuse_by_strain_alone(ap, args)
     refuse_extract_class_alone(ap, args)
+    refuse_pairs_alone(ap, args)
 
     fq_dir = args.input_fq
     fq2 = args.input_fq2 or ""
@@ -394,6 +422,7 @@ def main(argv=None):
     apply_bootstrap(args.bootstrap, args.bootstrap_seed)
     apply_classify_reads(args.classify_reads)
     apply_extract_class(args.extract_class)
+    apply_pairs(args.pairs)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)
     finally:

@@ -19,6 +19,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, read_reports.BOOTSTRAP)
     strainscan_amd.set_classify_reads                         (`strainscan --classify_reads M`: reads per node of the cluster tree, read_reports.CLASSIFY_READS)
     strainscan_amd.set_extract_class                          (`strainscan --extract_class LIST`: the reads of chosen classes, read_reports.EXTRACT_CLASS)
+    strainscan_amd.set_pairs                                  (`strainscan --pairs`: those reports on read pairs as fragments, read_reports.PAIRS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
 """
@@ -104,6 +105,16 @@ def set_extract_class(names, out_dir=None):
     read_reports.extract_class_reset(items)
     if out_dir is not None:
         read_reports.EXTRACT_READS["dir"] = out_dir
+
+
+def set_pairs(on):
+    """`strainscan --pairs` for callers of the functions above: from here on every per-read report that is on (read support,
+    extracted reads, by strain, bootstrap, read classes, extracted classes) works on the sample's read PAIRS -- record i of the
+    first file, an N, record i of the second, joined on the device (db.resident_pairs) -- in the place of its reads; the scans of
+    the identification keep the plain set.  Where the pairs cannot be joined (one file, a BAM, several ranks, no room, unequal
+    record counts) one line on stderr says why and those reports write nothing.  Off by default; nothing runs while it is off."""
+    from . import read_reports
+    read_reports.pairs_reset(bool(on))
 
 
 def get_min_base_qual():

@@ -123,6 +123,10 @@ SIGNATURES = {
     "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
+    "ss_extract_write_pairs": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
+    "ss_reads_join_pairs_dev": (i32, [vp, u64, vp, u64, i32, P(vp)]),
+    "ss_reads_join_pairs_calls": (i32, [P(u64)]),
+    "ss_reads_load_pairs": (i32, [cp, cp, i32, P(vp)]),
     "ss_scan_reset": (i32, [vp, vp]),
     "ss_scan_flat_dev": (i32, [vp, vp, u64, vp]),
     "ss_scan_flat_host": (i32, [vp, cp, u64]),
@@ -457,6 +461,27 @@ class ReadSet:
         self._h = h
         return self
 
+    @classmethod
+    def join_pairs_dev(cls, dptr1, n1, dptr2, n2, order=True):
+        """A resident set whose records are the PAIRS of two flat base blocks on the device: record i is line i of block 1,
+        'N', line i of block 2 (ss_reads_join_pairs_dev; tests/pairs_model.py restates it).  order=False: in line order."""
+        require_gpu()
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        check(lib().ss_reads_join_pairs_dev(dptr1, int(n1), dptr2, int(n2), int(bool(order)), C.byref(h)), "ss_reads_join_pairs_dev")
+        self._h = h
+        return self
+
+    @classmethod
+    def load_pairs(cls, p1, p2, order=True):
+        """The same set from the two files of a paired sample, each read in file order (ss_reads_load_pairs)."""
+        require_gpu()
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        check(lib().ss_reads_load_pairs(os.fsencode(p1), os.fsencode(p2), int(bool(order)), C.byref(h)), "ss_reads_load_pairs")
+        self._h = h
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
             lib().ss_reads_destroy(self._h)
@@ -684,6 +709,27 @@ def extract_write(in_paths, keys, out_paths):
     check(lib().ss_extract_write((C.c_char_p * len(ins))(*ins), len(ins), ptr(keys) if keys.size else None, keys.shape[0],
                                  (C.c_char_p * len(outs))(*outs), c), "ss_extract_write")
     return dict(zip(("read", "written", "mate1_only", "mate2_only"), (int(v) for v in c)))
+
+
+def extract_write_pairs(in_paths, keys, out_paths):
+    """extract_write for a selection made on joined pairs (ReadSet.load_pairs): both records of pair i go to the two out_paths
+    when the digest of mate 1 + 'N' + mate 2 is among `keys` (ss_extract_write_pairs).  -> dict(read=, written=, pairs=)."""
+    ins = [os.fsencode(p) for p in in_paths]
+    outs = [os.fsencode(p) for p in out_paths]
+    if len(ins) != 2 or len(outs) != 2:
+        raise ValueError("two input paths and two output paths")
+    keys = np.ascontiguousarray(keys, np.uint64).reshape(-1, 2)
+    c = (C.c_uint64 * 4)()
+    check(lib().ss_extract_write_pairs((C.c_char_p * 2)(*ins), 2, ptr(keys) if keys.size else None, keys.shape[0],
+                                       (C.c_char_p * 2)(*outs), c), "ss_extract_write_pairs")
+    return dict(zip(("read", "written", "pairs"), (int(v) for v in c)))
+
+
+def join_pairs_calls():
+    """Joins (ss_reads_join_pairs_dev, ss_reads_load_pairs) so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_reads_join_pairs_calls(C.byref(n)), "ss_reads_join_pairs_calls")
+    return n.value
 
 
 def support_calls():

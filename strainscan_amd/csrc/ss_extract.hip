@@ -29,14 +29,9 @@
 #include <vector>
 
 #include "strainscan_hip.h"
+#include "ss_input_text.h"
 
-namespace ss {
-// (ss_host.hip, ss_ingest.hip; the values of input_kind are those of ss_input_kind)
-int min_base_qual();
-int input_kind(const char *path);
-bool inflate_whole(const char *path, uint64_t budget, char **text, uint64_t *len, int mode, unsigned threads);
-uint64_t inflate_budget_bytes();
-}  // namespace ss
+using ss::InputText;
 
 namespace {
 
@@ -135,72 +130,6 @@ bool next_record(const char *t, uint64_t len, uint64_t *pos, unsigned thr, Recor
     return false;
 }
 
-// an input file as one text in memory: a plain file mapped, a .gz inflated whole
-struct InputText {
-    const char *p = nullptr;
-    uint64_t n = 0;
-    void *map = nullptr;
-    uint64_t map_n = 0;
-    char *owned = nullptr;
-    ~InputText()
-    {
-        if (map) munmap(map, map_n);
-        free(owned);
-    }
-    int open_path(const char *path)
-    {
-        if (!path || !path[0]) return SS_EINVAL;
-        const int kind = ss::input_kind(path);
-        if (kind == 1 || kind == 2 || kind == 3) return SS_EINVAL;      // BAM, CRAM: not extracted from
-        if (kind == 4) {
-            if (ss::inflate_whole(path, ss::inflate_budget_bytes(), &owned, &n, 0, 0)) { p = owned; return SS_OK; }
-            owned = nullptr;
-            return inflate_zlib(path);
-        }
-        const int fd = open(path, O_RDONLY);
-        if (fd < 0) return SS_EIO;
-        struct stat st;
-        if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); return SS_EIO; }
-        n = (uint64_t)st.st_size;
-        if (n) {
-            void *m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { close(fd); n = 0; return SS_EIO; }
-            map = m;
-            map_n = n;
-            p = (const char *)m;
-        }
-        close(fd);
-        return SS_OK;
-    }
-    int inflate_zlib(const char *path)
-    {
-        gzFile f = gzopen(path, "rb");
-        if (!f) return SS_EIO;
-        gzbuffer(f, 1 << 20);
-        uint64_t cap = 1 << 22, got = 0;
-        char *buf = (char *)malloc(cap);
-        int rc = buf ? SS_OK : SS_ENOMEM;
-        while (rc == SS_OK) {
-            if (got == cap) {
-                char *nb = (char *)realloc(buf, cap * 2);
-                if (!nb) { rc = SS_ENOMEM; break; }
-                buf = nb;
-                cap *= 2;
-            }
-            const int r = gzread(f, buf + got, (unsigned)std::min<uint64_t>(cap - got, 1u << 30));
-            if (r < 0) { rc = SS_EIO; break; }
-            if (r == 0) break;
-            got += (uint64_t)r;
-        }
-        gzclose(f);
-        if (rc != SS_OK) { free(buf); return rc; }
-        owned = buf;
-        p = buf;
-        n = got;
-        return SS_OK;
-    }
-};
-
 // an output file that exists under its name only once everything went well
 struct OutputFile {
     std::string path, tmp;
@@ -259,8 +188,10 @@ int ss_flat_record_keys(const char *flat, uint64_t len, uint64_t *keys, uint64_t
     return (keys && n > cap) ? SS_ERANGE : SS_OK;
 }
 
-int ss_extract_write(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys, const char *const *out_paths,
-                     uint64_t counters[4])
+// ss_extract_write (fragments = false: a pair goes out when either mate's digest is selected) and ss_extract_write_pairs
+// (fragments = true: the pair is ONE record, mate 1 + 'N' + mate 2, the record ss_reads_join_pairs_dev makes of it)
+static int extract_write(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys, const char *const *out_paths,
+                         uint64_t counters[4], bool fragments)
 {
     if (!in_paths || !out_paths || !counters || n_in < 1 || n_in > 2 || (n_keys && !keys)) return SS_EINVAL;
     for (int f = 0; f < n_in; f++)
@@ -281,11 +212,26 @@ int ss_extract_write(const char *const *in_paths, int n_in, const uint64_t *keys
         if (!out[f].open_tmp(out_paths[f])) return SS_EIO;
     uint64_t pos[2] = {0, 0};
     Record rec[2];
+    std::string frag;
     for (;;) {
         bool have[2] = {false, false}, hit[2] = {false, false};
         for (int f = 0; f < n_in; f++) have[f] = next_record(in[f].p, in[f].n, &pos[f], thr, &rec[f]);
         if (n_in == 2 && have[0] != have[1]) return SS_EIO;          // unequal record counts (the outputs' destructors clean up)
         if (!have[0]) break;
+        if (fragments) {
+            counters[0] += 2;
+            // a FASTQ record without bases ends behind its '+' line for next_record; its empty quality line is its text too
+            for (int f = 0; f < 2; f++)
+                if (rec[f].fastq && rec[f].flat.empty() && pos[f] < in[f].n && in[f].p[pos[f]] == '\n') rec[f].t1 = ++pos[f];
+            frag.assign(rec[0].flat);
+            frag.push_back('N');
+            frag.append(rec[1].flat);
+            if (!std::binary_search(sel.begin(), sel.end(), record_digest(frag.data(), frag.size()))) continue;
+            for (int f = 0; f < 2; f++) out[f].put(in[f].p + rec[f].t0, rec[f].t1 - rec[f].t0);
+            counters[1] += 2;
+            counters[2]++;
+            continue;
+        }
         for (int f = 0; f < n_in; f++) {
             counters[0]++;
             if (!rec[f].flat.empty()) hit[f] = std::binary_search(sel.begin(), sel.end(), record_digest(rec[f].flat.data(), rec[f].flat.size()));
@@ -305,6 +251,19 @@ int ss_extract_write(const char *const *in_paths, int n_in, const uint64_t *keys
         return SS_EIO;
     }
     return SS_OK;
+}
+
+int ss_extract_write(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys, const char *const *out_paths,
+                     uint64_t counters[4])
+{
+    return extract_write(in_paths, n_in, keys, n_keys, out_paths, counters, false);
+}
+
+int ss_extract_write_pairs(const char *const *in_paths, int n_in, const uint64_t *keys, uint64_t n_keys, const char *const *out_paths,
+                           uint64_t counters[4])
+{
+    if (n_in != 2) return SS_EINVAL;
+    return extract_write(in_paths, n_in, keys, n_keys, out_paths, counters, true);
 }
 
 }  // extern "C"

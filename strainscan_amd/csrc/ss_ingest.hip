@@ -93,6 +93,23 @@ bool head_is_simple(const char *t, uint64_t n, bool &fastq)
 }  // namespace
 
 namespace ss {
+// The chunk rule of the parallel parse: false for a text it does not take (below 4 MB, or a head that is not plain four-line
+// FASTQ or FASTA), else starts[] = where the chunks begin, each at a record, and n behind the last.  parse_text_parallel places
+// the chunks as they finish, ss_reads_load_pairs (ss_pairs.hip) in file order.
+bool text_chunk_starts(const char *t, uint64_t n, std::vector<uint64_t> *starts)
+{
+    bool fastq = true;
+    if (n < (4u << 20) || !head_is_simple(t, n, fastq)) return false;
+    starts->assign(1, 0);
+    for (uint64_t off = CHUNK; off < n; off += CHUNK) {
+        const uint64_t s = sync_record(t, n, off, fastq);
+        if (s >= n) break;
+        if (s > starts->back()) starts->push_back(s);
+    }
+    starts->push_back(n);
+    return true;
+}
+
 unsigned host_cpus()
 {
     static const unsigned cached = [] {
@@ -492,18 +509,9 @@ static int parse_text_parallel(InputSink &sink, const char *t, uint64_t n, const
     ss_db::Worker *const workers = sink.workers;
     const bool copy = sink.copy;
     *handled = false;
-    bool fastq = true;
-    if (n < (4u << 20) || !head_is_simple(t, n, fastq)) return SS_OK;
-
     // chunk starts at record boundaries
     std::vector<uint64_t> starts;
-    starts.push_back(0);
-    for (uint64_t off = CHUNK; off < n; off += CHUNK) {
-        const uint64_t s = sync_record(t, n, off, fastq);
-        if (s >= n) break;
-        if (s > starts.back()) starts.push_back(s);
-    }
-    starts.push_back(n);
+    if (!text_chunk_starts(t, n, &starts)) return SS_OK;
     const size_t n_chunks = starts.size() - 1;
     uint64_t max_chunk = 0;
     for (size_t c = 0; c < n_chunks; c++) max_chunk = std::max(max_chunk, starts[c + 1] - starts[c]);

@@ -114,6 +114,7 @@ def resident_reads(paths):
             for old in _READS.values():
                 old.close()
             _READS.clear()
+            _close_pairs()
             # (.gz under torch.distributed: all ranks take the same inflate path for a file, dist.load_agreed)
             before = _lib.mask_counters() if MASK_REPORT["on"] else None
             rs = dist.load_agreed([p for p in paths if p], lambda use: _lib.ReadSet(use, rank, world), discard=lambda r: r.close())
@@ -123,6 +124,61 @@ def resident_reads(paths):
                 report_mask(after["masked"] - before["masked"], after["bam_no_qual"] - before["bam_no_qual"],
                             inf["n_bases"] - inf["n_records"])
     return rs
+
+
+_PAIRS = {}          # the joined pairs of the resident sample (--pairs): key -> _lib.ReadSet, closed with the resident set
+
+
+def _close_pairs():
+    for old in _PAIRS.values():
+        old.close()
+    _PAIRS.clear()
+
+
+def resident_pairs(paths):
+    """(set, None): the sample's read PAIRS as the records of a second resident set -- record i of the first file, an N, record i
+    of the second (ReadSet.load_pairs) -- cached beside the resident reads and closed with them; or (None, why) where it is not
+    built: one file, a BAM input, several ranks, the plain sample not resident, no room for a second copy of the bases, unequal
+    record counts.  The scans never use it: it serves the per-read reports (read_reports, --pairs).  One line on stderr after
+    the join: the pairs and the bytes of the set."""
+    import sys
+    from . import dist
+    rank, world = dist.rank_world()
+    ps = [p for p in paths if p]
+    if len(ps) != 2:
+        return None, "needs the two files of a paired sample (-i and -j)"
+    if any(_lib.input_kind(p) != "fastx" for p in ps):
+        return None, "takes FASTA/FASTQ inputs (the mates of a pair are not adjacent in a coordinate-sorted BAM; pairs from BAM are not built)"
+    if world > 1:
+        return None, "runs on one rank only (this run has several)"
+    rs = resident_reads(paths)
+    if rs is None:
+        return None, "needs the sample resident on the device (SS_READS_RESIDENT_GB)"
+    key = _reads_key(paths, rank, world)
+    with _READS_LOCK:
+        js = _PAIRS.get(key)
+        if js is not None:
+            return js, None
+        inf = rs.info()
+        # the load's peak beside the resident reads: the two flat blocks, the joined slab and its binned copy, each at most the
+        # bases and their line ends as ASCII
+        no_room = "has no room for the joined pairs beside the resident reads (SS_READS_RESIDENT_GB)"
+        if inf["device_bytes"] + 3 * (inf["n_bases"] + inf["n_records"]) > RESIDENT_LIMIT_BYTES:
+            return None, no_room
+        try:
+            js = _lib.ReadSet.load_pairs(ps[0], ps[1])
+        except _lib.SSError as e:
+            if e.code == _lib.SS_ENOMEM:        # (the device holds other things than this budget knows of)
+                return None, no_room
+            if e.code != _lib.SS_EIO:
+                raise
+            return None, "could not pair the records of the two files (unequal record counts, or a file that cannot be read)"
+        _close_pairs()
+        _PAIRS[key] = js
+        ji = js.info()
+        print("pairs: %d pairs joined\t%d bytes on the device" % (ji["n_records"], ji["device_bytes"]), file=sys.stderr)
+        sys.stderr.flush()
+    return js, None
 
 
 def prefetch_reads(paths):
@@ -783,3 +839,4 @@ def clear_cache():
     for rs in _READS.values():
         rs.close()
     _READS.clear()
+    _close_pairs()

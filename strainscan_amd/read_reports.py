@@ -1,5 +1,5 @@
 """The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
---classify_reads and --extract_class.
+--classify_reads and --extract_class; and --pairs, which makes all of them work on read pairs as fragments.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -37,6 +37,8 @@ def database_scope(label, out_dir):
 def tree_scanned(img, paths):
     """The tree image `img` (db.TreeImage) holds the scan of `paths`, or counts made elsewhere (img.is_external): the tree's
     table_scanned, then --classify_reads, which needs the node lists and the tree as well as the table."""
+    if not _pairs_gate(paths):
+        return
     if not img.is_external:
         table_scanned("tree", img.kdb, paths)
     collect_read_classes(img, paths)
@@ -45,6 +47,8 @@ def tree_scanned(img, paths):
 def table_scanned(table, kdb, paths):
     """`kdb` is open and holds the scan of `paths`: --read_support's row, -x's files and --bootstrap's order of the clusters.
     ("tree" enters that order too; write_bootstrap keeps only tables with rows, and the tree never has any.)"""
+    if not _pairs_gate(paths):
+        return
     collect_read_support(table, kdb, paths)
     collect_extract_reads(table, kdb, paths)
     bootstrap_scanned(table)
@@ -52,6 +56,8 @@ def table_scanned(table, kdb, paths):
 
 def cluster_reported(cls, cls_db_dir, report_path, ksize, paths):
     """Cluster `cls` ('C<id>') has written report_path: --by_strain, then --bootstrap."""
+    if not _pairs_gate(paths):
+        return
     collect_by_strain(cls, cls_db_dir, report_path, ksize, paths)
     collect_bootstrap(cls, cls_db_dir, report_path, ksize, paths)
 
@@ -70,6 +76,7 @@ def reset_all():
     bootstrap_reset()
     classify_reads_reset()
     extract_class_reset()
+    pairs_reset()
 
 
 def _skip(state, name, closing, rank0_only, why):
@@ -89,6 +96,54 @@ def _select_or_skip(select, skip, verb):
         if e.code != _lib.SS_ERANGE:
             raise
         return skip(RECORD_WAS_CUT % verb)
+
+
+# --pairs (StrainScan.apply_pairs turns it on; it needs -j and one of the reports below): the reports work on FRAGMENTS.  The
+# device calls decide per record from the record's bytes alone, so they are handed a second resident set whose records are the
+# pairs -- record i of the first file, an N, record i of the second (db.resident_pairs) -- and run unchanged; no k-mer spans the
+# N, so a fragment's hits are its mates' added up.  The scans of the identification keep the plain set.  _report_reads is where
+# every collect_* gets its set; _pairs_gate stands in front of the three hooks: where the pairs cannot be joined it says one line
+# and every per-read report of the run writes nothing (no silent fall-back to mates).
+PAIRS = {"on": False, "skipped": None}
+_PAIRS_LOCK = threading.Lock()
+
+
+def pairs_reset(on=False):
+    PAIRS.update(on=bool(on), skipped=None)
+
+
+def _pairs_gate(paths):
+    """True: the per-read reports may run on `paths` -- --pairs is off, or the joined set is there (built here the first time)."""
+    if not PAIRS["on"]:
+        return True
+    with _PAIRS_LOCK:
+        if PAIRS["skipped"] is None:
+            js, why = db.resident_pairs(paths)
+            if js is not None:
+                return True
+            PAIRS["skipped"] = why
+            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS):
+                if state["skipped"] is None:
+                    state["skipped"] = "--pairs " + why
+            if dist.rank_world()[0] == 0:
+                print("pairs: %s and no per-read report was written" % why, file=sys.stderr)
+                sys.stderr.flush()
+    return False
+
+
+def _report_reads(paths):
+    """The resident set the per-read reports work on: the joined pairs with --pairs, else the sample's reads; None when it is
+    not there."""
+    if PAIRS["on"]:
+        return db.resident_pairs(paths)[0] if PAIRS["skipped"] is None else None
+    return db.resident_reads(paths)
+
+
+def _extract_write(ps, keys, outs):
+    """-x's writer: with --pairs the keys name pairs and both records of a named pair are written"""
+    if PAIRS["on"]:
+        return _lib.extract_write_pairs(ps, keys, outs)
+    return _lib.extract_write(ps, keys, outs)
 
 
 def _write(out_dir, name, text):
@@ -150,7 +205,7 @@ def collect_read_support(table, kdb, paths):
             return
         if kdb.k < 17:
             return _read_support_skip(NEEDS_PAGE_INDEX % kdb.k)
-        rs = db.resident_reads(paths)
+        rs = _report_reads(paths)
         if rs is None:
             return _read_support_skip(NEEDS_RESIDENT)
         hist, hits = rs.support(kdb, READ_SUPPORT_BINS)
@@ -222,7 +277,7 @@ def collect_extract_reads(table, kdb, paths):
             return _extract_reads_skip("takes BAM inputs or FASTA/FASTQ inputs, not both (this run mixes them)")
         if True in bam:               # (BAM subsets, from the files and the open table alone: no resident set)
             return _write_selected_bam(table, kdb, None, 0, 0, ps, n, done)
-        rs = db.resident_reads(paths)
+        rs = _report_reads(paths)
         if rs is None:
             return _extract_reads_skip(NEEDS_RESIDENT)
         _write_selected(table, lambda: rs.select(kdb, n), ps, n, done)
@@ -257,7 +312,7 @@ def _write_selected(table, select, ps, n, done):
     out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
     os.makedirs(out_dir, exist_ok=True)
     outs = [os.path.join(out_dir, "%s_%d.%s" % (table, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
-    c = _lib.extract_write(ps, keys, outs)
+    c = _extract_write(ps, keys, outs)
     done.add(table)
     EXTRACT_READS["files"].extend(outs)
     print("extract_reads: %s\tN=%d\tselected on the device %d\twritten %d" % (table, n, selected, c["written"]), file=sys.stderr)
@@ -375,7 +430,7 @@ def collect_by_strain(cls, cls_db_dir, report_path, ksize, paths):
         indptr, indices, data = cluster_csr_arrays(os.path.join(cls_db_dir, "all_strains_re.npz"))
         ps = [p for p in paths if p]
         bam = extract and bool(ps) and all(_lib.input_kind(p) == "bam" for p in ps)      # (-x on a BAM needs no resident set)
-        rs = db.resident_reads(paths)
+        rs = _report_reads(paths)
         if rs is None:                                               # (said by --read_support / -x already)
             support = False
             if not bam:
@@ -548,7 +603,7 @@ def collect_bootstrap(cls, cls_db_dir, report_path, ksize, paths):
             return
         if int(ksize) < 17:
             return _bootstrap_skip(NEEDS_PAGE_INDEX % int(ksize))
-        rs = db.resident_reads(paths)
+        rs = _report_reads(paths)
         if rs is None:
             return _bootstrap_skip(NEEDS_RESIDENT)
         with contextlib.closing(db.fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2).expect_hits()) as kdb:
@@ -667,7 +722,7 @@ def _collect_read_classes(img, paths):
         node_ids = sorted(set(img.node_ids) | {nd.identifier for nd in tree.all_nodes()})
         if len(node_ids) > _lib.CLASS_NODES_MAX:
             return _classify_reads_skip("takes trees of up to %d nodes (this one has %d)" % (_lib.CLASS_NODES_MAX, len(node_ids)))
-        rs = db.resident_reads(paths)
+        rs = _report_reads(paths)
         if rs is None:
             return _classify_reads_skip(NEEDS_RESIDENT)
         num = {nid: v for v, nid in enumerate(node_ids, 1)}
@@ -818,7 +873,7 @@ def _write_class(item, sub, ps, m):
     out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
     os.makedirs(out_dir, exist_ok=True)
     outs = [os.path.join(out_dir, "class_%s_%d.%s" % (item, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
-    c = _lib.extract_write(ps, keys, outs)
+    c = _extract_write(ps, keys, outs)
     EXTRACT_CLASS["files"].extend(outs)
     print("extract_class: %s\tM=%d\tselected on the device %d\twritten %d" % (item, m, selected, c["written"]), file=sys.stderr)
     sys.stderr.flush()
@@ -828,7 +883,7 @@ def collect_called_classes(cluster_ids, tree_db_dir, upper_keys, paths):
     """--extract_class called, once the tree walk has identified the clusters `cluster_ids`: extracted/class_C<id>_* for each
     that is not written yet under the current scope, from a second ReadSet.select_class against the cached tree image.  A no-op
     unless `called` is listed and the scope's reads were classified."""
-    if EXTRACT_CLASS_CALLED not in EXTRACT_CLASS["items"] or EXTRACT_CLASS["skipped"] is not None:
+    if EXTRACT_CLASS_CALLED not in EXTRACT_CLASS["items"] or EXTRACT_CLASS["skipped"] is not None or not _pairs_gate(paths):
         return
     t = EXTRACT_CLASS["tree"].get(SCOPE["label"])
     if t is None:
@@ -845,7 +900,7 @@ def collect_called_classes(cluster_ids, tree_db_dir, upper_keys, paths):
         sys.stderr.flush()
     if not wanted:
         return
-    rs = db.resident_reads(paths)
+    rs = _report_reads(paths)
     if rs is None:
         return _extract_class_skip(NEEDS_RESIDENT)
     kdb = db.tree_image(tree_db_dir, upper_keys).kdb
