@@ -523,6 +523,44 @@ int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labe
 int ss_bgzf_write(const char *path, const void *head, uint64_t head_n, const void *body, uint64_t body_n, int level);
 int ss_bam_extract_calls(uint64_t *n);
 int ss_bam_extract_timing(double out[8]);
+/* --------------------------------------------------------------------------------------------
+ * Read pairs from a BAM (`--pairs` on a BAM sample; ss_bam_pairs.hip).  A paired BAM holds both mates in one stream, anywhere.
+ * The rule (tests/bam_pairs_model.py restates it):
+ *   KEPT is the loader's rule (neither 0x100 nor 0x800, l_seq != 0); flat(r) is the loader's form of kept record r (reverse-
+ *   complemented for 0x10, letters, the base-quality mask); the NAME is the bytes of read_name before the first NUL, compared by
+ *   BOTH 64-bit hashes of the digest ss_bam_select uses.  Records that are not kept never count.
+ *   A kept record with 0x1 clear is a SINGLE and takes no part in the name join.  A kept record with 0x1 set has ROLE 1 (0x40 set,
+ *   0x80 clear), ROLE 2 (0x80 set, 0x40 clear) or ROLE 0.  The 0x1 records of one name form a group: one record = an ORPHAN; two
+ *   records of roles {1, 2} = a PAIR; anything else (three and more, two of one role, a role 0 that shares its name) = a
+ *   VIOLATION: the call returns SS_EIO, builds nothing and still fills the counters.
+ *   Fragments: a pair gives flat(m1) 'N' flat(m2) '\n'; an orphan of role 2 gives 'N' flat '\n'; an orphan of role 0 or 1 and a
+ *   single give flat 'N' '\n'.  No k-mer spans the N: the hits of the fragments add up to those of the kept records.  The set
+ *   holds (flat_len - kept) + 2 x fragments bytes before padding; fragments stand in ascending stream position of each one's
+ *   earlier record.  One rank only.
+ * counters[6]: records, kept, pairs, orphans, singles, records in violating groups.
+ * ss_bam_mates: stream = an inflated BAM stream in HOST memory.  mate[r] (cap >= records, else SS_ERANGE with the counters set) =
+ *   the mate's record index, 0xFFFFFFFE no mate (single, orphan, member of a violating group), 0xFFFFFFFF not kept.  mate[] is
+ *   filled with a violation too (SS_EIO and counters[5] != 0); SS_EIO with counters[5] == 0 is a damaged stream.
+ * ss_reads_join_pairs_bam: the fragments of such a stream as a resident set.  order == 0: one ASCII slab in the layout of
+ *   ss_reads_select's *out; order != 0: the same set after ss_reads_order.  A stream without kept records: a valid set of 0
+ *   records.  On any error *out is NULL.
+ * ss_reads_load_pairs_bam: the same from one BAM file, brought to the device the way ss_bam_extract brings it.  SS_EINVAL: not a
+ *   BAM.  Both count under ss_reads_join_pairs_calls.  The file is inflated again beside ss_reads_load's own pass.
+ * ss_bam_select_pairs / ss_bam_extract_pairs: ss_bam_select / ss_bam_extract by FRAGMENT: a kept record is written iff its own hits
+ *   plus its mate's reach min_hits; there is no further name join.  counters: [0] records, [1] kept, [2] fragments selected, [3]
+ *   records written.  A violation: SS_EIO and no file.
+ * ss_bam_pairs_timing: the last successful ss_reads_load_pairs_bam, host clock around its synchronised steps (ms): out[0] stream
+ *   on the device, [1] walk + decode, [2] keys, [3] sort, [4] link, [5] lengths + scan, [6] join (and the ordering pass when
+ *   asked for), [7] the whole call.
+ * ------------------------------------------------------------------------------------------ */
+int ss_bam_mates(const void *stream, uint64_t n, uint32_t *mate, uint64_t cap, uint64_t counters[6]);
+int ss_reads_join_pairs_bam(const void *stream, uint64_t n, int order, ss_reads **out, uint64_t counters[6]);
+int ss_reads_load_pairs_bam(const char *path, int order, ss_reads **out, uint64_t counters[6]);
+int ss_bam_select_pairs(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                        uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4]);
+int ss_bam_extract_pairs(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                         uint32_t min_hits, const char *out_path, uint64_t counters[4]);
+int ss_bam_pairs_timing(double out[8]);
 /* The base-quality mask (jellyfish count -Q; off by default).  With a threshold q in 1..93 every decoder that turns a file or a
  * text into bases -- ss_reads_load, ss_scan_files, ss_scan_files_shard, ss_reader_open / ss_reader_next (a reader keeps the
  * threshold it was opened under), ss_fastx_to_flat, ss_bam_decode -- writes 'N' for a base whose quality is below it:

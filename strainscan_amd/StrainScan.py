@@ -160,20 +160,26 @@ def add_arguments(ap, multi=False):
                          "file order, selected by content, a pair when either mate is in the class -- so a pair under "
                          "`unclassified` has at least one unclassified mate.  Needs FASTA/FASTQ input and one rank (default: off)")
     ap.add_argument("--pairs", dest="pairs", action="store_true",
-                    help="With -j and at least one of --read_support, -x N, --bootstrap B, --classify_reads M: those reports (and "
+                    help="With -j (or a paired BAM under -i alone) and at least one of --read_support, -x N, --bootstrap B, "
+                         "--classify_reads M: those reports (and "
                          "--by_strain, --extract_class) treat a read PAIR as one fragment -- record i of -i, an N, record i of -j, "
-                         "joined on the device into a second resident set.  No k-mer spans the joint, so every kmers and hits "
+                         "joined on the device into a second resident set.  In a BAM the mates are found by read name and flag "
+                         "(0x1, 0x40, 0x80), wherever they lie; a record whose mate is missing, and an unpaired one, is a "
+                         "fragment of its own; a name that is not one first and one second mate stops the join.  "
+                         "No k-mer spans the joint, so every kmers and hits "
                          "column stays what it is without the flag; `reads` counts pairs, a fragment's hits are both mates' added "
                          "up, a pair is classified, extracted and resampled as a whole.  The files, headers and columns are "
-                         "unchanged; stdout and the identification reports do not depend on the flag.  Needs FASTA/FASTQ input, "
+                         "unchanged; stdout and the identification reports do not depend on the flag.  Needs two FASTA/FASTQ files "
+                         "or one BAM (--extract_class: FASTA/FASTQ only), "
                          "one rank and room for a second copy of the bases on the device; where the pairs cannot be joined, one "
                          "line says why and no per-read report is written (default: off)")
 
 
 def refuse_pairs_alone(ap, args):
-    """--pairs without -j has no pairs, and without a per-read report nothing to apply them to: the parser's error (exit status
-    2, before any input is opened)."""
-    if args.pairs and not args.input_fq2:
+    """--pairs without -j has no pairs -- unless -i is a BAM, which holds both mates -- and without a per-read report nothing to
+    apply them to: the parser's error (exit status 2; only the first bytes of -i are looked at)."""
+    from . import _lib
+    if args.pairs and not args.input_fq2 and _lib.input_kind(args.input_fq) != "bam":
         ap.error("--pairs needs -j (the second file of the pairs)")
     if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads):
         ap.error("--pairs needs at least one of --read_support, -x N, --bootstrap B, --classify_reads M")

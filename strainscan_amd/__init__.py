@@ -110,9 +110,10 @@ def set_extract_class(names, out_dir=None):
 def set_pairs(on):
     """`strainscan --pairs` for callers of the functions above: from here on every per-read report that is on (read support,
     extracted reads, by strain, bootstrap, read classes, extracted classes) works on the sample's read PAIRS -- record i of the
-    first file, an N, record i of the second, joined on the device (db.resident_pairs) -- in the place of its reads; the scans of
-    the identification keep the plain set.  Where the pairs cannot be joined (one file, a BAM, several ranks, no room, unequal
-    record counts) one line on stderr says why and those reports write nothing.  Off by default; nothing runs while it is off."""
+    first file, an N, record i of the second, or the mates of one BAM linked by name and flag, joined on the device
+    (db.resident_pairs) -- in the place of its reads; the scans of the identification keep the plain set.  Where the pairs cannot be
+    joined (one file that is no BAM, two BAMs, several ranks, no room, unequal record counts, BAM names that are not one first and
+    one second mate) one line on stderr says why and those reports write nothing.  Off by default; nothing runs while it is off."""
     from . import read_reports
     read_reports.pairs_reset(bool(on))
 

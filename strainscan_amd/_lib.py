@@ -157,6 +157,12 @@ SIGNATURES = {
     "ss_bgzf_write": (i32, [cp, vp, u64, vp, u64, i32]),
     "ss_bam_extract_calls": (i32, [P(u64)]),
     "ss_bam_extract_timing": (i32, [P(C.c_double)]),
+    "ss_bam_mates": (i32, [vp, u64, vp, u64, P(u64)]),
+    "ss_reads_join_pairs_bam": (i32, [vp, u64, i32, P(vp), P(u64)]),
+    "ss_reads_load_pairs_bam": (i32, [cp, i32, P(vp), P(u64)]),
+    "ss_bam_select_pairs": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, u64, P(u64), P(u64)]),
+    "ss_bam_extract_pairs": (i32, [cp, vp, vp, u32, u32, u32, cp, P(u64)]),
+    "ss_bam_pairs_timing": (i32, [P(C.c_double)]),
     "ss_set_min_base_qual": (i32, [i32]),
     "ss_get_min_base_qual": (i32, []),
     "ss_mask_counters": (i32, [P(u64)]),
@@ -481,6 +487,34 @@ class ReadSet:
         check(lib().ss_reads_load_pairs(os.fsencode(p1), os.fsencode(p2), int(bool(order)), C.byref(h)), "ss_reads_load_pairs")
         self._h = h
         return self
+
+    @classmethod
+    def _pairs_bam(cls, call, where):
+        require_gpu()
+        self = cls.__new__(cls)
+        h, c = C.c_void_p(), (C.c_uint64 * 6)()
+        rc = call(C.byref(h), c)
+        counters = dict(zip(BAM_PAIR_COUNTERS, (int(v) for v in c)))
+        if rc != SS_OK:
+            e = SSError(rc, where)
+            e.pair_counters = counters      # (SS_EIO with "violating" != 0: names that are not one first and one second mate)
+            raise e
+        self._h = h
+        self.pair_counters = counters
+        return self
+
+    @classmethod
+    def join_pairs_bam(cls, stream, order=True):
+        """A resident set whose records are the FRAGMENTS of an inflated BAM stream (bytes from b'BAM\\1'): mate 1, 'N', mate 2 of
+        every pair, orphans and singles with the N alone (ss_reads_join_pairs_bam; tests/bam_pairs_model.py restates the rule).
+        .pair_counters: dict(records=, kept=, pairs=, orphans=, singles=, violating=); an SSError carries them too."""
+        stream = bytes(stream)
+        return cls._pairs_bam(lambda h, c: lib().ss_reads_join_pairs_bam(stream, len(stream), int(bool(order)), h, c), "ss_reads_join_pairs_bam")
+
+    @classmethod
+    def load_pairs_bam(cls, path, order=True):
+        """The same set from one BAM file (ss_reads_load_pairs_bam)."""
+        return cls._pairs_bam(lambda h, c: lib().ss_reads_load_pairs_bam(os.fsencode(path), int(bool(order)), h, c), "ss_reads_load_pairs_bam")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -933,26 +967,57 @@ def _label_args(kdb, labels, n_labels, label):
     return ptr(_row_labels(kdb, labels)), max(int(n_labels), 0), max(int(label), 0)
 
 
-def bam_select(stream, kdb, min_hits, labels=None, n_labels=0, label=0):
+def bam_select(stream, kdb, min_hits, labels=None, n_labels=0, label=0, pairs=False):
     """The kept records of the selected templates of an inflated BAM stream (bytes from b'BAM\\1'), concatenated in file order,
     and dict(records=, kept=, selected=, written=) (ss_bam_select).  labels: one label per row of the table, the hits counted
-    are those of `label` (as ReadSet.select_labeled)."""
+    are those of `label` (as ReadSet.select_labeled).  pairs: by fragment (ss_bam_select_pairs) -- a kept record is written when
+    its hits and its mate's together reach min_hits, `selected` counts fragments."""
     stream = bytes(stream)
     lab, nl, lb = _label_args(kdb, labels, n_labels, label)
     out = np.empty(max(len(stream), 1), np.uint8)                  # (the records written are records of the stream)
     n, c = C.c_uint64(), (C.c_uint64 * 4)()
-    check(lib().ss_bam_select(stream, len(stream), kdb.handle, lab, nl, lb, int(min_hits), ptr(out), len(stream), C.byref(n), c),
-          "ss_bam_select")
+    name = "ss_bam_select_pairs" if pairs else "ss_bam_select"
+    check(getattr(lib(), name)(stream, len(stream), kdb.handle, lab, nl, lb, int(min_hits), ptr(out), len(stream), C.byref(n), c), name)
     return out[:n.value].tobytes(), dict(zip(BAM_SELECT_COUNTERS, (int(v) for v in c)))
 
 
-def bam_extract(in_path, kdb, min_hits, out_path, labels=None, n_labels=0, label=0):
+def bam_extract(in_path, kdb, min_hits, out_path, labels=None, n_labels=0, label=0, pairs=False):
     """One BAM file -> out_path, a BGZF BAM of the input's header and the kept records of the selected templates
-    (ss_bam_extract) -> dict(records=, kept=, selected=, written=).  No file is left behind when it fails (SSError)."""
+    (ss_bam_extract) -> dict(records=, kept=, selected=, written=).  No file is left behind when it fails (SSError).
+    pairs: by fragment, as bam_select (ss_bam_extract_pairs)."""
     lab, nl, lb = _label_args(kdb, labels, n_labels, label)
     c = (C.c_uint64 * 4)()
-    check(lib().ss_bam_extract(os.fsencode(in_path), kdb.handle, lab, nl, lb, int(min_hits), os.fsencode(out_path), c), "ss_bam_extract")
+    name = "ss_bam_extract_pairs" if pairs else "ss_bam_extract"
+    check(getattr(lib(), name)(os.fsencode(in_path), kdb.handle, lab, nl, lb, int(min_hits), os.fsencode(out_path), c), name)
     return dict(zip(BAM_SELECT_COUNTERS, (int(v) for v in c)))
+
+
+BAM_PAIR_COUNTERS = ("records", "kept", "pairs", "orphans", "singles", "violating")
+BAM_NO_MATE, BAM_NOT_KEPT = 0xFFFFFFFE, 0xFFFFFFFF
+
+
+def bam_mates(stream):
+    """The mate link of an inflated BAM stream (bytes from b'BAM\\1') -> (np.uint32[records], dict of BAM_PAIR_COUNTERS):
+    mate[r] = the record index of kept record r's mate, BAM_NO_MATE, or BAM_NOT_KEPT (ss_bam_mates).  Names that are not one first
+    and one second mate show in "violating" (the link of the other records is still returned); a damaged stream raises."""
+    require_gpu()
+    stream = bytes(stream)
+    c = (C.c_uint64 * 6)()
+    mate = np.empty(len(stream) // 36 + 1, np.uint32)              # (a record is 36 bytes and more)
+    rc = lib().ss_bam_mates(stream, len(stream), ptr(mate), mate.size, c)
+    if rc != SS_OK and not (rc == SS_EIO and c[5]):
+        raise SSError(rc, "ss_bam_mates")
+    return mate[:int(c[0])], dict(zip(BAM_PAIR_COUNTERS, (int(v) for v in c)))
+
+
+BAM_PAIRS_STEPS = ("stream", "walk_decode", "keys", "sort", "link", "lengths_scan", "join", "total")
+
+
+def bam_pairs_timing():
+    """The last ReadSet.load_pairs_bam in milliseconds, step by step (ss_bam_pairs_timing)."""
+    out = (C.c_double * 8)()
+    check(lib().ss_bam_pairs_timing(out), "ss_bam_pairs_timing")
+    return dict(zip(BAM_PAIRS_STEPS, (float(v) for v in out)))
 
 
 def bgzf_write(path, head, body, level=1):

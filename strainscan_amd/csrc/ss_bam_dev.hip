@@ -361,6 +361,7 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
         void *scratch[] = {d_lo, d_entry, d_exit, d_base, d_rec, d_len1, d_off, d_count, d_which, d_keep, d_kidx, d_masked, d_tmp};
         for (void *q : scratch) {
             if (r == 0 && recs && q && (q == d_rec || q == d_keep || q == d_kidx)) continue;      // the caller's from here on
+            if (r == 0 && recs && recs->want_off && q && q == d_off) continue;
             if (q) hipFreeAsync(q, st);
         }
         hipStreamSynchronize(st);
@@ -522,7 +523,44 @@ int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t
     g_bam_kept += kept;
     g_bam_skipped += n_rec - kept;
     if (recs) { recs->d_rec = d_rec; recs->d_keep = d_keep; recs->d_kidx = d_kidx; recs->n_rec = n_rec; recs->kept = kept; recs->hdr_end = hdr_end; }
+    if (recs && recs->want_off) recs->d_off = d_off;
     return done(0);
+}
+
+void BamRecords::release()
+{
+    bool any = false;
+    for (void *q : {(void *)d_rec, (void *)d_keep, (void *)d_kidx, (void *)d_off})
+        if (q) { (void)hipFreeAsync(q, ss::l2s::stream()); any = true; }
+    if (any) (void)ss::l2s::sync();
+    d_rec = nullptr;
+    d_keep = d_kidx = nullptr;
+    d_off = nullptr;
+}
+
+int bam_records_flat_dev(const char *d_stream, uint64_t n, const uint8_t *h_stream, const std::vector<uint64_t> &seg, char **d_flat,
+                         uint64_t *flat_len, uint64_t *flat_cap, BamRecords *recs)
+{
+    uint64_t n_own = 0;
+    int rc = bam_to_flat_dev(d_stream, n, seg, 0, 1, d_flat, flat_len, flat_cap, &n_own, recs);
+    if (rc != 1) return rc;
+    // the device walk declined: the host walks
+    std::vector<uint8_t> copy;
+    if (!h_stream) {
+        copy.resize(n);
+        SS_HIP(hipMemcpy(copy.data(), d_stream, n, hipMemcpyDeviceToHost));
+        h_stream = copy.data();
+    }
+    std::vector<uint64_t> host_rec;
+    uint64_t hdr_end = 0;
+    rc = bam_host_records(h_stream, n, &host_rec, &hdr_end);
+    if (rc) return rc;
+    recs->host_rec = host_rec.data();
+    recs->host_n_rec = host_rec.size();
+    rc = bam_to_flat_dev(d_stream, n, seg, 0, 1, d_flat, flat_len, flat_cap, &n_own, recs);
+    recs->host_rec = nullptr;
+    recs->host_n_rec = 0;
+    return rc == 1 ? SS_ERANGE : rc;                                    // (1: more records than hipcub's int item count holds)
 }
 
 // One BAM file on the device: inflated there (ss_ginflate.hip), decoded there.  0 = done, 1 = declined (small file, not
@@ -613,6 +651,46 @@ int bam_host_stream(const char *path, int kind, BamHostStream *out)
         out->s = (const uint8_t *)text;
     }
     return SS_OK;
+}
+
+int BamDeviceStream::upload(const void *stream, uint64_t n_bytes)
+{
+    if (big_malloc((void **)&copy, ss_reads::padded(n_bytes), &copy_cap) != hipSuccess) { copy = nullptr; return SS_ENOMEM; }
+    if (n_bytes) SS_HIP(hipMemcpy(copy, stream, n_bytes, hipMemcpyHostToDevice));
+    d = copy;
+    n = n_bytes;
+    h = (const uint8_t *)stream;
+    seg = bam_segments(nullptr, 0, n);
+    return SS_OK;
+}
+
+int BamDeviceStream::open_file(const char *path, int kind)
+{
+    if (kind == INPUT_BAM_GZ && gz_on_gpu() && !g_hook_decline.load()) {
+        const int fd = open(path, O_RDONLY);
+        struct stat sb;
+        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= (1 << 20)) {
+            const uint64_t in_n = (uint64_t)sb.st_size;
+            const uint8_t *in = (const uint8_t *)mmap(nullptr, in_n, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (in != MAP_FAILED) {
+                if (in[0] == 0x1f && in[1] == 0x8b && gpu_gunzip(in, in_n, &d, &n, &lease, fd)) seg = bam_segments(in, in_n, n);
+                else d = nullptr;
+                munmap((void *)in, in_n);
+            }
+        }
+        if (fd >= 0) close(fd);
+    }
+    if (d) { inflated_on_device = true; return SS_OK; }
+    const int rc = bam_host_stream(path, kind, &hs);
+    return rc ? rc : upload(hs.s, hs.n);
+}
+
+void BamDeviceStream::release()
+{
+    if (lease) gpu_gunzip_done(lease);
+    if (copy) big_put(copy, copy_cap);
+    lease = nullptr;
+    copy = d = nullptr;
 }
 
 // The record starts of a stream in one sequential walk (what the device walk settles on); *hdr_end = the first record's offset.

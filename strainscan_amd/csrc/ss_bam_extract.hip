@@ -5,9 +5,10 @@
 // needs no such map: ss_bam_dev.hip leaves the start of every record (d_rec), the kept flag (d_keep) and the kept ordinal (d_kidx)
 // on the device, and its flat block holds kept record i as non-empty record i -- so the hits of rec_hits_of (ss_support.hip) on
 // that block are indexed by BAM record.  One path, for ss_bam_select (a stream in host memory) and ss_bam_extract (a file):
-//   1  the stream on the device (gpu_gunzip where the loader would use it; else the host inflaters and an upload)
-//   2  bam_to_flat_dev (shard_world 1) with BamRecords: walk, list, keep, length, decode; the record starts from the host walk
-//      when the device walk declines
+//   1  the stream on the device (BamDeviceStream, ss_bam_dev.hip: gpu_gunzip where the loader would use it; else the host
+//      inflaters and an upload)
+//   2  bam_records_flat_dev: bam_to_flat_dev (shard_world 1) with BamRecords: walk, list, keep, length, decode; the record starts
+//      from the host walk when the device walk declines
 //   3  the flat block wrapped as a one-slab ASCII set -> rec_hits_of (with slot labels: the hits of one label), rec_total == kept
 //   4  name_digest_kernel: one lane per record; a kept record's read name (the bytes before the first NUL) -> two independent
 //      64-bit hashes over the bytes and the length, and sel[r] = hits >= N.  ExclusiveSum + compact_kernel + hipcub SortPairs: the
@@ -18,6 +19,8 @@
 //      aligned 16-byte store where the piece is all the record's, byte stores at the edges it shares with its neighbours
 //   6  the result to the host through two pinned buffers, chunk by chunk; ss_bgzf_write compresses the members on host threads.
 // Records that the loader does not keep (0x100, 0x800, no bases) are never written, whatever their name.
+// ss_bam_select_pairs / ss_bam_extract_pairs (`--pairs`): the same path with the mate link of ss_bam_pairs.hip in the place of step
+// 4 -- a kept record is written iff its hits and its mate's together reach N, and nothing is joined by name after that.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  No device-wide barrier inside a kernel.
 #include "ss_scan_dev.h"
 #include "ss_support.h"
@@ -26,8 +29,6 @@
 #include <zlib.h>
 
 #include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cerrno>
@@ -42,9 +43,8 @@ __device__ __forceinline__ uint32_t ld32d(const uint8_t *s, uint64_t p)
     return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24;
 }
 
-// One lane per record r <= n_rec (entry n_rec closes the sums).  A kept record: h1 = FNV-1a (64-bit) over the name's bytes and the
-// eight bytes of its length, h2 = a rotate-xor-multiply hash over the same bytes, closed with the length and the splitmix64
-// finisher; sel = its hits reach min_hits.  A record that is not kept: sel = 0 and a digest nobody asks for.
+// One lane per record r <= n_rec (entry n_rec closes the sums).  A kept record: (h1, h2) = the digest of its name (bam_name_digest,
+// ss_support.h); sel = its hits reach min_hits.  A record that is not kept: sel = 0 and a digest nobody asks for.
 __global__ __launch_bounds__(256) void name_digest_kernel(const uint8_t *__restrict__ s, const uint64_t *__restrict__ rec,
                                                           const uint32_t *__restrict__ keep, const uint32_t *__restrict__ kidx,
                                                           const uint32_t *__restrict__ hits, uint64_t n_rec, uint32_t min_hits,
@@ -54,23 +54,7 @@ __global__ __launch_bounds__(256) void name_digest_kernel(const uint8_t *__restr
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (r > n_rec) return;
     if (r == n_rec || !keep[r]) { sel[r] = 0u; return; }
-    const uint64_t p = rec[r];
-    const uint32_t lrn = s[p + 12];                                  // (>= 1, the bytes lie inside the record: rec_len)
-    unsigned long long a = 0xCBF29CE484222325ull, b = 0x243F6A8885A308D3ull;
-    uint32_t len = 0;
-    for (; len + 1u < lrn; len++) {
-        const uint32_t c = s[p + 36 + len];
-        if (!c) break;
-        a = (a ^ c) * 0x100000001B3ull;
-        b = (((b << 7) | (b >> 57)) ^ c) * 0x9E3779B97F4A7C15ull;
-    }
-    for (int i = 0; i < 8; i++) a = (a ^ (i == 0 ? len : 0u)) * 0x100000001B3ull;
-    b ^= (unsigned long long)len * 0xD6E8FEB86659FD93ull;
-    b = (b ^ (b >> 30)) * 0xBF58476D1CE4E5B9ull;
-    b = (b ^ (b >> 27)) * 0x94D049BB133111EBull;
-    b ^= b >> 31;
-    h1[r] = a;
-    h2[r] = b;
+    ss::bam_name_digest(s, rec[r], &h1[r], &h2[r]);
     sel[r] = hits[kidx[r]] >= min_hits ? 1u : 0u;
 }
 
@@ -173,44 +157,31 @@ struct Selection {
     char *d_out = nullptr;
     uint64_t out_cap = 0, total = 0, hdr_end = 0;
     uint64_t counters[4] = {0, 0, 0, 0};
+    uint64_t pair_counters[6] = {0, 0, 0, 0, 0, 0};      // `pairs`: what the mate link counted
     double ms[4] = {0, 0, 0, 0};                   // walk + decode, hits, join, gather
     ~Selection() { if (d_out) ss::big_put(d_out, out_cap); }
 };
 
 // steps 2 to 5 on a stream that lies on the device (h_stream: the same bytes on the host, or nullptr)
+// pairs (ss_bam_select_pairs, ss_bam_extract_pairs): step 4 is the mate link of ss_bam_pairs.hip in the place of the template join
+// -- a kept record is written iff the hits of its fragment reach min_hits; counters[2] = fragments selected; SS_EIO (and
+// pair_counters filled) when a name is not one first and one second mate
 int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, const std::vector<uint64_t> &seg, const ss_db *db,
-                     const uint8_t *row_labels, uint32_t n_labels, uint32_t label, uint32_t min_hits, Selection *out)
+                     const uint8_t *row_labels, uint32_t n_labels, uint32_t label, uint32_t min_hits, Selection *out, bool pairs = false)
 {
     auto t0 = Clock::now();
     // 2. records, kept flags, flat block
     ss::BamRecords recs;
     char *flat = nullptr;
-    uint64_t flat_len = 0, flat_cap = 0, n_own = 0;
-    std::vector<uint64_t> host_rec;
-    int rc = ss::bam_to_flat_dev(d_stream, n, seg, 0, 1, &flat, &flat_len, &flat_cap, &n_own, &recs);
-    if (rc == 1) {                                                      // the device walk declined: the host walks
-        std::vector<uint8_t> copy;
-        if (!h_stream) {
-            copy.resize(n);
-            SS_HIP(hipMemcpy(copy.data(), d_stream, n, hipMemcpyDeviceToHost));
-            h_stream = copy.data();
-        }
-        uint64_t hdr_end = 0;
-        rc = ss::bam_host_records(h_stream, n, &host_rec, &hdr_end);
-        if (rc) return rc;
-        recs.host_rec = host_rec.data();
-        recs.host_n_rec = host_rec.size();
-        rc = ss::bam_to_flat_dev(d_stream, n, seg, 0, 1, &flat, &flat_len, &flat_cap, &n_own, &recs);
-        if (rc == 1) return SS_ERANGE;                                  // more records than hipcub's int item count holds
-    }
+    uint64_t flat_len = 0, flat_cap = 0;
+    int rc = ss::bam_records_flat_dev(d_stream, n, h_stream, seg, &flat, &flat_len, &flat_cap, &recs);
     if (rc) return rc;
     const hipStream_t st = ss::l2s::stream();
     struct Owned {                                                      // what bam_to_flat_dev handed over
         ss::BamRecords &r; char *&flat; uint64_t &cap;
         ~Owned()
         {
-            for (void *q : {(void *)r.d_rec, (void *)r.d_keep, (void *)r.d_kidx}) if (q) (void)hipFreeAsync(q, ss::l2s::stream());
-            (void)ss::l2s::sync();
+            r.release();
             if (flat) ss::big_put(flat, cap);
         }
     } owned{recs, flat, flat_cap};
@@ -247,7 +218,7 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
         return SS_EHIP;
     }
     out->ms[1] = ms_since(t0);
-    // 4. template join
+    // 4. template join; with `pairs` the mate link
     t0 = Clock::now();
     const uint8_t *s = reinterpret_cast<const uint8_t *>(d_stream);
     ss::PoolScratch &scratch = rh.scratch;
@@ -257,45 +228,55 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     void *d_tmp = nullptr;
     const int items = (int)(n_rec + 1);                                 // (n_rec < 0x7FFFFFF0: bam_to_flat_dev)
     const unsigned g1 = (unsigned)((n_rec + 1 + 255) / 256);
-    SS_HIP(scratch.get((void **)&d_h1, n_rec * 8));
-    SS_HIP(scratch.get((void **)&d_h2, n_rec * 8));
     SS_HIP(scratch.get((void **)&d_sel, (n_rec + 1) * 4));
     SS_HIP(scratch.get((void **)&d_sidx, (n_rec + 1) * 4));
     SS_HIP(scratch.get((void **)&d_len, (n_rec + 1) * 8));
     SS_HIP(scratch.get((void **)&d_off, (n_rec + 1) * 8));
     SS_HIP(scratch.get((void **)&d_tot, 16));
     SS_HIP(ss::l2s::set(d_tot, 0, 16));
-    hipLaunchKernelGGL(name_digest_kernel, dim3(g1), dim3(256), 0, st, s, (const uint64_t *)recs.d_rec, (const uint32_t *)recs.d_keep,
-                       (const uint32_t *)recs.d_kidx, (const uint32_t *)rh.d_rec_hits, n_rec, min_hits, d_h1, d_h2, d_sel);
-    SS_HIP(hipGetLastError());
     size_t tb1 = 0, tb2 = 0;
     SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, d_sel, d_sidx, items, st));
     SS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, d_len, d_off, items, st));
     const size_t tmp_bytes = std::max(tb1, tb2);
     SS_HIP(scratch.get(&d_tmp, tmp_bytes));
-    tb1 = tmp_bytes;
-    SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb1, d_sel, d_sidx, items, st));
-    uint32_t n_sel = 0;
-    SS_HIP(ss::l2s::copy(&n_sel, d_sidx + n_rec, 4, hipMemcpyDeviceToHost));
-    out->counters[2] = n_sel;
-    if (n_sel) {
-        SS_HIP(scratch.get((void **)&d_k1, (uint64_t)n_sel * 8));
-        SS_HIP(scratch.get((void **)&d_k2, (uint64_t)n_sel * 8));
-        SS_HIP(scratch.get((void **)&d_s1, (uint64_t)n_sel * 8));
-        SS_HIP(scratch.get((void **)&d_s2, (uint64_t)n_sel * 8));
-        hipLaunchKernelGGL(compact_kernel, dim3(g1), dim3(256), 0, st, (const uint32_t *)d_sel, (const uint32_t *)d_sidx,
-                           (const unsigned long long *)d_h1, (const unsigned long long *)d_h2, n_rec, d_k1, d_k2);
+    if (pairs) {
+        uint32_t *d_mate = nullptr;
+        uint8_t *d_role = nullptr;
+        rc = ss::bam_mates_dev(s, recs, scratch, &d_mate, &d_role, out->pair_counters, nullptr);
+        if (rc) return rc;
+        if (out->pair_counters[5]) return SS_EIO;
+        rc = ss::bam_fragment_out_len(s, recs, d_mate, rh.d_rec_hits, min_hits, d_len, d_tot);
+        if (rc) return rc;
+    } else {
+        SS_HIP(scratch.get((void **)&d_h1, n_rec * 8));
+        SS_HIP(scratch.get((void **)&d_h2, n_rec * 8));
+        hipLaunchKernelGGL(name_digest_kernel, dim3(g1), dim3(256), 0, st, s, (const uint64_t *)recs.d_rec, (const uint32_t *)recs.d_keep,
+                           (const uint32_t *)recs.d_kidx, (const uint32_t *)rh.d_rec_hits, n_rec, min_hits, d_h1, d_h2, d_sel);
         SS_HIP(hipGetLastError());
-        size_t sb = 0;
-        void *d_sort = nullptr;
-        SS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, d_k1, d_s1, d_k2, d_s2, (int)n_sel, 0, 64, st));
-        SS_HIP(scratch.get(&d_sort, sb));
-        SS_HIP(hipcub::DeviceRadixSort::SortPairs(d_sort, sb, d_k1, d_s1, d_k2, d_s2, (int)n_sel, 0, 64, st));
+        tb1 = tmp_bytes;
+        SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb1, d_sel, d_sidx, items, st));
+        uint32_t n_sel = 0;
+        SS_HIP(ss::l2s::copy(&n_sel, d_sidx + n_rec, 4, hipMemcpyDeviceToHost));
+        out->counters[2] = n_sel;
+        if (n_sel) {
+            SS_HIP(scratch.get((void **)&d_k1, (uint64_t)n_sel * 8));
+            SS_HIP(scratch.get((void **)&d_k2, (uint64_t)n_sel * 8));
+            SS_HIP(scratch.get((void **)&d_s1, (uint64_t)n_sel * 8));
+            SS_HIP(scratch.get((void **)&d_s2, (uint64_t)n_sel * 8));
+            hipLaunchKernelGGL(compact_kernel, dim3(g1), dim3(256), 0, st, (const uint32_t *)d_sel, (const uint32_t *)d_sidx,
+                               (const unsigned long long *)d_h1, (const unsigned long long *)d_h2, n_rec, d_k1, d_k2);
+            SS_HIP(hipGetLastError());
+            size_t sb = 0;
+            void *d_sort = nullptr;
+            SS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, d_k1, d_s1, d_k2, d_s2, (int)n_sel, 0, 64, st));
+            SS_HIP(scratch.get(&d_sort, sb));
+            SS_HIP(hipcub::DeviceRadixSort::SortPairs(d_sort, sb, d_k1, d_s1, d_k2, d_s2, (int)n_sel, 0, 64, st));
+        }
+        hipLaunchKernelGGL(template_len_kernel, dim3(g1), dim3(256), 0, st, s, (const uint64_t *)recs.d_rec, (const uint32_t *)recs.d_keep,
+                           (const uint32_t *)d_sel, (const unsigned long long *)d_h1, (const unsigned long long *)d_h2, n_rec,
+                           (const unsigned long long *)d_s1, (const unsigned long long *)d_s2, n_sel, d_len, d_tot);
+        SS_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(template_len_kernel, dim3(g1), dim3(256), 0, st, s, (const uint64_t *)recs.d_rec, (const uint32_t *)recs.d_keep,
-                       (const uint32_t *)d_sel, (const unsigned long long *)d_h1, (const unsigned long long *)d_h2, n_rec,
-                       (const unsigned long long *)d_s1, (const unsigned long long *)d_s2, n_sel, d_len, d_tot);
-    SS_HIP(hipGetLastError());
     // 5. offsets and copy
     tb2 = tmp_bytes;
     SS_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb2, d_len, d_off, items, st));
@@ -303,6 +284,7 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     SS_HIP(hipMemcpyAsync(&total, d_off + n_rec, 8, hipMemcpyDeviceToHost, st));
     SS_HIP(ss::l2s::copy(tot, d_tot, 16, hipMemcpyDeviceToHost));
     out->counters[3] = tot[0];
+    if (pairs) out->counters[2] = tot[1];
     out->total = total;
     out->ms[2] = ms_since(t0);
     if (!total) return SS_OK;
@@ -356,19 +338,6 @@ int check_args(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, ui
     if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
     return SS_OK;
 }
-
-// a device copy of a host stream (big_malloc; at least 16 bytes)
-struct DeviceCopy {
-    char *d = nullptr;
-    uint64_t cap = 0;
-    int upload(const void *src, uint64_t n)
-    {
-        if (ss::big_malloc((void **)&d, ss_reads::padded(n), &cap) != hipSuccess) { d = nullptr; return SS_ENOMEM; }
-        if (n) SS_HIP(hipMemcpy(d, src, n, hipMemcpyHostToDevice));
-        return SS_OK;
-    }
-    ~DeviceCopy() { if (d) ss::big_put(d, cap); }
-};
 
 unsigned bgzf_threads()
 {
@@ -488,18 +457,18 @@ int ss_bgzf_write(const char *path, const void *head, uint64_t head_n, const voi
     return SS_OK;
 }
 
-int ss_bam_select(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
-                  uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4])
+static int select_stream(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                         uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4], bool pairs)
 {
     if ((!stream && n) || !out_len || !counters || (!out && cap)) return SS_EINVAL;
     int rc = check_args(db, row_labels, n_labels, label, min_hits);
     if (rc) return rc;
     g_bam_extract_calls++;
-    DeviceCopy dc;
-    rc = dc.upload(stream, n);
+    ss::BamDeviceStream ds;
+    rc = ds.upload(stream, n);
     if (rc) return rc;
     Selection sel;
-    rc = select_on_device(dc.d, n, (const uint8_t *)stream, ss::bam_segments(nullptr, 0, n), db, row_labels, n_labels, label, min_hits, &sel);
+    rc = select_on_device(ds.d, n, ds.h, ds.seg, db, row_labels, n_labels, label, min_hits, &sel, pairs);
     if (rc) return rc;
     memcpy(counters, sel.counters, sizeof sel.counters);
     *out_len = sel.total;
@@ -507,8 +476,8 @@ int ss_bam_select(const void *stream, uint64_t n, const ss_db *db, const uint8_t
     return download_chunks(sel.d_out, sel.total, (char *)out);
 }
 
-int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
-                   uint32_t min_hits, const char *out_path, uint64_t counters[4])
+static int extract_file(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                        uint32_t min_hits, const char *out_path, uint64_t counters[4], bool pairs)
 {
     if (!in_path || !out_path || !counters) return SS_EINVAL;
     int rc = check_args(db, row_labels, n_labels, label, min_hits);
@@ -520,50 +489,25 @@ int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labe
     const auto t_all = Clock::now();
     auto t0 = t_all;
     // 1. the stream on the device: inflated there where the loader would do that, else inflated on the host and uploaded
-    char *d_text = nullptr;
-    uint64_t n = 0;
-    void *lease = nullptr;
-    std::vector<uint64_t> seg;
-    if (kind == ss::INPUT_BAM_GZ && ss::gz_on_gpu() && !ss::g_hook_decline.load()) {
-        const int fd = open(in_path, O_RDONLY);
-        struct stat sb;
-        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= (1 << 20)) {
-            const uint64_t in_n = (uint64_t)sb.st_size;
-            const uint8_t *in = (const uint8_t *)mmap(nullptr, in_n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (in != MAP_FAILED) {
-                if (in[0] == 0x1f && in[1] == 0x8b && ss::gpu_gunzip(in, in_n, &d_text, &n, &lease, fd)) seg = ss::bam_segments(in, in_n, n);
-                else d_text = nullptr;
-                munmap((void *)in, in_n);
-            }
-        }
-        if (fd >= 0) close(fd);
-    }
-    ss::BamHostStream hs;
-    DeviceCopy dc;
-    if (!d_text) {
-        rc = ss::bam_host_stream(in_path, kind, &hs);
-        if (rc) return rc;
-        n = hs.n;
-        rc = dc.upload(hs.s, n);
-        if (rc) return rc;
-        seg = ss::bam_segments(nullptr, 0, n);
-    }
+    ss::BamDeviceStream ds;
+    rc = ds.open_file(in_path, kind);
+    if (rc) return rc;
     ms[0] = ms_since(t0);
     Selection sel;
-    rc = select_on_device(d_text ? d_text : dc.d, n, hs.s, seg, db, row_labels, n_labels, label, min_hits, &sel);
+    rc = select_on_device(ds.d, ds.n, ds.h, ds.seg, db, row_labels, n_labels, label, min_hits, &sel, pairs);
     // 6. header and records to the host, then the file
     std::vector<uint8_t> head;
     char *body = nullptr;
     t0 = Clock::now();
     if (rc == SS_OK) {
         try { head.resize(sel.hdr_end); } catch (const std::bad_alloc &) { rc = SS_ENOMEM; }
-        if (rc == SS_OK && sel.hdr_end && hipMemcpy(head.data(), d_text ? d_text : dc.d, sel.hdr_end, hipMemcpyDeviceToHost) != hipSuccess) rc = SS_EHIP;
+        if (rc == SS_OK && sel.hdr_end && hipMemcpy(head.data(), ds.d, sel.hdr_end, hipMemcpyDeviceToHost) != hipSuccess) rc = SS_EHIP;
     }
     if (rc == SS_OK && sel.total) {
         body = (char *)malloc(sel.total);
         rc = body ? download_chunks(sel.d_out, sel.total, body) : SS_ENOMEM;
     }
-    if (lease) ss::gpu_gunzip_done(lease);
+    ds.release();
     ms[5] = ms_since(t0);
     if (rc == SS_OK) {
         t0 = Clock::now();
@@ -576,13 +520,37 @@ int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labe
     }
     free(body);
     if (rc) return rc;
-    (d_text ? ss::g_bam_dev_files : ss::g_bam_host_files)++;
+    (ds.inflated_on_device ? ss::g_bam_dev_files : ss::g_bam_host_files)++;
     memcpy(counters, sel.counters, sizeof sel.counters);
     for (int i = 0; i < 4; i++) ms[1 + i] = sel.ms[i];
     ms[7] = ms_since(t_all);
     std::lock_guard<std::mutex> g(g_timing_mu);
     memcpy(g_timing, ms, sizeof ms);
     return SS_OK;
+}
+
+int ss_bam_select(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                  uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4])
+{
+    return select_stream(stream, n, db, row_labels, n_labels, label, min_hits, out, cap, out_len, counters, false);
+}
+
+int ss_bam_select_pairs(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                        uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4])
+{
+    return select_stream(stream, n, db, row_labels, n_labels, label, min_hits, out, cap, out_len, counters, true);
+}
+
+int ss_bam_extract(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                   uint32_t min_hits, const char *out_path, uint64_t counters[4])
+{
+    return extract_file(in_path, db, row_labels, n_labels, label, min_hits, out_path, counters, false);
+}
+
+int ss_bam_extract_pairs(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
+                         uint32_t min_hits, const char *out_path, uint64_t counters[4])
+{
+    return extract_file(in_path, db, row_labels, n_labels, label, min_hits, out_path, counters, true);
 }
 
 }  // extern "C"

@@ -254,16 +254,24 @@ int bam_input(const char *path, int kind, int shard_rank, int shard_world, const
 // may keep -- record r of the stream starts at d_rec[r] (n_rec of them), d_keep[r] says whether the loader keeps it and d_kidx[r] is
 // its ordinal among the kept ones, so kept record i is non-empty record i of the flat block (shard_world 1); the three come from
 // the stream-ordered pool (hipFreeAsync on any stream).  host_rec / host_n_rec (in): record starts from bam_host_records, for a
-// stream whose device walk declined.
+// stream whose device walk declined.  want_off (in): d_off [n_rec + 1] stays too -- kept record r's letters begin at byte
+// d_off[r] of the flat block and d_off[r + 1] - d_off[r] is their number + 1, 0 for a record that is not kept.
 struct BamRecords {
     uint64_t *d_rec = nullptr;
     uint32_t *d_keep = nullptr, *d_kidx = nullptr;
     uint64_t n_rec = 0, kept = 0, hdr_end = 0;
     const uint64_t *host_rec = nullptr;
     uint64_t host_n_rec = 0;
+    bool want_off = false;
+    uint64_t *d_off = nullptr;
+    void release();      // the device arrays back to the pool (synchronises)
 };
 int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t> &seg, int shard_rank, int shard_world, char **d_flat,
                     uint64_t *flat_len, uint64_t *flat_cap, uint64_t *n_records, BamRecords *recs = nullptr);
+// bam_to_flat_dev for one rank with `recs` kept, and the host walk (bam_host_records) where the device walk declines.  h_stream:
+// the same bytes on the host, or nullptr (they are copied back then).  SS_ERANGE: more records than hipcub's int item count holds.
+int bam_records_flat_dev(const char *d_stream, uint64_t n, const uint8_t *h_stream, const std::vector<uint64_t> &seg, char **d_flat,
+                         uint64_t *flat_len, uint64_t *flat_cap, BamRecords *recs);
 std::vector<uint64_t> bam_segments(const uint8_t *in, uint64_t in_n, uint64_t n);      // in = NULL: 64 KB pieces
 struct BamHostStream {                   // the inflated stream on the host: s[0, n), released with the object
     const uint8_t *s = nullptr;
@@ -275,6 +283,25 @@ struct BamHostStream {                   // the inflated stream on the host: s[0
 };
 int bam_host_stream(const char *path, int kind, BamHostStream *out);
 int bam_host_records(const uint8_t *s, uint64_t n, std::vector<uint64_t> *rec, uint64_t *hdr_end);
+// The inflated stream of a BAM on the device, d[0, n): a file inflated there where the loader would do that (gpu_gunzip: 1 MB and
+// more, not under SS_GZ_GPU=0; `inflated_on_device`), else inflated on the host and uploaded; or a copy of a stream in host memory.
+// h: the same bytes on the host where they are there; seg: bam_segments.  release() (and the destructor) gives everything back.
+struct BamDeviceStream {
+    char *d = nullptr;
+    uint64_t n = 0;
+    const uint8_t *h = nullptr;
+    std::vector<uint64_t> seg;
+    bool inflated_on_device = false;
+    int open_file(const char *path, int kind);
+    int upload(const void *stream, uint64_t n_bytes);
+    void release();
+    ~BamDeviceStream() { release(); }
+private:
+    void *lease = nullptr;
+    char *copy = nullptr;
+    uint64_t copy_cap = 0;
+    BamHostStream hs;
+};
 extern std::atomic<uint64_t> g_bam_dev_files, g_bam_host_files;
 extern std::atomic<long long> g_hook_bam_walk_decline;      // ss_test_hook 7 (ss_bam_dev.hip)
 // What a consumer of input files does with their flat base blocks: ss_scan_files_shard scans them into a table, ss_reads_load

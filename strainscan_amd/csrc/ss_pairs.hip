@@ -40,6 +40,7 @@ using ss::SUP_TILE;
 
 namespace ss {
 bool text_chunk_starts(const char *t, uint64_t n, std::vector<uint64_t> *starts);      // (ss_ingest.hip)
+std::atomic<uint64_t> g_join_pairs_calls{0};      // ss_reads_join_pairs_calls: the joins of this file and of ss_bam_pairs.hip
 }
 
 namespace {
@@ -147,8 +148,6 @@ __global__ __launch_bounds__(256) void join_kernel(const uint8_t *__restrict__ s
     }
 }
 
-std::atomic<uint64_t> g_join_calls{0};
-
 // steps 1 and 2 for one block of n > 0 bytes: *d_le [*n_lines] in `scratch`
 int line_index(const uint8_t *b, uint64_t n, ss::PoolScratch &scratch, unsigned long long **d_le, uint64_t *n_lines)
 {
@@ -241,7 +240,7 @@ extern "C" {
 int ss_reads_join_pairs_calls(uint64_t *n)
 {
     if (!n) return SS_EINVAL;
-    *n = g_join_calls.load();
+    *n = ss::g_join_pairs_calls.load();
     return SS_OK;
 }
 
@@ -264,7 +263,7 @@ int ss_reads_join_pairs_dev(const void *flat1_dev, uint64_t n1, const void *flat
     if (rc != SS_OK) return rc;
     if (m1 != m2) return SS_EIO;
     if (m1 > 0xFFFFFFFFull) return SS_ERANGE;
-    g_join_calls++;                                                     // (a join: the blocks pair up)
+    ss::g_join_pairs_calls++;                                           // (a join: the blocks pair up)
     ss_reads *S = new (std::nothrow) ss_reads();
     if (!S) return SS_ENOMEM;
     const uint64_t total = n1 + n2;

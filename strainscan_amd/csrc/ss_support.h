@@ -63,6 +63,43 @@ struct RecSpans {
 };
 int record_spans_of(RecHits *rh, RecSpans *sp);
 int gather_records(RecHits *rh, RecSpans &sp, const char *who, ss_reads **out);
+// The 128-bit digest of the read name of the BAM record at s + p (the bytes before the first NUL; l_read_name >= 1 and the bytes
+// lie inside the record: rec_len of ss_bam_dev.hip): *h1 = FNV-1a (64-bit) over the name's bytes and the eight bytes of its length,
+// *h2 = a rotate-xor-multiply hash over the same bytes, closed with the length and the splitmix64 finisher.  The one hash of
+// ss_bam_extract.hip (the template join) and ss_bam_pairs.hip (the mate link).
+__device__ __forceinline__ void bam_name_digest(const uint8_t *__restrict__ s, uint64_t p, unsigned long long *h1, unsigned long long *h2)
+{
+    const uint32_t lrn = s[p + 12];
+    unsigned long long a = 0xCBF29CE484222325ull, b = 0x243F6A8885A308D3ull;
+    uint32_t len = 0;
+    for (; len + 1u < lrn; len++) {
+        const uint32_t c = s[p + 36 + len];
+        if (!c) break;
+        a = (a ^ c) * 0x100000001B3ull;
+        b = (((b << 7) | (b >> 57)) ^ c) * 0x9E3779B97F4A7C15ull;
+    }
+    for (int i = 0; i < 8; i++) a = (a ^ (i == 0 ? len : 0u)) * 0x100000001B3ull;
+    b ^= (unsigned long long)len * 0xD6E8FEB86659FD93ull;
+    b = (b ^ (b >> 30)) * 0xBF58476D1CE4E5B9ull;
+    b = (b ^ (b >> 27)) * 0x94D049BB133111EBull;
+    b ^= b >> 31;
+    *h1 = a;
+    *h2 = b;
+}
+
+// The mate link of a BAM stream's records (ss_bam_pairs.hip; the rule: strainscan_hip.h, "Read pairs from a BAM").  recs: what
+// bam_to_flat_dev left (ss_common.h).  *d_mate [n_rec] and *d_role [n_rec] (0, 1 or 2; kept 0x1 records only) come from `scratch`;
+// counters: records, kept, pairs, orphans, singles, records in violating groups; ms (or nullptr): keys, sort, link, each
+// synchronised.  SS_OK also with violations (counters[5] says so).  n_rec == 0: nothing is allocated.
+int bam_mates_dev(const uint8_t *d_stream, const BamRecords &recs, PoolScratch &scratch, uint32_t **d_mate, uint8_t **d_role,
+                  uint64_t counters[6], double *ms);
+// out_len[r] (r <= n_rec; [n_rec] = 0) = 4 + block_size when kept record r's FRAGMENT -- its own hits plus its mate's -- reaches
+// min_hits, else 0 (d_hits: per kept record, by d_kidx); tot[0] += records written, tot[1] += fragments selected.  Enqueued.
+int bam_fragment_out_len(const uint8_t *d_stream, const BamRecords &recs, const uint32_t *d_mate, const uint32_t *d_hits,
+                         uint32_t min_hits, unsigned long long *d_out_len, unsigned long long *d_tot);
+
+extern std::atomic<uint64_t> g_join_pairs_calls;      // ss_reads_join_pairs_calls (ss_pairs.hip)
+
 // row labels (host, db->n_rows of them; only != 0: folded to 1 = `only`, 0 = the rest) -> *d_slot_label [db->n_slots] in `scratch`
 // (ss_label.hip); SS_EINVAL for a label above n_labels
 int slot_labels_for(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t only, PoolScratch &scratch, uint8_t **d_slot_label);

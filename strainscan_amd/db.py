@@ -137,17 +137,20 @@ def _close_pairs():
 
 def resident_pairs(paths):
     """(set, None): the sample's read PAIRS as the records of a second resident set -- record i of the first file, an N, record i
-    of the second (ReadSet.load_pairs) -- cached beside the resident reads and closed with them; or (None, why) where it is not
-    built: one file, a BAM input, several ranks, the plain sample not resident, no room for a second copy of the bases, unequal
-    record counts.  The scans never use it: it serves the per-read reports (read_reports, --pairs).  One line on stderr after
-    the join: the pairs and the bytes of the set."""
+    of the second (ReadSet.load_pairs); or, for one BAM, the fragments its mates make by name and flag (ReadSet.load_pairs_bam) --
+    cached beside the resident reads and closed with them; or (None, why) where it is not built: one file that is no BAM, two BAMs
+    or a BAM beside a FASTQ, several ranks, the plain sample not resident, no room for a second copy of the bases, unequal record
+    counts, a BAM whose names are not one first and one second mate.  The scans never use it: it serves the per-read reports
+    (read_reports, --pairs).  One line on stderr after the join: the pairs (a BAM: the orphans and singles too) and the bytes of
+    the set."""
     import sys
     from . import dist
     rank, world = dist.rank_world()
     ps = [p for p in paths if p]
-    if len(ps) != 2:
+    bam = len(ps) == 1 and _lib.input_kind(ps[0]) == "bam"
+    if len(ps) != 2 and not bam:
         return None, "needs the two files of a paired sample (-i and -j)"
-    if any(_lib.input_kind(p) != "fastx" for p in ps):
+    if not bam and any(_lib.input_kind(p) != "fastx" for p in ps):
         return None, "takes FASTA/FASTQ inputs (the mates of a pair are not adjacent in a coordinate-sorted BAM; pairs from BAM are not built)"
     if world > 1:
         return None, "runs on one rank only (this run has several)"
@@ -161,22 +164,33 @@ def resident_pairs(paths):
             return js, None
         inf = rs.info()
         # the load's peak beside the resident reads: the two flat blocks, the joined slab and its binned copy, each at most the
-        # bases and their line ends as ASCII
+        # bases and their line ends as ASCII; a BAM: its one flat block and, budgeted as resident_reads does, the inflated stream
         no_room = "has no room for the joined pairs beside the resident reads (SS_READS_RESIDENT_GB)"
-        if inf["device_bytes"] + 3 * (inf["n_bases"] + inf["n_records"]) > RESIDENT_LIMIT_BYTES:
+        peak = 3 * (inf["n_bases"] + inf["n_records"]) + (4 * os.path.getsize(ps[0]) if bam else 0)
+        if inf["device_bytes"] + peak > RESIDENT_LIMIT_BYTES:
             return None, no_room
         try:
-            js = _lib.ReadSet.load_pairs(ps[0], ps[1])
+            js = _lib.ReadSet.load_pairs_bam(ps[0]) if bam else _lib.ReadSet.load_pairs(ps[0], ps[1])
         except _lib.SSError as e:
             if e.code == _lib.SS_ENOMEM:        # (the device holds other things than this budget knows of)
                 return None, no_room
             if e.code != _lib.SS_EIO:
                 raise
+            if bam:
+                bad = getattr(e, "pair_counters", {}).get("violating", 0)
+                if not bad:
+                    raise
+                return None, "has read names that are not one first and one second mate (%d records)" % bad
             return None, "could not pair the records of the two files (unequal record counts, or a file that cannot be read)"
         _close_pairs()
         _PAIRS[key] = js
         ji = js.info()
-        print("pairs: %d pairs joined\t%d bytes on the device" % (ji["n_records"], ji["device_bytes"]), file=sys.stderr)
+        if bam:
+            c = js.pair_counters
+            print("pairs: %d pairs joined\t%d orphans\t%d singles\t%d bytes on the device" %
+                  (c["pairs"], c["orphans"], c["singles"], ji["device_bytes"]), file=sys.stderr)
+        else:
+            print("pairs: %d pairs joined\t%d bytes on the device" % (ji["n_records"], ji["device_bytes"]), file=sys.stderr)
         sys.stderr.flush()
     return js, None
 

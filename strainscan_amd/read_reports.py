@@ -98,9 +98,10 @@ def _select_or_skip(select, skip, verb):
         return skip(RECORD_WAS_CUT % verb)
 
 
-# --pairs (StrainScan.apply_pairs turns it on; it needs -j and one of the reports below): the reports work on FRAGMENTS.  The
+# --pairs (StrainScan.apply_pairs turns it on; it needs -j or a BAM under -i, and one of the reports below): the reports work on FRAGMENTS.  The
 # device calls decide per record from the record's bytes alone, so they are handed a second resident set whose records are the
-# pairs -- record i of the first file, an N, record i of the second (db.resident_pairs) -- and run unchanged; no k-mer spans the
+# pairs -- record i of the first file, an N, record i of the second; for one BAM under -i, the mates its names and flags link
+# (db.resident_pairs) -- and run unchanged; -x on a BAM selects by fragment (_write_selected_bam); no k-mer spans the
 # N, so a fragment's hits are its mates' added up.  The scans of the identification keep the plain set.  _report_reads is where
 # every collect_* gets its set; _pairs_gate stands in front of the three hooks: where the pairs cannot be joined it says one line
 # and every per-read report of the run writes nothing (no silent fall-back to mates).
@@ -285,15 +286,16 @@ def collect_extract_reads(table, kdb, paths):
 
 def _write_selected_bam(table, kdb, labels, n_labels, label, ps, n, done):
     """extracted/<table>_<i>.bam for each BAM input i: its header and the kept records of the templates with a record of at least n
-    hits against kdb (of `label` when labels are given), selected and copied on the device (bam_extract; _EXTRACT_READS_LOCK held)."""
+    hits against kdb (of `label` when labels are given), selected and copied on the device (bam_extract; _EXTRACT_READS_LOCK held).
+    With --pairs the unit is the fragment: both records of a pair whose hits together reach n, and the line counts fragments."""
     out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
     os.makedirs(out_dir, exist_ok=True)
     for i, p in enumerate(ps):
         out = os.path.join(out_dir, "%s_%d.bam" % (table, i + 1))
-        c = _lib.bam_extract(p, kdb, n, out, labels, n_labels, label)
+        c = _lib.bam_extract(p, kdb, n, out, labels, n_labels, label, pairs=PAIRS["on"])
         EXTRACT_READS["files"].append(out)
-        print("extract_reads: %s\tN=%d\tfile %d\tkept %d\tselected on the device %d\twritten %d" %
-              (table, n, i + 1, c["kept"], c["selected"], c["written"]), file=sys.stderr)
+        print("extract_reads: %s\tN=%d\tfile %d\tkept %d\t%s on the device %d\twritten %d" %
+              (table, n, i + 1, c["kept"], "fragments selected" if PAIRS["on"] else "selected", c["selected"], c["written"]), file=sys.stderr)
     done.add(table)
     sys.stderr.flush()
 
