@@ -14,15 +14,14 @@
 //      64-bit hashes over the bytes and the length, and sel[r] = hits >= N.  ExclusiveSum + compact_kernel + hipcub SortPairs: the
 //      digests of the selected records, sorted by the first hash.  template_len_kernel: a kept record is written when it is
 //      selected or a binary search finds its digest (both hashes) among them; out_len[r] = 4 + block_size, else 0
-//   5  a 64-bit ExclusiveSum of out_len -> offsets; record_gather_kernel: sixteen lanes per written record walk the 16-byte
-//      aligned pieces of the destination (the shape of gather_kernel, ss_select.hip): one load clamped into the stream, one
-//      aligned 16-byte store where the piece is all the record's, byte stores at the edges it shares with its neighbours
+//   5  a 64-bit ExclusiveSum of out_len -> offsets; record_gather_kernel: sixteen lanes per written record copy it in 16-byte
+//      aligned pieces of the destination (the piece copy, ss_piece_copy.h)
 //   6  the result to the host through two pinned buffers, chunk by chunk; ss_bgzf_write compresses the members on host threads.
 // Records that the loader does not keep (0x100, 0x800, no bases) are never written, whatever their name.
 // ss_bam_select_pairs / ss_bam_extract_pairs (`--pairs`): the same path with the mate link of ss_bam_pairs.hip in the place of step
 // 4 -- a kept record is written iff its hits and its mate's together reach N, and nothing is joined by name after that.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  No device-wide barrier inside a kernel.
-#include "ss_scan_dev.h"
+#include "ss_piece_copy.h"
 #include "ss_support.h"
 
 #include <hipcub/hipcub.hpp>
@@ -32,16 +31,15 @@
 #include <unistd.h>
 
 #include <cerrno>
-#include <chrono>
 #include <string>
 #include <thread>
 
-namespace {
+using namespace ss::dev;
+using ss::Clock;
+using ss::grid_for;
+using ss::ms_since;
 
-__device__ __forceinline__ uint32_t ld32d(const uint8_t *s, uint64_t p)
-{
-    return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24;
-}
+namespace {
 
 // One lane per record r <= n_rec (entry n_rec closes the sums).  A kept record: (h1, h2) = the digest of its name (bam_name_digest,
 // ss_support.h); sel = its hits reach min_hits.  A record that is not kept: sel = 0 and a digest nobody asks for.
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(256) void template_len_kernel(const uint8_t *__rest
                 }
                 for (; lo < n_sel && k1[lo] == a && !w; lo++) w = k2[lo] == b;
             }
-            if (w) { len = 4ull + ld32d(s, rec[r]); cnt = 1; }
+            if (w) { len = 4ull + ss::ld32_le(s, rec[r]); cnt = 1; }
         }
         out_len[r] = len;
     }
@@ -104,11 +102,8 @@ __global__ __launch_bounds__(256) void template_len_kernel(const uint8_t *__rest
     if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&tot[0], cnt);
 }
 
-// Sixteen lanes per record; src holds n >= 16 bytes and every written record lies inside them; dst is 16-byte aligned.  A lane takes
-// one aligned 16-byte piece of the destination at a time.  The source bytes that belong there begin at `base`, any alignment, and
-// at an edge piece partly outside the record, even outside the stream: so the 16 bytes are fetched from `base` clamped into the
-// stream, ONE load, and moved to their places with a 128-bit shift.  A piece that is all the record's is one aligned 16-byte store;
-// a piece it shares with a neighbour stores the record's own bytes one by one, and not a byte more.
+// Sixteen lanes per record; src holds n >= 16 bytes and every written record lies inside them; dst is 16-byte aligned.  The piece
+// copy of ss_piece_copy.h, the record's bytes as they are.
 __global__ __launch_bounds__(256) void record_gather_kernel(const uint8_t *__restrict__ src, uint64_t n, const uint64_t *__restrict__ rec,
                                                             const unsigned long long *__restrict__ out_len,
                                                             const unsigned long long *__restrict__ out_off, uint64_t n_rec,
@@ -119,38 +114,13 @@ __global__ __launch_bounds__(256) void record_gather_kernel(const uint8_t *__res
     const uint64_t ol = out_len[r];
     if (!ol) return;                                                    // not written
     const uint64_t D = out_off[r], S = rec[r];
-    const uint64_t A0 = D & ~15ull, n_pieces = (D + ol - A0 + 15u) >> 4;
-    for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
-        const uint64_t a = A0 + 16u * c;
-        const uint64_t lo = a > D ? a : D, hi = a + 16u < D + ol ? a + 16u : D + ol;      // the record's bytes of this piece: [lo, hi)
-        const int64_t base = (int64_t)S + ((int64_t)a - (int64_t)D);    // source position of the piece's byte 0
-        const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
-        uint4 v;
-        __builtin_memcpy(&v, src + q, 16);
-        unsigned __int128 x;
-        __builtin_memcpy(&x, &v, 16);
-        const int shift = (int)(base - q);                              // byte j of the piece is byte j + shift of what was fetched
-        if (shift >= 16 || shift <= -16) x = 0;                         // (never: a byte of the record lies in the piece)
-        else if (shift > 0) x >>= 8 * shift;
-        else if (shift < 0) x <<= 8 * -shift;
-        if (lo == a && hi == a + 16u) {
-            __builtin_memcpy(&v, &x, 16);
-            *reinterpret_cast<uint4 *>(dst + a) = v;
-        } else {
-            const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
-#pragma unroll
-            for (uint32_t j = 0; j < 16u; j++)
-                if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
-        }
-    }
+    write_span(dst, D, D + ol, threadIdx.x & 15u,
+               [&](uint64_t a, uint64_t, uint64_t) { return fetch16(src, n, (int64_t)S + ((int64_t)a - (int64_t)D)); });
 }
 
 std::atomic<uint64_t> g_bam_extract_calls{0};
 std::mutex g_timing_mu;
 double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the last ss_bam_extract (ms): ss_bam_extract_timing
-
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 // What the selection leaves: the written records back to back in d_out (big_malloc'ed, out_cap; nullptr when nothing is written)
 struct Selection {
@@ -177,14 +147,7 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     int rc = ss::bam_records_flat_dev(d_stream, n, h_stream, seg, &flat, &flat_len, &flat_cap, &recs);
     if (rc) return rc;
     const hipStream_t st = ss::l2s::stream();
-    struct Owned {                                                      // what bam_to_flat_dev handed over
-        ss::BamRecords &r; char *&flat; uint64_t &cap;
-        ~Owned()
-        {
-            r.release();
-            if (flat) ss::big_put(flat, cap);
-        }
-    } owned{recs, flat, flat_cap};
+    const ss::BamFlatOwner owned{recs, flat, flat_cap};
     const uint64_t n_rec = recs.n_rec, kept = recs.kept;
     out->hdr_end = recs.hdr_end;
     out->counters[0] = n_rec;
@@ -227,7 +190,7 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     uint32_t *d_sel = nullptr, *d_sidx = nullptr;
     void *d_tmp = nullptr;
     const int items = (int)(n_rec + 1);                                 // (n_rec < 0x7FFFFFF0: bam_to_flat_dev)
-    const unsigned g1 = (unsigned)((n_rec + 1 + 255) / 256);
+    const unsigned g1 = grid_for(n_rec + 1);
     SS_HIP(scratch.get((void **)&d_sel, (n_rec + 1) * 4));
     SS_HIP(scratch.get((void **)&d_sidx, (n_rec + 1) * 4));
     SS_HIP(scratch.get((void **)&d_len, (n_rec + 1) * 8));
@@ -291,7 +254,7 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     t0 = Clock::now();
     if (n < 16 || total > n) return SS_EHIP;                            // (a record is 36 bytes and more; the records are the stream's)
     if (ss::big_malloc((void **)&out->d_out, ss_reads::padded(total), &out->out_cap) != hipSuccess) { out->d_out = nullptr; return SS_ENOMEM; }
-    hipLaunchKernelGGL(record_gather_kernel, dim3((unsigned)((n_rec * 16u + 255u) / 256u)), dim3(256), 0, st, s, n, (const uint64_t *)recs.d_rec,
+    hipLaunchKernelGGL(record_gather_kernel, dim3(grid_for(n_rec * 16u)), dim3(256), 0, st, s, n, (const uint64_t *)recs.d_rec,
                        (const unsigned long long *)d_len, (const unsigned long long *)d_off, n_rec, (uint8_t *)out->d_out);
     SS_HIP(hipGetLastError());
     SS_HIP(ss::l2s::sync());

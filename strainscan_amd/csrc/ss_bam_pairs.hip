@@ -16,19 +16,21 @@
 //      It writes mate[] and counts pairs, orphans and the records of violating groups
 //   5  length_kernel: a fragment's LEADER is its earlier record; lead[r] and the fragment's bytes -> two ExclusiveSums (the
 //      lengths in 64 bits): each fragment's index and byte offset; leader_list_kernel: fragment -> its leader
-//   6  join_kernel: sixteen lanes per fragment walk the 16-byte aligned pieces of the destination (the shape of join_kernel,
-//      ss_pairs.hip): per piece and mate ONE 16-byte load at the source position of the piece's byte 0, clamped into the flat block,
-//      and a 128-bit shift; the 'N' and the '\n' are put into the piece; a piece wholly inside the fragment is one aligned 16-byte
-//      store, an edge piece stores the fragment's own bytes one by one.  Both mates are read from the one flat block.
+//   6  join_kernel: sixteen lanes per fragment write it in 16-byte aligned pieces of the destination (the piece copy,
+//      ss_piece_copy.h): per piece a masked fetch for either mate, both from the one flat block, and the 'N' and the '\n' put in.
 // Every per-read kernel decides per record from the record's bytes, so all of them run unchanged on the set this makes.
 // ss_bam_select_pairs / ss_bam_extract_pairs (ss_bam_extract.hip) take steps 2 to 4 and fragment_len_kernel from here.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  Plain launches, no device-wide barrier inside a kernel.  All
 // byte offsets are 64-bit; record counts are below 0x7FFFFFF0 (bam_to_flat_dev).
+#include "ss_piece_copy.h"
 #include "ss_support.h"
 
 #include <hipcub/hipcub.hpp>
 
-#include <chrono>
+using namespace ss::dev;
+using ss::Clock;
+using ss::grid_for;
+using ss::ms_since;
 
 namespace {
 
@@ -142,33 +144,6 @@ __global__ __launch_bounds__(256) void leader_list_kernel(const uint32_t *__rest
     if (r < n_rec && lead[r]) leader[fidx[r]] = (uint32_t)r;
 }
 
-// bytes [j0, j1) of a 16-byte piece, 0 <= j0 < j1 <= 16
-__device__ __forceinline__ unsigned __int128 piece_mask(uint32_t j0, uint32_t j1)
-{
-    return (~(unsigned __int128)0 >> (8u * (16u - (j1 - j0)))) << (8u * j0);
-}
-
-// the 16 bytes that stand at source positions [base, base + 16) of a block of n >= 16 bytes: one load at base clamped into the
-// block and a shift; positions outside the block read as anything
-__device__ __forceinline__ unsigned __int128 fetch16(const uint8_t *__restrict__ src, uint64_t n, int64_t base)
-{
-    const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
-    uint4 v;
-    __builtin_memcpy(&v, src + q, 16);
-    unsigned __int128 x;
-    __builtin_memcpy(&x, &v, 16);
-    const int64_t shift = base - q;                                     // byte j of the piece is byte j + shift of what was fetched
-    if (shift >= 16 || shift <= -16) x = 0;
-    else if (shift > 0) x >>= 8 * (int)shift;
-    else if (shift < 0) x <<= 8 * (int)-shift;
-    return x;
-}
-
-__device__ __forceinline__ unsigned __int128 with_byte(unsigned __int128 x, uint32_t j, char c)
-{
-    return (x & ~((unsigned __int128)0xFFu << (8u * j))) | ((unsigned __int128)(uint8_t)c << (8u * j));
-}
-
 // Sixteen lanes per fragment; flat holds n >= 16 bytes, dst is 16-byte aligned.  Fragment g of leader r begins at foff[r]:
 // [D, J) mate 1's letters (none for an orphan of role 2), 'N' at J, [M2, E - 1) mate 2's (none for a single and an orphan of role
 // 0 or 1), '\n' at E - 1.
@@ -191,32 +166,12 @@ __global__ __launch_bounds__(256) void join_kernel(const uint8_t *__restrict__ f
         s1 = off[r], len1 = bases_of(off, r);
     }
     const uint64_t D = foff[r], J = D + len1, M2 = J + 1u, L = M2 + len2, E = L + 1u;      // the fragment: [D, E); '\n' at L
-    const uint64_t A0 = D & ~15ull, n_pieces = (E - A0 + 15u) >> 4;
-    for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
-        const uint64_t a = A0 + 16u * c;
-        const uint64_t lo = a > D ? a : D, hi = a + 16u < E ? a + 16u : E;        // the fragment's bytes of this piece: [lo, hi)
-        unsigned __int128 x = 0;
-        if (lo < J) {                                                   // mate 1: [D, J)
-            const uint64_t h = hi < J ? hi : J;
-            x = fetch16(flat, n, (int64_t)s1 + ((int64_t)a - (int64_t)D)) & piece_mask((uint32_t)(lo - a), (uint32_t)(h - a));
-        }
-        if (hi > M2 && lo < L) {                                        // mate 2: [M2, L)
-            const uint64_t l = lo > M2 ? lo : M2, h = hi < L ? hi : L;
-            if (l < h) x |= fetch16(flat, n, (int64_t)s2 + ((int64_t)a - (int64_t)M2)) & piece_mask((uint32_t)(l - a), (uint32_t)(h - a));
-        }
+    write_span(dst, D, E, threadIdx.x & 15u, [&](uint64_t a, uint64_t lo, uint64_t hi) {
+        piece_t x = masked_fetch16(flat, n, s1, D, J, a, lo, hi) | masked_fetch16(flat, n, s2, M2, L, a, lo, hi);
         if (J >= lo && J < hi) x = with_byte(x, (uint32_t)(J - a), 'N');
         if (L >= lo && L < hi) x = with_byte(x, (uint32_t)(L - a), '\n');
-        if (lo == a && hi == a + 16u) {
-            uint4 v;
-            __builtin_memcpy(&v, &x, 16);
-            *reinterpret_cast<uint4 *>(dst + a) = v;
-        } else {
-            const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
-#pragma unroll
-            for (uint32_t j = 0; j < 16u; j++)
-                if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
-        }
-    }
+        return x;
+    });
 }
 
 // One lane per record r <= n_rec: out_len[r] = 4 + block_size when the hits of kept record r's fragment reach min_hits
@@ -235,31 +190,18 @@ __global__ __launch_bounds__(256) void fragment_len_kernel(const uint8_t *__rest
             const uint64_t h = (uint64_t)hits[kidx[r]] + (m != NO_MATE ? (uint64_t)hits[kidx[m]] : 0u);
             if (h >= min_hits) {
                 const uint64_t p = rec[r];
-                len = 4ull + ((uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24);
+                len = 4ull + ss::ld32_le(s, p);
                 written = 1;
                 frags = m == NO_MATE || m > r ? 1 : 0;
             }
         }
         out_len[r] = len;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        written += __shfl_xor(written, d, 64);
-        frags += __shfl_xor(frags, d, 64);
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        if (written) atomicAdd(&tot[0], written);
-        if (frags) atomicAdd(&tot[1], frags);
-    }
+    add_selected(written, frags, tot);      // (no fragment without a written record)
 }
 
 std::mutex g_timing_mu;
 double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the last ss_reads_load_pairs_bam (ms): ss_bam_pairs_timing
-
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
-unsigned grid_for(uint64_t items) { return (unsigned)((items + 255u) / 256u); }
 
 // steps 1 (second half) to 6 on a stream that lies on the device; ms[1..6]
 int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uint64_t counters[6], double *ms)
@@ -271,14 +213,7 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
     uint64_t flat_len = 0, flat_cap = 0;
     int rc = ss::bam_records_flat_dev(ds.d, ds.n, ds.h, ds.seg, &flat, &flat_len, &flat_cap, &recs);
     if (rc) return rc;
-    struct Owned {
-        ss::BamRecords &r; char *&flat; uint64_t &cap;
-        ~Owned()
-        {
-            r.release();
-            if (flat) ss::big_put(flat, cap);
-        }
-    } owned{recs, flat, flat_cap};
+    const ss::BamFlatOwner owned{recs, flat, flat_cap};
     ms[1] = ms_since(t0);
     const hipStream_t st = ss::l2s::stream();
     const uint64_t n_rec = recs.n_rec, kept = recs.kept;
@@ -290,10 +225,9 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
     if (counters[5]) return SS_EIO;
     const uint64_t n_frag = kept - counters[2];
     const uint64_t total = (flat_len - kept) + 2u * n_frag;
-    ss_reads *S = new (std::nothrow) ss_reads();
-    if (!S) return SS_ENOMEM;
-    S->n_records = n_frag;
-    S->n_bases = total - n_frag;
+    const char *const who = "ss_reads_join_pairs_bam";
+    ss_reads *S = nullptr;
+    uint8_t *slab = nullptr;
     if (n_frag) {
         // 5. leaders, lengths, offsets
         t0 = Clock::now();
@@ -304,8 +238,7 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
         size_t tb1 = 0, tb2 = 0;
         unsigned long long tot = 0;
         uint32_t nf = 0;
-        ss_reads::Slab sl;
-        auto fail = [&](hipError_t e) { if (e != hipSuccess) ss::set_last_error("ss_reads_join_pairs_bam", __FILE__, __LINE__, e); return e != hipSuccess; };
+        const ss::HipFail fail{who};
         bool bad = fail(scratch.get((void **)&d_lead, (n_rec + 1) * 4)) || fail(scratch.get((void **)&d_fidx, (n_rec + 1) * 4)) ||
                    fail(scratch.get((void **)&d_flen, (n_rec + 1) * 8)) || fail(scratch.get((void **)&d_foff, (n_rec + 1) * 8)) ||
                    fail(scratch.get((void **)&d_leader, n_frag * 4)) ||
@@ -333,22 +266,18 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
         // 6. the slab
         t0 = Clock::now();
         if (!bad) {
-            sl.used = ss_reads::padded(total);
-            if (ss::big_malloc((void **)&sl.d, sl.used, &sl.cap) != hipSuccess) { delete S; return SS_ENOMEM; }
-            S->slabs.push_back(sl);
-            S->device_bytes = sl.cap;
-            S->n_blocks = 1;
-            S->first_slab = sl.cap;
-            bad = fail(ss::l2s::set(sl.d + total, '\n', sl.used - total));
-        }
-        if (!bad) {
+            rc = ss::one_slab_set(n_frag, total, who, &S, &slab);
+            if (rc) return rc;
             hipLaunchKernelGGL(join_kernel, dim3(grid_for(n_frag * 16u)), dim3(256), 0, st, (const uint8_t *)flat, ss_reads::padded(flat_len),
                                (const uint64_t *)recs.d_off, (const uint32_t *)d_leader, (const uint32_t *)d_mate, (const uint8_t *)d_role,
-                               (const unsigned long long *)d_foff, n_frag, (uint8_t *)sl.d);
+                               (const unsigned long long *)d_foff, n_frag, slab);
             bad = fail(hipGetLastError());
         }
         bad = fail(ss::l2s::sync()) || bad;
         if (bad) { ss_reads_destroy(S); return SS_EHIP; }
+    } else {
+        rc = ss::one_slab_set(0, 0, who, &S, &slab);
+        if (rc) return rc;
     }
     if (order) {
         rc = ss_reads_order(S);

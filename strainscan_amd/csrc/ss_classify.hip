@@ -26,9 +26,9 @@
 // scratch of the call.  ss_reads_classify copies them back.
 //
 // ss_reads_select_class (`--extract_class`) runs classify_records once and then, per listed clade:
-//   5. select_class_len_kernel: one thread per record, out_len[rec] = the record's class lies in the clade ? length + 1 : 0 -- the
-//      shape of select_len_kernel (ss_select.hip) with the Euler interval of the clade's node in the place of the hit threshold;
-//      clade 0 is class 0.  gather_records (ss_select.hip) then makes the new set from out_len[], which is reset for the next clade.
+//   5. select_class_len_kernel: one thread per record, out_len[rec] = the record's class lies in the clade ? length + 1 : 0 --
+//      select_len_kernel (ss_select.hip) with the Euler interval of the clade's node in the place of the hit threshold, the span
+//      rule and the totals shared with it (record_span, add_selected: ss_scan_dev.h); clade 0 is class 0.  gather_records (ss_select.hip) then makes the new set from out_len[], which is reset for the next clade.
 // The classes never leave the device, and a second clade costs a length pass, a prefix sum and a gather.
 #include "ss_scan_dev.h"
 #include "ss_support.h"
@@ -107,16 +107,10 @@ struct ClassArgs {
     uint32_t *long_list;                        // [n_rec] records of this slab (slab-relative) left to the general pass
 };
 
-__device__ __forceinline__ bool span_of(const ClassArgs &A, uint64_t g, uint64_t *s, uint64_t *e)
+// record g of the slab (every record has a span; one that has none, or a wild one, reads nothing)
+__device__ __forceinline__ RecordSpan span_of(const ClassArgs &A, uint64_t g)
 {
-    if (A.slot) {
-        *s = g * (uint64_t)A.slot;
-        *e = *s + A.fixed_len;
-    } else {
-        *s = A.start[A.rec0 + g];
-        *e = A.end[A.rec0 + g];
-    }
-    return *s < *e && *e <= A.n;            // (every record has a span; one that has none, or a wild one, reads nothing)
+    return record_span(A.slot != 0u, g, A.rec0, A.start, A.end, A.slot, A.fixed_len, A.n);
 }
 
 __global__ __launch_bounds__(256) void classify_kernel(const ClassArgs A, const Forest F)
@@ -131,9 +125,10 @@ __global__ __launch_bounds__(256) void classify_kernel(const ClassArgs A, const 
     }
     unsigned long long ties = 0;
     for (uint64_t g = (uint64_t)blockIdx.x * 256u + t; g < A.n_rec; g += (uint64_t)gridDim.x * 256u) {
-        uint64_t s, e;
-        const bool ok = span_of(A, g, &s, &e);
-        bool over = ok && e - s > CLS_LONG;
+        const RecordSpan sp = span_of(A, g);
+        const uint64_t s = sp.s, e = sp.s + sp.len;
+        const bool ok = sp.ok;
+        bool over = ok && sp.len > CLS_LONG;
         uint32_t d = 0, cur = 0;                  // kept nodes; the one met last
         if (ok && !over) {
             for (uint64_t c = s & ~7ull; c < e && !over; c += 8u) {
@@ -218,8 +213,9 @@ __global__ __launch_bounds__(256) void classify_long_kernel(const ClassArgs A, c
     const uint64_t n_list = A.tot[1];
     for (uint64_t li = blockIdx.x; li < n_list; li += gridDim.x) {
         const uint64_t g = A.long_list[li];
-        uint64_t s, e;
-        if (!span_of(A, g, &s, &e)) continue;      // (uniform over the workgroup)
+        const RecordSpan sp = span_of(A, g);
+        if (!sp.ok) continue;                      // (uniform over the workgroup)
+        const uint64_t s = sp.s, e = sp.s + sp.len;
         for (uint64_t p = s + t; p < e; p += 256u) {
             const uint32_t v = A.pos_node[p];
             if (v) atomicAdd(&h[v], 1u);
@@ -265,8 +261,8 @@ __global__ __launch_bounds__(256) void classify_long_kernel(const ClassArgs A, c
 // records [rec0, rec0 + n_rec) of one slab: out_len = the bytes a record takes in the new slab (its length + '\n'; 0 when its
 // class is not in the clade), tot[0] += selected records, tot[1] += their bytes.  The clade of node c > 0 is the classes whose tin
 // lies in [lo, hi) = [tin[c], tout[c]); unclassified == true is the clade 0: class 0 alone.  fixed_len != 0: a packed slab, every record
-// that long.  A span that does not lie inside the slab's n positions selects nothing, as in select_len_kernel: classify_kernel gave
-// such a record no class, and the gather must not read outside the slab.
+// that long.  A span that does not lie inside the slab (record_span) selects nothing: classify_kernel gave such a record no class,
+// and the gather must not read outside the slab.
 __global__ __launch_bounds__(256) void select_class_len_kernel(const uint32_t *__restrict__ rec_class, const uint32_t *__restrict__ tin,
                                                                const unsigned long long *__restrict__ start, const unsigned long long *__restrict__ end,
                                                                uint64_t rec0, uint64_t n_rec, uint64_t n, uint32_t slot, uint32_t fixed_len,
@@ -275,8 +271,7 @@ __global__ __launch_bounds__(256) void select_class_len_kernel(const uint32_t *_
 {
     unsigned long long cnt = 0, bytes = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
-        const uint64_t r = rec0 + i;
-        const uint32_t c = rec_class[r];
+        const uint32_t c = rec_class[rec0 + i];
         unsigned long long len = 0;
         bool in = unclassified ? c == 0u : false;
         if (!unclassified && c != 0u && c <= n_nodes) {
@@ -284,23 +279,12 @@ __global__ __launch_bounds__(256) void select_class_len_kernel(const uint32_t *_
             in = lo <= t && t < hi;
         }
         if (in) {
-            bool ok = true;
-            if (fixed_len) {
-                ok = i * (unsigned long long)slot + fixed_len <= n;      // (span_of's test)
-                len = fixed_len;
-            } else {
-                const unsigned long long s = start[r], e = end[r];
-                ok = s < e && e <= n;
-                len = e - s;
-            }
-            if (ok) { len += 1ull; cnt++; bytes += len; }
-            else len = 0;
+            const RecordSpan sp = record_span(fixed_len != 0u, i, rec0, start, end, slot, fixed_len, n);
+            if (sp.ok) { len = sp.len + 1ull; cnt++; bytes += len; }
         }
-        out_len[r] = len;
+        out_len[rec0 + i] = len;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); bytes += __shfl_xor(bytes, d, 64); }
-    if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
+    add_selected(cnt, bytes, tot);
 }
 
 std::atomic<uint64_t> g_classify_calls{0}, g_select_class_calls{0};

@@ -15,19 +15,16 @@
 //   2. line_ends_kernel: the same walk writes line_end[i] = the position of the i-th '\n'.  Line i begins at line_end[i - 1] + 1.
 //   3. join_kernel.  No scan is needed for the output offsets: with start1[i] bytes of block 1 and start2[i] bytes of block 2 in
 //      front of pair i, and the 'N' taking the place of mate 1's '\n', the joined record i begins at start1[i] + start2[i] and
-//      the output holds exactly n1 + n2 bytes.  Sixteen lanes per fragment walk the 16-byte ALIGNED pieces of the destination
-//      (gather_kernel's scheme, ss_select.hip): per piece and source ONE 16-byte load at the source position of the piece's byte
-//      0, clamped into the source block, and a 128-bit shift; mate 1 brings its '\n' along, which the 'N' then replaces, mate 2
-//      brings the closing '\n'.  A piece wholly inside the fragment is one aligned 16-byte store, an edge piece stores the
-//      fragment's own bytes one by one: no lane writes a byte that is not its fragment's.  The clamp needs 16 bytes of source:
-//      a block below 16 bytes is joined from a private copy padded to 16.
+//      the output holds exactly n1 + n2 bytes.  Sixteen lanes per fragment write it in 16-byte aligned pieces of the destination
+//      (the piece copy, ss_piece_copy.h): per piece a masked fetch from either block; mate 1 brings its '\n' along, which the 'N'
+//      then replaces, mate 2 brings the closing '\n'.  A block below 16 bytes is joined from a private copy padded to 16.
 // All byte offsets are 64-bit.
 //
 // ss_reads_load_pairs brings each file to the device as ONE flat block in file order -- the text in memory (ss_input_text.h:
 // mapped, or inflated whole), cut at record boundaries by the chunk rule of the parallel parse where that applies, the chunks
 // turned into flat blocks by ss_fastx_to_flat on worker threads and put behind each other BY CHUNK INDEX -- and joins the two.
 // ss_reads_load and ingest_inputs are not involved.
-#include "ss_scan_dev.h"
+#include "ss_piece_copy.h"
 #include "ss_support.h"
 #include "ss_input_text.h"
 
@@ -85,28 +82,6 @@ __global__ __launch_bounds__(256) void line_ends_kernel(const uint8_t *__restric
         if (r < n_lines) line_end[r] = off + ((uint32_t)__ffs(nl) - 1u);
 }
 
-// bytes [j0, j1) of a 16-byte piece, 0 <= j0 < j1 <= 16
-__device__ __forceinline__ unsigned __int128 piece_mask(uint32_t j0, uint32_t j1)
-{
-    return (~(unsigned __int128)0 >> (8u * (16u - (j1 - j0)))) << (8u * j0);
-}
-
-// the 16 bytes that stand at source positions [base, base + 16) of a block of n >= 16 bytes: one load at base clamped into the
-// block and a shift; positions outside the block read as anything
-__device__ __forceinline__ unsigned __int128 fetch16(const uint8_t *__restrict__ src, uint64_t n, int64_t base)
-{
-    const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
-    uint4 v;
-    __builtin_memcpy(&v, src + q, 16);
-    unsigned __int128 x;
-    __builtin_memcpy(&x, &v, 16);
-    const int64_t shift = base - q;                                     // byte j of the piece is byte j + shift of what was fetched
-    if (shift >= 16 || shift <= -16) x = 0;
-    else if (shift > 0) x >>= 8 * (int)shift;
-    else if (shift < 0) x <<= 8 * (int)-shift;
-    return x;
-}
-
 // Sixteen lanes per fragment; n1, n2 >= 16, dst 16-byte aligned with room for n1 + n2 bytes.
 __global__ __launch_bounds__(256) void join_kernel(const uint8_t *__restrict__ src1, uint64_t n1, const unsigned long long *__restrict__ le1,
                                                    const uint8_t *__restrict__ src2, uint64_t n2, const unsigned long long *__restrict__ le2,
@@ -118,34 +93,10 @@ __global__ __launch_bounds__(256) void join_kernel(const uint8_t *__restrict__ s
     const uint64_t len1 = le1[g] - s1, len2 = le2[g] - s2;
     if (le1[g] >= n1 || le2[g] >= n2 || s1 > le1[g] || s2 > le2[g]) return;      // (never: the line index lies in its block)
     const uint64_t D = s1 + s2, J = D + len1, M2 = J + 1u, E = M2 + len2 + 1u;    // the fragment: [D, E); 'N' at J; mate 2 (+ '\n') from M2
-    const uint64_t A0 = D & ~15ull, n_pieces = (E - A0 + 15u) >> 4;
-    for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
-        const uint64_t a = A0 + 16u * c;
-        const uint64_t lo = a > D ? a : D, hi = a + 16u < E ? a + 16u : E;        // the fragment's bytes of this piece: [lo, hi)
-        unsigned __int128 x = 0;
-        if (lo <= J) {                                                  // mate 1 and the byte behind it: [D, J]
-            const uint64_t h1 = hi < M2 ? hi : M2;
-            x = fetch16(src1, n1, (int64_t)s1 + ((int64_t)a - (int64_t)D)) & piece_mask((uint32_t)(lo - a), (uint32_t)(h1 - a));
-        }
-        if (hi > M2) {                                                  // mate 2 and its '\n': [M2, E)
-            const uint64_t l2 = lo > M2 ? lo : M2;
-            x |= fetch16(src2, n2, (int64_t)s2 + ((int64_t)a - (int64_t)M2)) & piece_mask((uint32_t)(l2 - a), (uint32_t)(hi - a));
-        }
-        if (J >= a && J < a + 16u) {
-            const uint32_t j = (uint32_t)(J - a);
-            x = (x & ~((unsigned __int128)0xFFu << (8u * j))) | ((unsigned __int128)'N' << (8u * j));
-        }
-        if (lo == a && hi == a + 16u) {
-            uint4 v;
-            __builtin_memcpy(&v, &x, 16);
-            *reinterpret_cast<uint4 *>(dst + a) = v;
-        } else {
-            const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
-#pragma unroll
-            for (uint32_t j = 0; j < 16u; j++)
-                if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
-        }
-    }
+    write_span(dst, D, E, threadIdx.x & 15u, [&](uint64_t a, uint64_t lo, uint64_t hi) {
+        const piece_t x = masked_fetch16(src1, n1, s1, D, M2, a, lo, hi) | masked_fetch16(src2, n2, s2, M2, E, a, lo, hi);
+        return J >= a && J < a + 16u ? with_byte(x, (uint32_t)(J - a), 'N') : x;
+    });
 }
 
 // steps 1 and 2 for one block of n > 0 bytes: *d_le [*n_lines] in `scratch`
@@ -264,21 +215,13 @@ int ss_reads_join_pairs_dev(const void *flat1_dev, uint64_t n1, const void *flat
     if (m1 != m2) return SS_EIO;
     if (m1 > 0xFFFFFFFFull) return SS_ERANGE;
     ss::g_join_pairs_calls++;                                           // (a join: the blocks pair up)
-    ss_reads *S = new (std::nothrow) ss_reads();
-    if (!S) return SS_ENOMEM;
-    const uint64_t total = n1 + n2;
-    S->n_records = m1;
-    S->n_bases = total - m1;
-    if (total) {
-        ss_reads::Slab sl;
-        sl.used = ss_reads::padded(total);
-        if (ss::big_malloc((void **)&sl.d, sl.used, &sl.cap) != hipSuccess) { delete S; return SS_ENOMEM; }
-        S->slabs.push_back(sl);
-        S->device_bytes = sl.cap;
-        S->n_blocks = 1;
-        S->first_slab = sl.cap;
-        auto fail = [&](hipError_t e) { if (e != hipSuccess) ss::set_last_error("ss_reads_join_pairs_dev", __FILE__, __LINE__, e); return e != hipSuccess; };
-        bool bad = fail(ss::l2s::set(sl.d + total, '\n', sl.used - total));
+    const ss::HipFail fail{"ss_reads_join_pairs_dev"};
+    ss_reads *S = nullptr;
+    uint8_t *slab = nullptr;
+    rc = ss::one_slab_set(m1, n1 + n2, fail.who, &S, &slab);
+    if (rc != SS_OK) return rc;
+    if (slab) {
+        bool bad = false;
         // join_kernel's clamped loads need 16 bytes of source: a block below that is joined from a private copy padded to 16
         const uint8_t *src[2] = {b1, b2};
         uint64_t src_n[2] = {n1, n2};
@@ -292,7 +235,7 @@ int ss_reads_join_pairs_dev(const void *flat1_dev, uint64_t n1, const void *flat
         }
         if (!bad) {
             hipLaunchKernelGGL(join_kernel, dim3((unsigned)((m1 * 16u + 255u) / 256u)), dim3(256), 0, ss::l2s::stream(), src[0], src_n[0], d_le1, src[1],
-                               src_n[1], d_le2, m1, (uint8_t *)sl.d);
+                               src_n[1], d_le2, m1, slab);
             bad = fail(hipGetLastError());
         }
         bad = fail(ss::l2s::sync()) || bad;

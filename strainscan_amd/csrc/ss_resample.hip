@@ -82,8 +82,8 @@ __device__ __forceinline__ uint64_t record_key(const uint8_t *__restrict__ src, 
 
 // records [rec0, rec0 + n_rec) of one slab, one per lane: out_len = w * (length + 1), the bytes the record's w copies take in the
 // new slab; tot[0] += w, tot[1] += those bytes.  mix = 0x9E3779B97F4A7C15 * (replicate + 1) + 0xD6E8FEB86659FD93 * seed.
-// PACKED: record r - rec0 at position (r - rec0) * slot, fixed_len letters; else start[] / end[] say where, and a span that
-// does not lie inside the slab's n positions (none should: they come filled with ~0) draws nothing, as in select_len_kernel.
+// PACKED: record r - rec0 at position (r - rec0) * slot, fixed_len letters; else start[] / end[] say where.  A span that does not
+// lie inside the slab (record_span) draws nothing.
 template <bool PACKED>
 __global__ __launch_bounds__(256) void resample_len_kernel(const uint8_t *__restrict__ src, uint64_t n, const unsigned long long *__restrict__ start,
                                                            const unsigned long long *__restrict__ end, uint64_t rec0, uint64_t n_rec, uint32_t slot,
@@ -92,34 +92,20 @@ __global__ __launch_bounds__(256) void resample_len_kernel(const uint8_t *__rest
 {
     unsigned long long cnt = 0, bytes = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
-        const uint64_t r = rec0 + i;
-        uint64_t s, len;
-        bool ok;
-        if (PACKED) {
-            s = i * (uint64_t)slot;
-            len = fixed_len;
-            ok = len > 0 && s + len <= n;
-        } else {
-            const unsigned long long a = start[r], e = end[r];
-            s = a;
-            len = e - a;
-            ok = a < e && e <= n;
-        }
+        const RecordSpan sp = record_span(PACKED, i, rec0, start, end, slot, fixed_len, n);
         unsigned long long ol = 0;
-        if (ok) {
-            const uint32_t u = (uint32_t)(splitmix_finish(record_key<PACKED>(src, n, s, len) + mix) >> 32);
+        if (sp.ok) {
+            const uint32_t u = (uint32_t)(splitmix_finish(record_key<PACKED>(src, n, sp.s, sp.len) + mix) >> 32);
             uint32_t w = 0;
 #pragma unroll
             for (int k = 0; k < 13; k++) w += POISSON1_CDF[k] <= u ? 1u : 0u;
-            ol = (unsigned long long)w * (len + 1ull);
+            ol = (unsigned long long)w * (sp.len + 1ull);
             cnt += w;
             bytes += ol;
         }
-        out_len[r] = ol;
+        out_len[rec0 + i] = ol;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); bytes += __shfl_xor(bytes, d, 64); }
-    if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
+    add_selected(cnt, bytes, tot);
 }
 
 std::atomic<uint64_t> g_resample_calls{0};

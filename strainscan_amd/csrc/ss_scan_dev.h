@@ -237,6 +237,31 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v)
     return v;
 }
 
+// Where record i of a slab of n positions stands (the slab's records are rec0 + i in the numbering of the set): a packed slab's
+// record fills the first fixed_len positions of slot i, an ASCII slab's start[rec0 + i] .. end[rec0 + i] say (record_spans_kernel,
+// ss_select.hip; they come filled with ~0).  ok: the span is not empty and lies inside the slab.  Whoever reads a record's
+// positions asks here first, so that a wild span selects nothing, draws nothing, has no class -- and is never read.  The packed
+// test is always true on a well-formed slab, which holds n_rec whole slots; it is made all the same, for every caller alike.
+struct RecordSpan { uint64_t s, len; bool ok; };
+__device__ __forceinline__ RecordSpan record_span(bool packed, uint64_t i, uint64_t rec0, const unsigned long long *__restrict__ start,
+                                                  const unsigned long long *__restrict__ end, uint32_t slot, uint32_t fixed_len, uint64_t n)
+{
+    if (packed) {
+        const uint64_t s = i * (uint64_t)slot, len = fixed_len;
+        return {s, len, len > 0 && s + len <= n};
+    }
+    const uint64_t s = start[rec0 + i], e = end[rec0 + i];
+    return {s, e - s, s < e && e <= n};
+}
+
+// the close of a length pass: cnt records and their bytes, summed over the wave, added to tot[0] and tot[1]
+__device__ __forceinline__ void add_selected(unsigned long long cnt, unsigned long long bytes, unsigned long long *__restrict__ tot)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); bytes += __shfl_xor(bytes, d, 64); }
+    if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
+}
+
 // positions [s, s + 16) of a packed slab (s + 16 <= its positions) as the 16 letters its ASCII form holds inside a record: the
 // three 3-byte units around them, fetched as twelve bytes from the first unit on (a packed slab has 8 readable bytes behind its
 // last group, IN_PACKED, and its last unit but one begins 6 bytes before the end).  ss_select.hip's gather, ss_resample.hip's digest.

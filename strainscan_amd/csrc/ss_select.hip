@@ -18,17 +18,14 @@
 //      belong to no record.  A packed slab needs no kernel: start = rec * slot, length = L.
 //   3. select_len_kernel: out_len[rec] = hits >= min_hits ? length + 1 : 0, the selected records counted on the way; hipcub's
 //      64-bit ExclusiveSum turns the lengths into byte offsets in the new slab, which is allocated once (ss::big_malloc).
-//   4. gather_kernel: sixteen lanes per selected record copy its bytes and a '\n' to its offset.  Source and destination are
-//      unaligned in general.  The lanes walk the 16-byte ALIGNED pieces of the destination that the record touches: a piece that
-//      is all the record's is one 16-byte load (any alignment) and one aligned 16-byte store; the piece at either end, which
-//      the record shares with its neighbours, is the same one load and then byte stores of the record's own bytes -- no lane
-//      ever writes a byte that is not its record's.  From a packed slab a piece is three 3-byte units turned back into letters
-//      ("ACTG"[code], 'N' where invalid: what ss_reads_read_back writes).  All offsets are 64-bit.
+//   4. gather_kernel: sixteen lanes per selected record copy its bytes and a '\n' to its offset, in 16-byte aligned pieces of
+//      the destination (the piece copy, ss_piece_copy.h).  From a packed slab a piece is three 3-byte units turned back into
+//      letters ("ACTG"[code], 'N' where invalid: what ss_reads_read_back writes).
 // select_records is three steps (ss_support.h): record_spans_of (pass 2 and the scratch of pass 3), the length pass, and
 // gather_records (the prefix sum, the new slab, pass 4).  out_len[rec] may be any multiple of length + 1: the gather writes that
 // many copies of the record back to back.  ss_reads_resample (ss_resample.hip) is the same three steps with its own length pass,
 // a Poisson multiplicity in the place of the 0/1 choice.
-#include "ss_scan_dev.h"
+#include "ss_piece_copy.h"
 #include "ss_support.h"
 
 #include <hipcub/hipcub.hpp>
@@ -79,43 +76,29 @@ __global__ __launch_bounds__(256) void record_spans_kernel(const uint8_t *__rest
 }
 
 // records [rec0, rec0 + n_rec) of one slab: out_len = the bytes a record takes in the new slab (its length + '\n', 0 when it is
-// not selected); tot[0] += selected records, tot[1] += their bytes.  fixed_len != 0: a packed slab, every record that long.
-// A span that does not lie inside the slab's n positions (none should: start[] and end[] come filled with ~0) selects nothing,
-// so that the gather never reads outside the slab.
+// not selected); tot[0] += selected records, tot[1] += their bytes.  fixed_len != 0: a packed slab, every record that long in a
+// slot of `slot` positions.  A span that does not lie inside the slab (record_span) selects nothing, so that the gather never reads
+// outside the slab.
 __global__ __launch_bounds__(256) void select_len_kernel(const uint32_t *__restrict__ rec_hits, const unsigned long long *__restrict__ start,
                                                          const unsigned long long *__restrict__ end, uint64_t rec0, uint64_t n_rec, uint64_t n,
-                                                         uint32_t fixed_len, uint32_t min_hits, unsigned long long *__restrict__ out_len,
+                                                         uint32_t slot, uint32_t fixed_len, uint32_t min_hits, unsigned long long *__restrict__ out_len,
                                                          unsigned long long *__restrict__ tot)
 {
     unsigned long long cnt = 0, bytes = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
-        const uint64_t r = rec0 + i;
         unsigned long long len = 0;
-        if (rec_hits[r] >= min_hits) {
-            bool ok = true;
-            if (fixed_len) len = fixed_len;
-            else {
-                const unsigned long long s = start[r], e = end[r];
-                ok = s < e && e <= n;
-                len = e - s;
-            }
-            if (ok) { len += 1ull; cnt++; bytes += len; }
-            else len = 0;
+        if (rec_hits[rec0 + i] >= min_hits) {
+            const RecordSpan sp = record_span(fixed_len != 0u, i, rec0, start, end, slot, fixed_len, n);
+            if (sp.ok) { len = sp.len + 1ull; cnt++; bytes += len; }
         }
-        out_len[r] = len;
+        out_len[rec0 + i] = len;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); bytes += __shfl_xor(bytes, d, 64); }
-    if ((threadIdx.x & 63u) == 0 && cnt) { atomicAdd(&tot[0], cnt); atomicAdd(&tot[1], bytes); }
+    add_selected(cnt, bytes, tot);
 }
 
-// Sixteen lanes per record of one slab of n >= 16 positions (records [rec0, rec0 + n_rec)); dst is 16-byte aligned.  PACKED: src
-// is a packed slab, record r - rec0 at position (r - rec0) * slot; else src is an ASCII slab and start[] says where.
-// A lane takes one aligned 16-byte piece of the destination at a time.  The source bytes that belong there begin at `base`, any
-// alignment, and at an edge piece partly outside the record -- even outside the slab: so the 16 bytes are fetched from `base`
-// clamped into the slab, ONE load, and moved to their places with a 128-bit shift (every byte the piece needs lies in what was
-// fetched, because the record lies in the slab).  A piece that is all the record's (its '\n' included) is one aligned 16-byte
-// store; a piece it shares with a neighbour stores its own bytes one by one, and not a byte more.
+// Sixteen lanes per record of one slab of n >= 16 positions (records [rec0, rec0 + n_rec)) copy it and a '\n' behind it to dst,
+// 16-byte aligned, by the piece copy of ss_piece_copy.h.  PACKED: src is a packed slab, record r - rec0 at position
+// (r - rec0) * slot, and a piece is its letters (fetch16_packed); else src is an ASCII slab and start[] says where.
 // out_len[r] is a multiple of the record's length + 1: that many copies of it stand back to back from out_off[r] on (one for
 // ss_reads_select, 0..13 for ss_reads_resample), and the sixteen lanes write one after the other.
 template <bool PACKED>
@@ -131,37 +114,12 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint8_t *__restrict__
     if (!all) return;                                                   // not selected
     const uint64_t S = PACKED ? g * (uint64_t)slot : (uint64_t)start[r];
     const uint64_t len = PACKED ? (uint64_t)fixed_len : (uint64_t)end[r] - S, ol = len + 1u, D_end = out_off[r] + all;
-    for (uint64_t D = out_off[r]; D + ol <= D_end; D += ol) {
-        const uint64_t A0 = D & ~15ull, n_pieces = (D + ol - A0 + 15u) >> 4;
-        for (uint64_t c = threadIdx.x & 15u; c < n_pieces; c += 16u) {
-            const uint64_t a = A0 + 16u * c;
-            const uint64_t lo = a > D ? a : D, hi = a + 16u < D + ol ? a + 16u : D + ol;      // the record's bytes of this piece: [lo, hi)
+    for (uint64_t D = out_off[r]; D + ol <= D_end; D += ol)
+        write_span(dst, D, D + ol, threadIdx.x & 15u, [&](uint64_t a, uint64_t, uint64_t) {
             const int64_t base = (int64_t)S + ((int64_t)a - (int64_t)D);    // source position of the piece's byte 0
-            const int64_t q = base < 0 ? 0 : (base > (int64_t)n - 16 ? (int64_t)n - 16 : base);
-            uint4 v;
-            if (PACKED) v = packed_letters16(src, (uint64_t)q);
-            else __builtin_memcpy(&v, src + q, 16);
-            unsigned __int128 x;
-            __builtin_memcpy(&x, &v, 16);
-            const int shift = (int)(base - q);                              // byte j of the piece is byte j + shift of what was fetched
-            if (shift >= 16) x = 0;                                         // (only the '\n' behind a record that ends with the slab)
-            else if (shift > 0) x >>= 8 * shift;
-            else if (shift < 0) x <<= 8 * -shift;
-            if (D + len < a + 16u) {                                        // the byte behind the record
-                const uint32_t j = (uint32_t)(D + len - a);
-                x = (x & ~((unsigned __int128)0xFFu << (8u * j))) | ((unsigned __int128)0x0Au << (8u * j));
-            }
-            if (lo == a && hi == a + 16u) {
-                __builtin_memcpy(&v, &x, 16);
-                *reinterpret_cast<uint4 *>(dst + a) = v;
-            } else {
-                const uint64_t xl = (uint64_t)x, xh = (uint64_t)(x >> 64);
-#pragma unroll
-                for (uint32_t j = 0; j < 16u; j++)
-                    if (a + j >= lo && a + j < hi) dst[a + j] = (uint8_t)((j < 8u ? xl >> (8u * j) : xh >> (8u * (j - 8u))) & 0xFFu);
-            }
-        }
-    }
+            const piece_t x = PACKED ? fetch16_packed(src, n, base) : fetch16(src, n, base);
+            return D + len < a + 16u ? with_byte(x, (uint32_t)(D + len - a), '\n') : x;      // the byte behind the record
+        });
 }
 
 std::atomic<uint64_t> g_select_calls{0};
@@ -203,7 +161,7 @@ int ss::select_records(RecHits *rhp, const uint32_t *d_rec_hits, uint32_t min_hi
         if (!pt.n_rec) continue;
         const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 4096);
         hipLaunchKernelGGL(select_len_kernel, dim3(blocks), dim3(256), 0, ss::l2s::stream(), d_rec_hits, sp.d_start, sp.d_end, pt.rec_base, pt.n_rec,
-                           pt.n, pt.sl->packed ? pt.sl->L : 0u, min_hits, sp.d_len, sp.d_tot);
+                           pt.n, pt.sl->packed ? pt.sl->slot : 0u, pt.sl->packed ? pt.sl->L : 0u, min_hits, sp.d_len, sp.d_tot);
         SS_HIP(hipGetLastError());
     }
     return ss::gather_records(&rh, sp, "ss_reads_select", out);
@@ -258,34 +216,50 @@ int ss::gather_records(RecHits *rhp, RecSpans &sp, const char *who, ss_reads **o
         SS_HIP(ss::l2s::copy(tot, sp.d_tot, 16, hipMemcpyDeviceToHost));
     }
     unsigned long long *const d_off = sp.d_off;
-    ss_reads *S = new (std::nothrow) ss_reads();
-    if (!S) return SS_ENOMEM;
-    S->n_records = tot[0];
-    S->n_bases = tot[1] - tot[0];
-    if (tot[1]) {
-        // the new slab, allocated once from the total
-        ss_reads::Slab sl;
-        sl.used = ss_reads::padded(tot[1]);
-        if (ss::big_malloc((void **)&sl.d, sl.used, &sl.cap) != hipSuccess) { delete S; return SS_ENOMEM; }
-        S->slabs.push_back(sl);
-        S->device_bytes = sl.cap;
-        S->n_blocks = 1;
-        S->first_slab = sl.cap;
+    // the new slab, allocated once from the total
+    ss_reads *S = nullptr;
+    uint8_t *slab = nullptr;
+    const int rc = ss::one_slab_set(tot[0], tot[1], who, &S, &slab);
+    if (rc) return rc;
+    if (slab) {
         // 4. gather
-        auto fail = [&](hipError_t e) { if (e != hipSuccess) ss::set_last_error(who, __FILE__, __LINE__, e); return e != hipSuccess; };
-        bool bad = fail(ss::l2s::set(sl.d + tot[1], '\n', sl.used - tot[1]));
+        const ss::HipFail fail{who};
+        bool bad = false;
         for (const auto &pt : rh.parts) {
             if (bad || !pt.n_rec) continue;
             if (pt.n < 16) { bad = fail(hipErrorInvalidValue); continue; }      // (a slab is padded to a multiple of 16)
             const dim3 grid((unsigned)((pt.n_rec * 16u + 255u) / 256u));
             with_bool(pt.sl->packed, [&](auto packed) {
                 hipLaunchKernelGGL(gather_kernel<decltype(packed)::value>, grid, dim3(256), 0, st, (const uint8_t *)pt.sl->d, pt.n, sp.d_start, sp.d_end,
-                                   sp.d_len, d_off, pt.rec_base, pt.n_rec, pt.sl->slot, pt.sl->packed ? pt.sl->L : 0u, (uint8_t *)sl.d);
+                                   sp.d_len, d_off, pt.rec_base, pt.n_rec, pt.sl->slot, pt.sl->packed ? pt.sl->L : 0u, slab);
             });
             bad = fail(hipGetLastError());
         }
         bad = fail(ss::l2s::sync()) || bad;
         if (bad) { ss_reads_destroy(S); return SS_EHIP; }
+    }
+    *out = S;
+    return SS_OK;
+}
+
+int ss::one_slab_set(uint64_t n_records, uint64_t total, const char *who, ss_reads **out, uint8_t **slab)
+{
+    *out = nullptr;
+    *slab = nullptr;
+    ss_reads *S = new (std::nothrow) ss_reads();
+    if (!S) return SS_ENOMEM;
+    S->n_records = n_records;
+    S->n_bases = total - n_records;
+    if (total) {
+        ss_reads::Slab sl;
+        sl.used = ss_reads::padded(total);
+        if (ss::big_malloc((void **)&sl.d, sl.used, &sl.cap) != hipSuccess) { delete S; return SS_ENOMEM; }
+        S->slabs.push_back(sl);
+        S->device_bytes = sl.cap;
+        S->n_blocks = 1;
+        S->first_slab = sl.cap;
+        if (HipFail{who}(ss::l2s::set(sl.d + total, '\n', sl.used - total))) { ss_reads_destroy(S); return SS_EHIP; }
+        *slab = (uint8_t *)sl.d;
     }
     *out = S;
     return SS_OK;

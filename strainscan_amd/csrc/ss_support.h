@@ -4,6 +4,7 @@
 #include "ss_common.h"
 
 #include <algorithm>
+#include <chrono>
 
 namespace ss {
 
@@ -63,6 +64,40 @@ struct RecSpans {
 };
 int record_spans_of(RecHits *rh, RecSpans *sp);
 int gather_records(RecHits *rh, RecSpans &sp, const char *who, ss_reads **out);
+// The resident set that a gather or a join fills (ss_select.hip): n_records records, `total` bytes, in ONE slab allocated from the
+// total and padded to a multiple of 16, the '\n' of the padding enqueued.  *slab: where the caller writes the `total` bytes;
+// nullptr for total == 0, the valid empty set without a slab.  SS_ENOMEM: no memory; SS_EHIP: the fill failed.  Nothing is left then.
+int one_slab_set(uint64_t n_records, uint64_t total, const char *who, ss_reads **out, uint8_t **slab);
+// ... and what the calls that fill it do with a HIP error: fail(e) is true, and ss_last_error names `who`, when e is one
+struct HipFail {
+    const char *who;
+    bool operator()(hipError_t e) const
+    {
+        if (e != hipSuccess) set_last_error(who, __FILE__, __LINE__, e);
+        return e != hipSuccess;
+    }
+};
+
+// What ss_bam_extract.hip and ss_bam_pairs.hip share beside the kernels below.  BamFlatOwner: what bam_records_flat_dev handed
+// over, given back on every way out.
+struct BamFlatOwner {
+    BamRecords &recs;
+    char *&flat;
+    uint64_t &cap;
+    ~BamFlatOwner()
+    {
+        recs.release();
+        if (flat) big_put(flat, cap);
+    }
+};
+using Clock = std::chrono::steady_clock;
+inline double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+inline unsigned grid_for(uint64_t items) { return (unsigned)((items + 255u) / 256u); }      // workgroups of 256 threads, one item each
+// the little-endian 32-bit field at s + p (any alignment): a BAM record's block_size stands at its start
+__device__ __forceinline__ uint32_t ld32_le(const uint8_t *__restrict__ s, uint64_t p)
+{
+    return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24;
+}
 // The 128-bit digest of the read name of the BAM record at s + p (the bytes before the first NUL; l_read_name >= 1 and the bytes
 // lie inside the record: rec_len of ss_bam_dev.hip): *h1 = FNV-1a (64-bit) over the name's bytes and the eight bytes of its length,
 // *h2 = a rotate-xor-multiply hash over the same bytes, closed with the length and the splitmix64 finisher.  The one hash of

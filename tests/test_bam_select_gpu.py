@@ -151,6 +151,7 @@ def _streams(genome):
     s["header_only"] = []
     s["one_record_selected"] = [R("only", H())]
     s["one_record_not_selected"] = [R("only", C())]
+    s["first_record_alone"] = [R("first", H())] + [R("c%d" % i, C(80)) for i in range(40)]
     s["mates_adjacent"] = [R("a", C(), flag=0x41), R("a", H(), flag=0x81), R("b", C(), flag=0x41), R("b", C(), flag=0x81),
                            R("c", H(), flag=0x41), R("c", C(), flag=0x81)]
     far = [R("f%d" % i, C(80)) for i in range(520)]
@@ -193,7 +194,7 @@ def streams(genome):
     return _streams(genome)
 
 
-NAMES = ["header_only", "one_record_selected", "one_record_not_selected", "mates_adjacent", "mates_500_apart", "three_of_one_name", "names",
+NAMES = ["header_only", "one_record_selected", "one_record_not_selected", "first_record_alone", "mates_adjacent", "mates_500_apart", "three_of_one_name", "names",
          "decoys_share_a_selected_name", "no_bases", "reverse_strand", "iupac_and_n", "lengths_around_k_and_aux", "long_records",
          "all_from_the_table"]
 
@@ -209,6 +210,8 @@ def test_hand_built_streams_equal_the_model(L, table, streams, name, n):
         assert wc == [0, 0, 0, 0]
     if name == "one_record_selected":
         assert wc == [1, 1, 1, 1]
+    if name == "first_record_alone":
+        assert wc == [41, 41, 1, 1]                        # the copy's first piece begins with the stream's first record
     if name == "mates_500_apart":
         assert wc[2] == 1 and wc[3] == 2
     if name == "three_of_one_name":

@@ -84,8 +84,23 @@ def _blocks(n_lines, seed):
     return out
 
 
-@pytest.mark.parametrize("n_lines", LINE_COUNTS)
+def _cycle_blocks():
+    """2 166 lines whose lengths cycle through 0 .. 18 on either side, independently: every pair of lengths six times over"""
+    rs = np.random.RandomState(19)
+    n = 19 * 19 * 6
+    return [b"".join(r + b"\n" for r in _rand_lines(rs, lengths)) for lengths in ([i % 19 for i in range(n)], [(i // 19) % 19 for i in range(n)])]
+
+
+@pytest.mark.parametrize("n_lines", LINE_COUNTS + ("lengths_0_18",))
 def test_line_order_exact(L, dev, n_lines):
+    if n_lines == "lengths_0_18":
+        b1, b2 = _cycle_blocks()
+        _check_exact(L, dev, b1, b2)
+        l1, l2 = ([len(r) for r in pm.lines_of(b)] for b in (b1, b2))
+        starts = np.cumsum([0] + [a + b + 2 for a, b in zip(l1, l2)][:-1])
+        assert {(a, b) for a, b in zip(l1, l2)} == {(a, b) for a in range(19) for b in range(19)}
+        assert len({(int(s) % 16, a) for s, a in zip(starts, l1)}) == 16 * 19 and len({(int(s) % 16, b) for s, b in zip(starts, l2)}) == 16 * 19
+        return
     b1, b2 = _blocks(n_lines, 1000 + n_lines)
     want = _check_exact(L, dev, b1, b2)
     print("lines", n_lines, "bytes", len(b1), len(b2), "joined", len(want))

@@ -124,6 +124,25 @@ def _dense_block(material):
     return b"".join(g[s:s + 150] + b"\n" for s in rs.randint(0, 20000 - 150, size=531))
 
 
+def _cycle_block(material):
+    """2 074 reads cut from g[:30000], no N, their lengths cycling through 1 .. 33 and then 18 (which makes the bytes of a cycle's
+    selected records odd): against k17 every read of 17 bases and more has a hit (no shorter one can), and the selected records, 17 ..
+    33 bases back to back, come at every residue modulo 16, each length at each"""
+    rs = np.random.RandomState(8)
+    g = material["g"]
+    lengths = (list(range(1, 34)) + [18]) * 61
+    return b"".join(g[s:s + ln] + b"\n" for ln, s in zip(lengths, rs.randint(0, 30000 - 33, size=len(lengths))))
+
+
+def _one_short_length_block(material, ln):
+    """2 000 reads of ln bases cut from g[:30000], no N: one length, so the binned set is packed (ln >= 32: shorter reads are not
+    packed, so 31 bases, a record of two whole pieces, cannot be had from a packed slab).  32 is the shortest: 33 bytes a record,
+    every offset modulo 16; 47 makes 48 bytes a record: every record three whole pieces and never an edge piece"""
+    rs = np.random.RandomState(9 + ln)
+    g = material["g"]
+    return b"".join(g[s:s + ln] + b"\n" for s in rs.randint(0, 30000 - ln, size=2000))
+
+
 def _edges_block(material):
     """the first and the last record of the slab come from g[:20000]; the 300 between them (lengths 1 .. 200) from the junk"""
     rs = np.random.RandomState(6)
@@ -180,6 +199,10 @@ def read_sets(L, material, tmp_path_factory):
     out["ragged_1025"] = flat(_ragged_block(material, 1), False)
     out["all_dense"] = flat(_dense_block(material), False)
     out["edges"] = flat(_edges_block(material), False)
+    out["cycle_33"] = flat(_cycle_block(material), False)
+    out["packed_32"] = flat(_one_short_length_block(material, 32), True)
+    out["packed_47"] = flat(_one_short_length_block(material, 47), True)
+    assert out["cycle_33"].packed_slabs() == 0 and out["packed_32"].packed_slabs() >= 1 and out["packed_47"].packed_slabs() >= 1
     # two .fastq.gz files of 1 MB and more: the device path gives each a slab of its own -- record indices run on across slabs
     rs = np.random.RandomState(13)
     src = np.frombuffer(material["src"], np.uint8)
@@ -254,14 +277,28 @@ def test_select_equals_model(L, tables, read_sets, tname, sname, min_hits):
         sub.close()
 
 
-def test_everything_is_selected(L, tables, read_sets):
-    """reads cut from g[:20000] against the dense table at min_hits 1: the whole set, first and last record included"""
-    recs, per = _model(tables, read_sets, "k31_dense", "all_dense")
-    assert len(recs) == 531 and (per == 120).all()
-    sub = read_sets["all_dense"][0].select(tables["k31_dense"][0], 1)
+@pytest.mark.parametrize("tname,sname,n_rec,shortest", [("k31_dense", "all_dense", 531, 150), ("k17", "cycle_33", 61 * 34, 17),
+                                                        ("k17", "packed_32", 2000, 32), ("k17", "packed_47", 2000, 47)])
+def test_everything_is_selected(L, tables, read_sets, tname, sname, n_rec, shortest):
+    """reads cut from the table's stretch of g at min_hits 1: every record that holds a k-mer -- the whole set, first and last record
+    included; of the lengths 1 .. 33 those from k = 17 on, each a record of one or two pieces at every offset modulo 16 -- against
+    the read-back of the source"""
+    recs, per = _model(tables, read_sets, tname, sname)
+    k = tables[tname][1]
+    assert len(recs) == n_rec
+    assert (per == np.array([max(len(r) - k + 1, 0) for r in recs])).all()
+    want = [r for r in recs if len(r) >= k]
+    assert min(map(len, want)) == shortest and (sname == "cycle_33") == (len(want) < len(recs))
+    sub = read_sets[sname][0].select(tables[tname][0], 1)
     try:
-        assert sorted(p for p in sub.read_back().split(b"\n") if p) == sorted(recs)
-        assert sub.info()["n_records"] == 531 and sub.info()["n_bases"] == 531 * 150
+        text = sub.read_back()
+        assert sorted(p for p in text.split(b"\n") if p) == sorted(want)
+        assert len(text) % 16 == 0 and len(text.rstrip(b"\n")) + 1 == sum(map(len, want)) + len(want)      # one '\n' a record, then padding
+        assert sub.info()["n_records"] == len(want) and sub.info()["n_bases"] == sum(map(len, want))
+        if sname == "cycle_33":      # the source is in file order, so is the copy: each record begins where the lengths before it say
+            assert text.rstrip(b"\n") + b"\n" == b"".join(r + b"\n" for r in want)
+            starts = np.cumsum([0] + [len(r) + 1 for r in want[:-1]])
+            assert {(int(s) % 16, len(r)) for s, r in zip(starts, want)} == {(d, ln) for d in range(16) for ln in range(17, 34)}
     finally:
         sub.close()
 
