@@ -561,6 +561,55 @@ int ss_bam_select_pairs(const void *stream, uint64_t n, const ss_db *db, const u
 int ss_bam_extract_pairs(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
                          uint32_t min_hits, const char *out_path, uint64_t counters[4]);
 int ss_bam_pairs_timing(double out[8]);
+/* --------------------------------------------------------------------------------------------
+ * Tagged BAM (`--tag_bam`; ss_bam_tag.hip): a BAM stream written back with the class of every read as two aux tags.  The rule
+ * (tests/bam_tag_model.py restates it):
+ *   KEPT is the loader's rule (neither 0x100 nor 0x800, l_seq != 0); flat(r) is the loader's form of kept record r (reverse-
+ *   complemented for 0x10, codes turned to letters, the base-quality mask).  The CLASS of kept record r is that of
+ *   ss_reads_classify on flat(r) for the same row_node, n_nodes, parent and min_score; its SCORE is the largest score(v) of the
+ *   record, 0 when no hit has a node -- reported also where it is below min_score and the class is therefore 0.
+ *   The output body is EVERY record of the stream in file order.  A record that is not kept is copied byte for byte.  A kept
+ *   record is copied byte for byte with SS_BAM_TAG_BYTES = 14 bytes appended behind its last aux field, and its block_size field
+ *   is raised by 14:   t0 t1 'i' <int32 LE node_value[class]>   t2 t3 'i' <int32 LE score>
+ *   node_value[0..n_nodes] (host memory) is the caller's: the CLI passes the node ids of read_classes.tsv and -1 for class 0.
+ *   tags is four bytes, t0 t1 t2 t3; the CLI passes "snsc" (lower-case tags are reserved for end users by the SAM specification).
+ *   The body holds (n - hdr_end) + 14 x kept bytes; kept record r moves to rec[r] - hdr_end + 14 x (the kept records before it),
+ *   and so does a record that is not kept.
+ *   pairs != 0: the mates are linked and the fragments built as "Read pairs from a BAM" states (a pair is flat(m1) N flat(m2),
+ *   orphans and singles stand alone), from the same stream inside the call -- no second inflation; the fragments are classified and
+ *   BOTH records of a pair receive the fragment's class and score.  A violating name group: SS_EIO and no output.
+ *   Existing tags.  The aux fields of every kept record are walked by field -- tag[2], type[1], then the value: A c C 1 byte, s S
+ *   2, i I f 4, Z H up to and with a NUL, B subtype[1] count[4] and count x size(subtype) bytes.  A kept record that already has a
+ *   field named t0t1 or t2t3 would make an invalid BAM: SS_EIO, nothing is written, counters[3] = the number of such records.  A
+ *   byte pair that merely occurs inside a value is no field.  A field of unknown type, or one that runs past the record's end, is a
+ *   damaged stream: SS_EIO with counters[3] == 0 (also when other records bear a tag).  Records that are not kept are not walked.
+ * counters: [0] records, [1] kept == tagged, [2] kept records of a class != 0, [3] kept records that already bear one of the tags,
+ *   [4] fragments (== kept when pairs == 0), [5] fragments whose class came from a tie.  direct, node_hits, kmers: each NULL or
+ *   [n_nodes + 1], what ss_reads_classify returns for the same reads (under pairs: for the fragments).
+ * ss_bam_tag_stream: stream = an inflated BAM stream in HOST memory (from "BAM\1"); out: the body (no header), *out_len its bytes.
+ * ss_bam_tag_file: one BAM file (BGZF, plain gzip or uncompressed), brought to the device the way ss_bam_extract brings it ->
+ *   out_path, a BGZF BAM through ss_bgzf_write: the input's header from "BAM\1" to the first record, byte for byte, then the
+ *   body; zlib level 1 (SS_BAM_OUT_LEVEL=0..9 changes it); written to <out_path>.tmp and renamed; nothing is left on any error.
+ * ss_bam_tag_calls: calls of the two so far in this process ("flag off = not run").
+ * ss_bam_tag_timing: the last successful ss_bam_tag_file, host clock around its synchronised steps (ms): out[0] stream on the
+ *   device, [1] walk + decode, [2] mate link + join, [3] classify, [4] tag check + copy, [5] download, [6] compress + write, [7] the
+ *   whole call.
+ * SS_EINVAL: a NULL argument other than direct, node_hits and kmers; min_score == 0; n_nodes outside 1..SS_CLASS_NODES_MAX, a row
+ *   node or a parent above n_nodes, a cycle; a tag that is not [A-Za-z][A-Za-z0-9], two equal tags; a file that is not a BAM.
+ * SS_ERANGE: a flat table (k below 17); with *out_len and the counters set when cap is too small.  SS_EIO: as the rule states (the
+ *   counters are set), and a damaged stream.
+ * ------------------------------------------------------------------------------------------ */
+#define SS_BAM_TAG_BYTES 14
+int ss_bam_tag_stream(const void *stream, uint64_t n, const ss_db *db, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent,
+                      uint32_t min_score, const int32_t *node_value /* [n_nodes + 1] */, const char tags[4], int pairs, void *out,
+                      uint64_t cap, uint64_t *out_len, uint64_t counters[6], uint64_t *direct, uint64_t *node_hits,
+                      uint64_t *kmers /* each NULL, or [n_nodes + 1] */);
+int ss_bam_tag_file(const char *in_path, const ss_db *db, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent,
+                    uint32_t min_score, const int32_t *node_value /* [n_nodes + 1] */, const char tags[4], int pairs,
+                    const char *out_path, uint64_t counters[6], uint64_t *direct, uint64_t *node_hits,
+                    uint64_t *kmers /* each NULL, or [n_nodes + 1] */);
+int ss_bam_tag_calls(uint64_t *n);
+int ss_bam_tag_timing(double out[8]);
 /* The base-quality mask (jellyfish count -Q; off by default).  With a threshold q in 1..93 every decoder that turns a file or a
  * text into bases -- ss_reads_load, ss_scan_files, ss_scan_files_shard, ss_reader_open / ss_reader_next (a reader keeps the
  * threshold it was opened under), ss_fastx_to_flat, ss_bam_decode -- writes 'N' for a base whose quality is below it:

@@ -159,6 +159,15 @@ def add_arguments(ap, multi=False):
                          "clusters the tree walk identifies, each as class_C<id>_*).  Written with -x's rules: the original text in "
                          "file order, selected by content, a pair when either mate is in the class -- so a pair under "
                          "`unclassified` has at least one unclassified mate.  Needs FASTA/FASTQ input and one rank (default: off)")
+    ap.add_argument("--tag_bam", dest="tag_bam", action="store_true",
+                    help="With --classify_reads M and BAM input (every input a BAM): also write OUT/classified_<i>.bam per input "
+                         "file, the input written back with the class of every read as two aux tags -- sn:i:<node of "
+                         "read_classes.tsv, -1 for unclassified> and sc:i:<hits on the best path, reported below M too> behind the "
+                         "last tag of every record the loader keeps; secondary (0x100) and supplementary (0x800) records and "
+                         "records without bases are copied as they are.  A BGZF BAM (zlib level 1) with the input's header, "
+                         "every record in file order; `samtools view -d sn:<id>` gives the reads of one node.  With --pairs "
+                         "both mates carry the fragment's class.  A record that already bears sn or sc stops the file (remove "
+                         "them with `samtools view -x sn -x sc`).  Needs one rank (default: off)")
     ap.add_argument("--pairs", dest="pairs", action="store_true",
                     help="With -j (or a paired BAM under -i alone) and at least one of --read_support, -x N, --bootstrap B, "
                          "--classify_reads M: those reports (and "
@@ -190,6 +199,19 @@ def refuse_extract_class_alone(ap, args):
     input is opened)."""
     if args.extract_class and not args.classify_reads:
         ap.error("--extract_class needs --classify_reads M")
+
+
+def refuse_tag_bam_alone(ap, args):
+    """--tag_bam without --classify_reads has no classes to write, and tags go into BAM records only: the parser's error (exit
+    status 2; only the first bytes of the inputs are looked at, no read is touched)."""
+    if not args.tag_bam:
+        return
+    from . import _lib
+    if not args.classify_reads:
+        ap.error("--tag_bam needs --classify_reads M")
+    for p in (args.input_fq, args.input_fq2):
+        if p and _lib.input_kind(p) != "bam":
+            ap.error("--tag_bam needs BAM input, %s is not a BAM (per-read classes of FASTA/FASTQ reads are not written)" % p)
 
 
 def refuse_by_strain_alone(ap, args):
@@ -318,6 +340,14 @@ def apply_extract_class(items):
     read_reports.extract_class_reset(items)
 
 
+def apply_tag_bam(on, out_dir=None):
+    """--tag_bam (strainscan_amd.set_tag_bam): the tree scans from here on, which classify the reads, also write every BAM input
+    back as out_dir/classified_<i>.bam with each read's class as tags (read_reports.collect_read_classes).  stdout and the other
+    files are untouched."""
+    from . import read_reports
+    read_reports.tag_bam_reset(on, out_dir)
+
+
 def apply_pairs(on):
     """--pairs (strainscan_amd.set_pairs): the per-read reports collected from here on work on the set of joined pairs
     (db.resident_pairs) in the place of the resident reads; the scans do not.  stdout and the identification reports are
@@ -408,6 +438,7 @@ def main(argv=None):
     refuse_by_strain_alone(ap, args)
     refuse_extract_class_alone(ap, args)
     refuse_pairs_alone(ap, args)
+    refuse_tag_bam_alone(ap, args)
 
     fq_dir = args.input_fq
     fq2 = args.input_fq2 or ""
@@ -428,6 +459,7 @@ def main(argv=None):
     apply_bootstrap(args.bootstrap, args.bootstrap_seed)
     apply_classify_reads(args.classify_reads)
     apply_extract_class(args.extract_class)
+    apply_tag_bam(args.tag_bam, out_dir)
     apply_pairs(args.pairs)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)

@@ -19,6 +19,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, read_reports.BOOTSTRAP)
     strainscan_amd.set_classify_reads                         (`strainscan --classify_reads M`: reads per node of the cluster tree, read_reports.CLASSIFY_READS)
     strainscan_amd.set_extract_class                          (`strainscan --extract_class LIST`: the reads of chosen classes, read_reports.EXTRACT_CLASS)
+    strainscan_amd.set_tag_bam                                (`strainscan --tag_bam`: a BAM sample written back with each read's class as tags, read_reports.TAG_BAM)
     strainscan_amd.set_pairs                                  (`strainscan --pairs`: those reports on read pairs as fragments, read_reports.PAIRS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
@@ -105,6 +106,17 @@ def set_extract_class(names, out_dir=None):
     read_reports.extract_class_reset(items)
     if out_dir is not None:
         read_reports.EXTRACT_READS["dir"] = out_dir
+
+
+def set_tag_bam(on, out_dir=None):
+    """`strainscan --tag_bam` for callers of the functions above, with set_classify_reads on and a sample of BAM files: from here on
+    identify_cluster, where it classifies the reads, also writes input file i back as out_dir/classified_<i>.bam -- every record in
+    file order, each one the loader keeps with sn:i:<node id of read_classes.tsv, -1 for unclassified> and sc:i:<hits on the best
+    path> appended (_lib.bam_tag_file; with set_pairs both mates carry the fragment's class); out_dir defaults to the directory of
+    set_extract_reads, then to the current one.  Where no file can be written (FASTA/FASTQ input, several ranks, a record that
+    already bears sn or sc) one line on stderr says why.  Off by default; nothing runs while it is off."""
+    from . import read_reports
+    read_reports.tag_bam_reset(bool(on), out_dir)
 
 
 def set_pairs(on):

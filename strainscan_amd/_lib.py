@@ -163,6 +163,10 @@ SIGNATURES = {
     "ss_bam_select_pairs": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, u64, P(u64), P(u64)]),
     "ss_bam_extract_pairs": (i32, [cp, vp, vp, u32, u32, u32, cp, P(u64)]),
     "ss_bam_pairs_timing": (i32, [P(C.c_double)]),
+    "ss_bam_tag_stream": (i32, [vp, u64, vp, vp, u32, vp, u32, vp, cp, i32, vp, u64, P(u64), P(u64), vp, vp, vp]),
+    "ss_bam_tag_file": (i32, [cp, vp, vp, u32, vp, u32, vp, cp, i32, cp, P(u64), vp, vp, vp]),
+    "ss_bam_tag_calls": (i32, [P(u64)]),
+    "ss_bam_tag_timing": (i32, [P(C.c_double)]),
     "ss_set_min_base_qual": (i32, [i32]),
     "ss_get_min_base_qual": (i32, []),
     "ss_mask_counters": (i32, [P(u64)]),
@@ -1018,6 +1022,84 @@ def bam_pairs_timing():
     out = (C.c_double * 8)()
     check(lib().ss_bam_pairs_timing(out), "ss_bam_pairs_timing")
     return dict(zip(BAM_PAIRS_STEPS, (float(v) for v in out)))
+
+
+BAM_TAG_COUNTERS = ("records", "tagged", "classified", "already_tagged", "fragments", "ties")
+BAM_TAG_BYTES = 14      # SS_BAM_TAG_BYTES (strainscan_hip.h)
+BAM_TAG_STEPS = ("stream", "walk_decode", "mates_join", "classify", "check_copy", "download", "compress_write", "total")
+
+
+class BamTagError(SSError):
+    """SSError of bam_tag / bam_tag_file with `counters`, the dict of BAM_TAG_COUNTERS the call had filled: SS_EIO with
+    counters["already_tagged"] != 0 says how many kept records already bear one of the tags."""
+    def __init__(self, code, where, counters):
+        super().__init__(code, where)
+        self.counters = counters
+
+
+def _tag_args(kdb, row_node, parent, node_value, tags, want_counts):
+    rn = np.ascontiguousarray(row_node, np.uint32)
+    if rn.ndim != 1 or rn.size != kdb.n_rows:
+        raise ValueError("one node per row of the table (%d), not %r" % (kdb.n_rows, rn.shape))
+    par = np.ascontiguousarray(parent, np.uint32)
+    if par.ndim != 1 or par.size < 1:
+        raise ValueError("parent holds an entry per node and entry 0")
+    n = par.size - 1
+    val = np.ascontiguousarray(node_value, np.int32)
+    if val.ndim != 1 or val.size != n + 1:
+        raise ValueError("node_value holds an entry per node and entry 0 (%d), not %r" % (n + 1, val.shape))
+    tags = bytes(tags)
+    if len(tags) != 4:
+        raise ValueError("tags is four bytes: two tags of two")
+    counts = tuple(np.zeros(n + 1, np.uint64) if want_counts else None for _ in range(3))
+    return rn if rn.size else np.zeros(1, np.uint32), par, n, val, tags, counts
+
+
+def bam_tag(stream, kdb, row_node, parent, m, node_value, pairs=False, tags=b"snsc", want_counts=False):
+    """An inflated BAM stream (bytes from b'BAM\\1') with the class of every kept record appended as two aux tags
+    (ss_bam_tag_stream; tests/bam_tag_model.py restates it): every record behind the header in file order, a kept one with
+    tags[0:2]:i:node_value[class] and tags[2:4]:i:score behind its last aux field and its block_size raised by 14.  row_node,
+    parent and m as ReadSet.classify; node_value: one int32 per node and entry 0.  pairs: both mates of a pair carry the class of
+    the fragment.  -> (body bytes, dict of BAM_TAG_COUNTERS[, direct, node_hits, kmers]).  BamTagError (code SS_EIO) when a kept
+    record already bears one of the tags, has damaged aux fields, or a name group is no pair."""
+    stream = bytes(stream)
+    rn, par, n, val, tags, counts = _tag_args(kdb, row_node, parent, node_value, tags, want_counts)
+    cap = len(stream) + BAM_TAG_BYTES * (len(stream) // 36 + 1)      # (a record is 36 bytes and more)
+    out = np.empty(max(cap, 1), np.uint8)
+    ln, c = C.c_uint64(), (C.c_uint64 * 6)()
+    rc = lib().ss_bam_tag_stream(stream, len(stream), kdb.handle, ptr(rn), n, ptr(par), int(m), ptr(val), tags, int(bool(pairs)), ptr(out),
+                                 cap, C.byref(ln), c, *(ptr(a) if want_counts else None for a in counts))
+    cd = dict(zip(BAM_TAG_COUNTERS, (int(v) for v in c)))
+    if rc != SS_OK:
+        raise BamTagError(rc, "ss_bam_tag_stream", cd)
+    return (out[:ln.value].tobytes(), cd) + (counts if want_counts else ())
+
+
+def bam_tag_file(in_path, kdb, row_node, parent, m, node_value, out_path, pairs=False, tags=b"snsc", want_counts=False):
+    """One BAM file -> out_path, a BGZF BAM of the input's header and bam_tag's body (ss_bam_tag_file) -> dict of
+    BAM_TAG_COUNTERS[, direct, node_hits, kmers].  No file is left behind when it fails (BamTagError)."""
+    rn, par, n, val, tags, counts = _tag_args(kdb, row_node, parent, node_value, tags, want_counts)
+    c = (C.c_uint64 * 6)()
+    rc = lib().ss_bam_tag_file(os.fsencode(in_path), kdb.handle, ptr(rn), n, ptr(par), int(m), ptr(val), tags, int(bool(pairs)),
+                               os.fsencode(out_path), c, *(ptr(a) if want_counts else None for a in counts))
+    cd = dict(zip(BAM_TAG_COUNTERS, (int(v) for v in c)))
+    if rc != SS_OK:
+        raise BamTagError(rc, "ss_bam_tag_file", cd)
+    return (cd,) + counts if want_counts else cd
+
+
+def bam_tag_calls():
+    """Calls of ss_bam_tag_stream and ss_bam_tag_file so far in this process."""
+    n = C.c_uint64()
+    check(lib().ss_bam_tag_calls(C.byref(n)), "ss_bam_tag_calls")
+    return n.value
+
+
+def bam_tag_timing():
+    """The last bam_tag_file in milliseconds, step by step (ss_bam_tag_timing)."""
+    out = (C.c_double * 8)()
+    check(lib().ss_bam_tag_timing(out), "ss_bam_tag_timing")
+    return dict(zip(BAM_TAG_STEPS, (float(v) for v in out)))
 
 
 def bgzf_write(path, head, body, level=1):

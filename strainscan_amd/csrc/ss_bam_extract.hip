@@ -364,6 +364,8 @@ bool write_all(int fd, const uint8_t *p, size_t n)
 
 }  // namespace
 
+int ss::bam_download_chunks(const char *d_src, uint64_t total, char *dst) { return download_chunks(d_src, total, dst); }
+
 extern "C" {
 
 int ss_bam_extract_calls(uint64_t *n)

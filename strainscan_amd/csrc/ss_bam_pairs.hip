@@ -19,7 +19,8 @@
 //   6  join_kernel: sixteen lanes per fragment write it in 16-byte aligned pieces of the destination (the piece copy,
 //      ss_piece_copy.h): per piece a masked fetch for either mate, both from the one flat block, and the 'N' and the '\n' put in.
 // Every per-read kernel decides per record from the record's bytes, so all of them run unchanged on the set this makes.
-// ss_bam_select_pairs / ss_bam_extract_pairs (ss_bam_extract.hip) take steps 2 to 4 and fragment_len_kernel from here.
+// ss_bam_select_pairs / ss_bam_extract_pairs (ss_bam_extract.hip) take steps 2 to 4 and fragment_len_kernel from here;
+// ss_bam_tag.hip takes steps 2 to 4 (bam_mates_dev) and 5 to 6 (bam_join_dev), with the fragment index of every leader.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  Plain launches, no device-wide barrier inside a kernel.  All
 // byte offsets are 64-bit; record counts are below 0x7FFFFFF0 (bam_to_flat_dev).
 #include "ss_piece_copy.h"
@@ -215,22 +216,45 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
     if (rc) return rc;
     const ss::BamFlatOwner owned{recs, flat, flat_cap};
     ms[1] = ms_since(t0);
-    const hipStream_t st = ss::l2s::stream();
-    const uint64_t n_rec = recs.n_rec, kept = recs.kept;
     ss::PoolScratch scratch;
     uint32_t *d_mate = nullptr;
     uint8_t *d_role = nullptr;
     rc = ss::bam_mates_dev((const uint8_t *)ds.d, recs, scratch, &d_mate, &d_role, counters, ms + 2);
     if (rc) return rc;
     if (counters[5]) return SS_EIO;
-    const uint64_t n_frag = kept - counters[2];
+    const uint64_t n_frag = recs.kept - counters[2];
+    ss_reads *S = nullptr;
+    rc = ss::bam_join_dev(flat, flat_len, recs, scratch, d_mate, d_role, n_frag, &S, nullptr, ms + 5);      // steps 5 and 6
+    if (rc) return rc;
+    t0 = Clock::now();
+    if (order) {
+        rc = ss_reads_order(S);
+        if (rc != SS_OK) { ss_reads_destroy(S); return rc; }
+    }
+    if (n_frag) ms[6] += ms_since(t0);
+    *out = S;
+    return SS_OK;
+}
+
+}  // namespace
+
+namespace ss {
+
+int bam_join_dev(const char *flat, uint64_t flat_len, const BamRecords &recs, PoolScratch &scratch, const uint32_t *d_mate,
+                 const uint8_t *d_role, uint64_t n_frag, ss_reads **out, uint32_t **d_fidx_out, double *ms)
+{
+    const hipStream_t st = l2s::stream();
+    const uint64_t n_rec = recs.n_rec, kept = recs.kept;
     const uint64_t total = (flat_len - kept) + 2u * n_frag;
     const char *const who = "ss_reads_join_pairs_bam";
     ss_reads *S = nullptr;
     uint8_t *slab = nullptr;
+    int rc = SS_OK;
+    *out = nullptr;
+    if (d_fidx_out) *d_fidx_out = nullptr;
     if (n_frag) {
         // 5. leaders, lengths, offsets
-        t0 = Clock::now();
+        auto t0 = Clock::now();
         uint32_t *d_lead = nullptr, *d_fidx = nullptr, *d_leader = nullptr;
         unsigned long long *d_flen = nullptr, *d_foff = nullptr;
         void *d_tmp = nullptr;
@@ -262,7 +286,7 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
             ss::set_last_error("ss_reads_join_pairs_bam: the leaders are not the fragments", __FILE__, __LINE__, hipErrorUnknown);
             bad = true;
         }
-        ms[5] = ms_since(t0);
+        if (ms) ms[0] = ms_since(t0);
         // 6. the slab
         t0 = Clock::now();
         if (!bad) {
@@ -275,22 +299,15 @@ int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uin
         }
         bad = fail(ss::l2s::sync()) || bad;
         if (bad) { ss_reads_destroy(S); return SS_EHIP; }
+        if (ms) ms[1] = ms_since(t0);
+        if (d_fidx_out) *d_fidx_out = d_fidx;
     } else {
         rc = ss::one_slab_set(0, 0, who, &S, &slab);
         if (rc) return rc;
     }
-    if (order) {
-        rc = ss_reads_order(S);
-        if (rc != SS_OK) { ss_reads_destroy(S); return rc; }
-    }
-    if (n_frag) ms[6] = ms_since(t0);
     *out = S;
     return SS_OK;
 }
-
-}  // namespace
-
-namespace ss {
 
 int bam_mates_dev(const uint8_t *s, const BamRecords &recs, PoolScratch &scratch, uint32_t **d_mate, uint8_t **d_role, uint64_t counters[6],
                   double *ms)

@@ -23,7 +23,8 @@
 //      the workgroup reduces (score, node) with the same tie fold, and h[] is cleared by the positions that filled it.
 //   direct[] and node_hits[] are added up in LDS per workgroup where n_nodes + 1 <= CLS_LDS, with 64-bit global atomics otherwise.
 // All of this is classify_records, which leaves its results -- the classes of the records among them -- on the device, in the
-// scratch of the call.  ss_reads_classify copies them back.
+// scratch of the call.  ss_reads_classify copies them back.  ss_bam_tag.hip (`--tag_bam`) calls it through ss_support.h and asks
+// for the best score of every record as well (ClassArgs::rec_score, written only where it is not null: nobody here asks).
 //
 // ss_reads_select_class (`--extract_class`) runs classify_records once and then, per listed clade:
 //   5. select_class_len_kernel: one thread per record, out_len[rec] = the record's class lies in the clade ? length + 1 : 0 --
@@ -42,9 +43,8 @@ constexpr uint32_t CLS_LONG = 4096;      // positions a record may have there
 constexpr uint32_t CLS_LDS = 4096;       // nodes (+ 1) whose direct[] / node_hits[] a workgroup adds up in LDS
 constexpr uint32_t CLS_LONG_WGS = 64;    // workgroups (and dense h[] arrays) of the general pass
 
-struct Forest {                          // device arrays [n_nodes + 1]; entry 0: parent 0, depth 0, an empty interval
-    const uint32_t *parent, *depth, *tin, *tout;
-};
+using ss::Classified;
+using ss::Forest;
 
 __global__ __launch_bounds__(256) void slot_nodes_kernel(const uint16_t *__restrict__ row_node, const uint32_t *__restrict__ slot_of_row,
                                                          uint64_t n_rows, uint64_t n_slots, uint32_t *__restrict__ lo, uint32_t *__restrict__ hi)
@@ -104,6 +104,7 @@ struct ClassArgs {
     unsigned long long *direct, *node_hits;     // [n_nodes + 1]
     unsigned long long *tot;                    // [0] records whose class came from a tie, [1] records on the list
     uint32_t *rec_class;                        // [records of the set] or nullptr
+    uint32_t *rec_score;                        // [records of the set] or nullptr: the largest score of the record, below min_score too
     uint32_t *long_list;                        // [n_rec] records of this slab (slab-relative) left to the general pass
 };
 
@@ -171,6 +172,7 @@ __global__ __launch_bounds__(256) void classify_kernel(const ClassArgs A, const 
             if (sc > best) { best = sc; cls = v; tie = false; }
             else if (sc == best) { cls = lca_of(F, cls, v); tie = true; }
         }
+        if (A.rec_score) A.rec_score[A.rec0 + g] = best;
         if (best < A.min_score) { cls = 0; tie = false; }
         ties += tie;
         if (A.rec_class) A.rec_class[A.rec0 + g] = cls;
@@ -249,6 +251,7 @@ __global__ __launch_bounds__(256) void classify_long_kernel(const ClassArgs A, c
         }
         if (t == 0) {
             Best r = red[0];
+            if (A.rec_score) A.rec_score[A.rec0 + g] = r.score;
             if (r.score < A.min_score) { r.node = 0u; r.tie = 0u; }
             if (r.tie) atomicAdd(&A.tot[0], 1ull);
             atomicAdd(&A.direct[r.node], 1ull);
@@ -331,20 +334,12 @@ bool walk_forest(const uint32_t *parent, uint32_t n_nodes, std::vector<uint32_t>
     return seen == n_nodes;
 }
 
-// What classify_records leaves behind: everything on the device lives in rh.scratch and is enqueued on ss::l2s::stream() when
-// the call returns.
-struct Classified {
-    ss::RecHits rh;
-    ss::RecSpans sp;
-    Forest F{nullptr, nullptr, nullptr, nullptr};
-    unsigned long long *d_out = nullptr;      // direct[n1], node_hits[n1], kmers[n1], tot[2]
-    uint32_t *d_class = nullptr;              // [rh.rec_total] the class of every record (keep_class; nullptr for a set without records)
-    std::vector<uint32_t> tin, tout;          // the host's copy of the Euler intervals
-};
+}  // namespace
 
-// The whole of ss_reads_classify but the copy back (the passes 0-4 above).  *calls is counted once the arguments have passed.
-int classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
-                     bool keep_class, std::atomic<uint64_t> *calls, Classified *C)
+// The whole of ss_reads_classify but the copy back (the passes 0-4 above; declared in ss_support.h: ss_bam_tag.hip calls it too).
+// *calls (or nullptr) is counted once the arguments have passed.
+int ss::classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
+                         bool keep_class, std::atomic<uint64_t> *calls, Classified *C, bool keep_score)
 {
     if (!db || !R || !row_node || !parent || min_score == 0 || n_nodes < 1 || n_nodes > SS_CLASS_NODES_MAX) return SS_EINVAL;
     if (db->layout != 1) return SS_ERANGE;                          // page-index tables only
@@ -424,6 +419,10 @@ int classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_nod
         SS_HIP(scratch.get((void **)&d_class, rec_total * 4));
         SS_HIP(ss::l2s::set(d_class, 0, rec_total * 4));
     }
+    if (keep_score && rec_total) {
+        SS_HIP(scratch.get((void **)&C->d_score, rec_total * 4));
+        SS_HIP(ss::l2s::set(C->d_score, 0, rec_total * 4));
+    }
     for (const auto &pt : rh.parts) {
         if (!pt.n_rec) continue;
         if (pt.n >= (uint64_t)db->k) {
@@ -434,7 +433,7 @@ int classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_nod
         }
         SS_HIP(ss::l2s::set(d_tot + 1, 0, 8));
         const ClassArgs A{d_pos, sp.d_start, sp.d_end, pt.rec_base, pt.n_rec, pt.n, pt.sl->packed ? pt.sl->slot : 0u, pt.sl->packed ? pt.sl->L : 0u,
-                          n_nodes, min_score, d_direct, d_hits, d_tot, d_class, d_list};
+                          n_nodes, min_score, d_direct, d_hits, d_tot, d_class, C->d_score, d_list};
         const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 8192);
         hipLaunchKernelGGL(classify_kernel, dim3(blocks), dim3(256), 0, st, A, F);
         SS_HIP(hipGetLastError());
@@ -443,6 +442,10 @@ int classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_nod
     }
     return SS_OK;
 }
+
+namespace {
+
+using ss::classify_records;
 
 // direct / node_hits / kmers [n1] (each nullptr to skip) and the calling thread's ties from what classify_records left; synchronous
 int classify_results(const Classified &C, size_t n1, uint64_t *direct, uint64_t *node_hits, uint64_t *kmers)
@@ -480,6 +483,13 @@ int select_clades(Classified &C, uint32_t n_nodes, const uint32_t *clades, uint3
 }
 
 }  // namespace
+
+int ss::classified_counts(const Classified &C, uint32_t n_nodes, uint64_t *direct, uint64_t *node_hits, uint64_t *kmers, uint64_t *ties)
+{
+    const int rc = classify_results(C, (size_t)n_nodes + 1, direct, node_hits, kmers);
+    if (rc == SS_OK && ties) *ties = t_last_ties;
+    return rc;
+}
 
 extern "C" {
 

@@ -133,7 +133,38 @@ int bam_mates_dev(const uint8_t *d_stream, const BamRecords &recs, PoolScratch &
 int bam_fragment_out_len(const uint8_t *d_stream, const BamRecords &recs, const uint32_t *d_mate, const uint32_t *d_hits,
                          uint32_t min_hits, unsigned long long *d_out_len, unsigned long long *d_tot);
 
+// d_src[0, total) -> dst (host, pageable) through two pinned buffers, chunk by chunk (ss_bam_extract.hip); synchronous
+int bam_download_chunks(const char *d_src, uint64_t total, char *dst);
+// Steps 5 and 6 of ss_bam_pairs.hip on the linked records of a stream (recs with want_off, flat: its flat block of flat_len
+// bytes): the fragments joined into *out, one ASCII slab in fragment order.  n_frag = kept - pairs.  *d_fidx (or nullptr to skip;
+// [n_rec + 1], from `scratch`, nullptr when n_frag == 0): the fragment index of every LEADER -- the earlier record of a fragment;
+// what it holds for other records is the exclusive count of leaders before them.  ms (or nullptr): [0] lengths + scan, [1] join.
+int bam_join_dev(const char *flat, uint64_t flat_len, const BamRecords &recs, PoolScratch &scratch, const uint32_t *d_mate,
+                 const uint8_t *d_role, uint64_t n_frag, ss_reads **out, uint32_t **d_fidx, double *ms);
+
 extern std::atomic<uint64_t> g_join_pairs_calls;      // ss_reads_join_pairs_calls (ss_pairs.hip)
+
+// The classification of ss_reads_classify left on the device (ss_classify.hip), which ss_bam_tag.hip runs on the one-slab set
+// wrapped around a BAM's flat block.  Forest: device arrays [n_nodes + 1]; entry 0: parent 0, depth 0, an empty interval.
+struct Forest {
+    const uint32_t *parent, *depth, *tin, *tout;
+};
+// What classify_records leaves behind: everything on the device lives in rh.scratch and is enqueued on ss::l2s::stream() when
+// the call returns.
+struct Classified {
+    RecHits rh;
+    RecSpans sp;
+    Forest F{nullptr, nullptr, nullptr, nullptr};
+    unsigned long long *d_out = nullptr;      // direct[n1], node_hits[n1], kmers[n1], tot[2]
+    uint32_t *d_class = nullptr;              // [rh.rec_total] the class of every record (keep_class; nullptr for a set without records)
+    uint32_t *d_score = nullptr;              // [rh.rec_total] the largest score of every record, below min_score too (keep_score)
+    std::vector<uint32_t> tin, tout;          // the host's copy of the Euler intervals
+};
+// SS_EINVAL / SS_ERANGE as ss_reads_classify states them; *calls (or nullptr) is counted once the arguments have passed.
+int classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent, uint32_t min_score,
+                     bool keep_class, std::atomic<uint64_t> *calls, Classified *C, bool keep_score = false);
+// direct / node_hits / kmers [n_nodes + 1] (each nullptr to skip) and *ties (or nullptr) from what classify_records left; synchronous
+int classified_counts(const Classified &C, uint32_t n_nodes, uint64_t *direct, uint64_t *node_hits, uint64_t *kmers, uint64_t *ties);
 
 // row labels (host, db->n_rows of them; only != 0: folded to 1 = `only`, 0 = the rest) -> *d_slot_label [db->n_slots] in `scratch`
 // (ss_label.hip); SS_EINVAL for a label above n_labels

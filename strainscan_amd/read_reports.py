@@ -25,13 +25,14 @@ RECORD_WAS_CUT = "cannot %s the reads of a sample with a record longer than a bl
 
 @contextlib.contextmanager
 def database_scope(label, out_dir):
-    """strainscan-multi, around one database's work: its rows are kept under `label`, -x writes to out_dir/extracted/."""
-    before = SCOPE["label"], EXTRACT_READS["dir"]
-    SCOPE["label"], EXTRACT_READS["dir"] = label, out_dir
+    """strainscan-multi, around one database's work: its rows are kept under `label`, -x writes to out_dir/extracted/ and
+    --tag_bam to out_dir."""
+    before = SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"]
+    SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"] = label, out_dir, out_dir
     try:
         yield
     finally:
-        SCOPE["label"], EXTRACT_READS["dir"] = before
+        SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"] = before
 
 
 def tree_scanned(img, paths):
@@ -76,6 +77,7 @@ def reset_all():
     bootstrap_reset()
     classify_reads_reset()
     extract_class_reset()
+    tag_bam_reset()
     pairs_reset()
 
 
@@ -703,6 +705,8 @@ def collect_read_classes(img, paths):
     _collect_read_classes(img, paths)
     if EXTRACT_CLASS["items"] and CLASSIFY_READS["skipped"] is not None:
         _extract_class_skip("--classify_reads was skipped (%s)" % CLASSIFY_READS["skipped"])
+    if TAG_BAM["on"] and CLASSIFY_READS["skipped"] is not None:
+        _tag_bam_skip("--classify_reads was skipped (%s)" % CLASSIFY_READS["skipped"])
 
 
 def _collect_read_classes(img, paths):
@@ -756,6 +760,7 @@ def _collect_read_classes(img, paths):
             print("classify_reads: M=%d\trecords %d\tclassified %d\tfrom a tie %d" % (m, records, records - int(direct[0]), int(v[-1])),
                   file=sys.stderr)
             sys.stderr.flush()
+        _write_tagged_bams(kdb, row_node, parent, m, node_ids, paths)
 
 
 def write_read_classes(out_dir, scope=None):
@@ -764,6 +769,61 @@ def write_read_classes(out_dir, scope=None):
     if not CLASSIFY_READS["m"] or CLASSIFY_READS["skipped"] is not None or not r:
         return None
     return _write(out_dir, READ_CLASSES_FILE, read_classes_text(r["node_ids"], r["parent_of"], r["leaves"], r["direct"], r["node_hits"], r["kmers"]))
+
+
+# --tag_bam (StrainScan.apply_tag_bam turns it on; it needs --classify_reads M and BAM input): which read went where.  A resident
+# set keeps no map back to file order, a BAM needs none: _lib.bam_tag_file inflates input file i once more, classifies its records
+# (with --pairs: its fragments) against the same table with the same row_node, parent and M, and writes `dir`/classified_<i>.bam --
+# every record of the input in file order, each kept one with sn:i:<node id of read_classes.tsv, -1 for unclassified> and
+# sc:i:<score> behind its last tag (tests/bam_tag_model.py restates it).  Written behind read_classes.tsv's numbers, once per scope;
+# "dir" is the output directory where database_scope names none.  Whatever keeps a file from being written says one line and takes
+# the files of this run with it; the exit status and every other file stay as they are.
+TAG_BAM = {"on": False, "dir": None, "skipped": None, "files": []}
+TAG_BAM_TAGS = b"snsc"
+
+
+def tag_bam_reset(on=False, out_dir=None):
+    TAG_BAM.update(on=bool(on), dir=out_dir, skipped=None, files=[])
+
+
+def _tag_bam_skip(why):
+    for f in TAG_BAM["files"]:
+        with contextlib.suppress(OSError):
+            os.remove(f)
+    TAG_BAM["files"] = []
+    _skip(TAG_BAM, "tag_bam", "and no tagged BAM was written", True, why)
+
+
+def _write_tagged_bams(kdb, row_node, parent, m, node_ids, paths):
+    """classified_<i>.bam for input file i of `paths`, and one line per file on stderr whose numbers are read_classes.tsv's: tagged -
+    classified = the unclassified row's reads_direct, the histogram of sn its reads_direct column (summed over the files)."""
+    if not TAG_BAM["on"] or TAG_BAM["skipped"] is not None:
+        return
+    if dist.is_distributed():
+        return _tag_bam_skip("runs on one rank only (this run has several)")
+    ps = [p for p in paths if p]
+    if any(_lib.input_kind(p) != "bam" for p in ps):
+        return _tag_bam_skip("takes BAM inputs (per-read classes of FASTA/FASTQ reads are not written)")
+    if any(int(nid) != nid or not -(1 << 31) <= int(nid) < (1 << 31) for nid in node_ids):
+        return _tag_bam_skip("needs node ids that fit a 32-bit integer tag (this tree has one outside)")
+    node_value = np.array([-1] + [int(nid) for nid in node_ids], np.int32)
+    out_dir = TAG_BAM["dir"] or EXTRACT_READS["dir"] or "."
+    for i, p in enumerate(ps, 1):
+        out = os.path.join(out_dir, "classified_%d.bam" % i)
+        try:
+            c = _lib.bam_tag_file(p, kdb, row_node, parent, m, node_value, out, pairs=PAIRS["on"], tags=TAG_BAM_TAGS)
+        except _lib.BamTagError as e:
+            if e.code != _lib.SS_EIO:
+                raise
+            n = e.counters["already_tagged"]
+            if n:
+                return _tag_bam_skip("%d records of %s already bear an sn or sc tag (remove them first: samtools view -x sn -x sc)" % (n, p))
+            return _tag_bam_skip("%s: %s" % (p, "a read name is not one first and one second mate, or a record's tags are damaged,"
+                                             if PAIRS["on"] else "a record's tags are damaged,"))
+        TAG_BAM["files"].append(out)
+        print("tag_bam: %s\tM=%d\trecords %d\ttagged %d\tclassified %d\tfragments %d\tfrom a tie %d" %
+              (out, m, c["records"], c["tagged"], c["classified"], c["fragments"], c["ties"]), file=sys.stderr)
+        sys.stderr.flush()
 
 
 # --extract_class LIST (StrainScan.apply_extract_class turns it on; it needs --classify_reads M): the reads of chosen classes of
