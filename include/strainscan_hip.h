@@ -506,8 +506,9 @@ int ss_bam_counters(uint64_t out[4]);
  *   the first record, byte for byte, then those records.  The file is inflated on the device where ss_reads_load would do that
  *   (1 MB and more, not under SS_GZ_GPU=0), else on the host and uploaded; ss_bam_counters counts it under out[0] or out[1]
  *   accordingly.  Written to <out_path>.tmp and renamed at the end; nothing is left on an error.  Members are compressed at zlib
- *   level 1 (SS_BAM_OUT_LEVEL=0..9 changes it).  SS_EINVAL also for an input that is not a BAM.
- * ss_bgzf_write (host only): head's bytes, then body's, as BGZF members of at most 0xff00 stream bytes each -- the "BC" extra
+ *   level 1 (SS_BAM_OUT_LEVEL=0..9 changes it): the file step of ss_bam_out.hip, which ss_bam_tag_file takes too.  SS_EINVAL also
+ *   for an input that is not a BAM.
+ * ss_bgzf_write (host only; ss_bam_out.hip): head's bytes, then body's, as BGZF members of at most 0xff00 stream bytes each -- the "BC" extra
  *   field, raw deflate at `level` (0..9), CRC-32, ISIZE -- and the 28-byte EOF block; a member never holds bytes of both.  The
  *   members are compressed on up to min(16, SS_HOST_THREADS or the CPUs this process may use) threads.  SS_EIO (and no file)
  *   when path cannot be written.
@@ -588,8 +589,9 @@ int ss_bam_pairs_timing(double out[8]);
  *   [n_nodes + 1], what ss_reads_classify returns for the same reads (under pairs: for the fragments).
  * ss_bam_tag_stream: stream = an inflated BAM stream in HOST memory (from "BAM\1"); out: the body (no header), *out_len its bytes.
  * ss_bam_tag_file: one BAM file (BGZF, plain gzip or uncompressed), brought to the device the way ss_bam_extract brings it ->
- *   out_path, a BGZF BAM through ss_bgzf_write: the input's header from "BAM\1" to the first record, byte for byte, then the
- *   body; zlib level 1 (SS_BAM_OUT_LEVEL=0..9 changes it); written to <out_path>.tmp and renamed; nothing is left on any error.
+ *   out_path, a BGZF BAM through the same file step (ss_bam_out.hip, ss_bgzf_write): the input's header from "BAM\1" to the first
+ *   record, byte for byte, then the body; zlib level 1 (SS_BAM_OUT_LEVEL=0..9 changes it); written to <out_path>.tmp and renamed;
+ *   nothing is left on any error.
  * ss_bam_tag_calls: calls of the two so far in this process ("flag off = not run").
  * ss_bam_tag_timing: the last successful ss_bam_tag_file, host clock around its synchronised steps (ms): out[0] stream on the
  *   device, [1] walk + decode, [2] mate link + join, [3] classify, [4] tag check + copy, [5] download, [6] compress + write, [7] the

@@ -682,25 +682,26 @@ def _row_labels(kdb, row_labels):
     return lab if lab.size else np.zeros(1, np.uint8)
 
 
+def _calls(name):
+    """what the counter entry point `name` reports: calls so far in this process"""
+    n = C.c_uint64()
+    check(getattr(lib(), name)(C.byref(n)), name)
+    return n.value
+
+
 def labeled_calls():
     """Calls of ss_reads_support_labeled and ss_reads_select_labeled so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_labeled_calls(C.byref(n)), "ss_reads_labeled_calls")
-    return n.value
+    return _calls("ss_reads_labeled_calls")
 
 
 def select_calls():
     """Calls of ss_reads_select so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_select_calls(C.byref(n)), "ss_reads_select_calls")
-    return n.value
+    return _calls("ss_reads_select_calls")
 
 
 def resample_calls():
     """Calls of ss_reads_resample so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_resample_calls(C.byref(n)), "ss_reads_resample_calls")
-    return n.value
+    return _calls("ss_reads_resample_calls")
 
 
 CLASS_NODES_MAX = 65535     # SS_CLASS_NODES_MAX (strainscan_hip.h)
@@ -708,9 +709,7 @@ CLASS_NODES_MAX = 65535     # SS_CLASS_NODES_MAX (strainscan_hip.h)
 
 def classify_calls():
     """Calls of ss_reads_classify so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_classify_calls(C.byref(n)), "ss_reads_classify_calls")
-    return n.value
+    return _calls("ss_reads_classify_calls")
 
 
 CLASS_CLADES_MAX = 64       # SS_SELECT_CLADES_MAX (strainscan_hip.h): clades per call of select_class
@@ -718,9 +717,7 @@ CLASS_CLADES_MAX = 64       # SS_SELECT_CLADES_MAX (strainscan_hip.h): clades pe
 
 def select_class_calls():
     """Calls of ss_reads_select_class so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_select_class_calls(C.byref(n)), "ss_reads_select_class_calls")
-    return n.value
+    return _calls("ss_reads_select_class_calls")
 
 
 def flat_record_keys(flat):
@@ -765,16 +762,12 @@ def extract_write_pairs(in_paths, keys, out_paths):
 
 def join_pairs_calls():
     """Joins (ss_reads_join_pairs_dev, ss_reads_load_pairs) so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_join_pairs_calls(C.byref(n)), "ss_reads_join_pairs_calls")
-    return n.value
+    return _calls("ss_reads_join_pairs_calls")
 
 
 def support_calls():
     """Calls of ss_reads_support so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_reads_support_calls(C.byref(n)), "ss_reads_support_calls")
-    return n.value
+    return _calls("ss_reads_support_calls")
 
 
 def scan_multi_launches():
@@ -1014,14 +1007,19 @@ def bam_mates(stream):
     return mate[:int(c[0])], dict(zip(BAM_PAIR_COUNTERS, (int(v) for v in c)))
 
 
+def _bam_timing(name, steps):
+    """the eight slots of the timing entry point `name`, in milliseconds, under the names of `steps`"""
+    out = (C.c_double * 8)()
+    check(getattr(lib(), name)(out), name)
+    return dict(zip(steps, (float(v) for v in out)))
+
+
 BAM_PAIRS_STEPS = ("stream", "walk_decode", "keys", "sort", "link", "lengths_scan", "join", "total")
 
 
 def bam_pairs_timing():
     """The last ReadSet.load_pairs_bam in milliseconds, step by step (ss_bam_pairs_timing)."""
-    out = (C.c_double * 8)()
-    check(lib().ss_bam_pairs_timing(out), "ss_bam_pairs_timing")
-    return dict(zip(BAM_PAIRS_STEPS, (float(v) for v in out)))
+    return _bam_timing("ss_bam_pairs_timing", BAM_PAIRS_STEPS)
 
 
 BAM_TAG_COUNTERS = ("records", "tagged", "classified", "already_tagged", "fragments", "ties")
@@ -1090,16 +1088,12 @@ def bam_tag_file(in_path, kdb, row_node, parent, m, node_value, out_path, pairs=
 
 def bam_tag_calls():
     """Calls of ss_bam_tag_stream and ss_bam_tag_file so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_bam_tag_calls(C.byref(n)), "ss_bam_tag_calls")
-    return n.value
+    return _calls("ss_bam_tag_calls")
 
 
 def bam_tag_timing():
     """The last bam_tag_file in milliseconds, step by step (ss_bam_tag_timing)."""
-    out = (C.c_double * 8)()
-    check(lib().ss_bam_tag_timing(out), "ss_bam_tag_timing")
-    return dict(zip(BAM_TAG_STEPS, (float(v) for v in out)))
+    return _bam_timing("ss_bam_tag_timing", BAM_TAG_STEPS)
 
 
 def bgzf_write(path, head, body, level=1):
@@ -1110,9 +1104,7 @@ def bgzf_write(path, head, body, level=1):
 
 def bam_extract_calls():
     """Calls of ss_bam_select and ss_bam_extract so far in this process."""
-    n = C.c_uint64()
-    check(lib().ss_bam_extract_calls(C.byref(n)), "ss_bam_extract_calls")
-    return n.value
+    return _calls("ss_bam_extract_calls")
 
 
 BAM_EXTRACT_STEPS = ("stream", "walk_decode", "hits", "join", "gather", "download", "compress_write", "total")
@@ -1120,9 +1112,7 @@ BAM_EXTRACT_STEPS = ("stream", "walk_decode", "hits", "join", "gather", "downloa
 
 def bam_extract_timing():
     """The last bam_extract in milliseconds, step by step (ss_bam_extract_timing)."""
-    out = (C.c_double * 8)()
-    check(lib().ss_bam_extract_timing(out), "ss_bam_extract_timing")
-    return dict(zip(BAM_EXTRACT_STEPS, (float(v) for v in out)))
+    return _bam_timing("ss_bam_extract_timing", BAM_EXTRACT_STEPS)
 
 
 def set_min_base_qual(q):

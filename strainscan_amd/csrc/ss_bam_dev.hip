@@ -17,7 +17,7 @@
 //   3  the record starts, kept flags -> exclusive sum (blocks of 4096 KEPT records go round the ranks of a sharded run)
 //      -> each kept record's length + 1 -> exclusive sum -> 16 lanes per record decode the nibbles
 // Host path (bam_decode): the same rules in one sequential walk; it serves what the device declines and is the cross-check.
-#include "ss_common.h"
+#include "ss_bam.h"
 
 #include <hipcub/hipcub.hpp>
 #include <zlib.h>

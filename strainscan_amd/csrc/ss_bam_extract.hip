@@ -15,24 +15,16 @@
 //      digests of the selected records, sorted by the first hash.  template_len_kernel: a kept record is written when it is
 //      selected or a binary search finds its digest (both hashes) among them; out_len[r] = 4 + block_size, else 0
 //   5  a 64-bit ExclusiveSum of out_len -> offsets; record_gather_kernel: sixteen lanes per written record copy it in 16-byte
-//      aligned pieces of the destination (the piece copy, ss_piece_copy.h)
-//   6  the result to the host through two pinned buffers, chunk by chunk; ss_bgzf_write compresses the members on host threads.
+//      aligned pieces of the destination (the piece copy, ss_piece_copy.h: copy_span)
+//   6  the result to the host (bam_download_chunks); ss_bam_extract: through the file step and the call frame of ss_bam_out.hip.
 // Records that the loader does not keep (0x100, 0x800, no bases) are never written, whatever their name.
 // ss_bam_select_pairs / ss_bam_extract_pairs (`--pairs`): the same path with the mate link of ss_bam_pairs.hip in the place of step
 // 4 -- a kept record is written iff its hits and its mate's together reach N, and nothing is joined by name after that.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  No device-wide barrier inside a kernel.
+#include "ss_bam.h"
 #include "ss_piece_copy.h"
-#include "ss_support.h"
 
 #include <hipcub/hipcub.hpp>
-#include <zlib.h>
-
-#include <fcntl.h>
-#include <unistd.h>
-
-#include <cerrno>
-#include <string>
-#include <thread>
 
 using namespace ss::dev;
 using ss::Clock;
@@ -42,7 +34,7 @@ using ss::ms_since;
 namespace {
 
 // One lane per record r <= n_rec (entry n_rec closes the sums).  A kept record: (h1, h2) = the digest of its name (bam_name_digest,
-// ss_support.h); sel = its hits reach min_hits.  A record that is not kept: sel = 0 and a digest nobody asks for.
+// ss_bam.h); sel = its hits reach min_hits.  A record that is not kept: sel = 0 and a digest nobody asks for.
 __global__ __launch_bounds__(256) void name_digest_kernel(const uint8_t *__restrict__ s, const uint64_t *__restrict__ rec,
                                                           const uint32_t *__restrict__ keep, const uint32_t *__restrict__ kidx,
                                                           const uint32_t *__restrict__ hits, uint64_t n_rec, uint32_t min_hits,
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(256) void template_len_kernel(const uint8_t *__rest
 }
 
 // Sixteen lanes per record; src holds n >= 16 bytes and every written record lies inside them; dst is 16-byte aligned.  The piece
-// copy of ss_piece_copy.h, the record's bytes as they are.
+// copy of ss_piece_copy.h, the record's bytes as they are (copy_span).
 __global__ __launch_bounds__(256) void record_gather_kernel(const uint8_t *__restrict__ src, uint64_t n, const uint64_t *__restrict__ rec,
                                                             const unsigned long long *__restrict__ out_len,
                                                             const unsigned long long *__restrict__ out_off, uint64_t n_rec,
@@ -114,13 +106,11 @@ __global__ __launch_bounds__(256) void record_gather_kernel(const uint8_t *__res
     const uint64_t ol = out_len[r];
     if (!ol) return;                                                    // not written
     const uint64_t D = out_off[r], S = rec[r];
-    write_span(dst, D, D + ol, threadIdx.x & 15u,
-               [&](uint64_t a, uint64_t, uint64_t) { return fetch16(src, n, (int64_t)S + ((int64_t)a - (int64_t)D)); });
+    copy_span(dst, D, D + ol, threadIdx.x & 15u, src, n, S);
 }
 
 std::atomic<uint64_t> g_bam_extract_calls{0};
-std::mutex g_timing_mu;
-double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the last ss_bam_extract (ms): ss_bam_extract_timing
+ss::BamTiming g_timing;      // the last ss_bam_extract: ss_bam_extract_timing
 
 // What the selection leaves: the written records back to back in d_out (big_malloc'ed, out_cap; nullptr when nothing is written)
 struct Selection {
@@ -157,16 +147,7 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     // 3. hits per kept record
     t0 = Clock::now();
     ss_reads R;
-    {
-        ss_reads::Slab sl;
-        sl.d = flat;
-        sl.cap = flat_cap;
-        sl.used = ss_reads::padded(flat_len);
-        R.slabs.push_back(sl);
-        R.n_records = kept;
-        R.n_bases = flat_len - kept;
-        R.n_blocks = 1;
-    }
+    ss::bam_flat_as_set(flat, flat_len, flat_cap, kept, &R);
     ss::RecHits rh;
     uint8_t *d_lab = nullptr;
     if (row_labels) {
@@ -262,38 +243,6 @@ int select_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, 
     return SS_OK;
 }
 
-// d_src[0, total) -> dst (host, pageable) through two pinned buffers: the copy of a chunk runs beside the host's memcpy of the one before
-int download_chunks(const char *d_src, uint64_t total, char *dst)
-{
-    if (!total) return SS_OK;
-    const hipStream_t st = ss::l2s::stream();
-    const uint64_t CH = std::min<uint64_t>(total, 16ull << 20);
-    char *buf[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool ok = true;
-    for (int i = 0; i < 2 && ok; i++)
-        ok = hipHostMalloc((void **)&buf[i], CH, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
-    const uint64_t n_ch = (total + CH - 1) / CH;
-    for (uint64_t i = 0; i <= n_ch && ok; i++) {
-        if (i < n_ch) {
-            const uint64_t o = i * CH, l = std::min(CH, total - o);
-            ok = hipMemcpyAsync(buf[i & 1], d_src + o, l, hipMemcpyDeviceToHost, st) == hipSuccess && hipEventRecord(ev[i & 1], st) == hipSuccess;
-        }
-        if (i > 0 && ok) {
-            const uint64_t o = (i - 1) * CH, l = std::min(CH, total - o);
-            ok = hipEventSynchronize(ev[(i - 1) & 1]) == hipSuccess;
-            if (ok) memcpy(dst + o, buf[(i - 1) & 1], l);
-        }
-    }
-    (void)hipStreamSynchronize(st);
-    for (int i = 0; i < 2; i++) {
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-        if (buf[i]) (void)hipHostFree(buf[i]);
-    }
-    if (!ok) { (void)hipGetLastError(); return SS_EHIP; }
-    return SS_OK;
-}
-
 int check_args(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label, uint32_t min_hits)
 {
     if (!db || min_hits == 0) return SS_EINVAL;
@@ -302,69 +251,7 @@ int check_args(const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, ui
     return SS_OK;
 }
 
-unsigned bgzf_threads()
-{
-    unsigned t = ss::host_cpus();
-    if (const char *e = getenv("SS_HOST_THREADS")) t = (unsigned)std::max(1, atoi(e));
-    return std::max(1u, std::min(16u, t));
-}
-
-constexpr uint32_t BGZF_BLOCK = 0xff00;
-const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-// one member behind `out`: the 18-byte header with the "BC" field, raw deflate, CRC-32, ISIZE.  zs: a raw-deflate stream at the
-// caller's level; a member that would pass 64 KB (bytes that do not compress) is stored instead, as htslib does
-bool bgzf_member(z_stream *zs, const uint8_t *src, uint32_t len, std::vector<uint8_t> *out)
-{
-    const size_t at = out->size();
-    const size_t room = (size_t)len + (len >> 8) + 1024;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        out->resize(at + 18 + room + 8);
-        z_stream stored;
-        z_stream *z = zs;
-        if (attempt == 1) {
-            memset(&stored, 0, sizeof stored);
-            if (deflateInit2(&stored, 0, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
-            z = &stored;
-        } else if (deflateReset(z) != Z_OK) return false;
-        z->next_in = const_cast<Bytef *>(src);
-        z->avail_in = len;
-        z->next_out = out->data() + at + 18;
-        z->avail_out = (uInt)room;
-        const int r = deflate(z, Z_FINISH);
-        const size_t clen = room - z->avail_out;
-        if (attempt == 1) deflateEnd(&stored);
-        if (r != Z_STREAM_END) return false;
-        const size_t bsize = 18 + clen + 8;
-        if (bsize > 65536) continue;
-        uint8_t *h = out->data() + at;
-        const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 'B', 'C', 0x02, 0};
-        memcpy(h, head, 16);
-        h[16] = (uint8_t)((bsize - 1) & 0xFF);
-        h[17] = (uint8_t)((bsize - 1) >> 8);
-        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, len);
-        uint8_t *t = h + 18 + clen;
-        for (int i = 0; i < 4; i++) { t[i] = (uint8_t)(crc >> (8 * i)); t[4 + i] = (uint8_t)(len >> (8 * i)); }
-        out->resize(at + bsize);
-        return true;
-    }
-    return false;
-}
-
-bool write_all(int fd, const uint8_t *p, size_t n)
-{
-    while (n) {
-        const ssize_t w = write(fd, p, std::min<size_t>(n, 1u << 30));
-        if (w < 0) { if (errno == EINTR) continue; return false; }
-        p += w;
-        n -= (size_t)w;
-    }
-    return true;
-}
-
 }  // namespace
-
-int ss::bam_download_chunks(const char *d_src, uint64_t total, char *dst) { return download_chunks(d_src, total, dst); }
 
 extern "C" {
 
@@ -375,52 +262,7 @@ int ss_bam_extract_calls(uint64_t *n)
     return SS_OK;
 }
 
-int ss_bam_extract_timing(double out[8])
-{
-    if (!out) return SS_EINVAL;
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    memcpy(out, g_timing, sizeof g_timing);
-    return SS_OK;
-}
-
-int ss_bgzf_write(const char *path, const void *head, uint64_t head_n, const void *body, uint64_t body_n, int level)
-{
-    if (!path || (!head && head_n) || (!body && body_n) || level < 0 || level > 9) return SS_EINVAL;
-    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return SS_EIO;
-    // the members: the header's, then the body's (a member never holds bytes of both, so the first record starts a member)
-    struct Piece { const uint8_t *p; uint32_t n; };
-    std::vector<Piece> pieces;
-    for (uint64_t o = 0; o < head_n; o += BGZF_BLOCK) pieces.push_back({(const uint8_t *)head + o, (uint32_t)std::min<uint64_t>(BGZF_BLOCK, head_n - o)});
-    for (uint64_t o = 0; o < body_n; o += BGZF_BLOCK) pieces.push_back({(const uint8_t *)body + o, (uint32_t)std::min<uint64_t>(BGZF_BLOCK, body_n - o)});
-    const uint64_t M = pieces.size();
-    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(bgzf_threads(), (M + 63) / 64));
-    std::vector<std::vector<uint8_t>> outs(T);
-    std::vector<char> good(T, 1);
-    auto work = [&](unsigned t) {
-        z_stream zs;
-        memset(&zs, 0, sizeof zs);
-        if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { good[t] = 0; return; }
-        try {
-            for (uint64_t m = M * t / T; m < M * (t + 1) / T && good[t]; m++)
-                if (!bgzf_member(&zs, pieces[m].p, pieces[m].n, &outs[t])) good[t] = 0;
-        } catch (const std::bad_alloc &) { good[t] = 0; }
-        deflateEnd(&zs);
-    };
-    if (T == 1) work(0);
-    else {
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < T; t++) pool.emplace_back(work, t);
-        for (auto &th : pool) th.join();
-    }
-    bool ok = true;
-    for (unsigned t = 0; t < T; t++) ok = ok && good[t];
-    for (unsigned t = 0; t < T && ok; t++) ok = write_all(fd, outs[t].data(), outs[t].size());
-    ok = ok && write_all(fd, BGZF_EOF, sizeof BGZF_EOF);
-    ok = (close(fd) == 0) && ok;
-    if (!ok) { unlink(path); return SS_EIO; }
-    return SS_OK;
-}
+int ss_bam_extract_timing(double out[8]) { return g_timing.load(out); }
 
 static int select_stream(const void *stream, uint64_t n, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
                          uint32_t min_hits, void *out, uint64_t cap, uint64_t *out_len, uint64_t counters[4], bool pairs)
@@ -438,7 +280,7 @@ static int select_stream(const void *stream, uint64_t n, const ss_db *db, const 
     memcpy(counters, sel.counters, sizeof sel.counters);
     *out_len = sel.total;
     if (sel.total > cap) return SS_ERANGE;
-    return download_chunks(sel.d_out, sel.total, (char *)out);
+    return ss::bam_download_chunks(sel.d_out, sel.total, (char *)out);
 }
 
 static int extract_file(const char *in_path, const ss_db *db, const uint8_t *row_labels, uint32_t n_labels, uint32_t label,
@@ -447,50 +289,19 @@ static int extract_file(const char *in_path, const ss_db *db, const uint8_t *row
     if (!in_path || !out_path || !counters) return SS_EINVAL;
     int rc = check_args(db, row_labels, n_labels, label, min_hits);
     if (rc) return rc;
-    const int kind = ss::input_kind(in_path);
-    if (kind != ss::INPUT_BAM_GZ && kind != ss::INPUT_BAM_RAW) return SS_EINVAL;
-    g_bam_extract_calls++;
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const auto t_all = Clock::now();
-    auto t0 = t_all;
-    // 1. the stream on the device: inflated there where the loader would do that, else inflated on the host and uploaded
-    ss::BamDeviceStream ds;
-    rc = ds.open_file(in_path, kind);
+    ss::BamFileCall call;
+    rc = call.open(in_path, g_bam_extract_calls);                       // 1. the stream on the device
     if (rc) return rc;
-    ms[0] = ms_since(t0);
+    ss::BamDeviceStream &ds = call.ds;
     Selection sel;
     rc = select_on_device(ds.d, ds.n, ds.h, ds.seg, db, row_labels, n_labels, label, min_hits, &sel, pairs);
-    // 6. header and records to the host, then the file
-    std::vector<uint8_t> head;
-    char *body = nullptr;
-    t0 = Clock::now();
-    if (rc == SS_OK) {
-        try { head.resize(sel.hdr_end); } catch (const std::bad_alloc &) { rc = SS_ENOMEM; }
-        if (rc == SS_OK && sel.hdr_end && hipMemcpy(head.data(), ds.d, sel.hdr_end, hipMemcpyDeviceToHost) != hipSuccess) rc = SS_EHIP;
-    }
-    if (rc == SS_OK && sel.total) {
-        body = (char *)malloc(sel.total);
-        rc = body ? download_chunks(sel.d_out, sel.total, body) : SS_ENOMEM;
-    }
-    ds.release();
-    ms[5] = ms_since(t0);
-    if (rc == SS_OK) {
-        t0 = Clock::now();
-        int level = 1;
-        if (const char *e = getenv("SS_BAM_OUT_LEVEL")) level = std::max(0, std::min(9, atoi(e)));
-        const std::string tmp = std::string(out_path) + ".tmp";
-        rc = ss_bgzf_write(tmp.c_str(), head.data(), head.size(), body, sel.total, level);
-        if (rc == SS_OK && rename(tmp.c_str(), out_path) != 0) { unlink(tmp.c_str()); rc = SS_EIO; }
-        ms[6] = ms_since(t0);
-    }
-    free(body);
     if (rc) return rc;
-    (ds.inflated_on_device ? ss::g_bam_dev_files : ss::g_bam_host_files)++;
+    // 6. header and records to the host, then the file
+    rc = ss::bam_write_file(ds, sel.hdr_end, sel.d_out, sel.total, out_path, &call.ms[5], &call.ms[6]);
+    if (rc) return rc;
     memcpy(counters, sel.counters, sizeof sel.counters);
-    for (int i = 0; i < 4; i++) ms[1 + i] = sel.ms[i];
-    ms[7] = ms_since(t_all);
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    memcpy(g_timing, ms, sizeof ms);
+    for (int i = 0; i < 4; i++) call.ms[1 + i] = sel.ms[i];
+    call.finish(g_timing);
     return SS_OK;
 }
 

@@ -7,7 +7,7 @@
 //   1  the stream on the device (BamDeviceStream: gpu_gunzip where the loader would use it, else host inflate and upload), the
 //      records and the flat block (bam_records_flat_dev: the host walk where the device walk declines)
 //   2  key_kernel: one lane per record -> mate[r] = "no mate" / "not kept", and for a kept record with 0x1 set the digest of its
-//      name (bam_name_digest, the hash of ss_bam_extract.hip), its role and paired[r] = 1
+//      name (bam_name_digest, ss_bam.h: the hash of ss_bam_extract.hip), its role and paired[r] = 1
 //   3  ExclusiveSum + compact_kernel: (h2, r) of the paired records, in record order.  Two stable hipcub radix sorts, least
 //      significant key first: by h2, then -- h1 gathered into that order -- by h1.  The records of one name (both hashes equal) now
 //      stand side by side, in record order
@@ -23,8 +23,8 @@
 // ss_bam_tag.hip takes steps 2 to 4 (bam_mates_dev) and 5 to 6 (bam_join_dev), with the fragment index of every leader.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  Plain launches, no device-wide barrier inside a kernel.  All
 // byte offsets are 64-bit; record counts are below 0x7FFFFFF0 (bam_to_flat_dev).
+#include "ss_bam.h"
 #include "ss_piece_copy.h"
-#include "ss_support.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -32,10 +32,10 @@ using namespace ss::dev;
 using ss::Clock;
 using ss::grid_for;
 using ss::ms_since;
+using ss::NO_MATE;
+using ss::NOT_KEPT;
 
 namespace {
-
-constexpr uint32_t NO_MATE = 0xFFFFFFFEu, NOT_KEPT = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t flag_of(const uint8_t *s, uint64_t p) { return (uint32_t)s[p + 18] | (uint32_t)s[p + 19] << 8; }
 
@@ -201,8 +201,7 @@ __global__ __launch_bounds__(256) void fragment_len_kernel(const uint8_t *__rest
     add_selected(written, frags, tot);      // (no fragment without a written record)
 }
 
-std::mutex g_timing_mu;
-double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the last ss_reads_load_pairs_bam (ms): ss_bam_pairs_timing
+ss::BamTiming g_timing;      // the last ss_reads_load_pairs_bam: ss_bam_pairs_timing
 
 // steps 1 (second half) to 6 on a stream that lies on the device; ms[1..6]
 int join_on_device(const ss::BamDeviceStream &ds, int order, ss_reads **out, uint64_t counters[6], double *ms)
@@ -392,13 +391,7 @@ int bam_fragment_out_len(const uint8_t *s, const BamRecords &recs, const uint32_
 
 extern "C" {
 
-int ss_bam_pairs_timing(double out[8])
-{
-    if (!out) return SS_EINVAL;
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    memcpy(out, g_timing, sizeof g_timing);
-    return SS_OK;
-}
+int ss_bam_pairs_timing(double out[8]) { return g_timing.load(out); }
 
 int ss_bam_mates(const void *stream, uint64_t n, uint32_t *mate, uint64_t cap, uint64_t counters[6])
 {
@@ -446,21 +439,12 @@ int ss_reads_load_pairs_bam(const char *path, int order, ss_reads **out, uint64_
     *out = nullptr;
     if (!path || !counters) return SS_EINVAL;
     for (int i = 0; i < 6; i++) counters[i] = 0;
-    const int kind = ss::input_kind(path);
-    if (kind != ss::INPUT_BAM_GZ && kind != ss::INPUT_BAM_RAW) return SS_EINVAL;
-    ss::g_join_pairs_calls++;
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const auto t_all = Clock::now();
-    ss::BamDeviceStream ds;
-    int rc = ds.open_file(path, kind);
+    ss::BamFileCall call;
+    int rc = call.open(path, ss::g_join_pairs_calls);
     if (rc) return rc;
-    ms[0] = ms_since(t_all);
-    rc = join_on_device(ds, order, out, counters, ms);
+    rc = join_on_device(call.ds, order, out, counters, call.ms);
     if (rc) return rc;
-    (ds.inflated_on_device ? ss::g_bam_dev_files : ss::g_bam_host_files)++;
-    ms[7] = ms_since(t_all);
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    memcpy(g_timing, ms, sizeof ms);
+    call.finish(g_timing);
     return SS_OK;
 }
 

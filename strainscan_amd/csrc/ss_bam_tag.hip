@@ -17,23 +17,18 @@
 //      fixed 14 bytes per kept record, so the prefix the decoder left is the only one -- in 16-byte aligned pieces of the
 //      destination (the piece copy, ss_piece_copy.h); a kept record's span is composed from the patched block_size, the record's
 //      bytes and the 14 tag bytes (tagged_piece, ss_tag_copy.h)
-//   6  the body to the host through two pinned buffers; ss_bgzf_write compresses the members on host threads.
+//   6  the body to the host (bam_download_chunks); ss_bam_tag_file: through the file step and the call frame of ss_bam_out.hip.
 // Scratch: the stream-ordered pool (PoolScratch) and ss::big_malloc.  Plain launches, no device-wide barrier inside a kernel.
-#include "ss_support.h"
+#include "ss_bam.h"
 #include "ss_tag_copy.h"
-
-#include <unistd.h>
-
-#include <string>
 
 using namespace ss::dev;
 using ss::Clock;
 using ss::grid_for;
 using ss::ms_since;
+using ss::NO_MATE;
 
 namespace {
-
-constexpr uint32_t NO_MATE = 0xFFFFFFFEu;      // bam_mates_dev: a kept record without a mate
 
 // where the aux fields of the record at s + p begin (rec_len of ss_bam_dev.hip has checked that this is not behind its end)
 __device__ __forceinline__ uint64_t aux_begin(const uint8_t *__restrict__ s, uint64_t p)
@@ -117,14 +112,12 @@ __global__ __launch_bounds__(256) void tag_copy_kernel(const uint8_t *__restrict
         write_span(dst, D, D + ol + TAG_BYTES, threadIdx.x & 15u,
                    [&](uint64_t a, uint64_t lo, uint64_t hi) { return tagged_piece(src, n, S, ol, D, tag, a, lo, hi); });
     } else {
-        write_span(dst, D, D + ol, threadIdx.x & 15u,
-                   [&](uint64_t a, uint64_t, uint64_t) { return fetch16(src, n, (int64_t)S + ((int64_t)a - (int64_t)D)); });
+        copy_span(dst, D, D + ol, threadIdx.x & 15u, src, n, S);
     }
 }
 
 std::atomic<uint64_t> g_bam_tag_calls{0};
-std::mutex g_timing_mu;
-double g_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the last ss_bam_tag_file (ms): ss_bam_tag_timing
+ss::BamTiming g_timing;      // the last ss_bam_tag_file: ss_bam_tag_timing
 
 // What the call asks for, checked once
 struct TagArgs {
@@ -216,14 +209,7 @@ int tag_on_device(const char *d_stream, uint64_t n, const uint8_t *h_stream, con
         R = frags.s;
         out->ms[1] = ms_since(t0);
     } else if (kept) {
-        ss_reads::Slab sl;
-        sl.d = flat;
-        sl.cap = flat_cap;
-        sl.used = ss_reads::padded(flat_len);
-        wrapped.slabs.push_back(sl);
-        wrapped.n_records = kept;
-        wrapped.n_bases = flat_len - kept;
-        wrapped.n_blocks = 1;
+        ss::bam_flat_as_set(flat, flat_len, flat_cap, kept, &wrapped);
     }
     // 4. classes and scores
     t0 = Clock::now();
@@ -288,13 +274,7 @@ int ss_bam_tag_calls(uint64_t *n)
     return SS_OK;
 }
 
-int ss_bam_tag_timing(double out[8])
-{
-    if (!out) return SS_EINVAL;
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    memcpy(out, g_timing, sizeof g_timing);
-    return SS_OK;
-}
+int ss_bam_tag_timing(double out[8]) { return g_timing.load(out); }
 
 int ss_bam_tag_stream(const void *stream, uint64_t n, const ss_db *db, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent,
                       uint32_t min_score, const int32_t *node_value, const char tags[4], int pairs, void *out, uint64_t cap, uint64_t *out_len,
@@ -326,51 +306,20 @@ int ss_bam_tag_file(const char *in_path, const ss_db *db, const uint32_t *row_no
     TagArgs A;
     int rc = check_args(db, row_node, n_nodes, parent, min_score, node_value, tags, pairs, direct, node_hits, kmers, &A);
     if (rc) return rc;
-    const int kind = ss::input_kind(in_path);
-    if (kind != ss::INPUT_BAM_GZ && kind != ss::INPUT_BAM_RAW) return SS_EINVAL;
-    g_bam_tag_calls++;
     for (int i = 0; i < 6; i++) counters[i] = 0;
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const auto t_all = Clock::now();
-    auto t0 = t_all;
-    // 1. the stream on the device: inflated there where the loader would do that, else inflated on the host and uploaded
-    ss::BamDeviceStream ds;
-    rc = ds.open_file(in_path, kind);
+    ss::BamFileCall call;
+    rc = call.open(in_path, g_bam_tag_calls);                           // 1. the stream on the device
     if (rc) return rc;
-    ms[0] = ms_since(t0);
+    ss::BamDeviceStream &ds = call.ds;
     Tagged T;
     rc = tag_on_device(ds.d, ds.n, ds.h, ds.seg, A, ~0ull, &T);
     memcpy(counters, T.counters, sizeof T.counters);
-    // 6. header and body to the host, then the file
-    std::vector<uint8_t> head;
-    char *body = nullptr;
-    t0 = Clock::now();
-    if (rc == SS_OK) {
-        try { head.resize(T.hdr_end); } catch (const std::bad_alloc &) { rc = SS_ENOMEM; }
-        if (rc == SS_OK && T.hdr_end && hipMemcpy(head.data(), ds.d, T.hdr_end, hipMemcpyDeviceToHost) != hipSuccess) rc = SS_EHIP;
-    }
-    if (rc == SS_OK && T.total) {
-        body = (char *)malloc(T.total);
-        rc = body ? ss::bam_download_chunks(T.d_out, T.total, body) : SS_ENOMEM;
-    }
-    ds.release();
-    ms[5] = ms_since(t0);
-    if (rc == SS_OK) {
-        t0 = Clock::now();
-        int level = 1;
-        if (const char *e = getenv("SS_BAM_OUT_LEVEL")) level = std::max(0, std::min(9, atoi(e)));
-        const std::string tmp = std::string(out_path) + ".tmp";
-        rc = ss_bgzf_write(tmp.c_str(), head.data(), head.size(), body, T.total, level);
-        if (rc == SS_OK && rename(tmp.c_str(), out_path) != 0) { unlink(tmp.c_str()); rc = SS_EIO; }
-        ms[6] = ms_since(t0);
-    }
-    free(body);
     if (rc) return rc;
-    (ds.inflated_on_device ? ss::g_bam_dev_files : ss::g_bam_host_files)++;
-    for (int i = 0; i < 4; i++) ms[1 + i] = T.ms[i];
-    ms[7] = ms_since(t_all);
-    std::lock_guard<std::mutex> g(g_timing_mu);
-    memcpy(g_timing, ms, sizeof ms);
+    // 6. header and body to the host, then the file
+    rc = ss::bam_write_file(ds, T.hdr_end, T.d_out, T.total, out_path, &call.ms[5], &call.ms[6]);
+    if (rc) return rc;
+    for (int i = 0; i < 4; i++) call.ms[1 + i] = T.ms[i];
+    call.finish(g_timing);
     return SS_OK;
 }
 

@@ -68,7 +68,7 @@ unsigned ingest_threads();      // FASTQ parse threads of this process: its shar
 // The base-quality mask (ss_set_min_base_qual, ss_host.hip): a base whose Phred quality is below the threshold becomes 'N' in
 // whichever decoder turns its file into bases.  0 = off.  mask_count adds to the process-wide counters of ss_mask_counters.
 int min_base_qual();
-void mask_count(uint64_t bases, uint64_t bam_records_without_qual = 0);
+void mask_count(uint64_t bases, uint64_t records_without_qual = 0);
 
 }  // namespace ss
 
@@ -244,66 +244,6 @@ int gz_inputs_on_device(const char *const *paths, const std::vector<int> &gz, in
 // as text (the reader reports it).  Values up to INPUT_CRAM are those of ss_input_kind.
 enum InputKind { INPUT_TEXT = 0, INPUT_BAM_GZ = 1, INPUT_BAM_RAW = 2, INPUT_CRAM = 3, INPUT_GZ = 4, INPUT_EMPTY = 5 };
 int input_kind(const char *path);
-// one BAM input (INPUT_BAM_GZ or INPUT_BAM_RAW) of a load or a scan (ss_bam_dev.hip): on the device unless SS_GZ_GPU=0 or policy
-// 2, on the host for what the device declines (policy 0 and 2; policy 1: SS_EAGAIN).  on_dev takes over a big_malloc'ed device
-// block (len, cap, n_records), on_host a malloc'ed host block padded like a block of ss_reads (len, n_records; the callee frees
-// it).  SS_EIO: damaged.
-int bam_input(const char *path, int kind, int shard_rank, int shard_world, const std::function<int(char *, uint64_t, uint64_t, uint64_t)> &on_dev,
-              const std::function<int(char *, uint64_t, uint64_t)> &on_host);
-// The steps of that path that ss_bam_extract.hip takes on its own (ss_bam_dev.hip).  BamRecords: what a caller of bam_to_flat_dev
-// may keep -- record r of the stream starts at d_rec[r] (n_rec of them), d_keep[r] says whether the loader keeps it and d_kidx[r] is
-// its ordinal among the kept ones, so kept record i is non-empty record i of the flat block (shard_world 1); the three come from
-// the stream-ordered pool (hipFreeAsync on any stream).  host_rec / host_n_rec (in): record starts from bam_host_records, for a
-// stream whose device walk declined.  want_off (in): d_off [n_rec + 1] stays too -- kept record r's letters begin at byte
-// d_off[r] of the flat block and d_off[r + 1] - d_off[r] is their number + 1, 0 for a record that is not kept.
-struct BamRecords {
-    uint64_t *d_rec = nullptr;
-    uint32_t *d_keep = nullptr, *d_kidx = nullptr;
-    uint64_t n_rec = 0, kept = 0, hdr_end = 0;
-    const uint64_t *host_rec = nullptr;
-    uint64_t host_n_rec = 0;
-    bool want_off = false;
-    uint64_t *d_off = nullptr;
-    void release();      // the device arrays back to the pool (synchronises)
-};
-int bam_to_flat_dev(const char *d_stream, uint64_t n, const std::vector<uint64_t> &seg, int shard_rank, int shard_world, char **d_flat,
-                    uint64_t *flat_len, uint64_t *flat_cap, uint64_t *n_records, BamRecords *recs = nullptr);
-// bam_to_flat_dev for one rank with `recs` kept, and the host walk (bam_host_records) where the device walk declines.  h_stream:
-// the same bytes on the host, or nullptr (they are copied back then).  SS_ERANGE: more records than hipcub's int item count holds.
-int bam_records_flat_dev(const char *d_stream, uint64_t n, const uint8_t *h_stream, const std::vector<uint64_t> &seg, char **d_flat,
-                         uint64_t *flat_len, uint64_t *flat_cap, BamRecords *recs);
-std::vector<uint64_t> bam_segments(const uint8_t *in, uint64_t in_n, uint64_t n);      // in = NULL: 64 KB pieces
-struct BamHostStream {                   // the inflated stream on the host: s[0, n), released with the object
-    const uint8_t *s = nullptr;
-    uint64_t n = 0;
-    char *text = nullptr;
-    void *map = nullptr;
-    uint64_t map_n = 0;
-    ~BamHostStream();
-};
-int bam_host_stream(const char *path, int kind, BamHostStream *out);
-int bam_host_records(const uint8_t *s, uint64_t n, std::vector<uint64_t> *rec, uint64_t *hdr_end);
-// The inflated stream of a BAM on the device, d[0, n): a file inflated there where the loader would do that (gpu_gunzip: 1 MB and
-// more, not under SS_GZ_GPU=0; `inflated_on_device`), else inflated on the host and uploaded; or a copy of a stream in host memory.
-// h: the same bytes on the host where they are there; seg: bam_segments.  release() (and the destructor) gives everything back.
-struct BamDeviceStream {
-    char *d = nullptr;
-    uint64_t n = 0;
-    const uint8_t *h = nullptr;
-    std::vector<uint64_t> seg;
-    bool inflated_on_device = false;
-    int open_file(const char *path, int kind);
-    int upload(const void *stream, uint64_t n_bytes);
-    void release();
-    ~BamDeviceStream() { release(); }
-private:
-    void *lease = nullptr;
-    char *copy = nullptr;
-    uint64_t copy_cap = 0;
-    BamHostStream hs;
-};
-extern std::atomic<uint64_t> g_bam_dev_files, g_bam_host_files;
-extern std::atomic<long long> g_hook_bam_walk_decline;      // ss_test_hook 7 (ss_bam_dev.hip)
 // What a consumer of input files does with their flat base blocks: ss_scan_files_shard scans them into a table, ss_reads_load
 // keeps them.  ingest_inputs sends every input down the ladder -- BAM, .gz on the device, .gz inflated on the host, the chunked
 // parse, the sequential reader -- and hands each block to the entry of the rung it came from.  `records` / `bases` add up what

@@ -1,6 +1,6 @@
 // ss_host.hip -- host side of the C ABI: error text, device helpers, k-mer FASTA rows,
 // FASTA/FASTQ -> flat base blocks (what jellyfish's sequence parser hands its counter), revcomp.
-#include "ss_common.h"
+#include "ss_bam.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -147,10 +147,10 @@ namespace ss {
 static std::atomic<int> g_min_base_qual{0};
 static std::atomic<uint64_t> g_mask_bases{0}, g_mask_noqual{0};
 int min_base_qual() { return g_min_base_qual.load(); }
-void mask_count(uint64_t bases, uint64_t bam_records_without_qual)
+void mask_count(uint64_t bases, uint64_t records_without_qual)
 {
     if (bases) g_mask_bases += bases;
-    if (bam_records_without_qual) g_mask_noqual += bam_records_without_qual;
+    if (records_without_qual) g_mask_noqual += records_without_qual;
 }
 }  // namespace ss
 
@@ -233,7 +233,7 @@ const char *ss_strerror(int code)
 const char *ss_last_error(void) { return ss::g_last_error; }
 
 // Test hooks, switched by an explicit call only (never by the environment); each flag is defined beside the code that reads it
-// (ss_common.h).  1 = plant a wrong entry in search chunk `value` (0 = off; ss_ginflate.hip), 2 = this process declines .gz inputs
+// (ss_common.h; 7: ss_bam.h).  1 = plant a wrong entry in search chunk `value` (0 = off; ss_ginflate.hip), 2 = this process declines .gz inputs
 // on the device (range mode: it still serves the chain), 3 = this rank leaves range mode without serving the chain (what a crashed
 // peer looks like: the others' bounded wait must end it; ss_gz_range.hip), 4 = which scan
 // kernel of the page index a table goes through (ss_mini.hip launch_scan_mini: 1 = k = 31 through the per-position kernel, 2 = every

@@ -12,7 +12,7 @@
 // copies and kernels of different chunks overlap.  Counting is order independent (integer
 // atomics), so the result equals the sequential path bit for bit.  Anything else (gzip input,
 // multi-line FASTQ, files the boundary rule cannot segment) takes the sequential reader.
-#include "ss_common.h"
+#include "ss_bam.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>

@@ -1,6 +1,6 @@
 // The piece copy: how sixteen lanes write one record (or one joined fragment) to an unaligned place of a new slab.  The one copy
-// scheme of gather_kernel (ss_select.hip), record_gather_kernel (ss_bam_extract.hip) and the two join_kernels (ss_pairs.hip,
-// ss_bam_pairs.hip).  Not part of the C ABI.
+// scheme of gather_kernel (ss_select.hip), record_gather_kernel (ss_bam_extract.hip), tag_copy_kernel (ss_bam_tag.hip) and the two
+// join_kernels (ss_pairs.hip, ss_bam_pairs.hip).  Not part of the C ABI.
 //
 // The new slab is 16-byte aligned and holds records back to back: record after record begins wherever the one before ended, and
 // the sources are unaligned too.  The destination span [D, E) of a record is cut into the 16-byte ALIGNED pieces it touches,
@@ -100,6 +100,13 @@ SS_PIECE_FN void write_span(uint8_t *dst, uint64_t D, uint64_t E, uint32_t lane1
         const uint64_t lo = a > D ? a : D, hi = a + 16u < E ? a + 16u : E;
         store_piece(dst, a, lo, hi, piece_of(a, lo, hi));
     }
+}
+
+// write_span for a span that is a copy: [D, E) of dst = the E - D bytes that stand from position S on in src, a block of n >= 16
+// bytes that holds them all, as they are
+SS_PIECE_FN void copy_span(uint8_t *dst, uint64_t D, uint64_t E, uint32_t lane16, const uint8_t *src, uint64_t n, uint64_t S)
+{
+    write_span(dst, D, E, lane16, [&](uint64_t a, uint64_t, uint64_t) { return fetch16(src, n, (int64_t)S + ((int64_t)a - (int64_t)D)); });
 }
 
 }}  // namespace ss::dev

@@ -1,5 +1,6 @@
-// The first two passes of ss_reads_support (ss_support.hip), shared with ss_reads_select (ss_select.hip): the hits of every record
-// of a resident set against a page-index table, left on the device.  Not part of the C ABI.
+// What the per-read passes over a resident set share: the hits of every record against a page-index table, left on the device
+// (the first two passes of ss_reads_support, ss_support.hip), the records' spans and the gather of a selection into a new set
+// (ss_select.hip), the classification (ss_classify.hip) and the slot labels (ss_label.hip).  Not part of the C ABI.
 #pragma once
 #include "ss_common.h"
 
@@ -77,70 +78,10 @@ struct HipFail {
         return e != hipSuccess;
     }
 };
-
-// What ss_bam_extract.hip and ss_bam_pairs.hip share beside the kernels below.  BamFlatOwner: what bam_records_flat_dev handed
-// over, given back on every way out.
-struct BamFlatOwner {
-    BamRecords &recs;
-    char *&flat;
-    uint64_t &cap;
-    ~BamFlatOwner()
-    {
-        recs.release();
-        if (flat) big_put(flat, cap);
-    }
-};
+// the host clock around a step that ends with the stream synchronised
 using Clock = std::chrono::steady_clock;
 inline double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 inline unsigned grid_for(uint64_t items) { return (unsigned)((items + 255u) / 256u); }      // workgroups of 256 threads, one item each
-// the little-endian 32-bit field at s + p (any alignment): a BAM record's block_size stands at its start
-__device__ __forceinline__ uint32_t ld32_le(const uint8_t *__restrict__ s, uint64_t p)
-{
-    return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24;
-}
-// The 128-bit digest of the read name of the BAM record at s + p (the bytes before the first NUL; l_read_name >= 1 and the bytes
-// lie inside the record: rec_len of ss_bam_dev.hip): *h1 = FNV-1a (64-bit) over the name's bytes and the eight bytes of its length,
-// *h2 = a rotate-xor-multiply hash over the same bytes, closed with the length and the splitmix64 finisher.  The one hash of
-// ss_bam_extract.hip (the template join) and ss_bam_pairs.hip (the mate link).
-__device__ __forceinline__ void bam_name_digest(const uint8_t *__restrict__ s, uint64_t p, unsigned long long *h1, unsigned long long *h2)
-{
-    const uint32_t lrn = s[p + 12];
-    unsigned long long a = 0xCBF29CE484222325ull, b = 0x243F6A8885A308D3ull;
-    uint32_t len = 0;
-    for (; len + 1u < lrn; len++) {
-        const uint32_t c = s[p + 36 + len];
-        if (!c) break;
-        a = (a ^ c) * 0x100000001B3ull;
-        b = (((b << 7) | (b >> 57)) ^ c) * 0x9E3779B97F4A7C15ull;
-    }
-    for (int i = 0; i < 8; i++) a = (a ^ (i == 0 ? len : 0u)) * 0x100000001B3ull;
-    b ^= (unsigned long long)len * 0xD6E8FEB86659FD93ull;
-    b = (b ^ (b >> 30)) * 0xBF58476D1CE4E5B9ull;
-    b = (b ^ (b >> 27)) * 0x94D049BB133111EBull;
-    b ^= b >> 31;
-    *h1 = a;
-    *h2 = b;
-}
-
-// The mate link of a BAM stream's records (ss_bam_pairs.hip; the rule: strainscan_hip.h, "Read pairs from a BAM").  recs: what
-// bam_to_flat_dev left (ss_common.h).  *d_mate [n_rec] and *d_role [n_rec] (0, 1 or 2; kept 0x1 records only) come from `scratch`;
-// counters: records, kept, pairs, orphans, singles, records in violating groups; ms (or nullptr): keys, sort, link, each
-// synchronised.  SS_OK also with violations (counters[5] says so).  n_rec == 0: nothing is allocated.
-int bam_mates_dev(const uint8_t *d_stream, const BamRecords &recs, PoolScratch &scratch, uint32_t **d_mate, uint8_t **d_role,
-                  uint64_t counters[6], double *ms);
-// out_len[r] (r <= n_rec; [n_rec] = 0) = 4 + block_size when kept record r's FRAGMENT -- its own hits plus its mate's -- reaches
-// min_hits, else 0 (d_hits: per kept record, by d_kidx); tot[0] += records written, tot[1] += fragments selected.  Enqueued.
-int bam_fragment_out_len(const uint8_t *d_stream, const BamRecords &recs, const uint32_t *d_mate, const uint32_t *d_hits,
-                         uint32_t min_hits, unsigned long long *d_out_len, unsigned long long *d_tot);
-
-// d_src[0, total) -> dst (host, pageable) through two pinned buffers, chunk by chunk (ss_bam_extract.hip); synchronous
-int bam_download_chunks(const char *d_src, uint64_t total, char *dst);
-// Steps 5 and 6 of ss_bam_pairs.hip on the linked records of a stream (recs with want_off, flat: its flat block of flat_len
-// bytes): the fragments joined into *out, one ASCII slab in fragment order.  n_frag = kept - pairs.  *d_fidx (or nullptr to skip;
-// [n_rec + 1], from `scratch`, nullptr when n_frag == 0): the fragment index of every LEADER -- the earlier record of a fragment;
-// what it holds for other records is the exclusive count of leaders before them.  ms (or nullptr): [0] lengths + scan, [1] join.
-int bam_join_dev(const char *flat, uint64_t flat_len, const BamRecords &recs, PoolScratch &scratch, const uint32_t *d_mate,
-                 const uint8_t *d_role, uint64_t n_frag, ss_reads **out, uint32_t **d_fidx, double *ms);
 
 extern std::atomic<uint64_t> g_join_pairs_calls;      // ss_reads_join_pairs_calls (ss_pairs.hip)
 

@@ -1,4 +1,4 @@
-"""ss_bgzf_write (ss_bam_extract.hip, host only): head + body as BGZF -- members of at most 0xff00 stream bytes and 65536 file
+"""ss_bgzf_write (ss_bam_out.hip, host only): head + body as BGZF -- members of at most 0xff00 stream bytes and 65536 file
 bytes, each with the "BC" field and the right BSIZE, CRC-32 and ISIZE, then the 28-byte EOF block; gzip.decompress gives head +
 body back; a path that cannot be written gives SS_EIO and leaves no file."""
 import gzip
