@@ -428,6 +428,46 @@ int ss_reads_select_class_calls(uint64_t *n);  /* calls so far in this process (
 int ss_reads_join_pairs_dev(const void *flat1_dev, uint64_t n1, const void *flat2_dev, uint64_t n2, int order, ss_reads **out);
 int ss_reads_join_pairs_calls(uint64_t *n);    /* joins so far in this process (diagnostics; "flag off = not run") */
 int ss_reads_load_pairs(const char *path1, const char *path2, int order, ss_reads **out);
+/* The per-read table of `--read_calls` (ss_calls.hip, ss_pairs.hip, ss_extract.hip): which record went where, and on what evidence.
+ * ss_reads_calls: ss_reads_classify for the same arguments -- a record, a hit, h[v], score and class are exactly its -- with the
+ *   results per record.  `records` is the set's non-empty records, numbered in the record order of ss_reads_read_back.
+ *   rec_class[i]: the class of record i.  rec_score[i]: the largest score(v) of record i, 0 when no hit has a node; reported also
+ *   where it lies below min_score (ss_bam_tag_stream's sc).  The HIT LIST of record i is entries rec_first[i] .. rec_first[i + 1] - 1
+ *   of list_node / list_hits: every node v >= 1 with h[v] > 0, in ascending v, list_hits = h[v] (32 bits); hits of k-mers without
+ *   a node are not listed (they stay in node_hits[0]).  rec_first holds records + 1 entries, rec_first[records] == *n_list.
+ *   cap: the entries list_node / list_hits hold; both may be NULL with cap == 0.  That, or any cap < *n_list, returns SS_ERANGE
+ *   with *n_list set, and nothing else is to be used: the caller comes again with room for *n_list.  direct, node_hits, kmers (each
+ *   NULL or [n_nodes + 1]) and ss_reads_classify_ties are what ss_reads_classify gives.  Works on any set: file order, binned
+ *   ASCII, packed, several slabs (the lists then follow that set's record order).  Synchronous.  Errors otherwise as
+ *   ss_reads_classify states them; SS_EINVAL also for a NULL rec_class, rec_score, rec_first or n_list.
+ * ss_reads_load_ordered: ONE FASTA/FASTQ file as one ASCII, unbinned slab in FILE ORDER (plain or gzip, four-line and wrapped,
+ *   CRLF; the base-quality mask with the grammar of ss_fastx_to_flat): record i of the set is the i-th record of the file that
+ *   has a sequence.  ss_reads_load is not involved.  SS_EINVAL: a BAM or CRAM input, a NULL or empty path.  SS_EIO: an unreadable
+ *   file.
+ * ss_read_calls_write (host; no device needed): walks the n_in (1 or 2) input files with the record grammar of ss_fastx_to_flat,
+ *   as ss_extract_write does, and writes to out_paths[f] the header  name TAB node TAB score TAB length TAB hits  and one such
+ *   line per record of input f, in file order.  name: the header line behind its first character up to the first space, tab, CR
+ *   or LF (may be empty).  node: node_value[class] ([n_nodes + 1]; the commands pass the ids of read_classes.tsv and -1 for class
+ *   0).  length: the record's sequence characters (CR not counted).  hits: `id:h` items, id = node_value[v], separated by one
+ *   space, in list order; `-` for an empty list.  n_in == 1: the i-th record of the file that has a sequence takes entry i; a
+ *   record without one has no record in the set, is written as  name -1 0 0 -  and takes no entry.  n_in == 2 (a set of joined
+ *   pairs in line order): record j of BOTH files takes entry j -- a fragment is never empty --, length is the mate's own, node,
+ *   score and hits are the fragment's.  counters[0] records read, [1] lines written (the header apart), [2] lines of class != 0,
+ *   [3] records with an empty sequence.  One file is shared over up to min(16, SS_HOST_THREADS or the CPUs this process may use)
+ *   host threads by the chunks the ordered load parsed it in; the output does not depend on their number.  SS_EIO: the walk does not end at exactly n_records, the two files differ in records, an
+ *   unreadable input, an output that cannot be written.  SS_EINVAL: a BAM or CRAM input, a bad argument, offsets that do not
+ *   ascend, a class or a listed node outside 1..n_nodes (class: 0..n_nodes).  On any error no output file is left behind (the
+ *   text goes to <name>.tmp, renamed at the end). */
+int ss_reads_calls(const ss_db *db, const ss_reads *r, const uint32_t *row_node, uint32_t n_nodes, const uint32_t *parent,
+                   uint32_t min_score, uint32_t *rec_class, uint32_t *rec_score, uint64_t *rec_first /* [records + 1] */,
+                   uint32_t *list_node, uint32_t *list_hits, uint64_t cap, uint64_t *n_list,
+                   uint64_t *direct, uint64_t *node_hits, uint64_t *kmers /* each NULL, or [n_nodes + 1] */);
+int ss_reads_calls_calls(uint64_t *n);     /* calls so far in this process (diagnostics; "flag off = not run") */
+int ss_reads_load_ordered(const char *path, ss_reads **out);
+int ss_read_calls_write(const char *const *in_paths, int n_in /* 1, or 2 for a joined pair set */, const char *const *out_paths,
+                        uint64_t n_records, const uint32_t *rec_class, const uint32_t *rec_score, const uint64_t *rec_first,
+                        const uint32_t *list_node, const uint32_t *list_hits, const int64_t *node_value /* [n_nodes + 1] */,
+                        uint32_t n_nodes, uint64_t counters[4]);
 
 /* --------------------------------------------------------------------------------------------
  * Extracted reads on the host (ss_extract.hip; no device needed).  What ss_reads_select chose is carried back to the input

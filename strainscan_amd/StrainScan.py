@@ -168,6 +168,15 @@ def add_arguments(ap, multi=False):
                          "every record in file order; `samtools view -d sn:<id>` gives the reads of one node.  With --pairs "
                          "both mates carry the fragment's class.  A record that already bears sn or sc stops the file (remove "
                          "them with `samtools view -x sn -x sc`).  Needs one rank (default: off)")
+    ap.add_argument("--read_calls", dest="read_calls", action="store_true",
+                    help="With --classify_reads M and FASTA/FASTQ input: also write OUT/read_calls_<i>.tsv per input file (1 for -i, "
+                         "2 for -j), one line per read in file order: name (the header up to the first blank), node (the read's "
+                         "class as read_classes.tsv names it, -1 for unclassified), score (the hits on the best path, reported "
+                         "below M too), length, and hits (`node:hits` for every node whose k-mers the read carries, ascending by "
+                         "node as classified, `-` for none).  A read without a sequence is `name -1 0 0 -`.  Mates are classified "
+                         "independently; with --pairs both mates of a pair carry the fragment's node, score and hits.  The files "
+                         "are read and classified a second time for this.  Needs one rank and room for another copy of the bases "
+                         "on the device; BAM input has --tag_bam (default: off)")
     ap.add_argument("--pairs", dest="pairs", action="store_true",
                     help="With -j (or a paired BAM under -i alone) and at least one of --read_support, -x N, --bootstrap B, "
                          "--classify_reads M: those reports (and "
@@ -212,6 +221,19 @@ def refuse_tag_bam_alone(ap, args):
     for p in (args.input_fq, args.input_fq2):
         if p and _lib.input_kind(p) != "bam":
             ap.error("--tag_bam needs BAM input, %s is not a BAM (per-read classes of FASTA/FASTQ reads are not written)" % p)
+
+
+def refuse_read_calls_alone(ap, args):
+    """--read_calls without --classify_reads has no classes to write, and a BAM sample's per-read classes are --tag_bam's: the
+    parser's error (exit status 2; only the first bytes of the inputs are looked at, and only once --classify_reads is there)."""
+    if not args.read_calls:
+        return
+    if not args.classify_reads:
+        ap.error("--read_calls needs --classify_reads M")
+    from . import _lib
+    for p in (args.input_fq, args.input_fq2):
+        if p and _lib.input_kind(p) in ("bam", "cram"):
+            ap.error("--read_calls takes FASTA/FASTQ input, %s is a BAM or CRAM (--tag_bam writes a BAM sample's per-read classes)" % p)
 
 
 def refuse_by_strain_alone(ap, args):
@@ -348,6 +370,14 @@ def apply_tag_bam(on, out_dir=None):
     read_reports.tag_bam_reset(on, out_dir)
 
 
+def apply_read_calls(on, out_dir=None):
+    """--read_calls (strainscan_amd.set_read_calls): the tree scans from here on, which classify the reads, also write
+    out_dir/read_calls_<i>.tsv for every FASTA/FASTQ input: a line per read with its name, class, score, length and hit list
+    (read_reports.collect_read_classes).  stdout and the other files are untouched."""
+    from . import read_reports
+    read_reports.read_calls_reset(on, out_dir)
+
+
 def apply_pairs(on):
     """--pairs (strainscan_amd.set_pairs): the per-read reports collected from here on work on the set of joined pairs
     (db.resident_pairs) in the place of the resident reads; the scans do not.  stdout and the identification reports are
@@ -439,6 +469,7 @@ def main(argv=None):
     refuse_extract_class_alone(ap, args)
     refuse_pairs_alone(ap, args)
     refuse_tag_bam_alone(ap, args)
+    refuse_read_calls_alone(ap, args)
 
     fq_dir = args.input_fq
     fq2 = args.input_fq2 or ""
@@ -460,6 +491,7 @@ def main(argv=None):
     apply_classify_reads(args.classify_reads)
     apply_extract_class(args.extract_class)
     apply_tag_bam(args.tag_bam, out_dir)
+    apply_read_calls(args.read_calls, out_dir)
     apply_pairs(args.pairs)
     try:
         identify_database(fq_dir, fq2, db_dir, out_dir, **opts)

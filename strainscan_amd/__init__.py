@@ -20,6 +20,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_classify_reads                         (`strainscan --classify_reads M`: reads per node of the cluster tree, read_reports.CLASSIFY_READS)
     strainscan_amd.set_extract_class                          (`strainscan --extract_class LIST`: the reads of chosen classes, read_reports.EXTRACT_CLASS)
     strainscan_amd.set_tag_bam                                (`strainscan --tag_bam`: a BAM sample written back with each read's class as tags, read_reports.TAG_BAM)
+    strainscan_amd.set_read_calls                             (`strainscan --read_calls`: a line per read with its name, class, score and hit list, read_reports.READ_CALLS)
     strainscan_amd.set_pairs                                  (`strainscan --pairs`: those reports on read pairs as fragments, read_reports.PAIRS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
@@ -117,6 +118,19 @@ def set_tag_bam(on, out_dir=None):
     already bears sn or sc) one line on stderr says why.  Off by default; nothing runs while it is off."""
     from . import read_reports
     read_reports.tag_bam_reset(bool(on), out_dir)
+
+
+def set_read_calls(on, out_dir=None):
+    """`strainscan --read_calls` for callers of the functions above, with set_classify_reads on and a sample of FASTA/FASTQ files:
+    from here on identify_cluster, where it classifies the reads, also writes out_dir/read_calls_<i>.tsv for input file i -- one line
+    per read in file order: name, node (the id read_classes.tsv gives the read's class, -1 for unclassified), score (the hits on
+    the best path), length, and the hit list `id:hits ...` of every node whose k-mers the read carries.  Each file is loaded once
+    more in file order (ReadSet.load_ordered) and classified again (ReadSet.calls); with set_pairs the two files are joined in line
+    order and both mates carry the fragment's numbers.  out_dir defaults to the directory of set_extract_reads, then to the current
+    one.  Where no file can be written (BAM input, several ranks, no room on the device, a file that changed) one line on stderr
+    says why.  Off by default; nothing runs while it is off."""
+    from . import read_reports
+    read_reports.read_calls_reset(bool(on), out_dir)
 
 
 def set_pairs(on):

@@ -127,6 +127,10 @@ SIGNATURES = {
     "ss_reads_join_pairs_dev": (i32, [vp, u64, vp, u64, i32, P(vp)]),
     "ss_reads_join_pairs_calls": (i32, [P(u64)]),
     "ss_reads_load_pairs": (i32, [cp, cp, i32, P(vp)]),
+    "ss_reads_calls": (i32, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, u64, P(u64), vp, vp, vp]),
+    "ss_reads_calls_calls": (i32, [P(u64)]),
+    "ss_reads_load_ordered": (i32, [cp, P(vp)]),
+    "ss_read_calls_write": (i32, [P(cp), i32, P(cp), u64, vp, vp, vp, vp, vp, vp, u32, P(u64)]),
     "ss_scan_reset": (i32, [vp, vp]),
     "ss_scan_flat_dev": (i32, [vp, vp, u64, vp]),
     "ss_scan_flat_host": (i32, [vp, cp, u64]),
@@ -493,6 +497,17 @@ class ReadSet:
         return self
 
     @classmethod
+    def load_ordered(cls, path):
+        """One FASTA/FASTQ file as one ASCII, unbinned slab in FILE ORDER (ss_reads_load_ordered): record i of the set is the i-th
+        record of the file that has a sequence.  What `--read_calls` classifies."""
+        require_gpu()
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        check(lib().ss_reads_load_ordered(os.fsencode(path), C.byref(h)), "ss_reads_load_ordered")
+        self._h = h
+        return self
+
+    @classmethod
     def _pairs_bam(cls, call, where):
         require_gpu()
         self = cls.__new__(cls)
@@ -622,6 +637,42 @@ class ReadSet:
         if want_classes:
             classes = classes[:int(direct.sum())]
         return dict(direct=direct, node_hits=node_hits, kmers=kmers, ties=int(ties.value), classes=classes)
+
+    def calls(self, kdb, row_node, parent, min_score, cap=None):
+        """classify() per record (ss_reads_calls): -> dict(classes=, scores= np.uint32[records], first= np.uint64[records + 1],
+        list_node=, list_hits= np.uint32[n_list], direct=, node_hits=, kmers=, ties=).  The hit list of record i -- every node
+        v >= 1 the record has hits of, ascending, with the hits -- is entries first[i] .. first[i + 1] - 1 of list_node / list_hits;
+        records are numbered in read_back() order.  cap: the list entries to bring room for; None: four per record, and the call
+        is made again with the number it names where that was too few (a second classification: tens of milliseconds)."""
+        rn = np.ascontiguousarray(row_node, np.uint32)
+        if rn.ndim != 1 or rn.size != kdb.n_rows:
+            raise ValueError("one node per row of the table (%d), not %r" % (kdb.n_rows, rn.shape))
+        par = np.ascontiguousarray(parent, np.uint32)
+        if par.ndim != 1 or par.size < 1:
+            raise ValueError("parent holds an entry per node and entry 0")
+        n = par.size - 1
+        room = int(self.info()["n_records"]) + 1           # (ss_reads_info's count includes reads without a base: no fewer)
+        direct, node_hits, kmers = (np.zeros(n + 1, np.uint64) for _ in range(3))
+        classes, scores, first = np.zeros(room, np.uint32), np.zeros(room, np.uint32), np.zeros(room + 1, np.uint64)
+        n_list = C.c_uint64()
+        want = 4 * room + 1024 if cap is None else int(cap)
+        for _ in range(2):
+            list_node, list_hits = np.zeros(max(want, 1), np.uint32), np.zeros(max(want, 1), np.uint32)
+            rc = lib().ss_reads_calls(kdb.handle, self._h, ptr(rn if rn.size else np.zeros(1, np.uint32)), n, ptr(par), int(min_score),
+                                      ptr(classes), ptr(scores), ptr(first), ptr(list_node) if want else None,
+                                      ptr(list_hits) if want else None, want, C.byref(n_list), ptr(direct), ptr(node_hits), ptr(kmers))
+            if rc != SS_ERANGE or cap is not None or n_list.value <= want:
+                break
+            want = int(n_list.value)
+        if rc != SS_OK:
+            e = SSError(rc, "ss_reads_calls")
+            e.n_list = int(n_list.value)                    # (SS_ERANGE with n_list > cap: the room to come again with)
+            raise e
+        ties = C.c_uint64()
+        check(lib().ss_reads_classify_ties(C.byref(ties)), "ss_reads_classify_ties")
+        records = int(direct.sum())
+        return dict(classes=classes[:records], scores=scores[:records], first=first[:records + 1], list_node=list_node[:n_list.value],
+                    list_hits=list_hits[:n_list.value], direct=direct, node_hits=node_hits, kmers=kmers, ties=int(ties.value))
 
     def select_class(self, kdb, row_node, parent, min_score, clades, want_counts=False):
         """A list of new ReadSets, one per entry of `clades`: the records that classify() with the same arguments puts in that
@@ -758,6 +809,35 @@ def extract_write_pairs(in_paths, keys, out_paths):
     check(lib().ss_extract_write_pairs((C.c_char_p * 2)(*ins), 2, ptr(keys) if keys.size else None, keys.shape[0],
                                        (C.c_char_p * 2)(*outs), c), "ss_extract_write_pairs")
     return dict(zip(("read", "written", "pairs"), (int(v) for v in c)))
+
+
+def read_calls_calls():
+    """Calls of ss_reads_calls so far in this process."""
+    return _calls("ss_reads_calls_calls")
+
+
+def read_calls_write(in_paths, out_paths, calls, node_value):
+    """The table of `--read_calls` (ss_read_calls_write): out_paths[f] gets the header and one line  name, node, score, length,
+    hits  per record of in_paths[f], in file order.  calls: what ReadSet.calls returned for the set loaded from in_paths[0] in
+    file order (ReadSet.load_ordered) or, for two paths, joined from both in line order (ReadSet.load_pairs(order=False));
+    node_value: np.int64[n_nodes + 1], what is written for a class or a listed node.  -> dict(read=, written=, classified=,
+    empty=).  No output file is left behind when it fails (SSError; SS_EIO: the files are not those the set was loaded from)."""
+    ins = [os.fsencode(p) for p in in_paths]
+    outs = [os.fsencode(p) for p in out_paths]
+    if len(ins) != len(outs) or len(ins) not in (1, 2):
+        raise ValueError("one or two input paths and as many output paths")
+    classes, scores = (np.ascontiguousarray(calls[k], np.uint32) for k in ("classes", "scores"))
+    first = np.ascontiguousarray(calls["first"], np.uint64)
+    nodes, hits = (np.ascontiguousarray(calls[k], np.uint32) for k in ("list_node", "list_hits"))
+    value = np.ascontiguousarray(node_value, np.int64)
+    if first.size != classes.size + 1 or scores.size != classes.size or nodes.size != hits.size or value.size < 1:
+        raise ValueError("classes, scores [records], first [records + 1], list_node, list_hits [n_list], node_value [n_nodes + 1]")
+    c = (C.c_uint64 * 4)()
+    check(lib().ss_read_calls_write((C.c_char_p * len(ins))(*ins), len(ins), (C.c_char_p * len(outs))(*outs), classes.size,
+                                    ptr(classes) if classes.size else None, ptr(scores) if scores.size else None, ptr(first),
+                                    ptr(nodes) if nodes.size else None, ptr(hits) if hits.size else None, ptr(value), value.size - 1, c),
+          "ss_read_calls_write")
+    return dict(zip(("read", "written", "classified", "empty"), (int(v) for v in c)))
 
 
 def join_pairs_calls():

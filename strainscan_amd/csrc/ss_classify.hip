@@ -25,6 +25,9 @@
 // All of this is classify_records, which leaves its results -- the classes of the records among them -- on the device, in the
 // scratch of the call.  ss_reads_classify copies them back.  ss_bam_tag.hip (`--tag_bam`) calls it through ss_support.h and asks
 // for the best score of every record as well (ClassArgs::rec_score, written only where it is not null: nobody here asks).
+// ss_calls.hip (`--read_calls`, ss_reads_calls) asks for both and for every record's list of (node, hits): classify_kernel then
+// leaves its kept nodes in ClassArgs::stage and their number in ClassArgs::cnt, again behind a null test, and hit_lists_slab makes
+// the lists behind classify_long_kernel of each slab, while pos_node still holds that slab's fields.
 //
 // ss_reads_select_class (`--extract_class`) runs classify_records once and then, per listed clade:
 //   5. select_class_len_kernel: one thread per record, out_len[rec] = the record's class lies in the clade ? length + 1 : 0 --
@@ -43,6 +46,7 @@ constexpr uint32_t CLS_LONG = 4096;      // positions a record may have there
 constexpr uint32_t CLS_LDS = 4096;       // nodes (+ 1) whose direct[] / node_hits[] a workgroup adds up in LDS
 constexpr uint32_t CLS_LONG_WGS = 64;    // workgroups (and dense h[] arrays) of the general pass
 
+using ss::ClassArgs;
 using ss::Classified;
 using ss::Forest;
 
@@ -94,20 +98,6 @@ __device__ __forceinline__ uint32_t lca_of(const Forest &f, uint32_t a, uint32_t
     return a;
 }
 
-// the records of one slab and where their results go
-struct ClassArgs {
-    const uint16_t *pos_node;                   // the slab's fields
-    const unsigned long long *start, *end;      // ASCII slab: spans by record of the set; packed: unused
-    uint64_t rec0, n_rec, n;                    // the slab's first record, its records, its positions
-    uint32_t slot, fixed_len;                   // packed slab: positions per slot, bases per record; else 0
-    uint32_t n_nodes, min_score;
-    unsigned long long *direct, *node_hits;     // [n_nodes + 1]
-    unsigned long long *tot;                    // [0] records whose class came from a tie, [1] records on the list
-    uint32_t *rec_class;                        // [records of the set] or nullptr
-    uint32_t *rec_score;                        // [records of the set] or nullptr: the largest score of the record, below min_score too
-    uint32_t *long_list;                        // [n_rec] records of this slab (slab-relative) left to the general pass
-};
-
 // record g of the slab (every record has a span; one that has none, or a wild one, reads nothing)
 __device__ __forceinline__ RecordSpan span_of(const ClassArgs &A, uint64_t g)
 {
@@ -153,9 +143,21 @@ __global__ __launch_bounds__(256) void classify_kernel(const ClassArgs A, const 
         }
         if (over) {
             A.long_list[atomicAdd(&A.tot[1], 1ull)] = (uint32_t)g;
+            if (A.stage) A.stage[g * CLS_CAP] = 0u;      // (no kept node is 0: the general pass lists this record)
             continue;
         }
         if (!ok) continue;
+        if (A.cnt) {                                 // ss_reads_calls: the kept nodes are the record's list, still unsorted
+            A.cnt[g] = d;
+            if (A.stage) {
+                uint32_t x[CLS_CAP];
+#pragma unroll
+                for (uint32_t i = 0; i < CLS_CAP; i++) x[i] = i < d ? kept[i][t] : 0xFFFFFFFFu;
+                uint4 *dst = reinterpret_cast<uint4 *>(A.stage + g * CLS_CAP);
+                dst[0] = make_uint4(x[0], x[1], x[2], x[3]);
+                dst[1] = make_uint4(x[4], x[5], x[6], x[7]);
+            }
+        }
         // scores: the kept nodes on v's root path, v itself among them
         uint32_t best = 0, cls = 0;
         bool tie = false;
@@ -423,6 +425,13 @@ int ss::classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row
         SS_HIP(scratch.get((void **)&C->d_score, rec_total * 4));
         SS_HIP(ss::l2s::set(C->d_score, 0, rec_total * 4));
     }
+    ss::HitLists *const H = C->lists;
+    if (H) {
+        uint64_t positions = 0;
+        for (const auto &pt : rh.parts) positions += pt.n_rec ? pt.n : 0;
+        rc = ss::hit_lists_begin(H, scratch, rec_total, max_rec, positions);
+        if (rc) return rc;
+    }
     for (const auto &pt : rh.parts) {
         if (!pt.n_rec) continue;
         if (pt.n >= (uint64_t)db->k) {
@@ -433,12 +442,18 @@ int ss::classify_records(const ss_db *db, const ss_reads *R, const uint32_t *row
         }
         SS_HIP(ss::l2s::set(d_tot + 1, 0, 8));
         const ClassArgs A{d_pos, sp.d_start, sp.d_end, pt.rec_base, pt.n_rec, pt.n, pt.sl->packed ? pt.sl->slot : 0u, pt.sl->packed ? pt.sl->L : 0u,
-                          n_nodes, min_score, d_direct, d_hits, d_tot, d_class, C->d_score, d_list};
+                          n_nodes, min_score, d_direct, d_hits, d_tot, d_class, C->d_score, d_list, H ? H->d_cnt : nullptr,
+                          H && H->fill ? H->d_stage : nullptr};
+        if (H) SS_HIP(ss::l2s::set(H->d_cnt, 0, (pt.n_rec + 1) * 8));
         const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 256 * 4 - 1) / (256 * 4), 8192);
         hipLaunchKernelGGL(classify_kernel, dim3(blocks), dim3(256), 0, st, A, F);
         SS_HIP(hipGetLastError());
         hipLaunchKernelGGL(classify_long_kernel, dim3(CLS_LONG_WGS), dim3(256), 0, st, A, F, d_h);
         SS_HIP(hipGetLastError());
+        if (H) {
+            rc = ss::hit_lists_slab(H, A, d_h, CLS_LONG_WGS);
+            if (rc) return rc;
+        }
     }
     return SS_OK;
 }

@@ -23,7 +23,8 @@
 // ss_reads_load_pairs brings each file to the device as ONE flat block in file order -- the text in memory (ss_input_text.h:
 // mapped, or inflated whole), cut at record boundaries by the chunk rule of the parallel parse where that applies, the chunks
 // turned into flat blocks by ss_fastx_to_flat on worker threads and put behind each other BY CHUNK INDEX -- and joins the two.
-// ss_reads_load and ingest_inputs are not involved.
+// ss_reads_load and ingest_inputs are not involved.  ss_reads_load_ordered (`--read_calls`) takes the first half alone: one file as
+// one flat block in file order, kept as it is -- so file_to_flat_dev stays here, where both callers reach it.
 #include "ss_piece_copy.h"
 #include "ss_support.h"
 #include "ss_input_text.h"
@@ -266,6 +267,23 @@ int ss_reads_load_pairs(const char *path1, const char *path2, int order, ss_read
     if (rc == SS_OK) rc = ss_reads_join_pairs_dev(flat[0].d, flat[0].len, flat[1].d, flat[1].len, order, out);
     for (auto &f : flat)
         if (f.d) ss::big_put(f.d, f.cap);
+    return rc;
+}
+
+// One file as one ASCII, unbinned slab in FILE ORDER (`--read_calls`): file_to_flat_dev, then what ss_reads_from_flat_dev does
+// with order == 0.  Record i of the set is the i-th record of the file that has a sequence.
+int ss_reads_load_ordered(const char *path, ss_reads **out)
+{
+    if (!out) return SS_EINVAL;
+    *out = nullptr;
+    if (!path || !path[0]) return SS_EINVAL;
+    int device = 0;
+    SS_HIP(hipGetDevice(&device));
+    FlatDev flat;
+    int rc = file_to_flat_dev(path, device, std::max(1u, ss::ingest_threads()), &flat);
+    if (rc == SS_OK) rc = ss_reads_from_flat_dev(flat.d, flat.len, 0, out);
+    if (flat.d) ss::big_put(flat.d, flat.cap);
+    if (rc != SS_OK) *out = nullptr;
     return rc;
 }
 

@@ -90,9 +90,41 @@ extern std::atomic<uint64_t> g_join_pairs_calls;      // ss_reads_join_pairs_cal
 struct Forest {
     const uint32_t *parent, *depth, *tin, *tout;
 };
+// the records of one slab and where their results go (classify_kernel, classify_long_kernel; the list kernels of ss_calls.hip)
+struct ClassArgs {
+    const uint16_t *pos_node;                   // the slab's fields
+    const unsigned long long *start, *end;      // ASCII slab: spans by record of the set; packed: unused
+    uint64_t rec0, n_rec, n;                    // the slab's first record, its records, its positions
+    uint32_t slot, fixed_len;                   // packed slab: positions per slot, bases per record; else 0
+    uint32_t n_nodes, min_score;
+    unsigned long long *direct, *node_hits;     // [n_nodes + 1]
+    unsigned long long *tot;                    // [0] records whose class came from a tie, [1] records on the list
+    uint32_t *rec_class;                        // [records of the set] or nullptr
+    uint32_t *rec_score;                        // [records of the set] or nullptr: the largest score of the record, below min_score too
+    uint32_t *long_list;                        // [n_rec] records of this slab (slab-relative) left to the general pass
+    unsigned long long *cnt;                    // [n_rec + 1] or nullptr: the listed nodes of every record of this slab (ss_reads_calls)
+    uint32_t *stage;                            // [8 * n_rec] or nullptr: the kept nodes of a record of the fast path, node << 16 | hits
+};
+// The per-record hit lists of ss_reads_calls (ss_calls.hip), which classify_records fills slab by slab while a slab's fields are
+// there.  cap: the entries d_node / d_hits hold; n_list: the entries of all records, counted also where they were not written.
+struct HitLists {
+    uint64_t cap = 0, n_list = 0;
+    bool fill = false;                          // the lists are written (until one slab's do not fit any more)
+    uint32_t *d_node = nullptr, *d_hits = nullptr;
+    unsigned long long *d_first = nullptr;      // [rec_total + 1]
+    unsigned long long *d_cnt = nullptr, *d_off = nullptr;      // [max_rec + 1]: of the slab at work
+    uint32_t *d_stage = nullptr;                // [8 * max_rec]
+    void *d_tmp = nullptr;
+    size_t tmp_bytes = 0;
+};
+// scratch for a set of rec_total records in slabs of at most max_rec records and `positions` positions in all
+int hit_lists_begin(HitLists *H, PoolScratch &scratch, uint64_t rec_total, uint64_t max_rec, uint64_t positions);
+// behind classify_long_kernel of the slab A, whose pos_node, long_list and tot[1] are still there; d_h: the dense h[] arrays, all zero
+int hit_lists_slab(HitLists *H, const ClassArgs &A, uint32_t *d_h, uint32_t long_wgs);
 // What classify_records leaves behind: everything on the device lives in rh.scratch and is enqueued on ss::l2s::stream() when
 // the call returns.
 struct Classified {
+    HitLists *lists = nullptr;                // in: where ss_reads_calls wants the hit lists (nobody else asks)
     RecHits rh;
     RecSpans sp;
     Forest F{nullptr, nullptr, nullptr, nullptr};

@@ -115,6 +115,7 @@ def resident_reads(paths):
                 old.close()
             _READS.clear()
             _close_pairs()
+            _close_ordered()
             # (.gz under torch.distributed: all ranks take the same inflate path for a file, dist.load_agreed)
             before = _lib.mask_counters() if MASK_REPORT["on"] else None
             rs = dist.load_agreed([p for p in paths if p], lambda use: _lib.ReadSet(use, rank, world), discard=lambda r: r.close())
@@ -193,6 +194,67 @@ def resident_pairs(paths):
             print("pairs: %d pairs joined\t%d bytes on the device" % (ji["n_records"], ji["device_bytes"]), file=sys.stderr)
         sys.stderr.flush()
     return js, None
+
+
+_ORDERED = {}        # the sample once more in FILE order (--read_calls): key -> [_lib.ReadSet], closed with the resident set
+
+
+def _close_ordered():
+    for sets in _ORDERED.values():
+        for rs in sets:
+            rs.close()
+    _ORDERED.clear()
+
+
+def ordered_reads(paths, pairs=False):
+    """(sets, None): the sample's files each as one slab in FILE ORDER (ReadSet.load_ordered), one set per file -- or, with
+    `pairs`, ONE set of the two files' records joined in line order (ReadSet.load_pairs(order=False)) --, cached beside the
+    resident reads and closed with them; or (None, why) where they are not built: several ranks, an input that is no
+    FASTA/FASTQ, `pairs` without two files, the plain sample not resident, no room for another copy of the bases, unequal record
+    counts.  The scans never use them: they serve --read_calls (read_reports), which needs record i of a set to be record i of
+    its file."""
+    from . import dist
+    rank, world = dist.rank_world()
+    ps = [p for p in paths if p]
+    if world > 1:
+        return None, "runs on one rank only (this run has several)"
+    if any(_lib.input_kind(p) != "fastx" for p in ps):
+        return None, "takes FASTA/FASTQ inputs"
+    if pairs and len(ps) != 2:
+        return None, "needs the two files of a paired sample (-i and -j) under --pairs"
+    rs = resident_reads(paths)
+    if rs is None:
+        return None, "needs the sample resident on the device (SS_READS_RESIDENT_GB)"
+    key = _reads_key(paths, rank, world) + (bool(pairs),)
+    with _READS_LOCK:
+        sets = _ORDERED.get(key)
+        if sets is not None:
+            return sets, None
+        inf = rs.info()
+        held = inf["device_bytes"] + sum(js.info()["device_bytes"] for js in _PAIRS.values())
+        # the load's peak: the flat blocks of the files and the slab they are copied into, each the bases and their line ends
+        no_room = "has no room for the sample in file order beside the resident reads (SS_READS_RESIDENT_GB)"
+        if held + 2 * (inf["n_bases"] + inf["n_records"]) > RESIDENT_LIMIT_BYTES:
+            return None, no_room
+        sets = []
+        try:
+            if pairs:
+                sets.append(_lib.ReadSet.load_pairs(ps[0], ps[1], order=False))
+            else:
+                for p in ps:
+                    sets.append(_lib.ReadSet.load_ordered(p))
+        except _lib.SSError as e:
+            for s in sets:
+                s.close()
+            if e.code == _lib.SS_ENOMEM:
+                return None, no_room
+            if e.code != _lib.SS_EIO:
+                raise
+            return None, ("could not pair the records of the two files (unequal record counts, or a file that cannot be read)" if pairs
+                          else "could not read the sample's files once more")
+        _close_ordered()
+        _ORDERED[key] = sets
+    return sets, None
 
 
 def prefetch_reads(paths):
@@ -854,3 +916,4 @@ def clear_cache():
         rs.close()
     _READS.clear()
     _close_pairs()
+    _close_ordered()

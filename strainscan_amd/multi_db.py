@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B --classify_reads M --extract_class LIST --tag_bam --pairs]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B --classify_reads M --extract_class LIST --tag_bam --read_calls --pairs]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -78,6 +78,7 @@ def parse_args(argv=None):
     StrainScan.refuse_extract_class_alone(ap, args)
     StrainScan.refuse_pairs_alone(ap, args)
     StrainScan.refuse_tag_bam_alone(ap, args)
+    StrainScan.refuse_read_calls_alone(ap, args)
     try:
         opts = StrainScan.settings(args)
     except ValueError as e:
@@ -174,6 +175,7 @@ def main(argv=None):
     StrainScan.apply_classify_reads(args.classify_reads)
     StrainScan.apply_extract_class(args.extract_class)
     StrainScan.apply_tag_bam(args.tag_bam)      # (database_scope names each database's directory: OUT/<label>/classified_<i>.bam)
+    StrainScan.apply_read_calls(args.read_calls)      # (OUT/<label>/read_calls_<i>.tsv; db.ordered_reads loads the ordered sets once)
     StrainScan.apply_pairs(args.pairs)         # (db.resident_pairs caches the joined set: joined once for all databases)
     try:
         rows = identify_databases((args.input_fq, args.input_fq2 or ""), dbs, out_dir, ksize=opts["ksize"], ldep=opts["ldep"],

@@ -1,5 +1,5 @@
 """The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
---classify_reads and --extract_class; and --pairs, which makes all of them work on read pairs as fragments.
+--classify_reads, --extract_class, --tag_bam and --read_calls; and --pairs, which makes all of them work on read pairs as fragments.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -25,14 +25,14 @@ RECORD_WAS_CUT = "cannot %s the reads of a sample with a record longer than a bl
 
 @contextlib.contextmanager
 def database_scope(label, out_dir):
-    """strainscan-multi, around one database's work: its rows are kept under `label`, -x writes to out_dir/extracted/ and
-    --tag_bam to out_dir."""
-    before = SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"]
-    SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"] = label, out_dir, out_dir
+    """strainscan-multi, around one database's work: its rows are kept under `label`, -x writes to out_dir/extracted/,
+    --tag_bam and --read_calls to out_dir."""
+    before = SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"], READ_CALLS["dir"]
+    SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"], READ_CALLS["dir"] = label, out_dir, out_dir, out_dir
     try:
         yield
     finally:
-        SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"] = before
+        SCOPE["label"], EXTRACT_READS["dir"], TAG_BAM["dir"], READ_CALLS["dir"] = before
 
 
 def tree_scanned(img, paths):
@@ -78,6 +78,7 @@ def reset_all():
     classify_reads_reset()
     extract_class_reset()
     tag_bam_reset()
+    read_calls_reset()
     pairs_reset()
 
 
@@ -707,6 +708,8 @@ def collect_read_classes(img, paths):
         _extract_class_skip("--classify_reads was skipped (%s)" % CLASSIFY_READS["skipped"])
     if TAG_BAM["on"] and CLASSIFY_READS["skipped"] is not None:
         _tag_bam_skip("--classify_reads was skipped (%s)" % CLASSIFY_READS["skipped"])
+    if READ_CALLS["on"] and CLASSIFY_READS["skipped"] is not None:
+        _read_calls_skip("--classify_reads was skipped (%s)" % CLASSIFY_READS["skipped"])
 
 
 def _collect_read_classes(img, paths):
@@ -761,6 +764,7 @@ def _collect_read_classes(img, paths):
                   file=sys.stderr)
             sys.stderr.flush()
         _write_tagged_bams(kdb, row_node, parent, m, node_ids, paths)
+        _write_read_calls(kdb, row_node, parent, m, node_ids, paths)
 
 
 def write_read_classes(out_dir, scope=None):
@@ -823,6 +827,70 @@ def _write_tagged_bams(kdb, row_node, parent, m, node_ids, paths):
         TAG_BAM["files"].append(out)
         print("tag_bam: %s\tM=%d\trecords %d\ttagged %d\tclassified %d\tfragments %d\tfrom a tie %d" %
               (out, m, c["records"], c["tagged"], c["classified"], c["fragments"], c["ties"]), file=sys.stderr)
+        sys.stderr.flush()
+
+
+# --read_calls (StrainScan.apply_read_calls turns it on; it needs --classify_reads M and FASTA/FASTQ input): the per-read line of a
+# k-mer read classifier -- name, node, score, length and the hit list -- as `dir`/read_calls_<i>.tsv for input file i.  The resident
+# set keeps no map back to file order, so the table does not come from it: each file is loaded once more as one slab in FILE ORDER
+# (db.ordered_reads: ReadSet.load_ordered per file; with --pairs the two files joined in line order), classified again with
+# the row_node, parent and M of read_classes.tsv (ReadSet.calls: classes, scores and the hit lists per record), and the writer walks
+# the file a second time and puts the names beside the numbers by position (_lib.read_calls_write; tests/read_calls_model.py restates
+# it).  Without --pairs the mates are classified independently, each file on its own.  The ordered sets are cached beside the
+# resident reads, so strainscan-multi loads them once for all databases.  Written behind read_classes.tsv's numbers, once per scope;
+# whatever keeps a file from being written says one line and takes the files of this run with it; the exit status and every other
+# file stay as they are.
+READ_CALLS = {"on": False, "dir": None, "skipped": None, "files": []}
+READ_CALLS_FILE = "read_calls_%d.tsv"
+
+
+def read_calls_reset(on=False, out_dir=None):
+    READ_CALLS.update(on=bool(on), dir=out_dir, skipped=None, files=[])
+
+
+def _read_calls_skip(why):
+    for f in READ_CALLS["files"]:
+        with contextlib.suppress(OSError):
+            os.remove(f)
+    READ_CALLS["files"] = []
+    _skip(READ_CALLS, "read_calls", "and no per-read table was written", True, why)
+
+
+def _write_read_calls(kdb, row_node, parent, m, node_ids, paths):
+    """read_calls_<i>.tsv for input file i of `paths`, and one line per file on stderr: the file, M, its records, those with a
+    class, and its records without a sequence."""
+    if not READ_CALLS["on"] or READ_CALLS["skipped"] is not None:
+        return
+    if dist.is_distributed():
+        return _read_calls_skip("runs on one rank only (this run has several)")
+    ps = [p for p in paths if p]
+    if any(_lib.input_kind(p) != "fastx" for p in ps):
+        return _read_calls_skip("takes FASTA/FASTQ inputs (a BAM sample's per-read classes are --tag_bam's)")
+    if any(int(nid) != nid for nid in node_ids):
+        return _read_calls_skip("needs integer node ids (this tree has another)")
+    sets, why = db.ordered_reads(paths, PAIRS["on"])
+    if sets is None:
+        return _read_calls_skip(why)
+    node_value = np.array([-1] + [int(nid) for nid in node_ids], np.int64)
+    out_dir = READ_CALLS["dir"] or EXTRACT_READS["dir"] or "."
+    outs = [os.path.join(out_dir, READ_CALLS_FILE % i) for i in range(1, len(ps) + 1)]
+    groups = [(ps, outs, sets[0])] if PAIRS["on"] else [([p], [o], rs) for p, o, rs in zip(ps, outs, sets)]
+    for ins, to, rs in groups:
+        calls = _select_or_skip(lambda: rs.calls(kdb, row_node, parent, m), _read_calls_skip, "list")
+        if calls is None:
+            return
+        try:
+            c = _lib.read_calls_write(ins, to, calls, node_value)
+        except _lib.SSError as e:
+            if e.code != _lib.SS_EIO:
+                raise
+            return _read_calls_skip("%s: the records of the file are not those that were loaded (it changed, or it cannot be read or "
+                                    "written)" % ins[0])
+        READ_CALLS["files"].extend(to)
+        per = len(ins)
+        for o in to:
+            print("read_calls: %s\tM=%d\trecords %d\tclassified %d\tempty %d" %
+                  (o, m, c["read"] // per, c["classified"] // per, c["empty"]), file=sys.stderr)      # (--pairs: the empty mates of both files)
         sys.stderr.flush()
 
 
