@@ -361,6 +361,25 @@ int ss_reads_labeled_calls(uint64_t *n);   /* calls of either so far in this pro
  * Synchronous.  SS_EINVAL: a NULL argument.  SS_ERANGE: a set with a cut record; more records than hipcub's int item count holds. */
 int ss_reads_resample(const ss_reads *r, uint64_t seed, uint32_t replicate, ss_reads **out);
 int ss_reads_resample_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* The counts of several bootstrap replicates from ONE pass over the resident reads (`--bootstrap_clusters`): no replicate is
+ * materialised.  counts_rows_dev[j * n_rows + i] is, bit for bit, what ss_counts_rows_dev returns for row i after these three
+ * steps on a table with the same index:
+ *   1. ss_scan_reset
+ *   2. ss_scan_reads of the set ss_reads_resample(r, seed, first_replicate + j) returns
+ *   3. the read-out itself
+ * Equivalently, it is the sum over the records of r of w(record, seed, first_replicate + j) times the record's hits on the row's
+ * k-mer.  A record, a hit and w are those of ss_reads_support and ss_reads_resample.  Row validity and duplicate rows follow
+ * ss_counts_rows_dev (the last row owns the count).
+ * Synchronous.  Reads the table's index, never its counters (a scan's accumulated counts are the same before and after).  Works
+ * on any resident set (file order, binned ASCII, packed, several slabs) and on page-index tables at 17 <= k <= 31, behind a Bloom
+ * filter or flagged with ss_db_expect_hits.  counts_rows_dev is device memory; every entry is written, so the caller need not
+ * clear it.  The call takes n_replicates x the table's slots x 4 bytes of device scratch for its length.
+ * SS_ERANGE: a flat table (k below 17); a set with a cut record.  SS_EINVAL: a NULL argument; n_replicates outside
+ * 1..SS_SCAN_REPLICATES_MAX; a table and a set on different devices. */
+#define SS_SCAN_REPLICATES_MAX 16
+int ss_scan_reads_resampled(const ss_db *db, const ss_reads *r, uint64_t seed, uint32_t first_replicate, uint32_t n_replicates,
+                            uint32_t *counts_rows_dev /* [n_replicates][n_rows] */);
+int ss_scan_reads_resampled_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
 /* Every record of a resident set assigned to a node of a tree over the table's k-mers (`--classify_reads`); a record and a hit are
  * those of ss_reads_support.  row_node[i], i < the table's rows (host memory): 0 = the row counts for nobody, v in 1..n_nodes = it
  * is a k-mer of node v.  Rows that share a slot (the same k-mer listed twice) keep their common node; where they disagree the

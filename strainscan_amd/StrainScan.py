@@ -51,25 +51,25 @@ def _l1(mdb, in_fq, tdb, cutoff):
     return mod.identify_cluster(in_fq, tdb, cutoff)
 
 
+# the cutoff ladder of -l (StrainScan.py:192-217): [cov, weighted cov, abundance] per rung; -l 0 takes its second rung when the
+# first calls nothing (read_reports.collect_cluster_bootstrap walks the same rungs on resampled counts)
+LADDER_CUTOFFS = {0: ([0.1, 0.4, 1], [0.05, 0.05, 1]), 1: ([0.01, 0.05, 1],), 2: ([0.005, 0.01, 1],)}
+
+
 def identify_with_ladder(in_fq, tdb, ldep, mdb):
     """StrainScan.py:192-217 -> (cls_dict, l2)."""
-    l2 = 0
+    if ldep not in LADDER_CUTOFFS:
+        raise ValueError("-l must be 0, 1 or 2")
+    rungs = LADDER_CUTOFFS[ldep]
+    cls_dict = _l1(mdb, in_fq, tdb, list(rungs[0]))
+    l2 = 0 if ldep == 0 else 1
     if ldep == 0:
-        cls_dict = _l1(mdb, in_fq, tdb, [0.1, 0.4, 1])
         if len(cls_dict) == 0:
-            cls_dict = _l1(mdb, in_fq, tdb, [0.05, 0.05, 1])
+            cls_dict = _l1(mdb, in_fq, tdb, list(rungs[1]))
             l2 = 1
         if len(cls_dict) == 0:
             print("Warning: No clusters can be detected!")
             raise SystemExit
-    elif ldep == 1:
-        cls_dict = _l1(mdb, in_fq, tdb, [0.01, 0.05, 1])
-        l2 = 1
-    elif ldep == 2:
-        cls_dict = _l1(mdb, in_fq, tdb, [0.005, 0.01, 1])
-        l2 = 1
-    else:
-        raise ValueError("-l must be 0, 1 or 2")
     return cls_dict, l2
 
 
@@ -142,7 +142,17 @@ def add_arguments(ap, multi=False):
                          "integer in 2..1000; needs the "
                          "sample resident on the device and k >= 17 (default: off)")
     ap.add_argument("--bootstrap_seed", dest="bootstrap_seed", type=bootstrap_seed_arg, default=1, metavar="S",
-                    help="The seed of --bootstrap's replicates: the same S gives the same file.  An integer in 0..2^63-1 (default: 1)")
+                    help="The seed of --bootstrap's and --bootstrap_clusters' replicates: the same S gives the same files.  An integer in 0..2^63-1 (default: 1)")
+    ap.add_argument("--bootstrap_clusters", dest="bootstrap_clusters", type=bootstrap_arg, default=0, metavar="B",
+                    help="Also write cluster_bootstrap.tsv: would a second sequencing run have called the same clusters?  The "
+                         "reads are resampled B times under the tree walk (a Poisson bootstrap over reads, the replicates of "
+                         "--bootstrap_seed S); the counts of all replicates come from one pass per 16 over the resident reads, and "
+                         "each is walked with this run's -l ladder.  One row per cluster that the run or any replicate called: in "
+                         "how many replicates it is present, and the 2.5 %% and 97.5 %% points of its depth and coverage (0 where "
+                         "absent).  Identical reads share a weight, mates are resampled independently (as one fragment with "
+                         "--pairs); nothing is said about the strains inside a cluster, which is --bootstrap's job.  An integer in "
+                         "2..1000; needs the sample resident on the device, one rank and a database with more than one cluster "
+                         "(default: off)")
     ap.add_argument("--classify_reads", dest="classify_reads", type=classify_reads_arg, default=0, metavar="M",
                     help="Also write read_classes.tsv: every read assigned to a node of the cluster search tree.  A read's hits "
                          "against the tree's k-mers point at the nodes that list them; the read goes to the node whose path from the "
@@ -199,8 +209,8 @@ def refuse_pairs_alone(ap, args):
     from . import _lib
     if args.pairs and not args.input_fq2 and _lib.input_kind(args.input_fq) != "bam":
         ap.error("--pairs needs -j (the second file of the pairs)")
-    if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads):
-        ap.error("--pairs needs at least one of --read_support, -x N, --bootstrap B, --classify_reads M")
+    if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads or args.bootstrap_clusters):
+        ap.error("--pairs needs at least one of --read_support, -x N, --bootstrap B, --classify_reads M, --bootstrap_clusters B")
 
 
 def refuse_extract_class_alone(ap, args):
@@ -346,6 +356,14 @@ def apply_bootstrap(b, seed=1):
     read_reports.bootstrap_reset(b, seed)
 
 
+def apply_bootstrap_clusters(b, seed=1):
+    """--bootstrap_clusters B --bootstrap_seed S (strainscan_amd.set_bootstrap_clusters): the tree walks from here on are run B
+    more times on the counts of resampled reads (read_reports.collect_cluster_bootstrap); the command writes
+    cluster_bootstrap.tsv when it ends.  stdout and the other files are untouched; 0 turns it off."""
+    from . import read_reports
+    read_reports.cluster_bootstrap_reset(b, seed)
+
+
 def apply_classify_reads(m):
     """--classify_reads M (strainscan_amd.set_classify_reads): the tree scans from here on assign every read to a node of the tree
     (read_reports.collect_read_classes); the command writes read_classes.tsv when it ends.  stdout and the other files are
@@ -441,6 +459,7 @@ def identify_layer1(fq_dir, fq2, db_dir, out_dir, ldep, sprob):
     from . import read_reports
     read_reports.collect_called_classes(list(cls_dict), tdb, (identify_low_mem if mdb else identify)._UPPER_KEYS,
                                         [p for p in in_fq if p])      # (--extract_class called)
+    read_reports.collect_cluster_bootstrap(cls_dict, tdb, ldep, mdb, [p for p in in_fq if p])      # (--bootstrap_clusters: the main result is final)
     if len(cls_dict) == 0:
         print("Warning: No clusters can be detected!")
         raise SystemExit
@@ -488,6 +507,7 @@ def main(argv=None):
     apply_extract_reads(args.extract_reads, out_dir)
     apply_by_strain(args.by_strain)
     apply_bootstrap(args.bootstrap, args.bootstrap_seed)
+    apply_bootstrap_clusters(args.bootstrap_clusters, args.bootstrap_seed)
     apply_classify_reads(args.classify_reads)
     apply_extract_class(args.extract_class)
     apply_tag_bam(args.tag_bam, out_dir)

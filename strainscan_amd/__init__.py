@@ -17,6 +17,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_extract_reads                          (`strainscan -x N`: the reads behind each table, read_reports.EXTRACT_READS)
     strainscan_amd.set_by_strain                              (`strainscan --by_strain`: both of the above per called strain, read_reports.BY_STRAIN)
     strainscan_amd.set_bootstrap                              (`strainscan --bootstrap B`: strain depth intervals from resampled reads, read_reports.BOOTSTRAP)
+    strainscan_amd.set_bootstrap_clusters                     (`strainscan --bootstrap_clusters B`: the tree walk on resampled reads, read_reports.CLUSTER_BOOTSTRAP)
     strainscan_amd.set_classify_reads                         (`strainscan --classify_reads M`: reads per node of the cluster tree, read_reports.CLASSIFY_READS)
     strainscan_amd.set_extract_class                          (`strainscan --extract_class LIST`: the reads of chosen classes, read_reports.EXTRACT_CLASS)
     strainscan_amd.set_tag_bam                                (`strainscan --tag_bam`: a BAM sample written back with each read's class as tags, read_reports.TAG_BAM)
@@ -81,6 +82,22 @@ def set_bootstrap(b, seed=1):
         raise ValueError("bootstrap seed must be an integer in 0..2^63-1, not %r" % (seed,))
     from . import read_reports
     read_reports.bootstrap_reset(b or 0, seed)
+
+
+def set_bootstrap_clusters(b, seed=1):
+    """`strainscan --bootstrap_clusters B --bootstrap_seed S` for callers of the functions above: from here on
+    StrainScan.identify_layer1, once the tree walk has returned, takes the counts of the tree's table under `b` replicates of the
+    resident reads (ReadSet.scan_resampled: one pass per 16 replicates, nothing is materialised) and walks each with the run's
+    cutoff ladder.  read_reports.cluster_bootstrap_replicates() returns the replicates' {leaf id: (cls_ab, cls_cov)},
+    read_reports.write_cluster_bootstrap(out_dir) writes cluster_bootstrap.tsv.
+    b is an integer in 2..1000 (0 or None turns it off), seed an integer in 0..2^63-1.  Off by default; nothing runs while it is
+    off."""
+    if b and (isinstance(b, bool) or not isinstance(b, int) or not 2 <= b <= 1000):
+        raise ValueError("bootstrap_clusters must be an integer in 2..1000 (or 0 for off), not %r" % (b,))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= (1 << 63) - 1:
+        raise ValueError("bootstrap seed must be an integer in 0..2^63-1, not %r" % (seed,))
+    from . import read_reports
+    read_reports.cluster_bootstrap_reset(b or 0, seed)
 
 
 def set_classify_reads(m):

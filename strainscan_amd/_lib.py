@@ -115,6 +115,8 @@ SIGNATURES = {
     "ss_reads_labeled_calls": (i32, [P(u64)]),
     "ss_reads_resample": (i32, [vp, u64, u32, P(vp)]),
     "ss_reads_resample_calls": (i32, [P(u64)]),
+    "ss_scan_reads_resampled": (i32, [vp, vp, u64, u32, u32, vp]),
+    "ss_scan_reads_resampled_calls": (i32, [P(u64)]),
     "ss_reads_classify": (i32, [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp]),
     "ss_reads_classify_calls": (i32, [P(u64)]),
     "ss_reads_classify_ties": (i32, [P(u64)]),
@@ -722,6 +724,62 @@ class ReadSet:
         sub._h = h
         return sub
 
+    def scan_resampled(self, kdb, seed, first, n):
+        """The counts of bootstrap replicates first .. first + n - 1 of this set against `kdb` from ONE pass over the reads
+        (ss_scan_reads_resampled): a ReplicateCounts holding n row vectors on the device, vector j bit for bit what
+        resample(seed, first + j) scanned into the reset table would give.  n in 1..SCAN_REPLICATES_MAX.  The table's counters
+        are left alone.  The caller closes it."""
+        out = ReplicateCounts(max(int(n), 0), kdb.n_rows)
+        try:
+            check(lib().ss_scan_reads_resampled(kdb.handle, self._h, int(seed), int(first), max(int(n), 0), out.dptr),
+                  "ss_scan_reads_resampled")
+        except Exception:
+            out.close()
+            raise
+        return out
+
+
+SCAN_REPLICATES_MAX = 16    # SS_SCAN_REPLICATES_MAX (strainscan_hip.h): replicates per call of scan_resampled
+
+
+class ReplicateCounts:
+    """uint32[n, n_rows] on the device: the row vectors ReadSet.scan_resampled fills, one per replicate."""
+
+    def __init__(self, n, n_rows):
+        self.n, self.n_rows = int(n), int(n_rows)
+        d = C.c_void_p()
+        check(lib().ss_dev_alloc(C.byref(d), max(16, self.n * self.n_rows * 4)), "ss_dev_alloc")
+        self.dptr = d
+
+    def vector_dptr(self, j):
+        """The device address of replicate j's vector (what KmerDB.load_counts_rows_dev takes)."""
+        if not 0 <= int(j) < self.n:
+            raise IndexError("replicate %r of %d" % (j, self.n))
+        return C.c_void_p(self.dptr.value + int(j) * self.n_rows * 4)
+
+    def load_into(self, kdb, j, stream=None):
+        """Replicate j's counts become the table's (ss_counts_load_rows_dev)."""
+        kdb.load_counts_rows_dev(self.vector_dptr(j), stream)
+
+    def row_vector(self, j):
+        """A host copy of replicate j's vector, np.uint32[n_rows]."""
+        out = np.zeros(self.n_rows, np.uint32)
+        if self.n_rows:
+            check(lib().ss_memcpy_d2h(ptr(out), self.vector_dptr(j), self.n_rows * 4, None), "ss_memcpy_d2h")
+            check(lib().ss_device_sync(), "ss_device_sync")
+        return out
+
+    def close(self):
+        if getattr(self, "dptr", None):
+            lib().ss_dev_free(self.dptr)
+            self.dptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 LABELS_MAX = 15     # SS_LABELS_MAX (strainscan_hip.h): labels per call of the labelled forms
 
@@ -753,6 +811,11 @@ def select_calls():
 def resample_calls():
     """Calls of ss_reads_resample so far in this process."""
     return _calls("ss_reads_resample_calls")
+
+
+def scan_resampled_calls():
+    """Calls of ss_scan_reads_resampled so far in this process."""
+    return _calls("ss_scan_reads_resampled_calls")
 
 
 CLASS_NODES_MAX = 65535     # SS_CLASS_NODES_MAX (strainscan_hip.h)

@@ -296,6 +296,18 @@ int launch_label_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool 
 // every position of every tile: room for ((n + 1023) / 1024) * 1024 fields, 16-byte aligned.  *hits0 += the hits without a node.
 int launch_class_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, uint16_t *pos_node, const uint16_t *slot_node,
                        unsigned long long *hits0, hipStream_t stream);
+// ss_scan_reads_resampled (ss_scan_resampled.hip): the same with the weight sink.  A found k-mer adds the weights of its record,
+// one per replicate, to the replicates' slot counters: counts[j * stride + slot] += (weights[record] >> 4 j) & 15, slot indexed like
+// d_counts.  The record of a position is found as the support sink finds it; records at or beyond rec_limit add nothing.
+struct ResampledArgs {
+    uint32_t *counts;               // [n_replicates][stride] slot counters of the replicates, cleared by the caller
+    uint64_t stride;                // >= the table's n_slots
+    const uint64_t *weights;        // [rec_limit] sixteen 4-bit weights per record of the set, replicate j at bits 4 j
+    const uint32_t *tile_base;      // ASCII slab: record ends before each 1024-position tile of the slab; packed: unused
+    uint64_t rec_base, rec_limit;   // records of the slabs before this one; records of the set
+    uint32_t slot;                  // packed slab: positions per record
+};
+int launch_resampled_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const ResampledArgs &a, hipStream_t stream);
 // the scan of one table through the same kernel (ss_minik.hip): launch_scan_mini sends it the tables it does not take itself
 int launch_scan_minik(ss_db *db, const uint8_t *bases_dev, uint64_t n, hipStream_t stream, bool packed);
 // the filter kind of a table in a several-tables pass: its own Bloom filter (a tree table), none because it expects hits (a cluster

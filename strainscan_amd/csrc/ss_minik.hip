@@ -80,6 +80,33 @@ struct ClassSink {
     __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *bits, uint32_t p) const { mark(slot_node[cbase + page_slot], bits, p); }
 };
 static_assert(SS_CLASS_NODES_MAX <= 0xFFFF, "a position's node is a 16-bit field");
+// WeightSink (ss_scan_reads_resampled, ss_scan_resampled.hip): the counts of up to sixteen bootstrap replicates from one pass.
+// A found k-mer adds the WEIGHTS of its record -- a 64-bit word of 4-bit fields, one per replicate -- to the replicates' own
+// slot counters, one atomic per field that is not zero.  It needs the record of a hit when the hit is found (the drains keep
+// the lanes in position order: the atomics of one replicate land on neighbouring counters, as the scan's do), so the tile's
+// head leaves a record directory in LDS instead of hit bits, and there is no tail: ctx[0..1] = the record of the tile's first
+// position; packed: ctx[2] = that position's offset in its slot; ASCII: ctx[CTX_REL + l] = record ends in the tile before the 16
+// positions of lane l, and the low / high half of ctx[CTX_BND + l / 2] = the bit of each of those positions that is a record end.
+constexpr int PER_POS_CTX = 64;             // the PER_POS of a sink that keeps a record directory, not bits per position
+constexpr int CTX_REL = 4, CTX_BND = CTX_REL + KT, CTX_WORDS = CTX_BND + KT / 2;
+struct WeightSink {
+    static constexpr int PER_POS = PER_POS_CTX;
+    ss::ResampledArgs a;
+    uint32_t cbase;
+    __device__ __forceinline__ void add(uint32_t slot, const uint32_t *ctx, uint32_t p) const
+    {
+        uint64_t rec = (uint64_t)ctx[0] | ((uint64_t)ctx[1] << 32);
+        if (a.slot) rec += (ctx[2] + p) / a.slot;
+        else rec += ctx[CTX_REL + (p >> 4)] + (uint32_t)__popc((ctx[CTX_BND + (p >> 5)] >> (p & 16u)) & ((1u << (p & 15u)) - 1u));
+        if (rec >= a.rec_limit) return;
+        uint32_t *__restrict__ c = a.counts + slot;
+        for (uint64_t w = a.weights[rec]; w; c += a.stride, w >>= 4)
+            if (w & 15u) atomicAdd(c, (uint32_t)(w & 15u));
+    }
+    __device__ __forceinline__ void bucket(uint32_t slot, uint32_t *ctx, uint32_t p) const { add(slot, ctx, p); }
+    __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *ctx, uint32_t p) const { add(cbase + page_slot, ctx, p); }
+};
+static_assert(SS_SCAN_REPLICATES_MAX <= 16, "a record's weights are 4-bit fields of one 64-bit word");
 // the tile's LDS: the sinks with a tail add the positions' bits and the '\n' flags of the tile's bytes (nl[0]: bit 15 = the byte before the tile)
 // (LEAN: no '\n' flags -- the label sink over a packed slab, which has no '\n': the 132 bytes are what keeps the 21st one-wave
 // workgroup on a CU)
@@ -97,6 +124,11 @@ template <> struct KSharedT<4, true> : KShared {
 template <bool LEAN> struct KSharedT<16, LEAN> : KShared {      // the class sink: 16-bit fields, then a bit per position; no '\n' flags
     static constexpr int HIT_WORDS = KPOS / 2 + KPOS / 32;
     alignas(16) uint32_t hit[HIT_WORDS];
+    __device__ __forceinline__ uint32_t *bits() { return hit; }
+};
+template <bool LEAN> struct KSharedT<PER_POS_CTX, LEAN> : KShared {      // the weight sink: the tile's record directory
+    static constexpr int HIT_WORDS = CTX_WORDS;
+    alignas(8) uint32_t hit[HIT_WORDS];
     __device__ __forceinline__ uint32_t *bits() { return hit; }
 };
 template <bool LEAN> struct KSharedT<0, LEAN> : KShared { __device__ __forceinline__ uint32_t *bits() { return nullptr; } };
@@ -187,7 +219,29 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
             decode_in<IN>(w, code, inv);
             S.code[t] = code;
             S.inv[t] = (uint16_t)inv;
-            if constexpr (SINK::PER_POS != 0) {
+            if constexpr (SINK::PER_POS == PER_POS_CTX) {
+                // the record directory of the weight sink (read by the drains, behind the barriers below)
+                const ss::ResampledArgs &A = sink.a;
+                if constexpr (IN == IN_PACKED) {
+                    if (t == 0) {
+                        const uint64_t q = b0 / A.slot, r0 = A.rec_base + q;
+                        S.hit[0] = (uint32_t)r0;
+                        S.hit[1] = (uint32_t)(r0 >> 32);
+                        S.hit[2] = (uint32_t)(b0 - q * A.slot);
+                    }
+                } else {
+                    const uint32_t nl = newline_mask16(w), before = (uint32_t)__shfl_up((int)nl, 1, 64) >> 15;
+                    const uint32_t prev = t ? (before & 1u) : ((b0 == 0 || bases[b0 - 1] == 0x0Au) ? 1u : 0u);      // (a slab begins behind a boundary)
+                    const uint32_t bnd = nl & ~((nl << 1) | prev) & 0xFFFFu, mine = (uint32_t)__popc(bnd);
+                    S.hit[CTX_REL + t] = wave_inclusive_sum(mine) - mine;
+                    reinterpret_cast<uint16_t *>(&S.hit[CTX_BND])[t] = (uint16_t)bnd;
+                    if (t == 0) {
+                        const uint64_t r0 = A.rec_base + A.tile_base[tile];
+                        S.hit[0] = (uint32_t)r0;
+                        S.hit[1] = (uint32_t)(r0 >> 32);
+                    }
+                }
+            } else if constexpr (SINK::PER_POS != 0) {
                 for (int i = t; i < S.HIT_WORDS; i += KT) S.hit[i] = 0u;
                 if constexpr (IN != IN_PACKED && SINK::PER_POS != 16) {
                     S.nl[t + 1] = (uint16_t)newline_mask16(w);
@@ -330,7 +384,7 @@ __global__ __launch_bounds__(KT) void scan_minik_kernel(const uint8_t *__restric
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
             if (t == 0 && c) atomicAdd(sink.hits0, (unsigned long long)c);
-        } else if constexpr (SINK::PER_POS != 0) {
+        } else if constexpr (SINK::PER_POS != 0 && SINK::PER_POS != PER_POS_CTX) {
             const ss::SupportArgs &A = sink.a;
             uint32_t bnd = 0;
             uint64_t r = A.rec_base;
@@ -408,6 +462,14 @@ int launch_label_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool 
     if (!n || db->layout != 1 || (packed ? a.slot == 0 : a.tile_base == nullptr)) return SS_EINVAL;
     if (!slot_label || n_labels < 1 || n_labels > SS_LABELS_MAX) return SS_EINVAL;
     return launch_minik(db, (const uint8_t *)bases_dev, n, packed, LabelSink{a, slot_label, (uint32_t)db->n_mslots, n_labels}, stream);
+}
+
+// ... and for ss_scan_reads_resampled (ss_scan_resampled.hip): a found k-mer adds its record's weights to the replicates' counters
+int launch_resampled_minik(const ss_db *db, const void *bases_dev, uint64_t n, bool packed, const ResampledArgs &a, hipStream_t stream)
+{
+    if (!n || db->layout != 1 || (packed ? a.slot == 0 : (a.tile_base == nullptr || a.slot != 0))) return SS_EINVAL;
+    if (!a.counts || !a.weights || a.stride < db->n_slots) return SS_EINVAL;
+    return launch_minik(db, (const uint8_t *)bases_dev, n, packed, WeightSink{a, (uint32_t)db->n_mslots}, stream);
 }
 
 // ... and for ss_reads_classify (ss_classify.hip): a found k-mer leaves the node of its slot at its position in pos_node, which

@@ -14,9 +14,10 @@
 //   w   = the entries T_k <= u of POISSON1_CDF: T_k = floor(2^32 * e^-1 * sum_{i <= k} 1/i!), k = 0..12
 //
 // The passes are those of ss_reads_select with a multiplicity in the place of its 0/1 choice, and they are the same code
-// (ss_support.h): record_index_of numbers the records, record_spans_of finds their spans, resample_len_kernel -- the one kernel
-// of this file -- writes out_len[rec] = w * (length + 1), gather_records turns that into offsets, allocates the new slab and
-// copies every record w times.
+// (ss_support.h): record_index_of numbers the records, record_spans_of finds their spans, resample_len_kernel writes
+// out_len[rec] = w * (length + 1), gather_records turns that into offsets, allocates the new slab and copies every record w times.
+// resample_weights_kernel is the length pass of ss_scan_reads_resampled (ss_scan_resampled.hip), which adds w per hit and copies
+// nothing: the same digest and the same table, taken here so that neither is stated twice (resample_weights_of, ss_support.h).
 //
 // resample_len_kernel takes a record per lane: the digest is a chain of one multiply-rotate-multiply step per 8 bytes, 19 steps
 // for a 150-base read, each depending on the one before, so a record cannot be spread over lanes; the lanes of a wave walk
@@ -108,9 +109,53 @@ __global__ __launch_bounds__(256) void resample_len_kernel(const uint8_t *__rest
     add_selected(cnt, bytes, tot);
 }
 
+// The same pass for ss_scan_reads_resampled (ss_scan_resampled.hip), which weighs the hits of a record instead of copying it:
+// out_w[rec] = the weights of replicates first .. first + n_rep - 1 as 4-bit fields (w <= 13), replicate first + j at bits 4 j.
+// mix0 = the mix of replicate `first`; a step of one replicate adds 0x9E3779B97F4A7C15.  The digest is taken once per record.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void resample_weights_kernel(const uint8_t *__restrict__ src, uint64_t n, const unsigned long long *__restrict__ start,
+                                                               const unsigned long long *__restrict__ end, uint64_t rec0, uint64_t n_rec, uint32_t slot,
+                                                               uint32_t fixed_len, uint64_t mix0, uint32_t n_rep, unsigned long long *__restrict__ out_w)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * 256u) {
+        const RecordSpan sp = record_span(PACKED, i, rec0, start, end, slot, fixed_len, n);
+        unsigned long long word = 0;
+        if (sp.ok) {
+            const uint64_t key = record_key<PACKED>(src, n, sp.s, sp.len);
+            uint64_t mix = mix0;
+            for (uint32_t j = 0; j < n_rep; j++, mix += 0x9E3779B97F4A7C15ull) {
+                const uint32_t u = (uint32_t)(splitmix_finish(key + mix) >> 32);
+                uint32_t w = 0;
+#pragma unroll
+                for (int k = 0; k < 13; k++) w += POISSON1_CDF[k] <= u ? 1u : 0u;
+                word |= (unsigned long long)w << (4u * j);
+            }
+        }
+        out_w[rec0 + i] = word;
+    }
+}
+
 std::atomic<uint64_t> g_resample_calls{0};
 
 }  // namespace
+
+// ss_support.h: the weights of n_rep <= 16 replicates from `first` on for every record of the set, into the spans' len[]
+int ss::resample_weights_of(RecHits *rh, RecSpans &sp, uint64_t seed, uint32_t first, uint32_t n_rep)
+{
+    const uint64_t mix0 = 0x9E3779B97F4A7C15ull * ((uint64_t)first + 1ull) + 0xD6E8FEB86659FD93ull * seed;
+    for (const auto &pt : rh->parts) {
+        if (!pt.n_rec) continue;
+        if (pt.n < 16) return SS_EINVAL;                            // (a slab is padded to a multiple of 16)
+        const unsigned blocks = (unsigned)std::min<uint64_t>((pt.n_rec + 255) / 256, 65536);
+        with_bool(pt.sl->packed, [&](auto packed) {
+            hipLaunchKernelGGL(resample_weights_kernel<decltype(packed)::value>, dim3(blocks), dim3(256), 0, ss::l2s::stream(),
+                               (const uint8_t *)pt.sl->d, pt.n, sp.d_start, sp.d_end, pt.rec_base, pt.n_rec, pt.sl->slot,
+                               pt.sl->packed ? pt.sl->L : 0u, mix0, n_rep, sp.d_len);
+        });
+        SS_HIP(hipGetLastError());
+    }
+    return SS_OK;
+}
 
 extern "C" {
 

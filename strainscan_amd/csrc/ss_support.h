@@ -65,6 +65,10 @@ struct RecSpans {
 };
 int record_spans_of(RecHits *rh, RecSpans *sp);
 int gather_records(RecHits *rh, RecSpans &sp, const char *who, ss_reads **out);
+// The length pass of ss_scan_reads_resampled (ss_resample.hip, beside resample_len_kernel and with its digest and Poisson table):
+// len[rec] = the weights the record draws in replicates first .. first + n_rep - 1 of `seed` as 4-bit fields, replicate first + j
+// at bits 4 j (n_rep <= 16); a record whose span does not lie in its slab gets 0.  Enqueued on ss::l2s::stream().
+int resample_weights_of(RecHits *rh, RecSpans &sp, uint64_t seed, uint32_t first, uint32_t n_rep);
 // The resident set that a gather or a join fills (ss_select.hip): n_records records, `total` bytes, in ONE slab allocated from the
 // total and padded to a multiple of 16, the '\n' of the padding enqueued.  *slab: where the caller writes the `total` bytes;
 // nullptr for total == 0, the valid empty set without a slab.  SS_ENOMEM: no memory; SS_EHIP: the fill failed.  Nothing is left then.

@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B --classify_reads M --extract_class LIST --tag_bam --read_calls --pairs]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B --bootstrap_clusters B --classify_reads M --extract_class LIST --tag_bam --read_calls --pairs]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -152,7 +152,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
                 sys.stderr.flush()
                 status = "error:" + type(e).__name__
             finally:
-                read_reports.write_all(od, label)       # (OUT/<label>/read_support.tsv, strain_support.tsv, strain_bootstrap.tsv, read_classes.tsv)
+                read_reports.write_all(od, label)       # (OUT/<label>/read_support.tsv, strain_support.tsv, strain_bootstrap.tsv, cluster_bootstrap.tsv, read_classes.tsv)
             rows.append((label, d, status))
     if rank == 0:
         write_table(os.path.join(out_dir, TSV), rows)
@@ -172,6 +172,7 @@ def main(argv=None):
     StrainScan.apply_extract_reads(args.extract_reads)
     StrainScan.apply_by_strain(args.by_strain)
     StrainScan.apply_bootstrap(args.bootstrap, args.bootstrap_seed)
+    StrainScan.apply_bootstrap_clusters(args.bootstrap_clusters, args.bootstrap_seed)
     StrainScan.apply_classify_reads(args.classify_reads)
     StrainScan.apply_extract_class(args.extract_class)
     StrainScan.apply_tag_bam(args.tag_bam)      # (database_scope names each database's directory: OUT/<label>/classified_<i>.bam)

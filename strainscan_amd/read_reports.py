@@ -1,5 +1,5 @@
 """The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
---classify_reads, --extract_class, --tag_bam and --read_calls; and --pairs, which makes all of them work on read pairs as fragments.
+--bootstrap_clusters, --classify_reads, --extract_class, --tag_bam and --read_calls; and --pairs, which makes all of them work on read pairs as fragments.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -67,6 +67,7 @@ def write_all(out_dir, scope=None):
     write_read_support(out_dir, scope)
     write_strain_support(out_dir, scope)
     write_bootstrap(out_dir, scope)
+    write_cluster_bootstrap(out_dir, scope)
     write_read_classes(out_dir, scope)
 
 
@@ -75,6 +76,7 @@ def reset_all():
     extract_reads_reset()
     by_strain_reset()
     bootstrap_reset()
+    cluster_bootstrap_reset()
     classify_reads_reset()
     extract_class_reset()
     tag_bam_reset()
@@ -643,6 +645,170 @@ def write_bootstrap(out_dir, scope=None):
     lines = [("%s.%d" % (t, n), name, depth, frac, col, rows[t]["coefs"])
              for t in _in_order(BOOTSTRAP["order"].get(scope, []), rows) for n, name, depth, frac, col in rows[t]["called"]]
     return _write(out_dir, BOOTSTRAP_FILE, bootstrap_text(lines)) if lines else None
+
+
+# --bootstrap_clusters B (StrainScan.apply_bootstrap_clusters turns it on; it shares --bootstrap_seed): would a second sequencing
+# run of the library have called the same clusters?  Once the tree walk has returned, collect_cluster_bootstrap takes the counts of
+# the tree's table under B replicates of the reads -- ReadSet.scan_resampled: one pass over the resident reads per chunk of
+# replicates, no replicate is materialised -- loads each vector into the table and runs the walk of this run's cutoff ladder on it;
+# then the main run's counts go back.  "rows": per scope, the main run's {leaf id: (cls_ab, cls_cov)}, the list of the replicates'
+# and the replicates that called nothing (failed); cluster_bootstrap.tsv is a pure function of the first two
+# (cluster_bootstrap_text).  "skipped": per scope, why nothing is written (a database of strainscan-multi that cannot be walked
+# does not take the others with it).
+CLUSTER_BOOTSTRAP = {"b": 0, "seed": 1, "rows": {}, "skipped": {}}
+CLUSTER_BOOTSTRAP_FILE = "cluster_bootstrap.tsv"
+CLUSTER_BOOTSTRAP_VECTOR_BYTES = 1 << 30      # a chunk's row vectors take at most this much (and its slot counters 16 GB)
+CLUSTER_BOOTSTRAP_SLOT_BYTES = 16 << 30
+_CLUSTER_BOOTSTRAP_LOCK = threading.Lock()
+
+
+def cluster_bootstrap_reset(b=0, seed=1):
+    CLUSTER_BOOTSTRAP.update(b=int(b or 0), seed=int(seed), rows={}, skipped={})
+
+
+def _cluster_bootstrap_skip(why):
+    scope = SCOPE["label"]
+    if scope not in CLUSTER_BOOTSTRAP["skipped"]:
+        CLUSTER_BOOTSTRAP["skipped"][scope] = why
+        if dist.rank_world()[0] == 0:
+            print("bootstrap_clusters: %s and no intervals were computed" % why, file=sys.stderr)
+            sys.stderr.flush()
+
+
+def cluster_bootstrap_replicates(scope=None):
+    """The replicates collected under `scope`: a list of B dicts {leaf id: (cls_ab, cls_cov)}, empty for a replicate that called
+    no cluster (tests; cluster_bootstrap.tsv is cluster_bootstrap_text of these and the main run's dict)."""
+    return [dict(r) for r in CLUSTER_BOOTSTRAP["rows"].get(scope, {}).get("replicates", [])]
+
+
+def cluster_bootstrap_failed(scope=None):
+    """The replicates under `scope` whose ladder ended without a cluster."""
+    return int(CLUSTER_BOOTSTRAP["rows"].get(scope, {}).get("failed", 0))
+
+
+def cluster_bootstrap_walk_seed(seed, replicate):
+    """What numpy's global generator is seeded with before replicate `replicate`'s walk (the walk's Poisson draw,
+    cst.Walk.adjust_profile, is unseeded as in the reference): the same S gives the same file.  The generator's state is put
+    back afterwards, so the rest of the run draws what it draws without the flag."""
+    return (int(seed) * 1000003 + int(replicate)) % (1 << 32)
+
+
+def cluster_bootstrap_text(main, replicates):
+    """The text of cluster_bootstrap.tsv: main = the main run's {leaf id: (cls_ab, cls_cov)}, replicates = a list of B such
+    dicts.  One row per cluster that either identified, ascending by id; a replicate without the cluster contributes 0.0; the
+    bounds are the values at bootstrap_index(0.025 / 0.975, B) of the ascending replicate values, as in strain_bootstrap.tsv."""
+    b = len(replicates)
+    out = ["cluster\tcalled\treplicates\tpresent\tdepth\tdepth_lo\tdepth_hi\tcov\tcov_lo\tcov_hi\n"]
+    if not b:
+        return out[0]
+    lo, hi = (bootstrap_index(q, b) for q in BOOTSTRAP_QUANTILES)
+    ids = set(main)
+    for r in replicates:
+        ids.update(r)
+    for cid in sorted(ids):
+        depths = sorted(float(r[cid][0]) if cid in r else 0.0 for r in replicates)
+        covs = sorted(float(r[cid][1]) if cid in r else 0.0 for r in replicates)
+        depth, cov = (str(float(main[cid][0])), str(float(main[cid][1]))) if cid in main else ("-", "-")
+        out.append("\t".join(["C%s" % cid, "1" if cid in main else "0", str(b), str(sum(1 for r in replicates if cid in r)), depth,
+                              str(depths[lo]), str(depths[hi]), cov, str(covs[lo]), str(covs[hi])]) + "\n")
+    return "".join(out)
+
+
+def _ladder_walk(img, tree_db_dir, ldep, params):
+    """What StrainScan.identify_with_ladder runs for -l `ldep`, on the counts the image holds now: the walk at the first rung and,
+    at -l 0, at the second when the first calls nothing.  The trace lines go nowhere."""
+    from . import cst
+    from .StrainScan import LADDER_CUTOFFS
+    res = {}
+    for cutoff in LADDER_CUTOFFS[ldep]:
+        res = cst.Walk(cst.ImageProvider(img), tree_db_dir, list(cutoff), params, out=lambda *a: None).run()
+        if len(res):
+            break
+    return res
+
+
+def collect_cluster_bootstrap(cls_dict, tree_db_dir, ldep, mdb, paths):
+    """Once the tree walk has returned `cls_dict` (final: nothing of the main result is made after this): B walks on resampled
+    counts.  A no-op unless --bootstrap_clusters is on; a scope that has its replicates keeps them.  The table's counters and the
+    image's cached counts and statistics are what they were when this returns, whatever happens in between."""
+    b, seed = CLUSTER_BOOTSTRAP["b"], CLUSTER_BOOTSTRAP["seed"]
+    if not b:
+        return
+    from . import identify, identify_low_mem
+    from .tree import read_tree_structure
+    with _CLUSTER_BOOTSTRAP_LOCK:
+        scope = SCOPE["label"]
+        if scope in CLUSTER_BOOTSTRAP["rows"] or scope in CLUSTER_BOOTSTRAP["skipped"]:
+            return
+        if dist.is_distributed():
+            return _cluster_bootstrap_skip("runs on one rank (the replicates' counts are not summed over ranks),")
+        if PAIRS["on"] and not _pairs_gate(paths):
+            return _cluster_bootstrap_skip("--pairs %s" % PAIRS["skipped"])
+        mod = identify_low_mem if mdb else identify
+        img = db.tree_image(tree_db_dir, mod._UPPER_KEYS)
+        if img.is_external:
+            return _cluster_bootstrap_skip("needs the tree's table scanned by this process (its counts came from elsewhere)")
+        kdb = img.kdb
+        if kdb.k < 17:
+            return _cluster_bootstrap_skip(NEEDS_PAGE_INDEX % kdb.k)
+        if len(read_tree_structure(tree_db_dir)[0]) < 2:
+            return _cluster_bootstrap_skip("needs a cluster search tree (this database has a single cluster)")
+        if not len(cls_dict):
+            return _cluster_bootstrap_skip("the main run detected no cluster")
+        rs = _report_reads(paths)
+        if rs is None:
+            return _cluster_bootstrap_skip(NEEDS_RESIDENT)
+        n_rows, n_slots = max(int(kdb.n_rows), 1), max(int(kdb.info()["n_slots"]), 1)
+        chunk = max(1, min(_lib.SCAN_REPLICATES_MAX, CLUSTER_BOOTSTRAP_VECTOR_BYTES // (4 * n_rows), CLUSTER_BOOTSTRAP_SLOT_BYTES // (4 * n_slots)))
+        replicates, failed = [], 0
+        cached = img._counts, img._stats
+        rng = np.random.get_state()
+        saved = _lib.ReplicateCounts(1, kdb.n_rows)
+        try:
+            kdb.counts_rows_dev(saved.dptr)
+            _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
+            try:
+                for first in range(0, b, chunk):
+                    n = min(chunk, b - first)
+                    out = _select_or_skip(lambda: rs.scan_resampled(kdb, seed, first, n), _cluster_bootstrap_skip, "resample")
+                    if out is None:
+                        return
+                    with contextlib.closing(out):
+                        for j in range(n):
+                            out.load_into(kdb, j)
+                            img._counts = img._stats = None
+                            np.random.seed(cluster_bootstrap_walk_seed(seed, first + j))
+                            try:
+                                res = _ladder_walk(img, tree_db_dir, ldep, mod._PARAMS)
+                            except (ValueError, IndexError):      # (the empty max of the walk's last resort, as the reference raises it)
+                                res = {}
+                            failed += 0 if len(res) else 1
+                            replicates.append({cid: (float(e["cls_ab"]), float(e["cls_cov"])) for cid, e in res.items()})
+                        _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
+            finally:
+                # everything after this point sees the main run's counts
+                kdb.load_counts_rows_dev(saved.dptr)
+                _lib.check(_lib.lib().ss_device_sync(), "ss_device_sync")
+                img._counts, img._stats = cached
+                np.random.set_state(rng)
+        finally:
+            saved.close()
+        main = {cid: (float(e["cls_ab"]), float(e["cls_cov"])) for cid, e in cls_dict.items()}
+        CLUSTER_BOOTSTRAP["rows"][scope] = dict(main=main, replicates=replicates, failed=failed)
+        seen = set()
+        for r in replicates:
+            seen.update(r)
+        print("bootstrap_clusters: B=%d\tS=%d\tcalled %d\tseen in a replicate %d\tfailed %d" % (b, seed, len(main), len(seen), failed),
+              file=sys.stderr)
+        sys.stderr.flush()
+
+
+def write_cluster_bootstrap(out_dir, scope=None):
+    """out_dir/cluster_bootstrap.tsv from the replicates collected under `scope`; nothing without the flag or after a skip."""
+    r = CLUSTER_BOOTSTRAP["rows"].get(scope)
+    if not CLUSTER_BOOTSTRAP["b"] or scope in CLUSTER_BOOTSTRAP["skipped"] or not r:
+        return None
+    return _write(out_dir, CLUSTER_BOOTSTRAP_FILE, cluster_bootstrap_text(r["main"], r["replicates"]))
 
 
 
