@@ -424,6 +424,48 @@ int ss_reads_select_class(const ss_db *db, const ss_reads *r, const uint32_t *ro
                           uint32_t min_score, const uint32_t *clades, uint32_t n_clades, ss_reads **out /* [n_clades] */,
                           uint64_t *direct, uint64_t *node_hits, uint64_t *kmers /* each NULL, or [n_nodes + 1] */);
 int ss_reads_select_class_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* Every record of a resident set assigned to the SET of called strains that explain it best (`--classify_strains`); a record and a
+ * hit are those of ss_reads_support.  The caller numbers the called strains 1..n_strains.  row_sets[i], i < the table's rows (host
+ * memory), is the row's MASK: bit j - 1 is set when strain j has the row's k-mer.  Rows that share a slot (the same k-mer listed
+ * twice) keep their common mask; where they disagree the k-mer has mask 0.
+ *   h[j]   = the record's hits whose k-mer's mask has bit j - 1;  h0 = its hits whose k-mer has mask 0
+ *   score  = the largest h[j]
+ *   set    = { j : h[j] == score } when score >= min_score and score > 0, the empty set otherwise; one strain: a UNIQUE
+ *            assignment, several: a TIE, none: unassigned
+ * unique[j], j in 1..n_strains: records whose set is {j}; unique[0]: records with the empty set.  tied[j]: records with j in a set
+ * of two or more; tied[0]: records with such a set, so sum(unique) + tied[0] = the set's non-empty records.  strain_hits[j] = the
+ * sum of h[j] over all records, strain_hits[0] that of h0.  kmers[j]: the distinct k-mers (slots) whose mask has bit j - 1,
+ * kmers[0] = 0.  All four hold n_strains + 1 entries.  set_reads (NULL to skip): [1 << n_strains], set_reads[m] = records whose set
+ * is the mask m, so set_reads[0] = unique[0] and set_reads[1 << (j-1)] = unique[j].  rec_set / rec_score (host memory, NULL to
+ * skip): the set and the score of every record -- the score also where it is below min_score -- in the record order of
+ * ss_reads_read_back.  When every mask has at most one bit, h[j] is label j's hits of ss_reads_support_labeled.  Nothing depends on
+ * the order of the records: file order, binned ASCII and packed slabs give the same totals, and the results of a set's shards add
+ * up to the whole set's.  Synchronous.  Reads the table's index, never its counters.  SS_ERANGE: as ss_reads_select states it.
+ * SS_EINVAL: a NULL argument other than set_reads, rec_set and rec_score; min_score == 0; n_strains outside 1..SS_STRAIN_SET_MAX;
+ * a row mask with a bit at or above n_strains; a table and a set on different devices. */
+#define SS_STRAIN_SET_MAX 16
+int ss_reads_classify_strains(const ss_db *db, const ss_reads *r, const uint16_t *row_sets, uint32_t n_strains, uint32_t min_score,
+                              uint64_t *unique, uint64_t *tied, uint64_t *strain_hits, uint64_t *kmers /* each [n_strains + 1] */,
+                              uint64_t *set_reads, uint16_t *rec_set, uint32_t *rec_score);
+int ss_reads_classify_strains_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* the records with a tie (tied[0]) in the calling thread's last ss_reads_classify_strains or ss_reads_select_strains */
+int ss_reads_classify_strains_ties(uint64_t *n);
+/* The records of chosen strain sets as NEW resident sets (`--extract_strains`): one classification of the set, exactly that of
+ * ss_reads_classify_strains for the same row_sets, n_strains and min_score, and one set per entry i < n_want (host memory):
+ *   how[i] == 0:  out[i] holds the records whose set EQUALS the mask want[i]; want[i] == 0: the unassigned records
+ *   how[i] == 1:  out[i] holds the records whose set INTERSECTS want[i] (never a record with the empty set)
+ * The same entry may be listed twice: each gets its own set.  An empty record is never selected.  Every out[i] has the layout of
+ * ss_reads_select's *out, and the caller destroys each.  unique, tied, strain_hits and kmers, each NULL or [n_strains + 1], are
+ * what ss_reads_classify_strains returns.  The sets of the records stay on the device, and the set is classified once however
+ * many entries are listed.  Synchronous.  Reads the table's index, never its counters.  SS_ERANGE: as ss_reads_select states it.
+ * SS_EINVAL: as ss_reads_classify_strains states it (but the four arrays may be NULL), and want, how or out NULL, n_want outside
+ * 1..SS_SELECT_STRAINS_MAX, a want[i] with a bit at or above n_strains, a how[i] above 1.  On any error every set made so far is
+ * destroyed and every out[i] is NULL. */
+#define SS_SELECT_STRAINS_MAX 32
+int ss_reads_select_strains(const ss_db *db, const ss_reads *r, const uint16_t *row_sets, uint32_t n_strains, uint32_t min_score,
+                            const uint16_t *want, const uint8_t *how, uint32_t n_want, ss_reads **out /* [n_want] */,
+                            uint64_t *unique, uint64_t *tied, uint64_t *strain_hits, uint64_t *kmers /* each NULL, or [n_strains + 1] */);
+int ss_reads_select_strains_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
 /* Read PAIRS as the records of a resident set (`--pairs`, ss_pairs.hip).  A resident set keeps no pair map, and every call above
  * decides per record from the record's bytes alone: on a set whose records are the pairs they all work on fragments, unchanged.
  * The join rule: record i of the result is  line1[i] + 'N' + line2[i] + '\n'.  'N' ends a k-mer window, so no k-mer spans the

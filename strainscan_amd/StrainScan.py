@@ -169,6 +169,23 @@ def add_arguments(ap, multi=False):
                          "clusters the tree walk identifies, each as class_C<id>_*).  Written with -x's rules: the original text in "
                          "file order, selected by content, a pair when either mate is in the class -- so a pair under "
                          "`unclassified` has at least one unclassified mate.  Needs FASTA/FASTQ input and one rank (default: off)")
+    ap.add_argument("--classify_strains", dest="classify_strains", type=classify_strains_arg, default=0, metavar="M",
+                    help="Also write strain_classes.tsv and strain_sets.tsv: every read assigned to the called strains of a "
+                         "cluster that explain it best.  After a cluster's StrainVote.report is written, a read's hits against "
+                         "the cluster's k-mers vote for every called strain that has the k-mer; the read's set is the strains "
+                         "with the most votes -- one strain: a unique assignment, several: a tie -- and empty (`unassigned`) "
+                         "below M votes.  strain_classes.tsv has a row per called strain: its k-mers, their hits, the reads "
+                         "assigned to it alone (reads_unique), in a tie (reads_tied) and its share when a tied read is split "
+                         "evenly (reads_share); strain_sets.tsv has a row per set with reads.  Identical reads share a set, "
+                         "mates are assigned independently (as one fragment with --pairs), a strain that is not called gets "
+                         "no reads.  An integer >= 1; needs the sample resident on the device, one rank and clusters with at "
+                         "most 16 called strains (default: off)")
+    ap.add_argument("--extract_strains", dest="extract_strains", choices=("unique", "compatible"), default=None,
+                    help="With --classify_strains M: also write the reads of every called strain to "
+                         "OUT/extracted/strain_C<id>.<n>_1.<ext> (and _2 with -j) -- `unique`: the reads assigned to the strain "
+                         "alone; `compatible`: those whose set holds the strain.  Written with -x's rules: the original text "
+                         "in file order, selected by content, a pair when either mate is selected (with --pairs: the "
+                         "fragment).  Needs FASTA/FASTQ input (default: off)")
     ap.add_argument("--tag_bam", dest="tag_bam", action="store_true",
                     help="With --classify_reads M and BAM input (every input a BAM): also write OUT/classified_<i>.bam per input "
                          "file, the input written back with the class of every read as two aux tags -- sn:i:<node of "
@@ -209,7 +226,8 @@ def refuse_pairs_alone(ap, args):
     from . import _lib
     if args.pairs and not args.input_fq2 and _lib.input_kind(args.input_fq) != "bam":
         ap.error("--pairs needs -j (the second file of the pairs)")
-    if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads or args.bootstrap_clusters):
+    if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads or args.bootstrap_clusters
+                           or args.classify_strains):
         ap.error("--pairs needs at least one of --read_support, -x N, --bootstrap B, --classify_reads M, --bootstrap_clusters B")
 
 
@@ -218,6 +236,13 @@ def refuse_extract_class_alone(ap, args):
     input is opened)."""
     if args.extract_class and not args.classify_reads:
         ap.error("--extract_class needs --classify_reads M")
+
+
+def refuse_extract_strains_alone(ap, args):
+    """--extract_strains without --classify_strains has no sets to take reads from: the parser's error (exit status 2, before any
+    input is opened)."""
+    if args.extract_strains and not args.classify_strains:
+        ap.error("--extract_strains needs --classify_strains M")
 
 
 def refuse_tag_bam_alone(ap, args):
@@ -284,6 +309,11 @@ def classify_reads_arg(text):
     if m < 1 or m > 0xFFFFFFFF:
         raise argparse.ArgumentTypeError("%d is outside 1..%d" % (m, 0xFFFFFFFF))
     return m
+
+
+def classify_strains_arg(text):
+    """--classify_strains' value: an integer of at least 1, or the parser's error (exit status 2, before any input is opened)."""
+    return classify_reads_arg(text)
 
 
 def extract_class_arg(text):
@@ -378,6 +408,22 @@ def apply_extract_class(items):
     other files are untouched; nothing turns it off."""
     from . import read_reports
     read_reports.extract_class_reset(items)
+
+
+def apply_classify_strains(m):
+    """--classify_strains M (strainscan_amd.set_classify_strains): the multi-strain clusters solved from here on assign every read
+    to its best called strains (read_reports.collect_strain_classes); the command writes strain_classes.tsv and strain_sets.tsv
+    when it ends.  stdout and the other files are untouched; 0 turns it off."""
+    from . import read_reports
+    read_reports.classify_strains_reset(m)
+
+
+def apply_extract_strains(mode):
+    """--extract_strains unique|compatible (strainscan_amd.set_extract_strains): the clusters that assign their reads also write
+    each called strain's reads beside -x's files (read_reports.collect_strain_classes).  stdout and the other files are untouched;
+    None turns it off."""
+    from . import read_reports
+    read_reports.extract_strains_reset(mode)
 
 
 def apply_tag_bam(on, out_dir=None):
@@ -486,6 +532,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     refuse_by_strain_alone(ap, args)
     refuse_extract_class_alone(ap, args)
+    refuse_extract_strains_alone(ap, args)
     refuse_pairs_alone(ap, args)
     refuse_tag_bam_alone(ap, args)
     refuse_read_calls_alone(ap, args)
@@ -510,6 +557,8 @@ def main(argv=None):
     apply_bootstrap_clusters(args.bootstrap_clusters, args.bootstrap_seed)
     apply_classify_reads(args.classify_reads)
     apply_extract_class(args.extract_class)
+    apply_classify_strains(args.classify_strains)
+    apply_extract_strains(args.extract_strains)
     apply_tag_bam(args.tag_bam, out_dir)
     apply_read_calls(args.read_calls, out_dir)
     apply_pairs(args.pairs)

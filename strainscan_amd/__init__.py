@@ -22,6 +22,8 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_extract_class                          (`strainscan --extract_class LIST`: the reads of chosen classes, read_reports.EXTRACT_CLASS)
     strainscan_amd.set_tag_bam                                (`strainscan --tag_bam`: a BAM sample written back with each read's class as tags, read_reports.TAG_BAM)
     strainscan_amd.set_read_calls                             (`strainscan --read_calls`: a line per read with its name, class, score and hit list, read_reports.READ_CALLS)
+    strainscan_amd.set_classify_strains                       (`strainscan --classify_strains M`: every read assigned to its best called strains, read_reports.CLASSIFY_STRAINS)
+    strainscan_amd.set_extract_strains                        (`strainscan --extract_strains unique|compatible`: the reads of each called strain, read_reports.EXTRACT_STRAINS)
     strainscan_amd.set_pairs                                  (`strainscan --pairs`: those reports on read pairs as fragments, read_reports.PAIRS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
@@ -148,6 +150,32 @@ def set_read_calls(on, out_dir=None):
     says why.  Off by default; nothing runs while it is off."""
     from . import read_reports
     read_reports.read_calls_reset(bool(on), out_dir)
+
+
+def set_classify_strains(m):
+    """`strainscan --classify_strains M` for callers of the functions above: from here on vote_strain_L2_batch, after a multi-strain
+    cluster has written its StrainVote.report, assigns every read of the sample to the set of the cluster's called strains with the
+    most of the read's k-mer hits (ReadSet.classify_strains: one strain is a unique assignment, several a tie, none below m hits)
+    and keeps the numbers with read_reports.CLASSIFY_STRAINS; read_reports.write_strain_classes(out_dir) writes strain_classes.tsv
+    and strain_sets.tsv.  A cluster with more than 16 called strains is passed over with one line on stderr.
+    m is an integer >= 1 (0 or None turns it off).  Off by default; nothing runs while it is off."""
+    if m and (isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 0xFFFFFFFF):
+        raise ValueError("classify_strains must be an integer >= 1 (or 0 for off), not %r" % (m,))
+    from . import read_reports
+    read_reports.classify_strains_reset(m or 0)
+
+
+def set_extract_strains(mode, out_dir=None):
+    """`strainscan --extract_strains unique|compatible` for callers of the functions above, with set_classify_strains on: every
+    cluster that assigns its reads also writes out_dir/extracted/strain_C<id>.<n>_1.<ext> (and _2 for a pair) per called strain --
+    "unique": the reads assigned to the strain alone, "compatible": those whose set holds it; out_dir defaults to the directory of
+    set_extract_reads, then to the current one.  None turns it off.  Off by default; nothing runs while it is off."""
+    from . import read_reports
+    if mode is not None and mode not in read_reports.EXTRACT_STRAINS_MODES:
+        raise ValueError("extract_strains must be one of %s (or None for off), not %r" % (", ".join(read_reports.EXTRACT_STRAINS_MODES), mode))
+    read_reports.extract_strains_reset(mode)
+    if out_dir is not None:
+        read_reports.EXTRACT_READS["dir"] = out_dir
 
 
 def set_pairs(on):

@@ -122,6 +122,11 @@ SIGNATURES = {
     "ss_reads_classify_ties": (i32, [P(u64)]),
     "ss_reads_select_class": (i32, [vp, vp, vp, u32, vp, u32, vp, u32, P(vp), vp, vp, vp]),
     "ss_reads_select_class_calls": (i32, [P(u64)]),
+    "ss_reads_classify_strains": (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "ss_reads_classify_strains_calls": (i32, [P(u64)]),
+    "ss_reads_classify_strains_ties": (i32, [P(u64)]),
+    "ss_reads_select_strains": (i32, [vp, vp, vp, u32, u32, vp, vp, u32, P(vp), vp, vp, vp, vp]),
+    "ss_reads_select_strains_calls": (i32, [P(u64)]),
     "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
@@ -708,6 +713,58 @@ class ReadSet:
         check(lib().ss_reads_classify_ties(C.byref(ties)), "ss_reads_classify_ties")
         return sets, dict(direct=direct, node_hits=node_hits, kmers=kmers, ties=int(ties.value))
 
+    def classify_strains(self, kdb, row_sets, n_strains, min_score, want_sets=True, want_records=False):
+        """Every record assigned to the set of called strains that explain it best (ss_reads_classify_strains;
+        tests/strain_set_model.py restates it).  row_sets[i]: the mask of row i of the table, bit j - 1 set when called strain j
+        (1..n_strains) has its k-mer.  -> dict(unique=, tied=, strain_hits=, kmers= np.uint64[n_strains + 1], ties= records with a
+        tie, set_reads= np.uint64[1 << n_strains] or None, sets= np.uint16 and scores= np.uint32 per record in read_back() order,
+        or None).  Rows that share a k-mer under different masks count for mask 0.  The table's counters are left alone."""
+        rs = _row_sets(kdb, row_sets)
+        n = max(int(n_strains), 0)
+        uniq, tied, hits, kmers = (np.zeros(n + 1, np.uint64) for _ in range(4))
+        set_reads = np.zeros(1 << n, np.uint64) if want_sets and 1 <= n <= STRAIN_SET_MAX else None
+        sets = scores = None
+        if want_records:
+            # (the records as ss_reads_support counts them: ss_reads_info's count includes reads without a base)
+            room = max(1, int(self.support(kdb, 2)[0].sum()))
+            sets, scores = np.zeros(room, np.uint16), np.zeros(room, np.uint32)
+        check(lib().ss_reads_classify_strains(kdb.handle, self._h, ptr(rs), n, int(min_score), ptr(uniq), ptr(tied), ptr(hits), ptr(kmers),
+                                              ptr(set_reads) if set_reads is not None else None, ptr(sets) if want_records else None,
+                                              ptr(scores) if want_records else None), "ss_reads_classify_strains")
+        ties = C.c_uint64()
+        check(lib().ss_reads_classify_strains_ties(C.byref(ties)), "ss_reads_classify_strains_ties")
+        if want_records:
+            records = int(uniq.sum() + tied[0])
+            sets, scores = sets[:records], scores[:records]
+        return dict(unique=uniq, tied=tied, strain_hits=hits, kmers=kmers, ties=int(ties.value), set_reads=set_reads, sets=sets, scores=scores)
+
+    def select_strains(self, kdb, row_sets, n_strains, min_score, want, how, want_counts=False):
+        """A list of new ReadSets, one per entry of `want` (masks) and `how` (0: the records whose set equals the mask, mask 0 the
+        unassigned ones; 1: the records whose set shares a strain with it), from the sets classify_strains() with the same
+        arguments gives (ss_reads_select_strains).  The set is classified once.  Each set is one ASCII, unbinned block in an
+        unspecified order; the caller closes each.  want_counts: -> (sets, dict(unique=, tied=, strain_hits=, kmers=, ties=))."""
+        rs = _row_sets(kdb, row_sets)
+        n = max(int(n_strains), 0)
+        w = np.ascontiguousarray(want, np.uint16)
+        h = np.ascontiguousarray(how, np.uint8)
+        if w.ndim != 1 or h.shape != w.shape:
+            raise ValueError("want and how are lists of the same length")
+        uniq, tied, hits, kmers = (np.zeros(n + 1, np.uint64) if want_counts else None for _ in range(4))
+        hs = (C.c_void_p * max(int(w.size), 1))()
+        check(lib().ss_reads_select_strains(kdb.handle, self._h, ptr(rs), n, int(min_score), ptr(w if w.size else np.zeros(1, np.uint16)),
+                                            ptr(h if h.size else np.zeros(1, np.uint8)), int(w.size), hs,
+                                            *(ptr(a) if want_counts else None for a in (uniq, tied, hits, kmers))), "ss_reads_select_strains")
+        sets = []
+        for x in hs[:w.size]:
+            sub = ReadSet.__new__(ReadSet)
+            sub._h = C.c_void_p(x)
+            sets.append(sub)
+        if not want_counts:
+            return sets
+        ties = C.c_uint64()
+        check(lib().ss_reads_classify_strains_ties(C.byref(ties)), "ss_reads_classify_strains_ties")
+        return sets, dict(unique=uniq, tied=tied, strain_hits=hits, kmers=kmers, ties=int(ties.value))
+
     def order(self):
         """Put the records of a set in file order (from_flat_dev(order=False), select(), resample()) in locality order, in place
         (ss_reads_order): the records and every count stay, a scan of a cluster table gets faster.  -> self"""
@@ -832,6 +889,27 @@ CLASS_CLADES_MAX = 64       # SS_SELECT_CLADES_MAX (strainscan_hip.h): clades pe
 def select_class_calls():
     """Calls of ss_reads_select_class so far in this process."""
     return _calls("ss_reads_select_class_calls")
+
+
+STRAIN_SET_MAX = 16         # SS_STRAIN_SET_MAX (strainscan_hip.h): called strains per call of classify_strains
+SELECT_STRAINS_MAX = 32     # SS_SELECT_STRAINS_MAX (strainscan_hip.h): entries per call of select_strains
+
+
+def _row_sets(kdb, row_sets):
+    rs = np.ascontiguousarray(row_sets, np.uint16)
+    if rs.ndim != 1 or rs.size != kdb.n_rows:
+        raise ValueError("one mask per row of the table (%d), not %r" % (kdb.n_rows, rs.shape))
+    return rs if rs.size else np.zeros(1, np.uint16)
+
+
+def classify_strains_calls():
+    """Calls of ss_reads_classify_strains so far in this process."""
+    return _calls("ss_reads_classify_strains_calls")
+
+
+def select_strains_calls():
+    """Calls of ss_reads_select_strains so far in this process."""
+    return _calls("ss_reads_select_strains_calls")
 
 
 def flat_record_keys(flat):

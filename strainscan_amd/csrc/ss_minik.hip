@@ -80,6 +80,7 @@ struct ClassSink {
     __device__ __forceinline__ void inline_slot(uint32_t page_slot, uint32_t *bits, uint32_t p) const { mark(slot_node[cbase + page_slot], bits, p); }
 };
 static_assert(SS_CLASS_NODES_MAX <= 0xFFFF, "a position's node is a 16-bit field");
+static_assert(SS_STRAIN_SET_MAX <= 16, "... or a mask of called strains (ss_strain_sets.hip), a bit per strain");
 // WeightSink (ss_scan_reads_resampled, ss_scan_resampled.hip): the counts of up to sixteen bootstrap replicates from one pass.
 // A found k-mer adds the WEIGHTS of its record -- a 64-bit word of 4-bit fields, one per replicate -- to the replicates' own
 // slot counters, one atomic per field that is not zero.  It needs the record of a hit when the hit is found (the drains keep

@@ -1,5 +1,5 @@
 """The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
---bootstrap_clusters, --classify_reads, --extract_class, --tag_bam and --read_calls; and --pairs, which makes all of them work on read pairs as fragments.
+--bootstrap_clusters, --classify_reads, --extract_class, --tag_bam, --read_calls, --classify_strains and --extract_strains; and --pairs, which makes all of them work on read pairs as fragments.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -53,13 +53,15 @@ def table_scanned(table, kdb, paths):
     collect_read_support(table, kdb, paths)
     collect_extract_reads(table, kdb, paths)
     bootstrap_scanned(table)
+    strain_classes_scanned(table)
 
 
 def cluster_reported(cls, cls_db_dir, report_path, ksize, paths):
-    """Cluster `cls` ('C<id>') has written report_path: --by_strain, then --bootstrap."""
+    """Cluster `cls` ('C<id>') has written report_path: --by_strain, --classify_strains, then --bootstrap."""
     if not _pairs_gate(paths):
         return
     collect_by_strain(cls, cls_db_dir, report_path, ksize, paths)
+    collect_strain_classes(cls, cls_db_dir, report_path, ksize, paths)
     collect_bootstrap(cls, cls_db_dir, report_path, ksize, paths)
 
 
@@ -69,6 +71,7 @@ def write_all(out_dir, scope=None):
     write_bootstrap(out_dir, scope)
     write_cluster_bootstrap(out_dir, scope)
     write_read_classes(out_dir, scope)
+    write_strain_classes(out_dir, scope)
 
 
 def reset_all():
@@ -81,6 +84,8 @@ def reset_all():
     extract_class_reset()
     tag_bam_reset()
     read_calls_reset()
+    classify_strains_reset()
+    extract_strains_reset()
     pairs_reset()
 
 
@@ -128,7 +133,7 @@ def _pairs_gate(paths):
             if js is not None:
                 return True
             PAIRS["skipped"] = why
-            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS):
+            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS, CLASSIFY_STRAINS, EXTRACT_STRAINS):
                 if state["skipped"] is None:
                     state["skipped"] = "--pairs " + why
             if dist.rank_world()[0] == 0:
@@ -482,6 +487,205 @@ def write_strain_support(out_dir, scope=None):
     order = _in_order(READ_SUPPORT["rows"].get(scope, {}), rows)
     return _write(out_dir, STRAIN_SUPPORT_FILE,
                   strain_support_text([r for t in order for r in sorted(rows[t], key=lambda r: int(r[0].rsplit(".", 1)[1]))]))
+
+
+# --classify_strains M (StrainScan.apply_classify_strains turns it on): --by_strain sees only the reads with k-mers that ONE called
+# strain has; this says, for every read, which of a cluster's called strains it is compatible with.  After a cluster's
+# StrainVote.report has been written, collect_strain_classes gives every row of the cluster's table the MASK of the called strains
+# that have its k-mer (strain_row_sets: bit j - 1 for the j-th row of the report) and the device votes per read: h[j] = the read's
+# hits whose k-mer strain j has, the read's set = the strains with the most hits, empty below M (ReadSet.classify_strains;
+# tests/strain_set_model.py restates it).  Written as strain_classes.tsv (a row per called strain) and strain_sets.tsv (a row per
+# set with reads: the equivalence classes).  "rows": per scope and cluster, the called strains and the device's numbers (None: the
+# cluster was passed over); "order": the tables as they were scanned.
+# --extract_strains unique|compatible (apply_extract_strains; it needs --classify_strains): a second device call
+# (ReadSet.select_strains) gives, per called strain, the reads whose set is that strain alone / holds that strain, written as
+# extracted/strain_C<id>.<n>_<mate>.<ext> by -x's writer.  "files": what this run has written so far (a skip takes them away).
+CLASSIFY_STRAINS = {"m": 0, "rows": {}, "order": {}, "skipped": None}
+EXTRACT_STRAINS = {"mode": None, "skipped": None, "files": []}
+EXTRACT_STRAINS_MODES = ("unique", "compatible")
+STRAIN_CLASSES_FILE = "strain_classes.tsv"
+STRAIN_SETS_FILE = "strain_sets.tsv"
+_CLASSIFY_STRAINS_LOCK = threading.Lock()
+_classify_strains_skip = functools.partial(_skip, CLASSIFY_STRAINS, "classify_strains", "and no read was assigned", True)
+
+
+def classify_strains_reset(m=0):
+    CLASSIFY_STRAINS.update(m=int(m or 0), rows={}, order={}, skipped=None)
+
+
+def extract_strains_reset(mode=None):
+    EXTRACT_STRAINS.update(mode=mode or None, skipped=None, files=[])
+
+
+def _extract_strains_skip(why):
+    for f in EXTRACT_STRAINS["files"]:
+        with contextlib.suppress(OSError):
+            os.remove(f)
+            os.rmdir(os.path.dirname(f))      # (once it is empty)
+    EXTRACT_STRAINS["files"] = []
+    _skip(EXTRACT_STRAINS, "extract_strains", "and nothing was extracted", True, why)
+
+
+def strain_classes_scanned(table):
+    """A table has been scanned: strain_classes.tsv and strain_sets.tsv list the clusters in this order."""
+    if CLASSIFY_STRAINS["m"]:
+        order = CLASSIFY_STRAINS["order"].setdefault(SCOPE["label"], [])
+        if table not in order:
+            order.append(table)
+
+
+def strain_row_sets(indptr, indices, data, n_rows, called_cols):
+    """np.uint16[n_rows] from a cluster's CSR matrix (row = k-mer, column = strain) and the called columns c_1 .. c_L, L <= 16: bit
+    j - 1 of row r's mask is set when the row is non-zero in column c_j.  Uncalled columns are not looked at.  The mask twin of
+    strain_row_labels: where a mask has one bit, that row has the bit's label there."""
+    called_cols = list(called_cols)
+    if len(called_cols) > _lib.STRAIN_SET_MAX:
+        raise ValueError("%d called strains, a mask holds %d" % (len(called_cols), _lib.STRAIN_SET_MAX))
+    indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices)
+    n_mat = indptr.size - 1
+    n_cols = int(indices.max()) + 1 if indices.size else 0
+    col_bit = np.zeros(max(n_cols, max(called_cols + [0]) + 1), np.uint16)
+    for j, c in enumerate(called_cols):
+        col_bit[c] |= np.uint16(1 << j)
+    bits = col_bit[indices]                                          # the called columns only ...
+    if data is not None and not np.asarray(data).all():
+        bits = np.where(np.asarray(data) != 0, bits, 0).astype(np.uint16)
+    at = np.flatnonzero(bits)                                        # (a few of a cluster's many columns: short from here on)
+    rows = np.searchsorted(indptr, at, side="right") - 1
+    bits = bits[at]
+    mat = np.zeros(n_mat, np.uint16)
+    for j in range(len(called_cols)):                                # ... or-ed together row by row, a strain at a time
+        mat[rows[(bits >> j) & 1 != 0]] |= np.uint16(1 << j)
+    out = np.zeros(n_rows, np.uint16)
+    m = min(n_rows, n_mat)
+    out[:m] = mat[:m]
+    return out
+
+
+def strain_reads_share(set_reads, n):
+    """[share of strain j, j = 0..n]: the sum over the sets that hold j, in ascending mask order, of set_reads / |set|; entry 0:
+    the unassigned reads.  The entries add up to the sample's records."""
+    share = [float(int(set_reads[0]))] + [0.0] * n
+    for mask in np.flatnonzero(np.asarray(set_reads)[1:]) + 1:
+        members = [j for j in range(1, n + 1) if (int(mask) >> (j - 1)) & 1]
+        for j in members:
+            share[j] += int(set_reads[mask]) / len(members)
+    return share
+
+
+def strain_classes_text(clusters):
+    """The text of strain_classes.tsv for [(table, [(n, name)] in report order, the numbers of ReadSet.classify_strains)]."""
+    out = ["table\tstrain\tkmers\thits\treads_unique\treads_tied\treads_share\n"]
+    for table, called, r in clusters:
+        share = strain_reads_share(r["set_reads"], len(called))
+        out.append("%s\tunassigned\t0\t%d\t%d\t0\t%.3f\n" % (table, int(r["strain_hits"][0]), int(r["unique"][0]), share[0]))
+        for j, (n, name) in enumerate(called, 1):
+            out.append("%s.%d\t%s\t%d\t%d\t%d\t%d\t%.3f\n" % (table, n, name, int(r["kmers"][j]), int(r["strain_hits"][j]), int(r["unique"][j]),
+                                                             int(r["tied"][j]), share[j]))
+    return "".join(out)
+
+
+def strain_sets_text(clusters):
+    """The text of strain_sets.tsv: per cluster a row for every non-empty set with reads, the reads descending, then the mask
+    ascending; `set`: the report numbers of its strains."""
+    out = ["table\tset\tstrains\treads\n"]
+    for table, called, r in clusters:
+        sr = np.asarray(r["set_reads"])
+        masks = [int(m) for m in np.flatnonzero(sr[1:]) + 1]
+        for mask in sorted(masks, key=lambda m: (-int(sr[m]), m)):
+            members = [str(n) for j, (n, _) in enumerate(called) if (mask >> j) & 1]
+            out.append("%s\t%s\t%d\t%d\n" % (table, ",".join(members), len(members), int(sr[mask])))
+    return "".join(out)
+
+
+def collect_strain_classes(cls, cls_db_dir, report_path, ksize, paths):
+    """After cluster `cls` ('C<id>') has written report_path: its numbers for strain_classes.tsv and strain_sets.tsv and, with
+    --extract_strains, its called strains' extracted/strain_<cls>.<n>_* files.  A no-op unless --classify_strains is on.  The
+    solver's threads call this; a cluster that has its numbers under the current scope keeps them."""
+    m = CLASSIFY_STRAINS["m"]
+    if not m or CLASSIFY_STRAINS["skipped"] is not None or not os.path.exists(report_path):
+        return
+    from .tree import load_plain_pkl
+    with _CLASSIFY_STRAINS_LOCK:
+        rows = CLASSIFY_STRAINS["rows"].setdefault(SCOPE["label"], {})
+        if cls in rows or CLASSIFY_STRAINS["skipped"] is not None:
+            return
+        called = called_strains(report_path)
+        if not called:
+            return
+        if dist.is_distributed():
+            return _classify_strains_skip("runs on one rank only (this run has several)")
+        if len(called) > _lib.STRAIN_SET_MAX:
+            rows[cls] = None
+            print("classify_strains: %s has %d called strains, a read's set holds up to %d, and the cluster was not written" %
+                  (cls, len(called), _lib.STRAIN_SET_MAX), file=sys.stderr)
+            sys.stderr.flush()
+            return
+        rs = _report_reads(paths)
+        if rs is None:
+            return _classify_strains_skip(NEEDS_RESIDENT)
+        sid = load_plain_pkl(os.path.join(cls_db_dir, "id2strain_re.pkl"))
+        col_of = {name: c for c, name in (sid.items() if isinstance(sid, dict) else enumerate(sid))}
+        indptr, indices, data = cluster_csr_arrays(os.path.join(cls_db_dir, "all_strains_re.npz"))
+        with contextlib.closing(db.fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)) as kdb:
+            if kdb.k < 17:
+                return _classify_strains_skip(NEEDS_PAGE_INDEX % kdb.k)
+            row_sets = strain_row_sets(indptr, indices, data, kdb.n_rows, [col_of[name] for _, name in called])
+            res = _select_or_skip(lambda: rs.classify_strains(kdb, row_sets, len(called), m), _classify_strains_skip, "classify")
+            if res is None:
+                return
+            rows[cls] = (called, res)
+            records = int(res["unique"].sum() + res["tied"][0])
+            print("classify_strains: %s\tM=%d\trecords %d\tunique %d\ttied %d\tunassigned %d\tsets %d" %
+                  (cls, m, records, int(res["unique"][1:].sum()), int(res["tied"][0]), int(res["unique"][0]),
+                   int((res["set_reads"][1:] > 0).sum())), file=sys.stderr)
+            sys.stderr.flush()
+            _write_strain_sets(cls, called, rs, kdb, row_sets, m, paths)
+
+
+def _write_strain_sets(cls, called, rs, kdb, row_sets, m, paths):
+    """--extract_strains: extracted/strain_<cls>.<n>_<mate>.<ext> for every called strain of `cls`, from one ReadSet.select_strains
+    (_CLASSIFY_STRAINS_LOCK held)."""
+    mode = EXTRACT_STRAINS["mode"]
+    if not mode or EXTRACT_STRAINS["skipped"] is not None:
+        return
+    ps = [p for p in paths if p]
+    if any(_lib.input_kind(p) == "bam" for p in ps):
+        return _extract_strains_skip("takes FASTA/FASTQ inputs (BAM subsets per strain are not built)")
+    how = 0 if mode == "unique" else 1
+    sets = _select_or_skip(lambda: rs.select_strains(kdb, row_sets, len(called), m, [1 << j for j in range(len(called))], [how] * len(called)),
+                           _extract_strains_skip, "extract")
+    if sets is None:
+        return
+    try:
+        out_dir = os.path.join(EXTRACT_READS["dir"] or ".", EXTRACT_READS_DIR)
+        os.makedirs(out_dir, exist_ok=True)
+        for (n, _), sub in zip(called, sets):
+            selected = sub.info()["n_records"]
+            flat = sub.read_back()
+            sub.close()
+            keys = _lib.flat_record_keys(flat)
+            del flat
+            outs = [os.path.join(out_dir, "strain_%s.%d_%d.%s" % (cls, n, i + 1, fastx_record_type(p))) for i, p in enumerate(ps)]
+            c = _extract_write(ps, keys, outs)
+            EXTRACT_STRAINS["files"].extend(outs)
+            print("extract_strains: %s.%d\t%s\tM=%d\tselected on the device %d\twritten %d" % (cls, n, mode, m, selected, c["written"]),
+                  file=sys.stderr)
+        sys.stderr.flush()
+    finally:
+        for sub in sets:
+            sub.close()
+
+
+def write_strain_classes(out_dir, scope=None):
+    """out_dir/strain_classes.tsv and strain_sets.tsv from the numbers collected under `scope`, clusters in the order of the scans;
+    nothing without the flag, without numbers, or after a skip."""
+    rows = {t: r for t, r in (CLASSIFY_STRAINS["rows"].get(scope) or {}).items() if r is not None}
+    if not CLASSIFY_STRAINS["m"] or CLASSIFY_STRAINS["skipped"] is not None or not rows:
+        return None
+    clusters = [(t,) + rows[t] for t in _in_order(CLASSIFY_STRAINS["order"].get(scope, []), rows)]
+    _write(out_dir, STRAIN_SETS_FILE, strain_sets_text(clusters))
+    return _write(out_dir, STRAIN_CLASSES_FILE, strain_classes_text(clusters))
 
 
 # --bootstrap B (StrainScan.apply_bootstrap turns it on): how firm are a multi-strain cluster's numbers?  After the cluster has
