@@ -466,6 +466,44 @@ int ss_reads_select_strains(const ss_db *db, const ss_reads *r, const uint16_t *
                             const uint16_t *want, const uint8_t *how, uint32_t n_want, ss_reads **out /* [n_want] */,
                             uint64_t *unique, uint64_t *tied, uint64_t *strain_hits, uint64_t *kmers /* each NULL, or [n_strains + 1] */);
 int ss_reads_select_strains_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* The set counts of several bootstrap replicates from ONE classification of the set (`--em_strains`): set_reads[j][m] (host memory,
+ * [n_replicates][1 << n_strains], j < n_replicates <= SS_SCAN_REPLICATES_MAX) is, bit for bit, what ss_reads_classify_strains
+ * returns as set_reads[m] on the set that ss_reads_resample(r, seed, first_replicate + j) returns -- the sum, over the records of r
+ * whose set is the mask m, of the weight ss_reads_resample states for (the record, seed, first_replicate + j).  A record's set does
+ * not depend on its copies, so nothing is materialised: the records are classified once, their weights are drawn once (sixteen
+ * 4-bit fields of one word per record) and one pass adds every weight that is not zero to its replicate's counter of the
+ * record's set.  Works on every kind of resident set, as ss_reads_classify_strains does.  Synchronous.  Reads the table's index,
+ * never its counters.  SS_ERANGE and SS_EINVAL: as ss_reads_classify_strains states them (set_reads must not be NULL), and
+ * SS_EINVAL for n_replicates outside 1..SS_SCAN_REPLICATES_MAX. */
+int ss_reads_strain_sets_resampled(const ss_db *db, const ss_reads *r, const uint16_t *row_sets, uint32_t n_strains, uint32_t min_score,
+                                   uint64_t seed, uint32_t first_replicate, uint32_t n_replicates,
+                                   uint64_t *set_reads /* host, [n_replicates][1 << n_strains] */);
+int ss_reads_strain_sets_resampled_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* Read-based strain abundances by EM over the equivalence classes of ss_reads_classify_strains (`--em_strains`), n_vec count
+ * vectors in one launch.  masks[s], s < n_sets (host memory): a set of called strains, bit j - 1 for strain j in 1..n_strains;
+ * non-zero, distinct.  counts[v][s] (host memory): the reads of vector v whose set is masks[s].  Per vector, in float64, with
+ * n_s = counts[v][s] and N = the sum of the n_s (taken in integers):
+ *   active    strain j is ACTIVE when some set with n_s > 0 holds j; an inactive strain has rho_j = 0 throughout
+ *   start     rho_j = 1 / (the number of active strains)
+ *   one iteration, for every set with n_s > 0:  d_s = the sum of rho_i over i in the set, i ascending;  a set with d_s == 0
+ *             contributes nothing;  rho'_j = rho_j * (the sum over the sets s that hold j of n_s / d_s) / N
+ *             -- that is (1/N) * sum of n_s * rho_j / d_s, with the common factor rho_j taken out of the sum
+ *   stopping  after iteration t: when t == max_iter, or when the largest |rho'_j - rho_j| < tol; tol == 0 runs exactly max_iter
+ *             iterations.  iters[v] = the iterations run
+ *   N == 0    rho = 0 everywhere, iters[v] = 0
+ * rho[v][j - 1] = strain j's share of vector v's assigned reads; the rho of a vector sum to 1 up to rounding.  The order in which
+ * the device adds the sets' terms is fixed (a strided share per thread, a fixed tree within the wave, the waves in order), so the
+ * same input gives the same bits on every run; it is not the ascending order, so rho differs from tests/em_model.py's by the
+ * rounding of a sum taken in another order.  No floating-point atomics.  One launch per call, one workgroup per vector, which
+ * tests convergence itself; masks and counts stay in LDS up to SS_EM_LDS_SETS sets and are read from global memory in every
+ * iteration above.  Synchronous, on the current device.  SS_EINVAL: a NULL argument; n_sets outside 1..65535; n_strains outside
+ * 1..SS_STRAIN_SET_MAX; n_vec outside 1..SS_EM_VECTORS_MAX; max_iter == 0; tol negative or NaN; a mask that is zero, listed twice
+ * or has a bit at or above n_strains. */
+#define SS_EM_VECTORS_MAX 1024
+#define SS_EM_LDS_SETS 6144
+int ss_em_strain_sets(const uint64_t *counts /* [n_vec][n_sets] */, const uint16_t *masks /* [n_sets] */, uint32_t n_sets, uint32_t n_strains,
+                      uint32_t n_vec, uint32_t max_iter, double tol, double *rho /* [n_vec][n_strains] */, uint32_t *iters /* [n_vec] */);
+int ss_em_strain_sets_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
 /* Read PAIRS as the records of a resident set (`--pairs`, ss_pairs.hip).  A resident set keeps no pair map, and every call above
  * decides per record from the record's bytes alone: on a set whose records are the pairs they all work on fragments, unchanged.
  * The join rule: record i of the result is  line1[i] + 'N' + line2[i] + '\n'.  'N' ends a k-mer window, so no k-mer spans the

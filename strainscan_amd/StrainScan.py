@@ -186,6 +186,16 @@ def add_arguments(ap, multi=False):
                          "alone; `compatible`: those whose set holds the strain.  Written with -x's rules: the original text "
                          "in file order, selected by content, a pair when either mate is selected (with --pairs: the "
                          "fragment).  Needs FASTA/FASTQ input (default: off)")
+    ap.add_argument("--em_strains", dest="em_strains", type=em_strains_arg, default=None, metavar="B",
+                    help="With --classify_strains M: also write strain_em.tsv, the called strains' abundances estimated from the "
+                         "reads.  The reads of every set of called strains (strain_sets.tsv) are shared out among the set's strains "
+                         "by an EM over these equivalence classes -- a tied read goes to its strains in proportion to their current "
+                         "shares, iterated to a fixed point on the device -- which gives each strain its share of the assigned reads "
+                         "(frac_reads) and, divided by the strain's k-mers, a depth-like abundance beside the elastic-net fraction "
+                         "of StrainVote.report.  B = 0: the estimate alone; B in 2..1000: also its 2.5 %% and 97.5 %% bounds over B "
+                         "replicates that resample the reads (a Poisson bootstrap over reads, the replicates of --bootstrap_seed S), "
+                         "all replicates solved in one launch.  The bounds are conditional on the called strains, identical reads "
+                         "share a weight, a strain that is not called gets no reads (default: off)")
     ap.add_argument("--tag_bam", dest="tag_bam", action="store_true",
                     help="With --classify_reads M and BAM input (every input a BAM): also write OUT/classified_<i>.bam per input "
                          "file, the input written back with the class of every read as two aux tags -- sn:i:<node of "
@@ -243,6 +253,13 @@ def refuse_extract_strains_alone(ap, args):
     input is opened)."""
     if args.extract_strains and not args.classify_strains:
         ap.error("--extract_strains needs --classify_strains M")
+
+
+def refuse_em_strains_alone(ap, args):
+    """--em_strains without --classify_strains has no equivalence classes to start from: the parser's error (exit status 2, before
+    any input is opened)."""
+    if args.em_strains is not None and not args.classify_strains:
+        ap.error("--em_strains needs --classify_strains M")
 
 
 def refuse_tag_bam_alone(ap, args):
@@ -337,6 +354,18 @@ def bootstrap_arg(text):
     return b
 
 
+def em_strains_arg(text):
+    """--em_strains' value: 0 (the estimate alone) or an integer in 2..1000 (replicates), or the parser's error (exit status 2,
+    before any input is opened)."""
+    try:
+        b = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not 0 or an integer in 2..1000" % text)
+    if b != 0 and not 2 <= b <= 1000:
+        raise argparse.ArgumentTypeError("%d is neither 0 nor in 2..1000" % b)
+    return b
+
+
 def bootstrap_seed_arg(text):
     """--bootstrap_seed's value: an integer in 0..2^63-1, or the parser's error (exit status 2, before any input is opened)."""
     try:
@@ -424,6 +453,14 @@ def apply_extract_strains(mode):
     None turns it off."""
     from . import read_reports
     read_reports.extract_strains_reset(mode)
+
+
+def apply_em_strains(b, seed=1):
+    """--em_strains B --bootstrap_seed S (strainscan_amd.set_em_strains): the clusters that assign their reads (--classify_strains)
+    also estimate their called strains' abundances by EM over the sets, with B resampled replicates (read_reports.collect_em_strains);
+    the command writes strain_em.tsv when it ends.  stdout and the other files are untouched; None turns it off."""
+    from . import read_reports
+    read_reports.em_strains_reset(b, seed)
 
 
 def apply_tag_bam(on, out_dir=None):
@@ -533,6 +570,7 @@ def main(argv=None):
     refuse_by_strain_alone(ap, args)
     refuse_extract_class_alone(ap, args)
     refuse_extract_strains_alone(ap, args)
+    refuse_em_strains_alone(ap, args)
     refuse_pairs_alone(ap, args)
     refuse_tag_bam_alone(ap, args)
     refuse_read_calls_alone(ap, args)
@@ -559,6 +597,7 @@ def main(argv=None):
     apply_extract_class(args.extract_class)
     apply_classify_strains(args.classify_strains)
     apply_extract_strains(args.extract_strains)
+    apply_em_strains(args.em_strains, args.bootstrap_seed)
     apply_tag_bam(args.tag_bam, out_dir)
     apply_read_calls(args.read_calls, out_dir)
     apply_pairs(args.pairs)

@@ -24,6 +24,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_read_calls                             (`strainscan --read_calls`: a line per read with its name, class, score and hit list, read_reports.READ_CALLS)
     strainscan_amd.set_classify_strains                       (`strainscan --classify_strains M`: every read assigned to its best called strains, read_reports.CLASSIFY_STRAINS)
     strainscan_amd.set_extract_strains                        (`strainscan --extract_strains unique|compatible`: the reads of each called strain, read_reports.EXTRACT_STRAINS)
+    strainscan_amd.set_em_strains                             (`strainscan --em_strains B`: the called strains' read-based abundances by EM, read_reports.EM_STRAINS)
     strainscan_amd.set_pairs                                  (`strainscan --pairs`: those reports on read pairs as fragments, read_reports.PAIRS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
@@ -176,6 +177,21 @@ def set_extract_strains(mode, out_dir=None):
     read_reports.extract_strains_reset(mode)
     if out_dir is not None:
         read_reports.EXTRACT_READS["dir"] = out_dir
+
+
+def set_em_strains(b, seed=1):
+    """`strainscan --em_strains B --bootstrap_seed S` for callers of the functions above, with set_classify_strains on: every
+    cluster that assigns its reads also shares the reads of its sets out among the called strains by EM (_lib.em_strain_sets; the
+    rule is in strainscan_hip.h), on the sample's set counts and on those of b resampled replicates
+    (ReadSet.strain_sets_resampled), and keeps the numbers with read_reports.EM_STRAINS; read_reports.write_em_strains(out_dir)
+    writes strain_em.tsv, read_reports.em_replicates() hands the matrices over.  b: 0 (the estimate alone) or an integer in
+    2..1000; None turns it off.  seed: an integer in 0..2^63-1.  Off by default; nothing runs while it is off."""
+    if b is not None and (isinstance(b, bool) or not isinstance(b, int) or not (b == 0 or 2 <= b <= 1000)):
+        raise ValueError("em_strains must be 0 or an integer in 2..1000 (or None for off), not %r" % (b,))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= (1 << 63) - 1:
+        raise ValueError("seed must be an integer in 0..2^63-1, not %r" % (seed,))
+    from . import read_reports
+    read_reports.em_strains_reset(b, seed)
 
 
 def set_pairs(on):

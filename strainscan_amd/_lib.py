@@ -127,6 +127,10 @@ SIGNATURES = {
     "ss_reads_classify_strains_ties": (i32, [P(u64)]),
     "ss_reads_select_strains": (i32, [vp, vp, vp, u32, u32, vp, vp, u32, P(vp), vp, vp, vp, vp]),
     "ss_reads_select_strains_calls": (i32, [P(u64)]),
+    "ss_reads_strain_sets_resampled": (i32, [vp, vp, vp, u32, u32, u64, u32, u32, vp]),
+    "ss_reads_strain_sets_resampled_calls": (i32, [P(u64)]),
+    "ss_em_strain_sets": (i32, [vp, vp, u32, u32, u32, u32, C.c_double, vp, vp]),
+    "ss_em_strain_sets_calls": (i32, [P(u64)]),
     "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
@@ -765,6 +769,18 @@ class ReadSet:
         check(lib().ss_reads_classify_strains_ties(C.byref(ties)), "ss_reads_classify_strains_ties")
         return sets, dict(unique=uniq, tied=tied, strain_hits=hits, kmers=kmers, ties=int(ties.value))
 
+    def strain_sets_resampled(self, kdb, row_sets, n_strains, min_score, seed, first, n_rep):
+        """np.uint64[n_rep, 1 << n_strains]: row j is the set_reads that classify_strains() with the same arguments returns on
+        resample(seed, first + j) -- the weights of the records of every set added up, from one classification and one pass over
+        the records, nothing materialised (ss_reads_strain_sets_resampled).  n_rep in 1..SCAN_REPLICATES_MAX.  The table's
+        counters are left alone."""
+        rs = _row_sets(kdb, row_sets)
+        n, reps = max(int(n_strains), 0), max(int(n_rep), 0)
+        out = np.zeros((max(reps, 1), 1 << n if n <= STRAIN_SET_MAX else 1), np.uint64)
+        check(lib().ss_reads_strain_sets_resampled(kdb.handle, self._h, ptr(rs), n, int(min_score), int(seed), int(first), reps, ptr(out)),
+              "ss_reads_strain_sets_resampled")
+        return out
+
     def order(self):
         """Put the records of a set in file order (from_flat_dev(order=False), select(), resample()) in locality order, in place
         (ss_reads_order): the records and every count stay, a scan of a cluster table gets faster.  -> self"""
@@ -910,6 +926,37 @@ def classify_strains_calls():
 def select_strains_calls():
     """Calls of ss_reads_select_strains so far in this process."""
     return _calls("ss_reads_select_strains_calls")
+
+
+EM_VECTORS_MAX = 1024       # SS_EM_VECTORS_MAX (strainscan_hip.h): count vectors per call of em_strain_sets
+EM_LDS_SETS = 6144          # SS_EM_LDS_SETS (strainscan_hip.h): the sets a workgroup of em_strain_sets keeps in LDS
+
+
+def strain_sets_resampled_calls():
+    """Calls of ss_reads_strain_sets_resampled so far in this process."""
+    return _calls("ss_reads_strain_sets_resampled_calls")
+
+
+def em_strain_sets(counts, masks, n_strains, max_iter, tol):
+    """The EM over equivalence classes on the device (ss_em_strain_sets; tests/em_model.py restates it): counts[v][s] = the reads
+    of vector v whose set is masks[s] (non-zero, distinct masks of strains 1..n_strains) -> (rho np.float64[n_vec, n_strains],
+    iters np.uint32[n_vec]).  One launch for all vectors; the same input gives the same bits."""
+    counts = np.ascontiguousarray(counts, np.uint64)
+    masks = np.ascontiguousarray(masks, np.uint16)
+    if counts.ndim != 2 or masks.ndim != 1 or counts.shape[1] != masks.size:
+        raise ValueError("counts is [vectors][sets] and masks [sets], not %r and %r" % (counts.shape, masks.shape))
+    n_vec, n_sets = counts.shape
+    n = max(int(n_strains), 0)
+    rho = np.zeros((max(n_vec, 1), max(n, 1)), np.float64)
+    iters = np.zeros(max(n_vec, 1), np.uint32)
+    check(lib().ss_em_strain_sets(ptr(counts if counts.size else np.zeros(1, np.uint64)), ptr(masks if masks.size else np.zeros(1, np.uint16)),
+                                  n_sets, n, n_vec, int(max_iter), float(tol), ptr(rho), ptr(iters)), "ss_em_strain_sets")
+    return rho[:n_vec, :n], iters[:n_vec]
+
+
+def em_strain_sets_calls():
+    """Calls of ss_em_strain_sets so far in this process."""
+    return _calls("ss_em_strain_sets_calls")
 
 
 def flat_record_keys(flat):

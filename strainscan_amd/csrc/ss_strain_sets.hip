@@ -30,6 +30,15 @@
 //   5. select_strains_len_kernel: out_len[rec] = the record's set equals / intersects the wanted one ? length + 1 : 0 --
 //      select_class_len_kernel (ss_classify.hip) with a mask test in the place of the Euler interval; gather_records
 //      (ss_select.hip) then makes the new set from out_len[], which is written whole again for the next entry.
+//
+// ss_reads_strain_sets_resampled (`--em_strains`) runs it once too, keeps the sets, and then:
+//   6. resample_weights_of (ss_resample.hip): the weights every record draws in up to sixteen bootstrap replicates, 4-bit fields
+//      of one word per record, in the spans' len[] under the record's number -- the numbering of the sets.
+//   7. set_weights_kernel: a lane per record adds every field that is not zero to hist[replicate][set].  While the
+//      n_replicates << n_strains counters fit SETW_LDS 32-bit words a workgroup keeps them in LDS and adds its non-zero entries
+//      to the 64-bit ones in global memory when it ends; above that equal sets are folded within the wave as in pass 3, a
+//      replicate's weights over the lanes of one set summed by four ballots (a bit of the field each), and lane j issues
+//      replicate j's atomic: one per distinct (replicate, set) of a wave.
 #include "ss_scan_dev.h"
 #include "ss_support.h"
 
@@ -303,7 +312,54 @@ __global__ __launch_bounds__(256) void select_strains_len_kernel(const uint16_t 
     add_selected(cnt, bytes, tot);
 }
 
-std::atomic<uint64_t> g_classify_strains_calls{0}, g_select_strains_calls{0};
+// hist[j << n_strains | set] += the weight of replicate j, over every record of the set: w[rec] holds the weights as 4-bit fields
+// (resample_weights_kernel; 0 for a record without a span), rec_set[rec] the record's set.  lds: the counters fit SETW_LDS words.
+constexpr uint32_t SETW_LDS = 1u << 14;
+__global__ __launch_bounds__(256) void set_weights_kernel(const uint16_t *__restrict__ rec_set, const unsigned long long *__restrict__ w, uint64_t n_rec,
+                                                          uint32_t n_strains, uint32_t n_rep, bool lds, unsigned long long *__restrict__ hist)
+{
+    __shared__ uint32_t acc[SETW_LDS];
+    const uint32_t t = threadIdx.x, lane = t & 63u, cells = n_rep << n_strains;
+    if (lds) {
+        for (uint32_t c = t; c < cells; c += 256u) acc[c] = 0u;
+        __syncthreads();
+    }
+    for (uint64_t g0 = (uint64_t)blockIdx.x * 256u; g0 < n_rec; g0 += (uint64_t)gridDim.x * 256u) {      // (the same for the workgroup)
+        const uint64_t g = g0 + t;
+        const unsigned long long word = g < n_rec ? w[g] : 0ull;
+        const uint32_t set = word ? rec_set[g] : 0u;
+        if (lds) {
+            for (unsigned long long rest = word; rest;) {
+                const uint32_t j = (uint32_t)(__ffsll((long long)rest) - 1) >> 2;
+                atomicAdd(&acc[(j << n_strains) | set], (uint32_t)(word >> (4u * j)) & 15u);
+                rest &= ~(15ull << (4u * j));
+            }
+            continue;
+        }
+        for (unsigned long long rem = __ballot(word != 0ull); rem;) {
+            const int src = __ffsll((long long)rem) - 1;
+            const uint32_t key = (uint32_t)__shfl((int)set, src, 64);
+            const bool in = word != 0ull && set == key;
+            unsigned long long mine = 0;                // lane j: replicate j's weights over the lanes of this set
+            for (uint32_t j = 0; j < n_rep; j++) {
+                const uint32_t f = in ? (uint32_t)(word >> (4u * j)) & 15u : 0u;
+                unsigned long long c = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < 4u; b++) c += (unsigned long long)__popcll(__ballot((f >> b) & 1u)) << b;
+                if (lane == j) mine = c;
+            }
+            if (lane < n_rep && mine) atomicAdd(&hist[((size_t)lane << n_strains) | key], mine);
+            rem &= ~__ballot(in);
+        }
+    }
+    if (lds) {
+        __syncthreads();
+        for (uint32_t c = t; c < cells; c += 256u)
+            if (acc[c]) atomicAdd(&hist[c], (unsigned long long)acc[c]);
+    }
+}
+
+std::atomic<uint64_t> g_classify_strains_calls{0}, g_select_strains_calls{0}, g_sets_resampled_calls{0};
 thread_local uint64_t t_last_set_ties = 0;
 
 // what strain_sets_records leaves behind: everything on the device lives in rh.scratch and is enqueued on ss::l2s::stream()
@@ -458,6 +514,36 @@ int ss_reads_classify_strains(const ss_db *db, const ss_reads *R, const uint16_t
     if (set_reads) SS_HIP(ss::l2s::copy(set_reads, S.d_set_reads, 8ull << n_strains, hipMemcpyDeviceToHost));
     if (S.d_set) SS_HIP(ss::l2s::copy(rec_set, S.d_set, S.rh.rec_total * 2, hipMemcpyDeviceToHost));
     if (S.d_score) SS_HIP(ss::l2s::copy(rec_score, S.d_score, S.rh.rec_total * 4, hipMemcpyDeviceToHost));
+    return SS_OK;
+}
+
+int ss_reads_strain_sets_resampled_calls(uint64_t *n)
+{
+    if (!n) return SS_EINVAL;
+    *n = g_sets_resampled_calls.load();
+    return SS_OK;
+}
+
+int ss_reads_strain_sets_resampled(const ss_db *db, const ss_reads *R, const uint16_t *row_sets, uint32_t n_strains, uint32_t min_score, uint64_t seed,
+                                   uint32_t first_replicate, uint32_t n_replicates, uint64_t *set_reads)
+{
+    if (!set_reads || n_replicates < 1 || n_replicates > SS_SCAN_REPLICATES_MAX) return SS_EINVAL;
+    StrainSets S;
+    int rc = strain_sets_records(db, R, row_sets, n_strains, min_score, false, true, false, &g_sets_resampled_calls, &S);
+    if (rc) return rc;
+    const size_t cells = (size_t)n_replicates << n_strains;
+    unsigned long long *d_hist = nullptr;
+    SS_HIP(S.rh.scratch.get((void **)&d_hist, cells * 8));
+    SS_HIP(ss::l2s::set(d_hist, 0, std::max<size_t>(cells * 8, 16)));
+    if (S.rh.rec_total && S.d_set) {
+        rc = ss::resample_weights_of(&S.rh, S.sp, seed, first_replicate, n_replicates);      // (in the spans' len[], by record of the set)
+        if (rc) return rc;
+        const unsigned blocks = (unsigned)std::min<uint64_t>((S.rh.rec_total + 256 * 4 - 1) / (256 * 4), 512);
+        hipLaunchKernelGGL(set_weights_kernel, dim3(blocks), dim3(256), 0, ss::l2s::stream(), S.d_set, S.sp.d_len, S.rh.rec_total, n_strains,
+                           n_replicates, cells <= SETW_LDS, d_hist);
+        SS_HIP(hipGetLastError());
+    }
+    SS_HIP(ss::l2s::copy(set_reads, d_hist, cells * 8, hipMemcpyDeviceToHost));
     return SS_OK;
 }
 

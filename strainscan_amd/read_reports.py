@@ -1,5 +1,5 @@
 """The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
---bootstrap_clusters, --classify_reads, --extract_class, --tag_bam, --read_calls, --classify_strains and --extract_strains; and --pairs, which makes all of them work on read pairs as fragments.
+--bootstrap_clusters, --classify_reads, --extract_class, --tag_bam, --read_calls, --classify_strains, --extract_strains and --em_strains; and --pairs, which makes all of them work on read pairs as fragments.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -72,6 +72,7 @@ def write_all(out_dir, scope=None):
     write_cluster_bootstrap(out_dir, scope)
     write_read_classes(out_dir, scope)
     write_strain_classes(out_dir, scope)
+    write_em_strains(out_dir, scope)
 
 
 def reset_all():
@@ -86,6 +87,7 @@ def reset_all():
     read_calls_reset()
     classify_strains_reset()
     extract_strains_reset()
+    em_strains_reset()
     pairs_reset()
 
 
@@ -133,7 +135,7 @@ def _pairs_gate(paths):
             if js is not None:
                 return True
             PAIRS["skipped"] = why
-            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS, CLASSIFY_STRAINS, EXTRACT_STRAINS):
+            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS, CLASSIFY_STRAINS, EXTRACT_STRAINS, EM_STRAINS):
                 if state["skipped"] is None:
                     state["skipped"] = "--pairs " + why
             if dist.rank_world()[0] == 0:
@@ -506,7 +508,11 @@ EXTRACT_STRAINS_MODES = ("unique", "compatible")
 STRAIN_CLASSES_FILE = "strain_classes.tsv"
 STRAIN_SETS_FILE = "strain_sets.tsv"
 _CLASSIFY_STRAINS_LOCK = threading.Lock()
-_classify_strains_skip = functools.partial(_skip, CLASSIFY_STRAINS, "classify_strains", "and no read was assigned", True)
+
+
+def _classify_strains_skip(why):
+    _skip(CLASSIFY_STRAINS, "classify_strains", "and no read was assigned", True, why)
+    _em_strains_skip(why)      # (--em_strains starts from these sets: it writes nothing either, and says so itself)
 
 
 def classify_strains_reset(m=0):
@@ -619,6 +625,9 @@ def collect_strain_classes(cls, cls_db_dir, report_path, ksize, paths):
             rows[cls] = None
             print("classify_strains: %s has %d called strains, a read's set holds up to %d, and the cluster was not written" %
                   (cls, len(called), _lib.STRAIN_SET_MAX), file=sys.stderr)
+            if EM_STRAINS["on"] and EM_STRAINS["skipped"] is None:
+                print("em_strains: %s has %d called strains, a read's set holds up to %d, and the cluster was not written" %
+                      (cls, len(called), _lib.STRAIN_SET_MAX), file=sys.stderr)
             sys.stderr.flush()
             return
         rs = _report_reads(paths)
@@ -641,6 +650,7 @@ def collect_strain_classes(cls, cls_db_dir, report_path, ksize, paths):
                    int((res["set_reads"][1:] > 0).sum())), file=sys.stderr)
             sys.stderr.flush()
             _write_strain_sets(cls, called, rs, kdb, row_sets, m, paths)
+            collect_em_strains(cls, called, res, rs, kdb, row_sets, m, report_path)
 
 
 def _write_strain_sets(cls, called, rs, kdb, row_sets, m, paths):
@@ -686,6 +696,104 @@ def write_strain_classes(out_dir, scope=None):
     clusters = [(t,) + rows[t] for t in _in_order(CLASSIFY_STRAINS["order"].get(scope, []), rows)]
     _write(out_dir, STRAIN_SETS_FILE, strain_sets_text(clusters))
     return _write(out_dir, STRAIN_CLASSES_FILE, strain_classes_text(clusters))
+
+
+# --em_strains B (StrainScan.apply_em_strains turns it on; it needs --classify_strains): the read-based abundance estimate that
+# strain_sets.tsv's equivalence classes are the start of.  Behind a cluster's classification (collect_strain_classes, its lock
+# held) collect_em_strains takes the sample's set counts, the set counts of B resampled replicates -- sixteen per device call, from
+# one classification each and nothing materialised (ReadSet.strain_sets_resampled; replicate b of seed S is --bootstrap's) --
+# compacts all B + 1 vectors to the masks that have reads in any of them and runs ONE batched EM (_lib.em_strain_sets; the rule is
+# in strainscan_hip.h, tests/em_model.py restates it).  "rows": per scope and cluster, the called strains, their k-mers, the
+# elastic-net fractions of the report, N, rho[B + 1, L] (row 0: the sample) and the iterations, of which strain_em.tsv is a pure
+# function (em_text).  The clusters are listed in CLASSIFY_STRAINS' order.
+EM_STRAINS = {"on": False, "b": 0, "seed": 1, "rows": {}, "skipped": None}
+EM_STRAINS_FILE = "strain_em.tsv"
+EM_MAX_ITER = 1000
+EM_TOL = 1e-9
+
+
+def em_strains_reset(b=None, seed=1):
+    EM_STRAINS.update(on=b is not None, b=int(b or 0), seed=int(seed), rows={}, skipped=None)
+
+
+def _em_strains_skip(why):
+    if EM_STRAINS["on"]:
+        _skip(EM_STRAINS, "em_strains", "and no abundance was estimated", True, why)
+
+
+def em_replicates(scope=None):
+    """{cluster: (strain names in report order, rho np.float64[B + 1, L], iters np.uint32[B + 1])} collected under `scope`: row 0
+    is the sample's estimate, row 1 + b replicate b's."""
+    return {cls: ([name for _, name in r["called"]], r["rho"].copy(), r["iters"].copy()) for cls, r in EM_STRAINS["rows"].get(scope, {}).items()}
+
+
+def em_abundance(rho, kmers):
+    """theta[v][j] = (rho[v][j] / kmers[j]) / the sum of that over the strains with kmers > 0 (0 where the sum is 0): reads per
+    k-mer of the strain, as a share.  rho: [V, L]; kmers: [L]."""
+    rho = np.asarray(rho, np.float64)
+    km = np.asarray(kmers, np.float64)
+    per = np.divide(rho, km[None, :], out=np.zeros_like(rho), where=km[None, :] > 0)
+    tot = np.zeros(rho.shape[0], np.float64)
+    for j in range(rho.shape[1]):      # (strain after strain: one order of summation, whatever the shape)
+        tot += per[:, j]
+    return np.divide(per, tot[:, None], out=np.zeros_like(per), where=tot[:, None] != 0)
+
+
+def em_text(clusters):
+    """The text of strain_em.tsv for [(table, dict(called=[(n, name)] in report order, kmers=[L], enet=[L] texts, reads=N,
+    rho=[B + 1, L], iters=[B + 1]))]: the bounds are the replicates' abundances at bootstrap_index(0.025 / 0.975, B) of the
+    ascending values, `-` without replicates."""
+    out = ["table\tstrain\tkmers\treads_assigned\treads_em\tfrac_reads\tabundance\tabundance_lo\tabundance_hi\tpresent\tenet_frac\titerations\n"]
+    for table, r in clusters:
+        rho = np.asarray(r["rho"], np.float64)
+        theta = em_abundance(rho, r["kmers"])
+        b = rho.shape[0] - 1
+        if b:
+            lo, hi = (bootstrap_index(q, b) for q in BOOTSTRAP_QUANTILES)
+            ts = np.sort(theta[1:], axis=0)
+        for j, (n, name) in enumerate(r["called"]):
+            bounds = ["%.6f" % ts[lo, j], "%.6f" % ts[hi, j], str(int((rho[1:, j] > 0).sum()))] if b else ["-", "-", "-"]
+            out.append("\t".join(["%s.%d" % (table, n), name, str(int(r["kmers"][j])), str(int(r["reads"])), "%.3f" % (rho[0, j] * int(r["reads"])),
+                                  "%.6f" % rho[0, j], "%.6f" % theta[0, j]] + bounds + [r["enet"][j], str(int(r["iters"][0]))]) + "\n")
+    return "".join(out)
+
+
+def collect_em_strains(cls, called, res, rs, kdb, row_sets, m, report_path):
+    """Behind cluster `cls`' classification `res` (collect_strain_classes, _CLASSIFY_STRAINS_LOCK held): the EM on its set counts and
+    on those of the replicates.  A no-op unless --em_strains is on."""
+    if not EM_STRAINS["on"] or EM_STRAINS["skipped"] is not None:
+        return
+    b, seed, n = EM_STRAINS["b"], EM_STRAINS["seed"], len(called)
+    vectors = [np.asarray(res["set_reads"], np.uint64)[None, :]]
+    for first in range(0, b, _lib.SCAN_REPLICATES_MAX):
+        got = _select_or_skip(lambda: rs.strain_sets_resampled(kdb, row_sets, n, m, seed, first, min(_lib.SCAN_REPLICATES_MAX, b - first)),
+                              _em_strains_skip, "resample")
+        if got is None:
+            return
+        vectors.append(got)
+    counts = np.concatenate(vectors, axis=0)
+    counts[:, 0] = 0                                                  # the unassigned reads take no part
+    masks = np.flatnonzero(counts.any(axis=0))                        # the sets with reads in the sample or in any replicate
+    if masks.size:
+        rho, iters = _lib.em_strain_sets(counts[:, masks], masks.astype(np.uint16), n, EM_MAX_ITER, EM_TOL)
+    else:
+        rho, iters = np.zeros((b + 1, n), np.float64), np.zeros(b + 1, np.uint32)
+    enet = {name: frac for _, name, frac, _ in report_rows(report_path)}
+    EM_STRAINS["rows"].setdefault(SCOPE["label"], {})[cls] = dict(
+        called=list(called), kmers=[int(k) for k in res["kmers"][1:]], enet=[enet[name] for _, name in called], reads=int(counts[0].sum()), rho=rho,
+        iters=iters)
+    print("em_strains: %s\tB=%d\tseed=%d\tsets %d\titerations %d\tlargest over the replicates %d\treplicates at max_iter %d" %
+          (cls, b, seed, masks.size, int(iters[0]), int(iters[1:].max()) if b else 0, int((iters[1:] >= EM_MAX_ITER).sum())), file=sys.stderr)
+    sys.stderr.flush()
+
+
+def write_em_strains(out_dir, scope=None):
+    """out_dir/strain_em.tsv from the numbers collected under `scope`, clusters in the order of the scans; nothing without the
+    flag, without numbers, or after a skip."""
+    rows = EM_STRAINS["rows"].get(scope) or {}
+    if not EM_STRAINS["on"] or EM_STRAINS["skipped"] is not None or not rows:
+        return None
+    return _write(out_dir, EM_STRAINS_FILE, em_text([(t, rows[t]) for t in _in_order(CLASSIFY_STRAINS["order"].get(scope, []), rows)]))
 
 
 # --bootstrap B (StrainScan.apply_bootstrap turns it on): how firm are a multi-strain cluster's numbers?  After the cluster has
