@@ -504,6 +504,39 @@ int ss_reads_strain_sets_resampled_calls(uint64_t *n);  /* calls so far in this 
 int ss_em_strain_sets(const uint64_t *counts /* [n_vec][n_sets] */, const uint16_t *masks /* [n_sets] */, uint32_t n_sets, uint32_t n_strains,
                       uint32_t n_vec, uint32_t max_iter, double tol, double *rho /* [n_vec][n_strains] */, uint32_t *iters /* [n_vec] */);
 int ss_em_strain_sets_calls(uint64_t *n);  /* calls so far in this process (diagnostics; "flag off = not run") */
+/* The runs of missing k-mers inside the records of a resident set, against the k-mers of the called strains (`--divergence`): how
+ * far the sample's organism is from the nearest called strain, without an alignment.  A record and a hit are those of
+ * ss_reads_support.  row_called[i], i < the table's rows (host memory): non-zero = a called strain has the row's k-mer; NULL: every
+ * row is called.  A slot (a distinct k-mer) is CALLED when ANY of its rows is: a k-mer listed twice is one k-mer and takes the union
+ * of its rows -- not the agree-or-zero rule of the label and mask folds.  For a record of n bytes:
+ *   base      a byte that is one of ACGTacgt
+ *   window p  0 <= p <= n - k; VALID when bytes p .. p + k - 1 are all bases.  The state of a valid window: C, its k-mer is a called
+ *             slot; T, its k-mer is in the table but not called; X otherwise.  C and T together are the record's hits.  An invalid
+ *             window has state I.
+ *   counts    hits_called, hits_cluster, misses = the record's C, T, X; windows = their sum
+ *   assessed  hits_called >= min_hits; only assessed records add to the totals below
+ *   gap       a maximal run of windows [p, p + g) that are all T or X, with window p - 1 and window p + g both existing and both C.
+ *             An I window is never inside a gap and never flanks one: no gap spans an N, a masked base or the joint of a pair.
+ *             IN-CLUSTER: every window of it is T.  Length classes: gap_lt g < k - 1; gap_km1 g = k - 1 (a deleted base);
+ *             gap_k g = k (a substituted base); gap_k_2k k < g < 2 k (an insertion of g - k + 1 bases, two differences less than
+ *             k apart); gap_ge2k g >= 2 k
+ *   site      a gap with k - 1 <= g < 2 k that is not in-cluster
+ *   stretch   a maximal run of valid windows; for one that holds a C, first / last = its first / last C window
+ *   detectable  the sum over the record's stretches with a C of max(0, last - first - k): a substitution at base b of a fully
+ *             matching stretch gives a flanked gap exactly when first + k <= b <= last - 1.  A clean 150-base read at k = 31: 88.
+ * out[]: [0] records (all non-empty records of the set), then summed over the assessed records [1] assessed, [2] windows,
+ * [3] hits_called, [4] hits_cluster, [5] misses, [6] gap_lt, [7] gap_km1, [8] gap_k, [9] gap_k_2k, [10] gap_ge2k,
+ * [11] gaps_in_cluster, [12] sites, [13] reads_with_sites, [14] detectable; [15] kmers = the occupied slots of the table,
+ * [16] kmers_called = the called ones; [17] the records of more than 4095 bytes, which take the call's general pass
+ * (diagnostics).  rec_out (host memory, NULL to skip): four values per record -- hits_called, its gaps of all classes, its sites,
+ * its detectable -- in the record order of ss_reads_read_back, for the records that are not assessed too.  Nothing depends on the
+ * order of the records: file order, binned ASCII and packed slabs give the same totals, and the totals of a set's shards ([0]..[14],
+ * [17]) add up to the whole set's.  Synchronous.  Reads the table's index, never its counters.  SS_ERANGE: as ss_reads_select states
+ * it.  SS_EINVAL: db, r or out NULL; min_hits == 0; a table and a set on different devices. */
+#define SS_GAPS_OUT 18
+int ss_reads_gaps(const ss_db *db, const ss_reads *r, const uint8_t *row_called /* NULL: every row */, uint32_t min_hits,
+                  uint64_t out[SS_GAPS_OUT], uint32_t *rec_out /* NULL, or [records][4] */);
+int ss_reads_gaps_calls(uint64_t *n);      /* calls so far in this process (diagnostics; "flag off = not run") */
 /* Read PAIRS as the records of a resident set (`--pairs`, ss_pairs.hip).  A resident set keeps no pair map, and every call above
  * decides per record from the record's bytes alone: on a set whose records are the pairs they all work on fragments, unchanged.
  * The join rule: record i of the result is  line1[i] + 'N' + line2[i] + '\n'.  'N' ends a k-mer window, so no k-mer spans the

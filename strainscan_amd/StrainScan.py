@@ -196,6 +196,18 @@ def add_arguments(ap, multi=False):
                          "replicates that resample the reads (a Poisson bootstrap over reads, the replicates of --bootstrap_seed S), "
                          "all replicates solved in one launch.  The bounds are conditional on the called strains, identical reads "
                          "share a weight, a strain that is not called gets no reads (default: off)")
+    ap.add_argument("--divergence", dest="divergence", type=divergence_arg, default=0, metavar="M",
+                    help="Also write strain_divergence.tsv: how far the sample's organism is from the nearest called strain of "
+                         "each multi-strain cluster, from the ORDER of k-mer hits along every read.  After a cluster's "
+                         "StrainVote.report is written, a read's windows are C (a k-mer of a called strain), T (a k-mer of the "
+                         "cluster that no called strain has) or X (neither); a gap is a run of T/X windows between two C windows "
+                         "with no N inside.  One differing base removes k consecutive k-mers (gap_k), a deleted base k - 1 "
+                         "(gap_km1), an insertion or two close differences more (gap_k_2k); those are `sites` unless every "
+                         "window of the gap is T (gaps_in_cluster: the read follows an uncalled strain).  per_kb = 1000 x sites / "
+                         "detectable, detectable being the base positions at which a difference would have made such a gap.  It "
+                         "is divergence PLUS the sequencing error rate, relative to the union of the called strains.  Only reads "
+                         "with at least M k-mers of the called strains are assessed.  An integer >= 1; needs the sample resident "
+                         "on the device, k >= 17 and one rank (default: off)")
     ap.add_argument("--tag_bam", dest="tag_bam", action="store_true",
                     help="With --classify_reads M and BAM input (every input a BAM): also write OUT/classified_<i>.bam per input "
                          "file, the input written back with the class of every read as two aux tags -- sn:i:<node of "
@@ -237,7 +249,7 @@ def refuse_pairs_alone(ap, args):
     if args.pairs and not args.input_fq2 and _lib.input_kind(args.input_fq) != "bam":
         ap.error("--pairs needs -j (the second file of the pairs)")
     if args.pairs and not (args.read_support or args.extract_reads or args.bootstrap or args.classify_reads or args.bootstrap_clusters
-                           or args.classify_strains):
+                           or args.classify_strains or args.divergence):
         ap.error("--pairs needs at least one of --read_support, -x N, --bootstrap B, --classify_reads M, --bootstrap_clusters B")
 
 
@@ -330,6 +342,11 @@ def classify_reads_arg(text):
 
 def classify_strains_arg(text):
     """--classify_strains' value: an integer of at least 1, or the parser's error (exit status 2, before any input is opened)."""
+    return classify_reads_arg(text)
+
+
+def divergence_arg(text):
+    """--divergence's value: an integer of at least 1, or the parser's error (exit status 2, before any input is opened)."""
     return classify_reads_arg(text)
 
 
@@ -461,6 +478,14 @@ def apply_em_strains(b, seed=1):
     the command writes strain_em.tsv when it ends.  stdout and the other files are untouched; None turns it off."""
     from . import read_reports
     read_reports.em_strains_reset(b, seed)
+
+
+def apply_divergence(m):
+    """--divergence M (strainscan_amd.set_divergence): the multi-strain clusters solved from here on walk every read's k-mer hits
+    for gaps against the called strains (read_reports.collect_divergence); the command writes strain_divergence.tsv when it ends.
+    stdout and the other files are untouched; 0 turns it off."""
+    from . import read_reports
+    read_reports.divergence_reset(m)
 
 
 def apply_tag_bam(on, out_dir=None):
@@ -598,6 +623,7 @@ def main(argv=None):
     apply_classify_strains(args.classify_strains)
     apply_extract_strains(args.extract_strains)
     apply_em_strains(args.em_strains, args.bootstrap_seed)
+    apply_divergence(args.divergence)
     apply_tag_bam(args.tag_bam, out_dir)
     apply_read_calls(args.read_calls, out_dir)
     apply_pairs(args.pairs)

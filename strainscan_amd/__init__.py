@@ -25,6 +25,7 @@ host-side mirror of the reference's Python interface for that path:
     strainscan_amd.set_classify_strains                       (`strainscan --classify_strains M`: every read assigned to its best called strains, read_reports.CLASSIFY_STRAINS)
     strainscan_amd.set_extract_strains                        (`strainscan --extract_strains unique|compatible`: the reads of each called strain, read_reports.EXTRACT_STRAINS)
     strainscan_amd.set_em_strains                             (`strainscan --em_strains B`: the called strains' read-based abundances by EM, read_reports.EM_STRAINS)
+    strainscan_amd.set_divergence                             (`strainscan --divergence M`: k-mer gaps per read against the called strains, read_reports.DIVERGENCE)
     strainscan_amd.set_pairs                                  (`strainscan --pairs`: those reports on read pairs as fragments, read_reports.PAIRS)
 
 There is no CPU fallback: every entry point raises if the HIP library or a GPU is missing.
@@ -192,6 +193,19 @@ def set_em_strains(b, seed=1):
         raise ValueError("seed must be an integer in 0..2^63-1, not %r" % (seed,))
     from . import read_reports
     read_reports.em_strains_reset(b, seed)
+
+
+def set_divergence(m):
+    """`strainscan --divergence M` for callers of the functions above: from here on vote_strain_L2_batch, after a multi-strain
+    cluster has written its StrainVote.report, walks the k-mer hits of every read of the sample in order and counts the runs of
+    missing k-mers between two k-mers of the cluster's called strains (ReadSet.gaps; the rule is in strainscan_hip.h), over the reads
+    with at least m k-mers of the called strains, and keeps the totals with read_reports.DIVERGENCE;
+    read_reports.write_divergence(out_dir) writes strain_divergence.tsv.  m is an integer >= 1 (0 or None turns it off).  Off by
+    default; nothing runs while it is off."""
+    if m and (isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 0xFFFFFFFF):
+        raise ValueError("divergence must be an integer >= 1 (or 0 for off), not %r" % (m,))
+    from . import read_reports
+    read_reports.divergence_reset(m or 0)
 
 
 def set_pairs(on):

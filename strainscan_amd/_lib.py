@@ -131,6 +131,8 @@ SIGNATURES = {
     "ss_reads_strain_sets_resampled_calls": (i32, [P(u64)]),
     "ss_em_strain_sets": (i32, [vp, vp, u32, u32, u32, u32, C.c_double, vp, vp]),
     "ss_em_strain_sets_calls": (i32, [P(u64)]),
+    "ss_reads_gaps": (i32, [vp, vp, vp, u32, vp, vp]),
+    "ss_reads_gaps_calls": (i32, [P(u64)]),
     "ss_reads_order": (i32, [vp]),
     "ss_flat_record_keys": (i32, [cp, u64, vp, u64, P(u64)]),
     "ss_extract_write": (i32, [P(cp), i32, vp, u64, P(cp), P(u64)]),
@@ -781,6 +783,29 @@ class ReadSet:
               "ss_reads_strain_sets_resampled")
         return out
 
+    def gaps(self, kdb, row_called, min_hits, want_records=False):
+        """The runs of missing k-mers inside the records, against the k-mers of the called strains (ss_reads_gaps;
+        tests/gap_model.py restates it).  row_called[i]: non-zero when a called strain has the k-mer of row i of the table; None:
+        every row is called.  A k-mer listed twice is called when any of its rows is.  -> dict of GAPS_FIELDS (ints), and with
+        want_records (dict, np.uint32[n, 4]: hits_called, gaps, sites, detectable per record in read_back() order, also of the
+        records below min_hits).  The table's counters are left alone."""
+        rc = None
+        if row_called is not None:
+            rc = np.ascontiguousarray(np.asarray(row_called) != 0, np.uint8)
+            if rc.ndim != 1 or rc.size != kdb.n_rows:
+                raise ValueError("one flag per row of the table (%d), not %r" % (kdb.n_rows, rc.shape))
+            if not rc.size:
+                rc = np.zeros(1, np.uint8)
+        out = np.zeros(GAPS_OUT, np.uint64)
+        rec = None
+        if want_records:
+            # (the records as ss_reads_support counts them: ss_reads_info's count includes reads without a base)
+            rec = np.zeros((max(1, int(self.support(kdb, 2)[0].sum())), 4), np.uint32)
+        check(lib().ss_reads_gaps(kdb.handle, self._h, ptr(rc) if rc is not None else None, int(min_hits), ptr(out),
+                                  ptr(rec) if want_records else None), "ss_reads_gaps")
+        res = {name: int(v) for name, v in zip(GAPS_FIELDS, out)}
+        return (res, rec[:res["records"]]) if want_records else res
+
     def order(self):
         """Put the records of a set in file order (from_flat_dev(order=False), select(), resample()) in locality order, in place
         (ss_reads_order): the records and every count stay, a scan of a cluster table gets faster.  -> self"""
@@ -930,6 +955,16 @@ def select_strains_calls():
 
 EM_VECTORS_MAX = 1024       # SS_EM_VECTORS_MAX (strainscan_hip.h): count vectors per call of em_strain_sets
 EM_LDS_SETS = 6144          # SS_EM_LDS_SETS (strainscan_hip.h): the sets a workgroup of em_strain_sets keeps in LDS
+
+
+GAPS_OUT = 18               # SS_GAPS_OUT (strainscan_hip.h): the totals of gaps()
+GAPS_FIELDS = ("records", "assessed", "windows", "hits_called", "hits_cluster", "misses", "gap_lt", "gap_km1", "gap_k", "gap_k_2k", "gap_ge2k",
+               "gaps_in_cluster", "sites", "reads_with_sites", "detectable", "kmers", "kmers_called", "long_records")
+
+
+def gaps_calls():
+    """Calls of ss_reads_gaps so far in this process."""
+    return _calls("ss_reads_gaps_calls")
 
 
 def strain_sets_resampled_calls():

@@ -1,6 +1,6 @@
 """`strainscan-multi` -- one sample against several databases in one run.
 
-    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B --bootstrap_clusters B --classify_reads M --extract_class LIST --tag_bam --read_calls --classify_strains M --extract_strains unique|compatible --em_strains B --pairs]
+    strainscan-multi -i R1 [-j R2] -d DB1 -d DB2 [-d LABEL=DB3 ...] -o OUT [-k -l -b -e -s -q --read_support -x N --by_strain --bootstrap B --bootstrap_clusters B --classify_reads M --extract_class LIST --tag_bam --read_calls --classify_strains M --extract_strains unique|compatible --em_strains B --divergence M --pairs]
 
 For every database OUT/<label>/ receives the files `strainscan -i R1 [-j R2] -d DBn -o OUT/<label> [flags]` writes, and
 OUT/databases.tsv one line per database (command-line order): label, path, status -- `reports`, `no_clusters` (the "No
@@ -154,7 +154,7 @@ def identify_databases(in_fq, db_dirs, out_dir, ksize=31, ldep=0, sprob=0, emode
                 sys.stderr.flush()
                 status = "error:" + type(e).__name__
             finally:
-                read_reports.write_all(od, label)       # (OUT/<label>/read_support.tsv, strain_support.tsv, strain_bootstrap.tsv, cluster_bootstrap.tsv, read_classes.tsv, strain_classes.tsv, strain_sets.tsv, strain_em.tsv)
+                read_reports.write_all(od, label)       # (OUT/<label>/read_support.tsv, strain_support.tsv, strain_bootstrap.tsv, cluster_bootstrap.tsv, read_classes.tsv, strain_classes.tsv, strain_sets.tsv, strain_em.tsv, strain_divergence.tsv)
             rows.append((label, d, status))
     if rank == 0:
         write_table(os.path.join(out_dir, TSV), rows)
@@ -180,6 +180,7 @@ def main(argv=None):
     StrainScan.apply_classify_strains(args.classify_strains)      # (OUT/<label>/strain_classes.tsv, strain_sets.tsv, extracted/strain_*)
     StrainScan.apply_extract_strains(args.extract_strains)
     StrainScan.apply_em_strains(args.em_strains, args.bootstrap_seed)      # (OUT/<label>/strain_em.tsv)
+    StrainScan.apply_divergence(args.divergence)      # (OUT/<label>/strain_divergence.tsv)
     StrainScan.apply_tag_bam(args.tag_bam)      # (database_scope names each database's directory: OUT/<label>/classified_<i>.bam)
     StrainScan.apply_read_calls(args.read_calls)      # (OUT/<label>/read_calls_<i>.tsv; db.ordered_reads loads the ordered sets once)
     StrainScan.apply_pairs(args.pairs)         # (db.resident_pairs caches the joined set: joined once for all databases)

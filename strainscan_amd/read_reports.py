@@ -1,5 +1,5 @@
 """The opt-in reports about the sample's reads: --read_support, -x / --extract_reads, --by_strain, --bootstrap,
---bootstrap_clusters, --classify_reads, --extract_class, --tag_bam, --read_calls, --classify_strains, --extract_strains and --em_strains; and --pairs, which makes all of them work on read pairs as fragments.
+--bootstrap_clusters, --classify_reads, --extract_class, --tag_bam, --read_calls, --classify_strains, --extract_strains, --em_strains and --divergence; and --pairs, which makes all of them work on read pairs as fragments.
 
 Each report has a state dict (its flag, what it has collected per scope, and "skipped": why nothing is written, said once on
 stderr), a lock, a `*_reset`, its `collect_*` and its `write_*`, all no-ops while the flag is off.  The scans and the solver reach
@@ -54,14 +54,16 @@ def table_scanned(table, kdb, paths):
     collect_extract_reads(table, kdb, paths)
     bootstrap_scanned(table)
     strain_classes_scanned(table)
+    divergence_scanned(table)
 
 
 def cluster_reported(cls, cls_db_dir, report_path, ksize, paths):
-    """Cluster `cls` ('C<id>') has written report_path: --by_strain, --classify_strains, then --bootstrap."""
+    """Cluster `cls` ('C<id>') has written report_path: --by_strain, --classify_strains, --divergence, then --bootstrap."""
     if not _pairs_gate(paths):
         return
     collect_by_strain(cls, cls_db_dir, report_path, ksize, paths)
     collect_strain_classes(cls, cls_db_dir, report_path, ksize, paths)
+    collect_divergence(cls, cls_db_dir, report_path, ksize, paths)
     collect_bootstrap(cls, cls_db_dir, report_path, ksize, paths)
 
 
@@ -73,6 +75,7 @@ def write_all(out_dir, scope=None):
     write_read_classes(out_dir, scope)
     write_strain_classes(out_dir, scope)
     write_em_strains(out_dir, scope)
+    write_divergence(out_dir, scope)
 
 
 def reset_all():
@@ -88,6 +91,7 @@ def reset_all():
     classify_strains_reset()
     extract_strains_reset()
     em_strains_reset()
+    divergence_reset()
     pairs_reset()
 
 
@@ -135,7 +139,7 @@ def _pairs_gate(paths):
             if js is not None:
                 return True
             PAIRS["skipped"] = why
-            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS, CLASSIFY_STRAINS, EXTRACT_STRAINS, EM_STRAINS):
+            for state in (READ_SUPPORT, EXTRACT_READS, BOOTSTRAP, CLASSIFY_READS, EXTRACT_CLASS, CLASSIFY_STRAINS, EXTRACT_STRAINS, EM_STRAINS, DIVERGENCE):
                 if state["skipped"] is None:
                     state["skipped"] = "--pairs " + why
             if dist.rank_world()[0] == 0:
@@ -794,6 +798,107 @@ def write_em_strains(out_dir, scope=None):
     if not EM_STRAINS["on"] or EM_STRAINS["skipped"] is not None or not rows:
         return None
     return _write(out_dir, EM_STRAINS_FILE, em_text([(t, rows[t]) for t in _in_order(CLASSIFY_STRAINS["order"].get(scope, []), rows)]))
+
+
+# --divergence M (StrainScan.apply_divergence turns it on): every report above takes the called strains for the right ones; this asks
+# whether the sample's organism IS a called strain or a relative of one.  After a cluster's StrainVote.report has been written,
+# collect_divergence marks the rows of the cluster's table that any called strain has (called_rows: the union of their columns, no
+# limit on their number) and the device walks every read's k-mer hits in order (ReadSet.gaps; the rule is in strainscan_hip.h,
+# tests/gap_model.py restates it): a run of k missing k-mers between two k-mers of the called strains is one base that differs.
+# Written as strain_divergence.tsv, a row per cluster.  "rows": per scope and cluster, the report numbers of the called strains and
+# the device's totals; "order": the tables as they were scanned.
+DIVERGENCE = {"m": 0, "rows": {}, "order": {}, "skipped": None}
+DIVERGENCE_FILE = "strain_divergence.tsv"
+DIVERGENCE_COLUMNS = ("windows", "hits_called", "hits_cluster", "misses", "gap_lt", "gap_km1", "gap_k", "gap_k_2k", "gap_ge2k", "gaps_in_cluster",
+                      "sites", "reads_with_sites", "detectable")
+_DIVERGENCE_LOCK = threading.Lock()
+_divergence_skip = functools.partial(_skip, DIVERGENCE, "divergence", "and no divergence was estimated", True)
+
+
+def divergence_reset(m=0):
+    DIVERGENCE.update(m=int(m or 0), rows={}, order={}, skipped=None)
+
+
+def divergence_scanned(table):
+    """A table has been scanned: strain_divergence.tsv lists the clusters in this order."""
+    if DIVERGENCE["m"]:
+        order = DIVERGENCE["order"].setdefault(SCOPE["label"], [])
+        if table not in order:
+            order.append(table)
+
+
+def called_rows(indptr, indices, data, n_rows, called_cols):
+    """np.uint8[n_rows] from a cluster's CSR matrix (row = k-mer, column = strain) and the called columns, any number of them: 1
+    where the row is non-zero in a called column.  Uncalled columns are not looked at."""
+    indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices)
+    n_mat = indptr.size - 1
+    n_cols = int(indices.max()) + 1 if indices.size else 0
+    is_called = np.zeros(max(n_cols, max(list(called_cols) + [0]) + 1), bool)
+    is_called[list(called_cols)] = True
+    hit = is_called[indices]
+    if data is not None and not np.asarray(data).all():
+        hit = hit & (np.asarray(data) != 0)
+    rows = np.searchsorted(indptr, np.flatnonzero(hit), side="right") - 1
+    mat = np.zeros(n_mat, np.uint8)
+    mat[rows] = 1
+    out = np.zeros(n_rows, np.uint8)
+    m = min(n_rows, n_mat)
+    out[:m] = mat[:m]
+    return out
+
+
+def divergence_text(clusters):
+    """The text of strain_divergence.tsv for [(table, [report numbers of the called strains], the totals of ReadSet.gaps)]."""
+    out = ["\t".join(("table", "strains", "kmers", "kmers_called", "reads") + DIVERGENCE_COLUMNS + ("per_kb",)) + "\n"]
+    for table, numbers, r in clusters:
+        per_kb = "%.3f" % (1000.0 * r["sites"] / r["detectable"]) if r["detectable"] else "-"
+        out.append("\t".join([table, ",".join(str(n) for n in numbers), str(r["kmers"]), str(r["kmers_called"]), str(r["assessed"])] +
+                             [str(r[c]) for c in DIVERGENCE_COLUMNS] + [per_kb]) + "\n")
+    return "".join(out)
+
+
+def collect_divergence(cls, cls_db_dir, report_path, ksize, paths):
+    """After cluster `cls` ('C<id>') has written report_path: its row of strain_divergence.tsv.  A no-op unless --divergence is on.
+    The solver's threads call this; a cluster that has its numbers under the current scope keeps them."""
+    m = DIVERGENCE["m"]
+    if not m or DIVERGENCE["skipped"] is not None or not os.path.exists(report_path):
+        return
+    from .tree import load_plain_pkl
+    with _DIVERGENCE_LOCK:
+        rows = DIVERGENCE["rows"].setdefault(SCOPE["label"], {})
+        if cls in rows or DIVERGENCE["skipped"] is not None:
+            return
+        called = called_strains(report_path)
+        if not called:
+            return
+        if dist.is_distributed():
+            return _divergence_skip("runs on one rank only (this run has several)")
+        rs = _report_reads(paths)
+        if rs is None:
+            return _divergence_skip(NEEDS_RESIDENT)
+        sid = load_plain_pkl(os.path.join(cls_db_dir, "id2strain_re.pkl"))
+        col_of = {name: c for c, name in (sid.items() if isinstance(sid, dict) else enumerate(sid))}
+        indptr, indices, data = cluster_csr_arrays(os.path.join(cls_db_dir, "all_strains_re.npz"))
+        with contextlib.closing(db.fasta_index(os.path.join(cls_db_dir, "all_kmer.fasta"), int(ksize), 2)) as kdb:
+            if kdb.k < 17:
+                return _divergence_skip(NEEDS_PAGE_INDEX % kdb.k)
+            row_called = called_rows(indptr, indices, data, kdb.n_rows, [col_of[name] for _, name in called])
+            res = _select_or_skip(lambda: rs.gaps(kdb, row_called, m), _divergence_skip, "walk")
+            if res is None:
+                return
+            rows[cls] = ([n for n, _ in called], res)
+            print("divergence: %s\tM=%d\trecords %d\tassessed %d\tsites %d\tdetectable %d" %
+                  (cls, m, res["records"], res["assessed"], res["sites"], res["detectable"]), file=sys.stderr)
+            sys.stderr.flush()
+
+
+def write_divergence(out_dir, scope=None):
+    """out_dir/strain_divergence.tsv from the numbers collected under `scope`, clusters in the order of the scans; nothing without
+    the flag, without numbers, or after a skip."""
+    rows = DIVERGENCE["rows"].get(scope) or {}
+    if not DIVERGENCE["m"] or DIVERGENCE["skipped"] is not None or not rows:
+        return None
+    return _write(out_dir, DIVERGENCE_FILE, divergence_text([(t,) + rows[t] for t in _in_order(DIVERGENCE["order"].get(scope, []), rows)]))
 
 
 # --bootstrap B (StrainScan.apply_bootstrap turns it on): how firm are a multi-strain cluster's numbers?  After the cluster has
